@@ -2,9 +2,16 @@
 """Headline benchmark: Gelem/s of the prune(0.75, dims={1}) -> quantize(4-bit, tensor-wise) training
 step (forward + backward, live statistics every step) on a 256x256x56x56 bf16 activation per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without a launcher: starts its own N ranks)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                                  (N > 1 without a launcher: starts its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline step alone: set-up, W warm-up steps, K timed steps, the JSON line.  `--full` adds what the
+headline figure does not need, after the timed region: the other elision modes (`config.variants`), the CPU baseline and
+`configs` (below).  `--dump-outputs DIR` writes what the last timed step returned (y and grad_x, a fixed seeded sample of
+each) and the operator state it left (mask, scale) as float32 .npy files: the inputs are seeded, so two builds can be
+compared output for output.
 
 One "step" = one pass of the hot path over one batch of synthetic input, everything resident in HBM:
     stats   (read x)            staged per-channel mean|x| + per-channel max|x|
@@ -17,9 +24,9 @@ hold a NaN / Inf and those are loaded) does not load the x of pruned channels in
 mode that ran, and `config.variants` carries the dense step ("off") and the fully elided one ("all") next to it.
 
 Rank 0 prints ONE JSON line.  With N > 1 every rank processes its own batch shard (weak scaling) and the C-sized
-statistics are exchanged over RCCL each step (qsparse_amd/distributed.py); after the timed region the ranks also run
-BASELINE config 5 -- ResNet-50, the --pq recipe, DistributedDataParallel -- and the line carries its whole-job images/s
-in `configs.config5_resnet50_ddp` (under a watchdog: it can never cost the headline record).  At N == 1 the line also carries
+statistics are exchanged over RCCL each step (qsparse_amd/distributed.py); with `--full`, after the timed region the ranks
+also run BASELINE config 5 -- ResNet-50, the --pq recipe, DistributedDataParallel -- and the line carries its whole-job images/s
+in `configs.config5_resnet50_ddp` (under a watchdog: it can never cost the headline record).  At N == 1 `--full` adds
 `configs`: BASELINE.json's configs 2-4 (the 8-bit quantizer alone on 256x64x56x56; ResNet-18 CIFAR shape and ResNet-50
 ImageNet shape, plain vs converted, eager and hipGraph replay) measured in the same process.
 """
@@ -79,6 +86,24 @@ def make_pair(device):
         nn.Sequential(nn.Identity(), qs.prune(sparsity=0.75, dimensions={1}, start=0, interval=1, repetition=1)),
         qs.quantize(bits=4, channelwise=-1, timeout=1)).to(device).train()
     return fuse_prune_quantize_pairs(pair)
+
+
+DUMP_SAMPLE = 1 << 22       # elements kept of each full-size output by --dump-outputs: 16 MB of float32 apiece
+
+
+def dump_outputs(path, arrays, seed=0):
+    """write each array as <path>/<name>.npy in float32; one larger than DUMP_SAMPLE elements is reduced to a fixed sample:
+    the elements at DUMP_SAMPLE positions of its flattened view drawn from a CPU generator seeded with `seed` (the same
+    positions in every run and every build, since they depend on the element count alone)"""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed))
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(path, name + ".npy"), flat.float().cpu().numpy())
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -880,6 +905,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the other elision modes, the CPU baseline and BASELINE configs "
+                         "2-4 (N == 1) / config 5 (N > 1); the --no-* options below leave parts of that out")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (y, grad_x: a fixed seeded sample of each) and the operator "
+                         "state it left (mask, scale) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip BASELINE configs 2-4 (N == 1) / config 5 (N > 1)")
     ap.add_argument("--no-variants", action="store_true", help="skip the other elision modes after the timed region")
@@ -894,6 +925,8 @@ def main():
                     help="(child mode of the N = 1 bench) the config-3 / config-4 network in a one-rank RCCL group with the "
                          "statistics exchange live, under DistributedDataParallel; prints its record")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline(threads=args.cpu_baseline_only)))
         return
@@ -968,10 +1001,10 @@ def main():
     x.requires_grad_(True)
     pair = make_pair(device)
 
-    def step():
+    def step(keep=False):
         y = pair(x)
         (gx,) = torch.autograd.grad(y, x, gout)
-        return gx
+        return (y, gx) if keep else gx
 
     # setup: bring the operators to their steady state (schedule finished, mask refresh and running scale live,
     # allocator pools and clocks settled); not part of the W warm-up steps or the K timed steps
@@ -998,7 +1031,10 @@ def main():
             _hip.start_event_log(only=None)
         elif i % 4 == 3:
             _hip.start_event_log(only=dom)
-        step()
+        if i == args.steps - 1:
+            last = step(keep=True)      # what the last timed step returned, for --dump-outputs
+        else:
+            step()
         for kname, pairs in _hip.take_event_pairs().items():
             events.setdefault(kname, []).extend(pairs)
     fence()
@@ -1013,11 +1049,14 @@ def main():
         ones = torch.ones(1, device=device, dtype=torch.float64)
         dist.all_reduce(ones, op=dist.ReduceOp.SUM)
         ranks_seen = int(ones.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"y": last[0], "grad_x": last[1], "mask": pair[0][1].mask, "scale": pair[1].weight})
+    del last
 
     # the other two elision modes, outside the timed region, on rank 0's clock (continuity with round 1: "off" is the
     # dense 14 B/elem step; "all" also elides the backward, which then writes +0.0 for the reference's -0.0)
     variants = {}
-    if world == 1 and not args.no_variants:
+    if world == 1 and args.full and not args.no_variants:
         for other in ("off", "forward", "all"):
             if other == mode:
                 continue
@@ -1127,7 +1166,7 @@ def main():
                 emitted[0] = True
                 os.write(real_stdout, (json.dumps(out) + "\n").encode())
 
-    if world > 1 and not args.no_configs and os.environ.get("QS_BENCH_NO_DDP_CONFIG", "0") != "1":
+    if world > 1 and args.full and not args.no_configs and os.environ.get("QS_BENCH_NO_DDP_CONFIG", "0") != "1":
         # BASELINE config 5 after the headline's timed region.  It is collective, so a rank that fails alone would leave
         # the others waiting in RCCL: a watchdog on every rank ends the process cleanly at the deadline -- rank 0 after
         # writing the headline record with the failure noted -- so config 5 can never cost the headline line.
@@ -1180,11 +1219,11 @@ def main():
         torch.cuda.synchronize()
         dist.destroy_process_group()
     if rank == 0:
-        if world == 1 and not force_exchange and not args.no_configs:
+        if world == 1 and not force_exchange and args.full and not args.no_configs:
             del pair, x, gout
             torch.cuda.empty_cache()
             out["configs"] = extra_configs(device)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
     emit()
     os.close(real_stdout)

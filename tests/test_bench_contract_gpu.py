@@ -39,7 +39,8 @@ def _check(rec, n, steps):
 
 
 def test_single_gpu_line_with_roofline_variants_and_cpu_baseline():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "24", "--warmup", "2", "--no-configs"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "24", "--warmup", "2", "--no-configs",
+                        "--full"],
                        capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -57,10 +58,38 @@ def test_single_gpu_line_with_roofline_variants_and_cpu_baseline():
                                                                int(round(rec["config"]["algorithmic_bytes_per_elem"]["apply_fwd"] * 256 * 256 * 56 * 56)))
 
 
+def test_plain_line_is_the_headline_alone_and_dumps_the_same_outputs_every_run(tmp_path):
+    """without --full the line carries the headline and its roofline only; --dump-outputs writes the last timed step's outputs
+    and operator state as float32 .npy (64 MB at most), identical for two runs with the same arguments"""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        rec = json.loads(lines[0])
+        _check(rec, 1, 6)
+        assert "configs" not in rec and "cpu_baseline" not in rec and "variants" not in rec["config"]
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["grad_x.npy", "mask.npy", "scale.npy", "y.npy"], files
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64 << 20
+        arrays = {f[:-len(".npy")]: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float32 for a in arrays.values())
+        assert arrays["mask"].size == 256 and 0 < arrays["mask"].sum() < 256
+        assert np.isfinite(arrays["y"]).all() and np.isfinite(arrays["grad_x"]).all() and arrays["y"].any()
+        dumps.append(arrays)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
 def test_two_ranks_through_torch_distributed_run():
     env = dict(os.environ, QS_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0", QS_BENCH_DDP_BATCH="8")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "2"]
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "2",
+           "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -98,7 +127,8 @@ def test_config5_watchdog_keeps_the_headline_marks_it_degraded_and_fails_the_run
     env = dict(os.environ, QS_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0", QS_BENCH_DDP_BATCH="8",
                QS_BENCH_DDP_TIMEOUT="0.5")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2"]
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2",
+           "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert r.returncode != 0
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]

@@ -33,3 +33,26 @@ def test_gpus_2_without_a_launcher_reaches_both_ranks():
     assert r.stdout.strip() == ""
     assert r.stderr.count("bench.py needs a GPU") >= 2, r.stderr[-2000:]
     assert "AssertionError" not in r.stderr
+
+
+def test_dump_outputs_writes_a_fixed_float32_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every array as float32 .npy, one larger than DUMP_SAMPLE reduced to the same seeded positions each time"""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    y = torch.randn(5000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"y": y, "grad_x": y.bfloat16(), "mask": torch.ones(16, dtype=torch.bool)})
+    a = {f: np.load(tmp_path / "a" / (f + ".npy")) for f in ("y", "grad_x", "mask")}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["y"].shape == a["grad_x"].shape == (1000,) and a["mask"].shape == (16,)
+    assert np.isin(a["y"], y.numpy()).all()
+    for f, v in a.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / (f + ".npy"))), f
+
+
+def test_steps_must_be_positive():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, cwd=ROOT,
+                       timeout=300)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr

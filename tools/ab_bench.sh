@@ -1,13 +1,16 @@
 #!/bin/bash
 # A/B on ONE box: the whole bench line (no CPU baseline, no DDP children) of an older tree checked out under ab_old/ (git worktree add
 # ab_old <commit>; build it there) against the current tree, interleaved; prints the figures side by side
+# (records under $AB_OUT, default build/ab)
 export QS_BENCH_NO_EXCHANGE_LIVE=1
+export AB_OUT=$(realpath -m "${AB_OUT:-build/ab}"); mkdir -p "$AB_OUT"
+old_full=$(grep -q -- '"--full"' ab_old/bench.py && echo --full)     # (a tree from before --full measures everything by default)
 for i in 1 2; do
-  (cd ab_old && python3 bench.py --no-cpu-baseline > ../gpurun_out/abb_old_$i.json 2> ../gpurun_out/abb_old_$i.err)
-  python3 bench.py --no-cpu-baseline > gpurun_out/abb_new_$i.json 2> gpurun_out/abb_new_$i.err
+  (cd ab_old && python3 bench.py $old_full --no-cpu-baseline > "$AB_OUT/abb_old_$i.json" 2> "$AB_OUT/abb_old_$i.err")
+  python3 bench.py --full --no-cpu-baseline > "$AB_OUT/abb_new_$i.json" 2> "$AB_OUT/abb_new_$i.err"
 done
 python3 - <<'PY'
-import json
+import json, os
 def row(r):
     c, k = r["config"], r["configs"]
     out = {"value": r["value"], "dense": c["dense_gelem_s"], "all": c["elide_all_gelem_s"], "frozen": c["frozen_mask_gelem_s"],
@@ -21,7 +24,7 @@ def row(r):
     return out
 for t in ("old_1", "new_1", "old_2", "new_2"):
     try:
-        print(t, json.dumps(row(json.loads(open(f"gpurun_out/abb_{t}.json").read().strip().splitlines()[-1]))))
+        print(t, json.dumps(row(json.loads(open(os.path.join(os.environ["AB_OUT"], f"abb_{t}.json")).read().strip().splitlines()[-1]))))
     except Exception as e:
         print(t, "error", repr(e))
 PY

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Regenerates the evidence under profiles/ on an MI355X box (writes to gpurun_out/profiles/, to be copied):
 
-  rNN_bench_default.json                 the JSON record of a plain `python3 bench.py`
+  rNN_bench_default.json                 the JSON record of `python3 bench.py --full`
   rNN_bench_kernel_stats.csv             rocprofv3 --kernel-trace --stats summary of the same command
   rNN_bench_step_timeline.txt            the last three headline steps of that trace, kernel by kernel
   rNN_headline_kernel_stats.csv          the same summary for `python3 bench.py --no-configs --no-variants --no-cpu-baseline`:
@@ -55,8 +55,8 @@ def main():
         assert r.returncode == 0
         return pmc_passes(json.loads(r.stdout.strip().splitlines()[-1]), ["--elide", "all"], "_all")
 
-    # 1. the plain command
-    r = sh(["python3", BENCH], stdout=subprocess.PIPE)
+    # 1. the full command (headline, variants, configs, CPU baseline)
+    r = sh(["python3", BENCH, "--full"], stdout=subprocess.PIPE)
     assert r.returncode == 0
     rec = json.loads(r.stdout.strip().splitlines()[-1])
     with open(os.path.join(OUT, f"{TAG}_bench_default.json"), "w") as f:
@@ -65,7 +65,7 @@ def main():
     # 2. kernel stats of the same command
     d = os.path.join(OUT, "stats")
     assert sh(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "bench", "--",
-               "python3", BENCH]).returncode == 0
+               "python3", BENCH, "--full"]).returncode == 0
     shutil.copy(find(os.path.join(d, "**", "*kernel_stats.csv")), os.path.join(OUT, f"{TAG}_bench_kernel_stats.csv"))
     rows = list(csv.DictReader(open(find(os.path.join(d, "**", "*kernel_trace.csv")))))
     rows.sort(key=lambda x: int(x["Start_Timestamp"]))
@@ -79,7 +79,7 @@ def main():
     end = next((i for i, x in enumerate(qs_rows) if dense_fwd(x["Kernel_Name"])), len(qs_rows))
     tail = qs_rows[max(end - 15, 0):end]
     with open(os.path.join(OUT, f"{TAG}_bench_step_timeline.txt"), "w") as f:
-        f.write("rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py\n")
+        f.write("rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full\n")
         f.write("3 consecutive headline steps of the timed region (durations under the profiler; a gap holds a HIP event pair on sampled steps)\n\n")
         prev_end = None
         for x in tail:
@@ -92,7 +92,7 @@ def main():
     shutil.rmtree(d)
 
     # 2a. the headline alone (no configs, no variants, no CPU baseline): every row of this summary is a headline kernel, so its
-    #     averages ARE the per-launch durations the roofline quotes (the summary of the plain command mixes in configs 2-4)
+    #     averages ARE the per-launch durations the roofline quotes (the summary of the --full command mixes in configs 2-4)
     d = os.path.join(OUT, "stats_headline")
     if sh(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "bench", "--",
            "python3", BENCH, "--no-configs", "--no-variants", "--no-cpu-baseline"]).returncode == 0:

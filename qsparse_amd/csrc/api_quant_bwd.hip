@@ -28,100 +28,49 @@ int qs_quant_ste_bwd(const void* g, void* gx, const float* step, int64_t nstep, 
 }
 
 static int ste_relu_bwd_impl(const qs_ste_relu_bwd_args& a) {
-    const void *g = a.g, *x = a.x, *g2 = a.g2;
-    const uint8_t* gate = a.gate;
-    void* gx = a.gx;
-    const int gdt = a.gdt, xdt = a.xdt, g2dt = a.g2dt;
-    if ((!g && !g2) || (!x && !gate) || !gx) return QS_ERR_ARG;
     ActSpec act;
     if (qs_act_resolve(a.act > 0 ? a.act : 1, &act) != QS_OK) return QS_ERR_ARG;
-    if (!dt_ok(gdt) || !dt_ok(xdt) || !(gdt == QS_F32 || gdt == xdt)) return QS_ERR_DTYPE;
-    if (g2 && (!gate || gdt != QS_F32 || (g2dt != QS_BF16 && g2dt != QS_F16))) return QS_ERR_DTYPE;
-    if ((g && !aligned16(g)) || (!gate && !aligned16(x)) || !aligned16(gx) || (g2 && !aligned16(g2))) return QS_ERR_ALIGN;
-    // the riders of the all-fp32 kernel form (BwdRiders, qs_elementwise.h)
-    if (a.g3 && (!g2 || gdt != QS_F32 || xdt != QS_F32)) return QS_ERR_ARG;
-    if (a.gx_image && (gdt != QS_F32 || xdt != QS_F32 || (a.gx_image_dt != QS_BF16 && a.gx_image_dt != QS_F16))) return QS_ERR_DTYPE;
-    if ((a.g3 && !aligned16(a.g3)) || (a.gx_image && !aligned16(a.gx_image))) return QS_ERR_ALIGN;
-    const BwdRiders rd{a.g3, a.gx_image, a.gx_image_dt};
-    int st = check_param(a.step, a.nstep, a.C);
-    if (st) return st;
-    const bool ppc = a.nstep > 1;
-    const uint8_t* chan_mask = a.chan_mask;
     EwPlan plan;
-    st = plan_ew(a.outer, a.C, a.inner, ppc || chan_mask != nullptr, &plan, !ppc && aligned8(chan_mask));
-    if (st) return st;
-    if (plan.geo.numel == 0) return QS_OK;
+    const int st = ste_bwd_check(a, a.x, a.gate, true, &plan);
+    if (st || plan.geo.numel == 0) return st;
+    const bool ppc = a.nstep > 1;
     hipStream_t s = (hipStream_t)a.stream;
-    SteBwdOp op{a.step, a.step_host, a.step_is_decimal, a.lo_mul, a.hi_mul, 0, chan_mask};
+    SteBwdOp op{a.step, a.step_host, a.step_is_decimal, a.lo_mul, a.hi_mul, 0, a.chan_mask};
+    const BwdRiders rd{a.g3, a.gx_image, a.gx_image_dt};
     const int grid = grid_for(plan.geo.ngroups, 1);
     constexpr bool NT = QS_EW_NT != 0;
-    const void* second = gate ? (const void*)gate : x;       // the gate bitmap replaces the ReLU's input (GATE kernels)
-    if (g2) {
+    const void* second = a.gate ? (const void*)a.gate : a.x;     // the gate bitmap replaces the ReLU's input (GATE kernels)
+    if (a.g2) {
         // two gradient streams (fp32 + a 2-byte one, or the 2-byte one alone): gate bitmap kernels, never eliding
         auto dual = [&](auto X, auto G2) {
             constexpr int XD = decltype(X)::value, G2D = decltype(G2)::value;
-            int cm = plan.cm;
-            if (XD == QS_F32 && cm == CM_ELEM && plan.geo.inner % 4 == 0) cm = CM_ROW;
-            switch (cm) {
-                case CM_SCALAR:
-                    hipLaunchKernelGGL((ste_relu_bwd_kernel<QS_F32, XD, CM_SCALAR, NT, false, true, G2D>), dim3(grid), dim3(kBlock), 0, s,
-                                       op, plan.geo, (int)ppc, g, second, gx, act, g2, rd);
-                    break;
-                case CM_ROW:
-                    hipLaunchKernelGGL((ste_relu_bwd_kernel<QS_F32, XD, CM_ROW, NT, false, true, G2D>), dim3(grid), dim3(kBlock), 0, s,
-                                       op, plan.geo, (int)ppc, g, second, gx, act, g2, rd);
-                    break;
-                case CM_LAST:
-                    hipLaunchKernelGGL((ste_relu_bwd_kernel<QS_F32, XD, CM_LAST, NT, false, true, G2D>), dim3(grid), dim3(kBlock), 0, s,
-                                       op, plan.geo, (int)ppc, g, second, gx, act, g2, rd);
-                    break;
-                default:
-                    hipLaunchKernelGGL((ste_relu_bwd_kernel<QS_F32, XD, CM_ELEM, NT, false, true, G2D>), dim3(grid), dim3(kBlock), 0, s,
-                                       op, plan.geo, (int)ppc, g, second, gx, act, g2, rd);
-                    break;
-            }
-            return launch_status();
+            return with_cm(XD == QS_F32 ? cm_4(plan) : plan.cm, [&](auto M) {
+                hipLaunchKernelGGL((ste_relu_bwd_kernel<QS_F32, XD, decltype(M)::value, NT, false, true, G2D>), dim3(grid), dim3(kBlock),
+                                   0, s, op, plan.geo, (int)ppc, a.g, second, a.gx, act, a.g2, rd);
+                return launch_status();
+            });
         };
-        return with_dtype(xdt, [&](auto X) { return g2dt == QS_BF16 ? dual(X, IC<QS_BF16>{}) : dual(X, IC<QS_F16>{}); });
+        return with_dtype(a.xdt, [&](auto X) { return a.g2dt == QS_BF16 ? dual(X, IC<QS_BF16>{}) : dual(X, IC<QS_F16>{}); });
     }
-    return with_dtype(xdt, [&](auto X) {
+    const bool el = a.elide_masked != 0 && a.chan_mask != nullptr;
+    return with_dtype(a.xdt, [&](auto X) {
         constexpr int XD = decltype(X)::value;
         auto go = [&](auto G, auto GT) {
             constexpr int GD = decltype(G)::value;
             constexpr bool GATE = decltype(GT)::value;
-            int cm = plan.cm;
-            if (GD == QS_F32 && XD == QS_F32 && cm == CM_ELEM && plan.geo.inner % 4 == 0) cm = CM_ROW;   // 4 elements per lane
-            const bool el = a.elide_masked != 0 && chan_mask != nullptr;
-            switch (cm) {
-                case CM_SCALAR:
-                    hipLaunchKernelGGL((ste_relu_bwd_kernel<GD, XD, CM_SCALAR, NT, false, GATE>), dim3(grid), dim3(kBlock), 0, s,
-                                       op, plan.geo, (int)ppc, g, second, gx, act, nullptr, rd);
-                    break;
-                case CM_ROW:
-                    if (el)
-                        hipLaunchKernelGGL((ste_relu_bwd_kernel<GD, XD, CM_ROW, NT, true, GATE>), dim3(grid), dim3(kBlock), 0, s,
-                                           op, plan.geo, (int)ppc, g, second, gx, act, nullptr, rd);
-                    else
-                        hipLaunchKernelGGL((ste_relu_bwd_kernel<GD, XD, CM_ROW, NT, false, GATE>), dim3(grid), dim3(kBlock), 0, s,
-                                           op, plan.geo, (int)ppc, g, second, gx, act, nullptr, rd);
-                    break;
-                case CM_LAST:
-                    if (el)
-                        hipLaunchKernelGGL((ste_relu_bwd_kernel<GD, XD, CM_LAST, NT, true, GATE>), dim3(grid), dim3(kBlock), 0, s,
-                                           op, plan.geo, (int)ppc, g, second, gx, act, nullptr, rd);
-                    else
-                        hipLaunchKernelGGL((ste_relu_bwd_kernel<GD, XD, CM_LAST, NT, false, GATE>), dim3(grid), dim3(kBlock), 0, s,
-                                           op, plan.geo, (int)ppc, g, second, gx, act, nullptr, rd);
-                    break;
-                default:
-                    hipLaunchKernelGGL((ste_relu_bwd_kernel<GD, XD, CM_ELEM, NT, false, GATE>), dim3(grid), dim3(kBlock), 0, s,
-                                       op, plan.geo, (int)ppc, g, second, gx, act, nullptr, rd);
-                    break;
-            }
-            return launch_status();
+            return with_cm(GD == QS_F32 && XD == QS_F32 ? cm_4(plan) : plan.cm, [&](auto M) {
+                constexpr int CM = decltype(M)::value;
+                auto launch = [&](auto E) {
+                    hipLaunchKernelGGL((ste_relu_bwd_kernel<GD, XD, CM, NT, decltype(E)::value, GATE>), dim3(grid), dim3(kBlock), 0, s,
+                                       op, plan.geo, (int)ppc, a.g, second, a.gx, act, nullptr, rd);
+                    return launch_status();
+                };
+                if constexpr (CM == CM_ROW || CM == CM_LAST) return el ? launch(std::true_type{}) : launch(std::false_type{});
+                else return launch(std::false_type{});
+            });
         };
-        if (gate) return gdt == QS_F32 ? go(IC<QS_F32>{}, std::true_type{}) : go(X, std::true_type{});
-        return gdt == QS_F32 ? go(IC<QS_F32>{}, std::false_type{}) : go(X, std::false_type{});
+        if (a.gate) return a.gdt == QS_F32 ? go(IC<QS_F32>{}, std::true_type{}) : go(X, std::true_type{});
+        return a.gdt == QS_F32 ? go(IC<QS_F32>{}, std::false_type{}) : go(X, std::false_type{});
     });
 }
 

@@ -7,6 +7,39 @@
 extern "C" {
 
 // ------------------------------------------------------------------------------------------------
+// the kernels of a reduction over [outer, C, inner], in the order reduce_plan tries them
+enum ReduceRoute {
+    RR_ALL,       // tensor-wise: reduce_all_kernel
+    RR_COLWALK,   // the statistics kernel's column walk (mean_outer_vec_kernel)
+    RR_ROWS,      // rows of >= 64 elements: reduce_rows_kernel
+    RR_FEWCOLS,   // few columns, many rows: two stages through the caller's workspace (reduce_fewcols_kernel + finish)
+    RR_COLS_VEC,  // reduce_cols_vec_kernel
+    RR_COLS,      // reduce_cols_kernel
+};
+struct ReducePlan {
+    ReduceRoute route;
+    int64_t few_nblk;   // RR_FEWCOLS: first-stage workgroups
+};
+
+static ReducePlan reduce_plan(bool per_channel, int64_t outer, int64_t C, int64_t inner, bool vec_ptr, ActSpec relu, const void* ws,
+                              size_t ws_bytes) {
+    const int64_t cols = C * inner;
+    if (!per_channel) return {RR_ALL, 0};
+    if (vec_ptr && inner % 8 == 0 && outer >= 16 && cols / 8 >= 64 * 1024 && relu.kind <= QS_ACT_RELU) return {RR_COLWALK, 0};
+    // (rows of 64..511 elements -- 14x14 maps -- go to the column kernels when they can use vector loads: a wave there reads
+    //  1 KiB of consecutive columns per row instead of one short ragged row)
+    if (inner >= 64 && C < 65536 && !(inner < 512 && vec_ptr && cols % 8 == 0)) return {RR_ROWS, 0};
+    const bool vec = vec_ptr && cols % 8 == 0;
+    if (vec && ws && cols <= kFewColsMaxCols && cols / 8 <= kBlock) {
+        const int64_t rows_per_iter = kBlock / (cols / 8);
+        static const int fewcols_cap = env_int("QS_FEWCOLS_BLOCKS", kFewColsMaxBlocks);
+        int64_t nblk = outer / (rows_per_iter * 32);     // >= 4 rounds of 8 loads per workgroup
+        nblk = std::min<int64_t>(std::max<int64_t>(nblk, 1), std::min(fewcols_cap, kFewColsMaxBlocks));
+        if (ws_bytes >= (size_t)(2 * nblk * cols) * sizeof(uint32_t) && outer >= 32 * rows_per_iter) return {RR_FEWCOLS, nblk};
+    }
+    return {vec ? RR_COLS_VEC : RR_COLS, 0};
+}
+
 static int reduce_impl(const void* x, float* out_a, float* out_b, bool minmax, int per_channel, int64_t outer, int64_t C,
                        int64_t inner, int xdt, hipStream_t s, bool accumulate = false, ActSpec relu = ActSpec{0, 0.f, 0.f}, void* ws = nullptr,
                        size_t ws_bytes = 0, int lines = 1) {
@@ -19,30 +52,17 @@ static int reduce_impl(const void* x, float* out_a, float* out_b, bool minmax, i
     uint32_t* omin = minmax ? (uint32_t*)out_a : nullptr;
     const int ib = (int)((nout + 255) / 256);
     const bool vec_ptr = aligned16(x);
-    // the few-columns route (channels_last activations, 2-d inputs) ends in a finish kernel that can write the final
-    // floats itself: a non-accumulating call then needs neither the key initialisation nor the key -> float launch
-    // (two launches instead of four for a per-channel min/max)
-    int64_t few_nblk = 0;
-    if (per_channel && numel > 0 && vec_ptr && ws) {
-        const int64_t cols = C * inner;
-        const bool rows_route = !minmax && inner % 8 == 0 && outer >= 16 && cols / 8 >= 64 * 1024 && relu.kind <= QS_ACT_RELU;   // column walk
-        const bool long_rows = inner >= 64 && C < 65536 && !(inner < 512 && cols % 8 == 0);                     // reduce_rows
-        if (!rows_route && !long_rows && cols % 8 == 0 && cols <= kFewColsMaxCols && cols / 8 <= kBlock) {
-            const int64_t rows_per_iter = kBlock / (cols / 8);
-            static const int fewcols_cap = env_int("QS_FEWCOLS_BLOCKS", kFewColsMaxBlocks);
-            int64_t nblk = outer / (rows_per_iter * 32);     // >= 4 rounds of 8 loads per workgroup
-            nblk = std::min<int64_t>(std::max<int64_t>(nblk, 1), std::min(fewcols_cap, kFewColsMaxBlocks));
-            if (ws_bytes >= (size_t)(2 * nblk * cols) * sizeof(uint32_t) && outer >= 32 * rows_per_iter) few_nblk = nblk;
-        }
-    }
-    const bool finalize = few_nblk > 0 && !accumulate;
+    const ReducePlan plan = reduce_plan(per_channel != 0, outer, C, inner, vec_ptr, relu, ws, ws_bytes);
+    // the few-columns route ends in a finish kernel that can write the final floats itself: a non-accumulating call then needs
+    // neither the key initialisation nor the key -> float launch (two launches instead of four for a per-channel min/max)
+    const bool finalize = plan.route == RR_FEWCOLS && !accumulate;
     if (!accumulate && !finalize) hipLaunchKernelGGL(keys_init_kernel, dim3(ib), dim3(256), 0, s, omax, omin, nout);
     if (numel > 0) {
         int st = with_dtype(xdt, [&](auto X) {
             constexpr int XD = decltype(X)::value;
             auto run = [&](auto MM) {
                 constexpr bool M = decltype(MM)::value != 0;
-                if (!per_channel) {
+                if (plan.route == RR_ALL) {
                     if (!vec_ptr) return (int)QS_ERR_ALIGN;
                     // 512-thread workgroups, at most 256 of them: every one ends with an atomic on the same word, which
                     // serialise at ~12 ns each (256x512 vs 512x256 threads: 256x64x56x56 bf16 23.6 -> 21.2 us,
@@ -54,7 +74,7 @@ static int reduce_impl(const void* x, float* out_a, float* out_b, bool minmax, i
                     if (grid > cap) grid = cap;
                     hipLaunchKernelGGL((reduce_all_kernel<XD, M, 512>), dim3(grid), dim3(512), 0, s, x, numel, omax, omin, relu,
                                        lines);
-                } else if (vec_ptr && inner % 8 == 0 && outer >= 16 && (C * inner) / 8 >= 64 * 1024 && relu.kind <= QS_ACT_RELU) {
+                } else if (plan.route == RR_COLWALK) {
                     // big tensors ([N, C, H*W] with >= 1024 waves of column groups): the column walk of the statistics
                     // kernel -- a lane keeps 8 adjacent columns and loops over N in registers, one atomic per wave and
                     // channel at the end -- streams at the statistics kernel's rate, where workgroups that hop from row
@@ -74,9 +94,7 @@ static int reduce_impl(const void* x, float* out_a, float* out_b, bool minmax, i
                         hipLaunchKernelGGL((mean_outer_vec_kernel<XD, XD, QS_MEAN_ROWS_IN_FLIGHT, 4>), dim3(blocks), dim3(64), 0, s, x,
                                            (void*)nullptr, (int64_t)1, outer, post, post, 0, (const int32_t*)nullptr, omax, (int64_t)1,
                                            inner, (uint32_t)C, lanes);
-                } else if (inner >= 64 && C < 65536 && !(inner < 512 && vec_ptr && (C * inner) % 8 == 0)) {
-                    // (rows of 64..511 elements -- 14x14 maps -- go to the column kernel below when it can use vector
-                    //  loads: a wave there reads 1 KiB of consecutive columns per row instead of one short ragged row)
+                } else if (plan.route == RR_ROWS) {
                     int64_t slices = (2048 + C - 1) / C;              // ~2048 workgroups, one atomic each
                     if (slices > (outer + 3) / 4) slices = (outer + 3) / 4;
                     if (slices < 1) slices = 1;
@@ -84,20 +102,18 @@ static int reduce_impl(const void* x, float* out_a, float* out_b, bool minmax, i
                     const int vec_ok = vec_ptr ? (inner % 8 == 0 ? 1 : 2) : 0;
                     hipLaunchKernelGGL((reduce_rows_kernel<XD, M>), dim3((int)C, (int)((outer + opb - 1) / opb)), dim3(kBlock),
                                        0, s, x, outer, (uint32_t)C, inner, vec_ok, opb, omax, omin, relu);
+                } else if (plan.route == RR_FEWCOLS) {
+                    // few columns, many rows: two stages through the caller's workspace, no atomics
+                    const int64_t cols = C * inner, nblk = plan.few_nblk;
+                    uint32_t* pmax = (uint32_t*)ws;
+                    uint32_t* pmin = pmax + nblk * cols;
+                    hipLaunchKernelGGL((reduce_fewcols_kernel<XD, M>), dim3((int)nblk), dim3(kBlock), 0, s, x, outer,
+                                       cols, pmax, pmin, relu);
+                    hipLaunchKernelGGL((reduce_fewcols_finish_kernel<M>), dim3((int)((C + 15) / 16)), dim3(kBlock), 0, s,
+                                       pmax, pmin, (int)nblk, cols, inner, omax, omin, (int)finalize);
                 } else {
                     const int64_t cols = C * inner;
-                    const bool vec = vec_ptr && (cols % 8 == 0);
-                    if (few_nblk > 0) {
-                        // few columns, many rows: two stages through the caller's workspace, no atomics
-                        const int64_t nblk = few_nblk;
-                        uint32_t* pmax = (uint32_t*)ws;
-                        uint32_t* pmin = pmax + nblk * cols;
-                        hipLaunchKernelGGL((reduce_fewcols_kernel<XD, M>), dim3((int)nblk), dim3(kBlock), 0, s, x, outer,
-                                           cols, pmax, pmin, relu);
-                        hipLaunchKernelGGL((reduce_fewcols_finish_kernel<M>), dim3((int)((C + 15) / 16)), dim3(kBlock), 0, s,
-                                           pmax, pmin, (int)nblk, cols, inner, omax, omin, (int)finalize);
-                        return launch_status();
-                    }
+                    const bool vec = plan.route == RR_COLS_VEC;
                     const int64_t per_block = vec ? (int64_t)kBlock * 8 : kBlock;
                     const int gx = (int)((cols + per_block - 1) / per_block);
                     int64_t gy = 1;

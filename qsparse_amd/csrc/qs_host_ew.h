@@ -35,69 +35,63 @@ inline int ew_widen() {
     return v;
 }
 
+// the channel mode of a kernel whose lanes take 4 elements at a time (the widening kernel, the STE backward): rows of 4k
+// elements -- 14x14 maps -- keep one channel per lane there as well
+inline int cm_4(const EwPlan& plan) { return plan.cm == CM_ELEM && plan.geo.inner % 4 == 0 ? CM_ROW : plan.cm; }
+
+// the kernel a forward launch takes: the widening one (float32 output, no codes, a 4-per-lane channel mode; QS_EW_WIDEN:
+// 0 off, 1 two-byte inputs only, 2 (default) fp32 inputs as well) in its channel mode, or else the 8-per-lane one in the plan's
+struct EwRoute {
+    bool widen;
+    int cm;
+};
+inline EwRoute ew_route(const EwPlan& plan, int xdt, int ydt, bool codes) {
+    const int cm4 = cm_4(plan);
+    if (ydt == QS_F32 && ew_widen() >= (xdt == QS_F32 ? 2 : 1) && !codes && cm4 != CM_ELEM) return {true, cm4};
+    return {false, plan.cm};
+}
+
+// channel mode -> compile-time constant (as with_dtype)
+template <typename F>
+int with_cm(int cm, F&& f) {
+    switch (cm) {
+        case CM_SCALAR: return f(IC<CM_SCALAR>{});
+        case CM_ROW: return f(IC<CM_ROW>{});
+        case CM_LAST: return f(IC<CM_LAST>{});
+    }
+    return f(IC<CM_ELEM>{});
+}
+
 // `elide`: skip the loads of lanes whose elements are all pruned (qs_elementwise.h, "Mask-aware traffic elision");
 // only meaningful for ops that carry a channel mask, in the per-channel modes
 template <typename Op, int XDT, int YDT, bool ELIDE>
 int launch_ew_impl(const Op& op, const EwPlan& plan, bool param_per_channel, const void* x, void* y, int32_t* codes,
                    hipStream_t s) {
     constexpr bool NT = QS_EW_NT != 0;
-    constexpr int U = ELIDE ? QS_EW_UNROLL_ELIDE : QS_EW_UNROLL;
-    if constexpr (YDT == QS_F32) {   // QS_EW_WIDEN: 0 off, 1 two-byte inputs only, 2 (default) fp32 inputs as well
-        // (its lanes take 4 elements at a time, so rows of 4k elements -- 14x14 maps -- keep one channel per lane as well)
-        const int cm_w = (plan.cm == CM_ELEM && plan.geo.inner % 4 == 0) ? CM_ROW : plan.cm;
-        if (ew_widen() >= (XDT == QS_F32 ? 2 : 1) && !codes && cm_w != CM_ELEM) {
-            const int64_t waves = (plan.geo.ngroups * 8 + 511) / 512;
-            const int gridw = (int)std::max<int64_t>(1, (waves + kWidenBlock / 64 - 1) / (kWidenBlock / 64));   // < 8 elements: tail only
-            if (cm_w == CM_SCALAR) {
-                if constexpr (!ELIDE)
-                    hipLaunchKernelGGL((ew_widen_kernel<Op, XDT, CM_SCALAR, false, NT>), dim3(gridw), dim3(kWidenBlock), 0, s, op,
+    const EwRoute r = ew_route(plan, XDT, YDT, codes != nullptr);
+    return with_cm(r.cm, [&](auto M) {
+        constexpr int CM = decltype(M)::value;
+        auto go = [&](auto P) {
+            constexpr bool PPC = decltype(P)::value;
+            if constexpr (YDT == QS_F32 && CM != CM_ELEM) {
+                if (r.widen) {
+                    const int64_t waves = (plan.geo.ngroups * 8 + 511) / 512;
+                    const int gridw = (int)std::max<int64_t>(1, (waves + kWidenBlock / 64 - 1) / (kWidenBlock / 64));   // < 8 elements: tail only
+                    hipLaunchKernelGGL((ew_widen_kernel<Op, XDT, CM, PPC, NT, ELIDE>), dim3(gridw), dim3(kWidenBlock), 0, s, op,
                                        plan.geo, x, (float*)y);
-            } else if (cm_w == CM_LAST)
-                hipLaunchKernelGGL((ew_widen_kernel<Op, XDT, CM_LAST, false, NT, ELIDE>), dim3(gridw), dim3(kWidenBlock), 0, s, op,
-                                   plan.geo, x, (float*)y);
-            else if (param_per_channel)
-                hipLaunchKernelGGL((ew_widen_kernel<Op, XDT, CM_ROW, true, NT, ELIDE>), dim3(gridw), dim3(kWidenBlock), 0, s, op,
-                                   plan.geo, x, (float*)y);
-            else
-                hipLaunchKernelGGL((ew_widen_kernel<Op, XDT, CM_ROW, false, NT, ELIDE>), dim3(gridw), dim3(kWidenBlock), 0, s, op,
-                                   plan.geo, x, (float*)y);
-            return launch_status();
-        }
-    }
-    const int grid = grid_for(plan.geo.ngroups, U);
-    switch (plan.cm) {
-        case CM_SCALAR:
-            if constexpr (!ELIDE) {
-                constexpr int US = QS_EW_UNROLL_SCALAR;
-                hipLaunchKernelGGL((ew_kernel<Op, XDT, YDT, CM_SCALAR, false, NT, US>), dim3(grid_for(plan.geo.ngroups, US)),
-                                   dim3(kBlock), 0, s, op, plan.geo, x, y, codes);
+                    return launch_status();
+                }
             }
-            break;
-        case CM_ROW: {
-            constexpr int UR = ELIDE ? QS_EW_UNROLL_ELIDE : QS_EW_UNROLL_ROW;
-            const int grid_r = grid_for(plan.geo.ngroups, UR);
-            if (param_per_channel)
-                hipLaunchKernelGGL((ew_kernel<Op, XDT, YDT, CM_ROW, true, NT, UR, ELIDE>), dim3(grid_r), dim3(kBlock), 0, s, op,
-                                   plan.geo, x, y, codes);
-            else
-                hipLaunchKernelGGL((ew_kernel<Op, XDT, YDT, CM_ROW, false, NT, UR, ELIDE>), dim3(grid_r), dim3(kBlock), 0, s, op,
-                                   plan.geo, x, y, codes);
-            break;
-        }
-        case CM_LAST:
-            hipLaunchKernelGGL((ew_kernel<Op, XDT, YDT, CM_LAST, false, NT, U, ELIDE>), dim3(grid), dim3(kBlock), 0, s, op,
-                               plan.geo, x, y, codes);
-            break;
-        default:
-            if (param_per_channel)
-                hipLaunchKernelGGL((ew_kernel<Op, XDT, YDT, CM_ELEM, true, NT, 1, ELIDE>), dim3(grid_for(plan.geo.ngroups, 1)),
-                                   dim3(kBlock), 0, s, op, plan.geo, x, y, codes);
-            else
-                hipLaunchKernelGGL((ew_kernel<Op, XDT, YDT, CM_ELEM, false, NT, 1, ELIDE>), dim3(grid_for(plan.geo.ngroups, 1)),
-                                   dim3(kBlock), 0, s, op, plan.geo, x, y, codes);
-            break;
-    }
-    return launch_status();
+            constexpr int U =   // groups per lane
+                CM == CM_ELEM ? 1 : ELIDE ? QS_EW_UNROLL_ELIDE : CM == CM_SCALAR ? QS_EW_UNROLL_SCALAR : CM == CM_ROW ? QS_EW_UNROLL_ROW : QS_EW_UNROLL;
+            hipLaunchKernelGGL((ew_kernel<Op, XDT, YDT, CM, PPC, NT, U, ELIDE>), dim3(grid_for(plan.geo.ngroups, U)), dim3(kBlock),
+                               0, s, op, plan.geo, x, y, codes);
+            return launch_status();
+        };
+        if constexpr (ELIDE && CM == CM_SCALAR) return launch_status();   // (never asked: launch_ew elides per channel only)
+        else if constexpr (CM == CM_ROW || CM == CM_ELEM) return param_per_channel ? go(std::true_type{}) : go(std::false_type{});
+        else return go(std::false_type{});
+    });
 }
 
 template <typename Op, int XDT, int YDT>
@@ -117,20 +111,36 @@ int check_param(const float* p, int64_t nparam, int64_t C) {
     return QS_OK;
 }
 
+// the argument checks shared by the STE backward's two front ends (api_quant_bwd.hip: the ReLU family, or its gate bitmap;
+// api_quant_bwd_act.hip: the caller's activation at act_x) and the plan of their launch.  `x` is the input the backward reads,
+// `gate` the bitmap that may replace it; `g2_gate`: a second gradient stream (g2) is served by the gate bitmap kernels only.
+// QS_OK with plan->geo.numel == 0: nothing to launch.
+inline int ste_bwd_check(const qs_ste_relu_bwd_args& a, const void* x, const uint8_t* gate, bool g2_gate, EwPlan* plan) {
+    if ((!a.g && !a.g2) || (!x && !gate) || !a.gx) return QS_ERR_ARG;
+    if (!dt_ok(a.gdt) || !dt_ok(a.xdt) || !(a.gdt == QS_F32 || a.gdt == a.xdt)) return QS_ERR_DTYPE;
+    if (a.g2 && ((g2_gate && !gate) || a.gdt != QS_F32 || (a.g2dt != QS_BF16 && a.g2dt != QS_F16))) return QS_ERR_DTYPE;
+    if ((a.g && !aligned16(a.g)) || (!gate && !aligned16(x)) || !aligned16(a.gx) || (a.g2 && !aligned16(a.g2))) return QS_ERR_ALIGN;
+    // the riders of the all-fp32 kernel form (BwdRiders, qs_elementwise.h)
+    if (a.g3 && (!a.g2 || a.gdt != QS_F32 || a.xdt != QS_F32)) return QS_ERR_ARG;
+    if (a.gx_image && (a.gdt != QS_F32 || a.xdt != QS_F32 || (a.gx_image_dt != QS_BF16 && a.gx_image_dt != QS_F16))) return QS_ERR_DTYPE;
+    if ((a.g3 && !aligned16(a.g3)) || (a.gx_image && !aligned16(a.gx_image))) return QS_ERR_ALIGN;
+    const int st = check_param(a.step, a.nstep, a.C);
+    if (st) return st;
+    const bool ppc = a.nstep > 1;
+    return plan_ew(a.outer, a.C, a.inner, ppc || a.chan_mask != nullptr, plan, !ppc && aligned8(a.chan_mask));
+}
+
 }  // namespace
 
 namespace {
 // (shared by the forward units api_quant_fwd.hip / api_quant_fwd2.hip)
-// the image of a quantizer's float32 output is written by the gate-recording widening kernels only (ew_widen_kernel<GateOp<..>>):
-// float32 output, no codes, a gate bitmap, and a geometry those kernels serve (launch_ew_impl's own conditions)
-// (the same kernels write relu(x) back: xback_out)
+// the image of a quantizer's float32 output is written by the gate-recording widening kernels only (ew_widen_kernel<GateOp<..>>),
+// so it needs a gate bitmap and the widening route (ew_route) for the launch's plan (the same kernels write relu(x) back: xback_out)
 inline bool widen_route_ok(int64_t outer, int64_t C, int64_t inner, bool ppc, const uint8_t* chan_mask, const int32_t* codes,
                     const uint8_t* gate_out, int xdt, int ydt) {
-    if (!gate_out || codes || ydt != QS_F32) return false;
     EwPlan plan;
-    if (plan_ew(outer, C, inner, ppc || chan_mask != nullptr, &plan, !ppc && aligned8(chan_mask)) != QS_OK) return false;
-    const int cm_w = (plan.cm == CM_ELEM && plan.geo.inner % 4 == 0) ? CM_ROW : plan.cm;
-    return ew_widen() >= (xdt == QS_F32 ? 2 : 1) && cm_w != CM_ELEM;
+    return gate_out && plan_ew(outer, C, inner, ppc || chan_mask != nullptr, &plan, !ppc && aligned8(chan_mask)) == QS_OK &&
+           ew_route(plan, xdt, ydt, codes != nullptr).widen;
 }
 inline bool image_route_ok(int64_t outer, int64_t C, int64_t inner, bool ppc, const uint8_t* chan_mask, const int32_t* codes,
                     const uint8_t* gate_out, int xdt, int ydt, int imgdt, const void* image_out) {

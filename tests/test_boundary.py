@@ -5,6 +5,7 @@
 import ctypes
 import os
 import re
+import subprocess
 
 import pytest
 import torch
@@ -28,6 +29,10 @@ def test_library_exports_every_declared_symbol():
     assert len(declared) >= 20
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/qsparse_hip.h but not exported"
+    # and nothing else: kernel stubs and handles (the launch keys), C++ helpers and __hip_cuid_* stay local (csrc/exports.map)
+    nm = subprocess.run(["nm", "-D", "--defined-only", _hip.lib_path()], capture_output=True, text=True, check=True).stdout
+    exported = sorted(line.split()[-1] for line in nm.splitlines() if line.strip())
+    assert exported == declared, f"exports beyond the header: {sorted(set(exported) - set(declared))[:10]}"
     assert sorted(_hip.SIGNATURES) == declared, "ctypes prototypes out of sync with the header"
     lib.qs_version.restype = ctypes.c_int
     lib.qs_abi_floor.restype = ctypes.c_int

@@ -829,18 +829,29 @@ class _ActGrad(torch.autograd.Function):
 
 def act_rider(act, x):
     """`act_backward`: the nn.GELU (erf form) `act` in front of a site keeps ATen's forward, evaluated here under no_grad, and hands its
-    backward to the site (`_SiteStep(act_out=)`, qs_site_bwd_args::act_x; `_ActGrad` elsewhere).  Returns h = act(x) detached from the
-    graph, or None when the site should run `act` as an ordinary module (not a GELU, option off, nothing to differentiate, float16 --
-    see `_FastPair.try_run` --, a layout the kernels do not address in place)."""
+    backward to the site (`_SiteStep(act_out=)`, qs_site_bwd_args::act_x; `_ActGrad` elsewhere).  Returns (h, rides): h = act(x)
+    detached from the graph, or None when the site should run `act` as an ordinary module (not a GELU, option off, nothing to
+    differentiate, float16 -- see `_FastPair.try_run` --); rides: h has x's strides, dtype and alignment, so the kernels can address
+    both in place.  A GELU evaluated for a layout the kernels do not take is still handed back (the caller puts it into the graph with
+    `_ActGrad.apply(x, h)`): the activation runs once per forward on every route."""
     if not (type(act) is nn.GELU and getattr(act, "approximate", "none") == "none" and isinstance(x, torch.Tensor) and x.is_cuda
             and x.requires_grad and torch.is_grad_enabled() and get_option("act_backward") and x.data_ptr() % 16 == 0
             and x.dtype in (torch.float32, torch.bfloat16) and _hip.dense_any_order(x)):
-        return None
+        return None, False
     with torch.no_grad():
         h = act(x)           # ATen's own forward; the graph sees one node, x -> y, whose backward knows the GELU
-    if h.stride() == x.stride() and h.dtype == x.dtype and h.data_ptr() % 16 == 0:
-        return h
-    return None
+    return h, h.stride() == x.stride() and h.dtype == x.dtype and h.data_ptr() % 16 == 0
+
+
+def _act_once(act, x):
+    """(h, act_in): `act` applied to x exactly once -- through `act_rider` when it takes the GELU (act_in = x: h is detached and the
+    site's backward applies the GELU's; a rejected layout goes back into the graph through `_ActGrad`), else as the module"""
+    h, rides = act_rider(act, x)
+    if h is None:
+        return act(x), None
+    if rides:
+        return h, x
+    return _ActGrad.apply(x, h), None
 
 
 def fused_prune_quantize(p: PruneLayer, q: QuantizeLayer, h: torch.Tensor, pre_relu=False, act_in=None) -> torch.Tensor:
@@ -1173,6 +1184,17 @@ def _hooked(*modules) -> bool:
 # the host mirrors notice) takes the full path, which re-arms when it finds the steady state again.
 # ----------------------------------------------------------------------------------------------------------------------
 _MISS = object()
+
+
+class _ActMiss:
+    """a miss of the fold-3 fast path found after the activation ran (its output is not like the one the plan was built for): the
+    full path continues with that output instead of evaluating the activation again (a random one would draw twice)"""
+    __slots__ = ("h", "act_in")
+
+    def __init__(self, h, act_in):
+        self.h, self.act_in = h, act_in
+
+
 _FAST_PATH = os.environ.get("QS_NO_FAST_PATH", "0") != "1"      # (development switch for A/B measurements)
 
 
@@ -1196,7 +1218,7 @@ def _pair_config(act, p, q, cb, qc):
 
 class _FastPair:
     __slots__ = ("epoch", "mods", "hooks", "config", "xsig", "state", "ptrs", "plan", "pre_relu", "fold", "max_schedule", "C",
-                 "graph_safe", "notch", "k_of", "autocast", "dact")
+                 "graph_safe", "notch", "k_of", "autocast", "hsig")
 
     def __deepcopy__(self, memo):        # raw pointers and object identities: a copied network arms its own
         return None
@@ -1208,9 +1230,14 @@ class _FastPair:
     def _xsig(x):
         return (x.shape, x.dtype, x.device, x.stride(), x.data_ptr() % 16, x.requires_grad, x.is_leaf, x._is_view())
 
+    @staticmethod
+    def _hsig(h):
+        return (h.shape, h.dtype, h.stride(), h.device, h.data_ptr() % 16, h.requires_grad)
+
     @classmethod
-    def arm(cls, seq, x, fold, handle):
-        """called by the full path after a step; returns a fast path for the following steps, or None"""
+    def arm(cls, seq, x, fold, handle, h=None):
+        """called by the full path after a step; returns a fast path for the following steps, or None.  h: for fold 3, the
+        activation's output the site ran on (the plan was built for it)"""
         inner, q = seq[0], seq[1]
         act, p = inner[0], inner[1]
         cb, qc = p.callback, q.callback
@@ -1220,7 +1247,7 @@ class _FastPair:
         # ATen in front of the site); for 0 and 3 `handle` is 0 or the identity fold (`identity_fold_handle`)
         if type(act) is nn.Identity:
             fold = 0
-        elif not fold:
+        elif not fold or (fold == 3 and not isinstance(h, torch.Tensor)):
             return None
         if get_option("log_during_train") or not (seq.training and inner.training):
             return None
@@ -1247,9 +1274,8 @@ class _FastPair:
         f.graph_safe, f.notch = bool(get_option("graph_safe")), (1 if qc.flip_axis else 0)
         f.k_of = {}
         f.autocast = cls._autocast()         # (the identity fold is chosen per autocast state)
-        # `act_backward`: an nn.GELU (erf form) in front of the site -- its forward stays ATen's pass, its backward rides in the site's
-        # backward kernel (qs_site_bwd_args::act_x)
-        f.dact = fold == 3 and type(act) is nn.GELU and getattr(act, "approximate", "none") == "none"
+        # fold 3: the plan's geometry is that of the activation's OUTPUT, which the module may change while x stays the same
+        f.hsig = cls._hsig(h) if fold == 3 else None
         return f
 
     @staticmethod
@@ -1258,7 +1284,7 @@ class _FastPair:
         return (on, torch.get_autocast_dtype("cuda") if on else None)
 
     def try_run(self, seq, x):
-        """the step, or _MISS (nothing has been touched then)"""
+        """the step, _MISS (nothing has been touched then) or an `_ActMiss` (only the activation in front of the site ran)"""
         mods = seq._modules
         inner, q = mods.get("0"), mods.get("1")
         if inner is not self.mods[0] or q is not self.mods[3] or self.epoch != _options_epoch[0]:
@@ -1347,10 +1373,12 @@ class _FastPair:
             #  and in its tail block -- 2 of 20,000 (dy, x) pairs, tools/probes/probe_gelu_tail.py; the kernel here equals the full-block
             #  result everywhere, so a tensor whose size is not a multiple of ATen's block would differ from the module-by-module route.
             #  bf16 and float32 are one function of (dy, x) in ATen and here.)
-            h = act_rider(act, x) if self.dact else None
-            if h is not None:
-                return site(h, x)
-            return site(act(x))          # an activation the kernels do not fold: ATen applies it, the site follows
+            # `act_backward`: an nn.GELU (erf form) in front of the site -- its forward stays ATen's pass, its backward rides in the
+            # site's backward kernel (qs_site_bwd_args::act_x); any other activation the kernels do not fold: ATen applies it
+            h, act_in = _act_once(act, x)
+            if self._hsig(h) != self.hsig:
+                return _ActMiss(h, act_in)   # (before `site` advances a host mirror: the full path builds the plan for this h)
+            return site(h, act_in)
         return site(x)
 
 
@@ -1361,31 +1389,35 @@ class FusedPruneQuantize(nn.Sequential):
     @_hip.keeps_layout
     def forward(self, x):
         fast = self.__dict__.get("_qs_fast")
+        ran = None
         if fast is not None:
             out = fast.try_run(self, x)
-            if out is not _MISS:
+            if out is not _MISS and type(out) is not _ActMiss:
                 return out
             self.__dict__["_qs_fast"] = None
+            if out is not _MISS:
+                ran = out                # (the activation already ran: hooks, options and configuration are unchanged)
         inner, q = self[0], self[1]
         act, p = inner[0], inner[1]
-        if _hooked(inner, act, p, q, p.callback, q.callback):
-            return q(inner(x))
-        # a plain, out-of-place nn.ReLU in front of an active quantizer is folded into the kernels: relu(x) is
-        # never materialised (statistics, apply and backward read x itself); the gate of its backward rides in
-        # the fused backward kernel
-        fold, handle = _foldable_relu(act, x)
-        q.__dict__["_qs_last_route"] = None
-        if fold and q.is_active() and isinstance(x, torch.Tensor) and _eligible(p, q, x):
-            if fold == 2:
-                out = _with_owned_relu(x, lambda h: fused_prune_quantize(p, q, h, pre_relu=handle), handle)
-            else:
-                out = fused_prune_quantize(p, q, x, pre_relu=handle)
-            self.__dict__["_qs_fast"] = _FastPair.arm(self, x, fold, handle)
-            return out
-        h = act_rider(act, x) if q.is_active() else None
-        act_in = x if h is not None else None
-        if h is None:
-            h = act(x)
+        if ran is not None:
+            q.__dict__["_qs_last_route"] = None
+            h, act_in = ran.h, ran.act_in
+        else:
+            if _hooked(inner, act, p, q, p.callback, q.callback):
+                return q(inner(x))
+            # a plain, out-of-place nn.ReLU in front of an active quantizer is folded into the kernels: relu(x) is
+            # never materialised (statistics, apply and backward read x itself); the gate of its backward rides in
+            # the fused backward kernel
+            fold, handle = _foldable_relu(act, x)
+            q.__dict__["_qs_last_route"] = None
+            if fold and q.is_active() and isinstance(x, torch.Tensor) and _eligible(p, q, x):
+                if fold == 2:
+                    out = _with_owned_relu(x, lambda h: fused_prune_quantize(p, q, h, pre_relu=handle), handle)
+                else:
+                    out = fused_prune_quantize(p, q, x, pre_relu=handle)
+                self.__dict__["_qs_fast"] = _FastPair.arm(self, x, fold, handle)
+                return out
+            h, act_in = _act_once(act, x) if q.is_active() else (act(x), None)
         if _eligible(p, q, h):
             # (under autocast an active site folds the identity: it then writes its image like a site behind a foldable activation)
             ident = identity_fold_handle(h) if q.is_active() else 0
@@ -1393,7 +1425,7 @@ class FusedPruneQuantize(nn.Sequential):
             if h is x:
                 self.__dict__["_qs_fast"] = _FastPair.arm(self, x, 0, ident)
             elif isinstance(h, torch.Tensor) and not getattr(act, "inplace", False):
-                self.__dict__["_qs_fast"] = _FastPair.arm(self, x, 3, ident)
+                self.__dict__["_qs_fast"] = _FastPair.arm(self, x, 3, ident, h)
             return out
         return q(p(h if act_in is None else _ActGrad.apply(act_in, h)))
 
@@ -1452,9 +1484,9 @@ class FusedActQuantize(nn.Sequential):
             return fused_relu_quantize(q, x, handle)
         if type(act) is nn.GELU and q.is_active() and _quantizer_foldable(q, x) and not _hooked(act, q, q.callback):
             # `act_backward`: ATen's GELU forward under no_grad, its backward in the quantizer's backward kernel (`_QuantStep(act_out=)`)
-            h = act_rider(act, x)
+            h, rides = act_rider(act, x)
             if h is not None:
-                y = q.single_call_step(h, q._steps.read(q._n_updates), act_in=x) if q.initted else None
+                y = q.single_call_step(h, q._steps.read(q._n_updates), act_in=x) if (rides and q.initted) else None
                 return y if y is not None else q(_ActGrad.apply(x, h))
         return q(act(x))
 

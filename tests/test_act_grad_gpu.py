@@ -14,11 +14,13 @@ import torch
 import torch.nn as nn
 
 import qsparse_amd as qs
+import site_plan_guard
 from golden_io import same
 from qsparse_amd import _hip, fused
 from qsparse_amd.fused import fuse_prune_quantize_pairs
 
 pytestmark = pytest.mark.gpu
+_site_plan_guard = site_plan_guard.fixture()      # every composite site launch is checked against its plan first
 qs.set_qsparse_options(log_on_created=False, log_during_train=False)
 DEV = "cuda"
 INF = float("inf")

@@ -15,11 +15,13 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import qsparse_amd as qs
+import site_plan_guard
 from golden_io import same
 from qsparse_amd import _hip
 from qsparse_amd.fused import AutocastImageTensor, fuse_prune_quantize_pairs
 
 pytestmark = pytest.mark.gpu
+_site_plan_guard = site_plan_guard.fixture()      # every composite site launch is checked against its plan first
 DEV = "cuda"
 qs.set_qsparse_options(log_on_created=False, log_during_train=False)
 

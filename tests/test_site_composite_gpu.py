@@ -13,11 +13,13 @@ import torch
 import torch.nn as nn
 
 import qsparse_amd as qs
+import site_plan_guard
 from golden_io import same
 from oracle import qs_oracle as O
 from qsparse_amd import _hip, fused
 
 pytestmark = pytest.mark.gpu
+_site_plan_guard = site_plan_guard.fixture()      # every composite site launch is checked against its plan first
 
 START, INTERVAL, REPS, TIMEOUT = 2, 2, 2, 3
 STEPS = 9

@@ -21,10 +21,13 @@ import torch.nn.functional as F
 
 import qsparse_amd as qs
 from examples.models import convert_pq, resnet18, resnet50
+import site_plan_guard
 from golden_io import same
 from oracle import qs_oracle as O
 from qsparse_amd.quantize import QuantizeLayer
 from qsparse_amd.sparse import PruneLayer
+
+_site_plan_guard = site_plan_guard.fixture()      # every composite site launch is checked against its plan first
 
 qs.set_qsparse_options(log_on_created=False, log_during_train=False)
 

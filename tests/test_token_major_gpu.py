@@ -14,12 +14,14 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import qsparse_amd as qs
+import site_plan_guard
 from golden_io import same
 from oracle import qs_oracle as O
 from qsparse_amd import _hip, fused, sparse
 from qsparse_amd.fused import fuse_prune_quantize_pairs
 
 pytestmark = pytest.mark.gpu
+_site_plan_guard = site_plan_guard.fixture()      # every composite site launch is checked against its plan first
 qs.set_qsparse_options(log_on_created=False, log_during_train=False)
 START, INTERVAL, REPS, TIMEOUT, STEPS = 2, 2, 2, 3, 9
 FREEZE = dict(mask_refresh_interval=1, stop_mask_refresh=3)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define QS_ABI_VERSION 26
+#define QS_ABI_VERSION 27
 /* ABI compatibility (from v25 on).
  *   - Every positional prototype in this header is FROZEN as of v25: a later version never changes the argument list of an
  *     existing symbol.  qs_abi_floor() returns the oldest version whose prototypes this library still honours (25); a binding
@@ -821,6 +821,41 @@ int qs_mailbox_publish(const float* rec, int64_t n, void* const* boxes, int worl
 int qs_mailbox_wait(void* box, int world, int64_t n, uint32_t step, int32_t* status, uint32_t max_spins, const float** records,
                     qs_stream_t stream);
 int qs_records_max(const float* records, int world, int64_t n, float* out, qs_stream_t stream);
+
+/* ---- MX block-scaled quantizer (OCP Microscaling Formats v1.0), ABI v27 ------------------------------------------------------
+ * The tensor is CONTIGUOUS memory seen as [outer, n, inner]; a block is 32 consecutive elements along `n` (the last block of a
+ * line is shorter when n % 32 != 0), nb = ceil(n / 32) blocks per line.  Per block, on the float32 widening of x:
+ *   amax = max |x_i|.  NaN or Inf: every y_i of the block is NaN, the scale byte 0xFF, every code 0.
+ *   e = clamp(floor(log2(amax)) - emax, -127, 127), -127 for amax == 0 (the exponent is taken from the bits, float32 subnormals
+ *   included);  scale byte = e + 127 (E8M0);  X = 2^e
+ *   q_i = x_i / X rounded to nearest, ties to even, onto the element format's value grid (its subnormals included), then clamped
+ *   to +- the largest normal; a zero keeps its sign; no format's own NaN / Inf code is ever produced
+ *   y_i = q_i * X (exact in float32, subnormals kept), rounded once to ydt
+ *   codes[i] (nullable; uint8, x's geometry) = the format's encoding of q_i -- sign, exponent, mantissa -- in the low bits
+ *   (QS_MX_FP8_E4M3 / _E5M2: the bytes of OCP e4m3fn / e5m2);  scales (nullable; uint8 [outer, nb, inner]) = the scale bytes.
+ * ydt is QS_F32 or xdt.  inner == 1 selects the innermost-axis kernels: with n % 32 == 0 and x, y (and codes: 8 bytes) 16-byte
+ * aligned the 16-bytes-per-lane form, otherwise one element per lane; inner > 1 the strided-axis kernel (lanes along `inner`).
+ * x, y need the alignment of their element type only (QS_ERR_ALIGN otherwise).  One pass over the data, no workspace. */
+enum qs_mx_format { QS_MX_FP8_E4M3 = 0, QS_MX_FP8_E5M2 = 1, QS_MX_FP6_E2M3 = 2, QS_MX_FP6_E3M2 = 3, QS_MX_FP4_E2M1 = 4 };
+#define QS_MX_BLOCK 32
+typedef struct qs_mx_quant_args {
+    uint32_t struct_size;        /* sizeof(qs_mx_quant_args) as the caller compiled it */
+    int32_t format;              /* enum qs_mx_format */
+    const void* x;
+    void* y;
+    uint8_t* codes;              /* nullable */
+    uint8_t* scales;             /* nullable */
+    int32_t xdt, ydt;
+    int64_t outer, n, inner;
+    qs_stream_t stream;
+} qs_mx_quant_args;
+int qs_mx_quant_fwd_v(const qs_mx_quant_args* args);
+/* the kernel qs_mx_quant_fwd_v launches for these operands, decided by the code that launches it and without enqueuing anything:
+ * one of QS_MX_ROUTE_*, 0 for an empty tensor, or the QS_ERR_* the call would return */
+#define QS_MX_ROUTE_INNER_VEC 1
+#define QS_MX_ROUTE_INNER_PLAIN 2
+#define QS_MX_ROUTE_STRIDED 3
+int qs_mx_quant_route(const qs_mx_quant_args* args);
 
 #ifdef __cplusplus
 }

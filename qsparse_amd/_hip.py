@@ -18,7 +18,7 @@ MEAN_ABS, MEAN_L0, MEAN_RELU = 1, 2, 4
 WS_KTH_VALUE = 1
 MAX_DIMS = 6
 
-ABI_VERSION = 26          # QS_ABI_VERSION of include/qsparse_hip.h this binding was written against: the version it NEEDS
+ABI_VERSION = 27          # QS_ABI_VERSION of include/qsparse_hip.h this binding was written against: the version it NEEDS
 _LIB_NAME = "libqsparse_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 
@@ -93,6 +93,8 @@ SIGNATURES = {
     "qs_quant_ste_relu_bwd_v": (c_int, [_P]),
     "qs_stats_pack": (c_int, [_P, _I, _P, _L, _L, _P, _P]),
     "qs_stats_combine": (c_int, [_P, _I, _L, _P, _P, _L, _P]),
+    "qs_mx_quant_fwd_v": (c_int, [_P]),
+    "qs_mx_quant_route": (c_int, [_P]),
 }
 
 
@@ -162,6 +164,13 @@ class SteReluBwdArgs(ctypes.Structure):
                 ("elide_masked", c_int32), ("act", c_int32), ("g2", c_void_p), ("stream", c_void_p),
                 ("g3", c_void_p), ("gx_image", c_void_p), ("gx_image_dt", c_int32), ("reserved0", c_int32),
                 ("act_x", c_void_p), ("act_x_kind", c_int32), ("reserved1", c_int32)]         # v26
+
+
+class MxQuantArgs(ctypes.Structure):
+    """`qs_mx_quant_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("format", c_int32), ("x", c_void_p), ("y", c_void_p), ("codes", c_void_p),
+                ("scales", c_void_p), ("xdt", c_int32), ("ydt", c_int32), ("outer", c_int64), ("n", c_int64), ("inner", c_int64),
+                ("stream", c_void_p)]
 
 
 class MultiRow(ctypes.Structure):
@@ -736,6 +745,66 @@ def quant_fwd(kind: str, x: torch.Tensor, param, channel_index: int, qdtype: tor
     if xb is not None:
         xback["done"] = True
     return (y, codes, gate) if want_gate else (y, codes)
+
+
+MX_FORMATS = ("mxfp8_e4m3", "mxfp8_e5m2", "mxfp6_e2m3", "mxfp6_e3m2", "mxfp4_e2m1")      # enum qs_mx_format, in order
+MX_BLOCK = 32
+MX_ROUTE_INNER_VEC, MX_ROUTE_INNER_PLAIN, MX_ROUTE_STRIDED = 1, 2, 3
+mx_last_route = None          # the QS_MX_ROUTE_* of the last `mx_quant_fwd` launch (None: an empty tensor), for tests and tools
+
+
+def _mx_memory_view(x: torch.Tensor, block_dim: int):
+    """(xm, dim in xm, like, copied): the dense tensor the MX kernels address and the index of the block axis in it.  A contiguous
+    tensor is used as it lies (whatever its base alignment), a dense channels_last one through its memory-order view; any other
+    layout goes through a contiguous copy"""
+    if x.is_contiguous():
+        return x, block_dim, x, False
+    if x.dim() in (4, 5):
+        fmt = torch.channels_last if x.dim() == 4 else torch.channels_last_3d
+        if x.is_contiguous(memory_format=fmt):
+            perm = (0, 2, 3, 1) if x.dim() == 4 else (0, 2, 3, 4, 1)
+            return x.permute(perm), perm.index(block_dim), x, False
+    xc = x.contiguous()
+    return xc, block_dim, xc, True
+
+
+def mx_quant_fwd(x: torch.Tensor, fmt: str, block_dim: int, out_dtype: torch.dtype = torch.float32, want_codes: bool = False):
+    """MX block-scaled quantization of a GPU tensor (qs_mx_quant_fwd_v): returns (y, codes|None, scales|None) -- `codes` uint8 of
+    x's shape, `scales` uint8 (E8M0) of x's shape with `block_dim` shrunk to ceil(n / 32) -- from ONE launch."""
+    global mx_last_route
+    lib = load()
+    block_dim = block_dim % x.dim()
+    xm, dim, like, copied = _mx_memory_view(x, block_dim)
+    outer, n, inner, numel = split3(xm.shape, dim)
+    y = torch.empty_like(like, dtype=out_dtype)
+    codes = torch.empty_like(like, dtype=torch.uint8) if want_codes else None
+    scales = None
+    if want_codes:
+        sshape = list(xm.shape)
+        sshape[dim] = (n + MX_BLOCK - 1) // MX_BLOCK
+        scales = torch.empty(sshape, dtype=torch.uint8, device=x.device)
+    mx_last_route = None
+    if numel:
+        a = MxQuantArgs()
+        a.struct_size = ctypes.sizeof(a)
+        a.format = MX_FORMATS.index(fmt)
+        a.x, a.y, a.codes, a.scales = _ptr(xm), _ptr(y), _ptr(codes), _ptr(scales)
+        a.xdt, a.ydt = dt(xm), _DT[out_dtype]
+        a.outer, a.n, a.inner = outer, n, inner
+        a.stream = _stream(xm)
+        route = lib.qs_mx_quant_route(ctypes.byref(a))
+        with _timed(f"mx_quant_fwd[{route}]", xm, y, codes, scales):
+            st = lib.qs_mx_quant_fwd_v(ctypes.byref(a))
+        _check(st, "qs_mx_quant_fwd_v")
+        mx_last_route = route
+    if scales is not None and xm is not like:         # (memory-order view of a channels_last tensor: back to the logical dim order)
+        inv = [0] * xm.dim()
+        for i, p in enumerate((0, 2, 3, 1) if xm.dim() == 4 else (0, 2, 3, 4, 1)):
+            inv[p] = i
+        scales = scales.permute(inv)
+    if copied:
+        y = laid_out_like(y, x)
+    return y, codes, scales
 
 
 def quant_line_fwd(x: torch.Tensor, lines: torch.Tensor, bits: int, channel_index: int, float_zero_point: bool,

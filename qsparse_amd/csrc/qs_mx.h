@@ -1,0 +1,240 @@
+// MX block-scaled quantizer kernels (OCP Microscaling Formats v1.0; include/qsparse_hip.h, "MX block-scaled quantizer").
+//
+// One block = 32 consecutive elements along one axis sharing a power-of-two scale X = 2^e.  Everything is float32 bit and
+// exponent arithmetic, no division, no transcendental:
+//   e      from the exponent field of the block's abs-max (integer maximum of |x| bit patterns: a NaN sorts above Inf above every
+//          finite value, so a non-finite block is recognised from the maximum alone)
+//   x / X  a multiplication by 2^-e (exact: |x / X| < 2^(emax + 1), and what underflows lies far below half the format's smallest
+//          subnormal)
+//   RNE onto the format's grid: (|v| + C) - C with C = 2^(max(exponent(v), 1 - bias) + 23 - mbits) -- the float32 addition rounds
+//          to nearest-even at exactly the grid's spacing in v's binade (the format's subnormal spacing below its smallest normal)
+//          and the subtraction is exact -- then the clamp to the largest normal
+//   q * X  a multiplication by 2^e (2^-127 is the float32 subnormal 0x00400000), exact
+// The element format is a RUN-TIME descriptor (wave-uniform scalars: shift counts, two constants), so the kernels are templated on
+// the input dtype alone: 3 kernels x 3 dtypes for the five formats.  Output dtype and `codes != nullptr` branch wave-uniformly.
+#pragma once
+#include "qs_common.h"
+
+namespace qs {
+
+struct MxFormat {
+    int32_t emax;            // exponent of the largest normal
+    int32_t mbits;           // mantissa bits
+    int32_t min_exp_biased;  // float32-biased exponent of the format's smallest normal: (1 - bias) + 127
+    uint32_t code_bias;      // (127 - bias) << mbits: float32 exponent|mantissa prefix -> the format's
+    uint32_t sign_shift;     // 31 - (ebits + mbits): float32 sign bit -> the code's
+    float max_normal;
+    float sub_scale;         // 2^(bias - 1 + mbits): a subnormal value -> its mantissa
+};
+
+struct MxScale {
+    float inv, X;            // 2^-e, 2^e
+    uint32_t byte;           // E8M0: e + 127, 0xFF for a non-finite block
+    bool nan;
+};
+
+__device__ __forceinline__ uint32_t mx_abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
+
+// `am`: the maximum of the block's |x| bit patterns
+__device__ __forceinline__ MxScale mx_scale(uint32_t am, const MxFormat& f) {
+    MxScale s;
+    s.nan = am >= 0x7f800000u;
+    int eb = (int)(am >> 23) - f.emax;          // e + 127; a float32 subnormal or zero abs-max lands below 0: the clamp at -127
+    eb = eb < 0 ? 0 : eb;                       // (the upper clamp cannot bind: eb <= 254 - emax)
+    s.byte = s.nan ? 0xffu : (uint32_t)eb;
+    s.X = __uint_as_float(eb ? ((uint32_t)eb << 23) : 0x00400000u);
+    s.inv = __uint_as_float((uint32_t)(254 - eb) << 23);
+    return s;
+}
+
+// |q| (on the grid, clamped) of one element and its sign bit; the caller forms y and the code
+__device__ __forceinline__ float mx_round_abs(float x, const MxScale& s, const MxFormat& f, uint32_t& sign) {
+    const uint32_t vb = __float_as_uint(x * s.inv);
+    sign = vb & 0x80000000u;
+    const uint32_t ab = vb & 0x7fffffffu;
+    int ex = (int)(ab >> 23);
+    ex = ex < f.min_exp_biased ? f.min_exp_biased : ex;
+    const float C = __uint_as_float((uint32_t)(ex + 23 - f.mbits) << 23);
+    const float r = (__uint_as_float(ab) + C) - C;
+    return r > f.max_normal ? f.max_normal : r;
+}
+
+__device__ __forceinline__ float mx_value(float r, uint32_t sign, const MxScale& s) {
+    return s.nan ? __uint_as_float(0x7fc00000u) : __uint_as_float(__float_as_uint(r * s.X) | sign);
+}
+
+__device__ __forceinline__ uint32_t mx_code(float r, uint32_t sign, const MxScale& s, const MxFormat& f) {
+    const uint32_t rb = __float_as_uint(r);
+    const uint32_t mag = (int)(rb >> 23) < f.min_exp_biased ? (uint32_t)(r * f.sub_scale) : (rb >> (23 - f.mbits)) - f.code_bias;
+    return s.nan ? 0u : (mag | (sign >> f.sign_shift));
+}
+
+// ------------------------------------------------------------------------------------------------
+// Innermost axis, aligned: n % 32 == 0 and 16-byte aligned bases, so blocks are aligned in flat memory.  One 16-byte load per
+// lane (8 two-byte or 4 float32 elements): a block is 4 / 8 adjacent lanes, its maximum two / three __shfl_xor steps.  A wave owns
+// 64 * V consecutive elements.  float32 results of two-byte inputs are transposed through a wave-private LDS region so that each
+// store instruction of the wave covers one contiguous 1 KiB span (as ew_widen_kernel, qs_elementwise.h); the other
+// combinations store what the lane holds, 16 bytes per lane.
+// ------------------------------------------------------------------------------------------------
+constexpr int kMxBlock = 256;
+
+template <int XDT>
+__global__ __launch_bounds__(kMxBlock) void mx_inner_vec_kernel(MxFormat f, const void* __restrict__ x, void* __restrict__ y,
+                                                                uint8_t* __restrict__ codes, uint8_t* __restrict__ scales,
+                                                                int64_t numel, int ydt) {
+    constexpr int V = XDT == QS_F32 ? 4 : 8;      // elements per lane
+    constexpr int LPB = QS_MX_BLOCK / V;          // lanes per block
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t e_wave = ((int64_t)blockIdx.x * (kMxBlock / 64) + wave) * (64 * V);
+    const int64_t e = e_wave + lane * V;
+    const bool in = e < numel;                    // (numel % 32 == 0: the lanes of a block are inside or outside together)
+    float v[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) v[j] = 0.0f;
+    if (in) {
+        if constexpr (XDT == QS_F32) {
+            const u32x4 a = ld16<true>((const u32x4*)x + (e >> 2));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = __uint_as_float(a[j]);
+        } else {
+            float w[8];
+            unpack8<XDT>(load8_raw<XDT, true>(x, e >> 3), w);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = w[j];
+        }
+    }
+    uint32_t am = 0;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const uint32_t a = mx_abs_bits(v[j]);
+        am = a > am ? a : am;
+    }
+#pragma unroll
+    for (int off = 1; off < LPB; off <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)am, off, 64);
+        am = o > am ? o : am;
+    }
+    const MxScale s = mx_scale(am, f);
+    float r[V];
+    uint32_t sg[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) r[j] = mx_round_abs(v[j], s, f, sg[j]);
+    if (scales && in && (lane & (LPB - 1)) == 0) scales[e >> 5] = (uint8_t)s.byte;
+    if (codes && in) {
+        uint32_t c[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) c[j] = mx_code(r[j], sg[j], s, f);
+        const uint32_t lo = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
+        if constexpr (V == 8) {
+            const uint32_t hi = c[4] | (c[5] << 8) | (c[6] << 16) | (c[7] << 24);
+            *(u32x2*)(codes + e) = u32x2{lo, hi};
+        } else {
+            *(uint32_t*)(codes + e) = lo;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) r[j] = mx_value(r[j], sg[j], s);
+    if constexpr (XDT == QS_F32) {
+        if (in) st16<true>((u32x4*)y + (e >> 2), u32x4{__float_as_uint(r[0]), __float_as_uint(r[1]), __float_as_uint(r[2]), __float_as_uint(r[3])});
+    } else {
+        __shared__ __attribute__((aligned(16))) float stage[kMxBlock * 8];
+        if (ydt == QS_F32) {
+            float* yf = (float*)y;
+            if (e_wave + 512 <= numel) {          // wave-uniform: the whole wave inside the tensor
+                float* ws = stage + wave * 512;
+                *(u32x4*)(ws + lane * 8) = u32x4{__float_as_uint(r[0]), __float_as_uint(r[1]), __float_as_uint(r[2]), __float_as_uint(r[3])};
+                *(u32x4*)(ws + lane * 8 + 4) = u32x4{__float_as_uint(r[4]), __float_as_uint(r[5]), __float_as_uint(r[6]), __float_as_uint(r[7])};
+                __builtin_amdgcn_wave_barrier();
+                const u32x4 o0 = *(const u32x4*)(ws + lane * 4);
+                const u32x4 o1 = *(const u32x4*)(ws + 256 + lane * 4);
+                st16<true>((u32x4*)(yf + e_wave + lane * 4), o0);
+                st16<true>((u32x4*)(yf + e_wave + 256 + lane * 4), o1);
+            } else if (in) {
+                float w[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) w[j] = r[j];
+                store8<QS_F32, true>(y, e >> 3, w);
+            }
+        } else if (in) {
+            float w[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) w[j] = r[j];
+            store8<XDT, true>(y, e >> 3, w);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Innermost axis, any line length and any element-aligned base: one element per lane, a block is half a wave (five __shfl_xor
+// steps), every access coalesced.  `nb` = ceil(n / 32) blocks per line; lanes past the end of a line load nothing and store nothing.
+// ------------------------------------------------------------------------------------------------
+template <int XDT>
+__global__ __launch_bounds__(kMxBlock) void mx_inner_plain_kernel(MxFormat f, const void* __restrict__ x, void* __restrict__ y,
+                                                                  uint8_t* __restrict__ codes, uint8_t* __restrict__ scales,
+                                                                  int64_t nblocks, int64_t n, int64_t nb, int ydt) {
+    const int64_t b = ((int64_t)blockIdx.x * kMxBlock + threadIdx.x) >> 5;       // block index = line * nb + kb
+    const int sub = threadIdx.x & 31;
+    const bool okb = b < nblocks;
+    const int64_t line = okb ? b / nb : 0;
+    const int64_t k = (b - line * nb) * QS_MX_BLOCK + sub;
+    const bool in = okb && k < n;
+    const int64_t e = line * n + k;
+    const float v = in ? load1<XDT>(x, e) : 0.0f;
+    uint32_t am = mx_abs_bits(v);
+#pragma unroll
+    for (int off = 1; off < 32; off <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)am, off, 64);
+        am = o > am ? o : am;
+    }
+    const MxScale s = mx_scale(am, f);
+    uint32_t sg;
+    const float r = mx_round_abs(v, s, f, sg);
+    if (scales && okb && sub == 0) scales[b] = (uint8_t)s.byte;
+    if (!in) return;
+    if (codes) codes[e] = (uint8_t)mx_code(r, sg, s, f);
+    const float out = mx_value(r, sg, s);
+    if (ydt == QS_F32) store1<QS_F32>(y, e, out);
+    else store1<XDT>(y, e, out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Strided axis: the tensor is [outer, n, inner] with inner > 1 and blocks along n.  Lanes run along `inner` (stride 1), so every
+// load and store of a wave is coalesced; a thread walks the <= 32 elements of its block at stride `inner` and keeps them in
+// registers.  Thread t = (o * nb + kb) * inner + i, which is also the index of its scale byte.
+// ------------------------------------------------------------------------------------------------
+template <int XDT>
+__global__ __launch_bounds__(kMxBlock) void mx_strided_kernel(MxFormat f, const void* __restrict__ x, void* __restrict__ y,
+                                                              uint8_t* __restrict__ codes, uint8_t* __restrict__ scales,
+                                                              int64_t total, int64_t n, int64_t inner, int64_t nb, int ydt) {
+    const int64_t t = (int64_t)blockIdx.x * kMxBlock + threadIdx.x;
+    if (t >= total) return;
+    const int64_t ob = t / inner, i = t - ob * inner;
+    const int64_t o = ob / nb, kb = ob - o * nb;
+    const int64_t base = (o * n + kb * QS_MX_BLOCK) * inner + i;
+    const int cnt = (int)((n - kb * QS_MX_BLOCK) < QS_MX_BLOCK ? (n - kb * QS_MX_BLOCK) : QS_MX_BLOCK);
+    float v[QS_MX_BLOCK];
+#pragma unroll
+    for (int j = 0; j < QS_MX_BLOCK; ++j) v[j] = j < cnt ? load1<XDT>(x, base + j * inner) : 0.0f;
+    uint32_t am = 0;
+#pragma unroll
+    for (int j = 0; j < QS_MX_BLOCK; ++j) {
+        const uint32_t a = mx_abs_bits(v[j]);
+        am = a > am ? a : am;
+    }
+    const MxScale s = mx_scale(am, f);
+    if (scales) scales[t] = (uint8_t)s.byte;
+#pragma unroll
+    for (int j = 0; j < QS_MX_BLOCK; ++j) {
+        if (j < cnt) {
+            uint32_t sg;
+            const float r = mx_round_abs(v[j], s, f, sg);
+            const int64_t e = base + j * inner;
+            if (codes) codes[e] = (uint8_t)mx_code(r, sg, s, f);
+            const float out = mx_value(r, sg, s);
+            if (ydt == QS_F32) store1<QS_F32>(y, e, out);
+            else store1<XDT>(y, e, out);
+        }
+    }
+}
+
+}  // namespace qs

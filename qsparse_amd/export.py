@@ -24,7 +24,7 @@ from typing import Dict, Optional
 import torch
 import torch.nn as nn
 
-from qsparse_amd.quantize import QuantizeLayer
+from qsparse_amd.quantize import MXQuantizer, QuantizeLayer, mx_dequantize
 from qsparse_amd.sparse import PruneLayer
 from qsparse_amd.util import logging
 
@@ -33,7 +33,9 @@ from qsparse_amd.util import logging
 class QuantizedTensor:
     """integer form of one quantized tensor.  ``kind``: "scaler" (``values = codes * scale``), "decimal"
     (``values = codes * 2^-decimal``) or "line" (``values = (codes + zero_point) * step``); per-channel parameters have one
-    entry per index of ``channel_index`` (-1: tensor-wise)."""
+    entry per index of ``channel_index`` (-1: tensor-wise).  "mx" (an ``MXQuantizer``): ``codes`` are uint8 bytes holding the
+    element format ``fmt``'s own encoding, ``block_scale`` the uint8 E8M0 scale of every block of 32 along ``block_dim``
+    (``values = decode(codes) * 2^(block_scale - 127)``)."""
     kind: str
     bits: int
     channel_index: int
@@ -45,6 +47,9 @@ class QuantizedTensor:
     step: Optional[torch.Tensor] = None
     zero_point: Optional[torch.Tensor] = None
     mask: Optional[torch.Tensor] = None
+    block_scale: Optional[torch.Tensor] = None
+    fmt: Optional[str] = None
+    block_dim: Optional[int] = None
 
     def _on_channel(self, p: torch.Tensor) -> torch.Tensor:
         if p.numel() == 1 or self.channel_index < 0:
@@ -55,6 +60,8 @@ class QuantizedTensor:
 
     def dequantize(self) -> torch.Tensor:
         """float32 values from the integers alone -- equal, bit for bit, to what the layer computes with"""
+        if self.kind == "mx":
+            return mx_dequantize(self.codes, self.block_scale, self.fmt, self.block_dim, self.values.dtype)
         q = self.codes.float()
         if self.kind == "scaler":
             return q * self._on_channel(self.scale)
@@ -173,6 +180,8 @@ def export_integer(model: nn.Module) -> Dict[str, LayerExport]:
                         and m._quantized):
                     act = dict(operator="quantize", bits=m.bits, channelwise=m.channelwise,
                                quantizer=type(m.callback).__name__, weight=m.weight.detach().clone())
+                    if isinstance(m.callback, MXQuantizer):      # (stateless: the format and the block axis are all there is)
+                        act.update(fmt=m.callback.fmt, block_dim=m.callback.block_dim)
                     out[path] = LayerExport(path=path, module="QuantizeLayer", activation=act)
                 elif isinstance(m, PruneLayer) and m.initted and m.mask.numel() > 1:
                     out[path] = LayerExport(path=path, module="PruneLayer",

@@ -61,7 +61,7 @@ def steady_state(model: nn.Module) -> bool:
                 if not m.initted or m._steps.read(m._n_updates) <= m.timeout or not m._quantized:
                     return False
                 qc = m.callback
-                if qc.group_num > 0 and qc.t <= qc.group_timeout + 1:
+                if getattr(qc, "group_num", 0) > 0 and qc.t <= qc.group_timeout + 1:     # (an MXQuantizer has no groups, no state)
                     return False
     return True
 

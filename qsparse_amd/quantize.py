@@ -478,6 +478,175 @@ class ScalerQuantizer(DecimalQuantizer):
         self.function = ScalerQuantization.apply
 
 
+# ----------------------------------------------------------------------------------------------
+# MX block-scaled formats (OCP Microscaling Formats v1.0): FP8 / FP6 / FP4 elements, one E8M0 scale per block of 32
+# ----------------------------------------------------------------------------------------------
+# name -> (element bits, exponent bits, mantissa bits, exponent bias, emax, largest normal)
+MX_FORMATS = {
+    "mxfp8_e4m3": (8, 4, 3, 7, 8, 448.0),
+    "mxfp8_e5m2": (8, 5, 2, 15, 15, 57344.0),
+    "mxfp6_e2m3": (6, 2, 3, 1, 2, 7.5),
+    "mxfp6_e3m2": (6, 3, 2, 3, 4, 28.0),
+    "mxfp4_e2m1": (4, 2, 1, 1, 2, 6.0),
+}
+MX_BLOCK = 32
+
+
+def _mx_format(fmt: str):
+    try:
+        return MX_FORMATS[fmt]
+    except KeyError:
+        raise ValueError(f"unknown MX format {fmt!r}: one of {sorted(MX_FORMATS)}") from None
+
+
+def _exp2_f64(k: torch.Tensor) -> torch.Tensor:
+    """2^k as float64 for an integer tensor k in [-1022, 1023], assembled from the exponent bits (exact on every device)"""
+    return ((k.to(torch.int64) + 1023) << 52).view(torch.float64)
+
+
+def _floor_log2(a: torch.Tensor) -> torch.Tensor:
+    """unbiased binary exponent of a positive finite float64 tensor (from frexp, never from a logarithm); 0 maps to -1"""
+    return torch.frexp(a)[1].to(torch.int64) - 1
+
+
+def _mx_blocks(x: torch.Tensor, dim: int):
+    """x with `dim` moved last, padded with zeros to a multiple of 32 and split: [..., nb, 32] float64 (a zero changes no abs-max)"""
+    v = x.movedim(dim, -1).to(torch.float32).to(torch.float64)
+    n = v.shape[-1]
+    nb = (n + MX_BLOCK - 1) // MX_BLOCK
+    if nb * MX_BLOCK != n:
+        v = torch.nn.functional.pad(v, (0, nb * MX_BLOCK - n))
+    return v.reshape(v.shape[:-1] + (nb, MX_BLOCK)), n
+
+
+def _mx_aten(x: torch.Tensor, fmt: str, dim: int, out_dtype: torch.dtype, want_codes: bool):
+    """the definition as an ATen expression (CPU tensors, float64 GPU tensors): exact float64 arithmetic on the float32 widening of
+    x -- exponents from frexp, powers of two from their bits, one rounding (torch.round: half to even) per element"""
+    bits, ebits, mbits, bias, emax, max_normal = _mx_format(fmt)
+    blk, n = _mx_blocks(x, dim)
+    amax = blk.abs().amax(-1, keepdim=True)
+    bad = ~torch.isfinite(amax)                   # (amax propagates a NaN)
+    safe = torch.where(bad | (amax == 0), torch.ones_like(amax), amax)
+    e = (_floor_log2(safe) - emax).clamp(-127, 127)
+    e = torch.where(amax == 0, torch.full_like(e, -127), e)
+    v = torch.where(bad, torch.zeros_like(blk), blk) * _exp2_f64(-e)           # x / X, exact
+    a = v.abs()
+    ex = _floor_log2(torch.where(a == 0, torch.ones_like(a), a)).clamp(min=1 - bias)
+    ex = torch.where(a == 0, torch.full_like(ex, 1 - bias), ex)
+    quantum = _exp2_f64(ex - mbits)
+    q = (torch.round(a / quantum) * quantum).clamp(max=max_normal)             # (a / quantum is exact: a power of two)
+    y = torch.copysign(q, v) * _exp2_f64(e)
+    y = torch.where(bad, torch.full_like(y, float("nan")), y)
+
+    def unblock(t):
+        t = t.reshape(t.shape[:-2] + (-1,))[..., :n]
+        return t.movedim(-1, dim)
+
+    out = unblock(y).to(out_dtype).contiguous()
+    if not want_codes:
+        return out, None, None
+    sub = q < 2.0 ** (1 - bias)
+    qe = _floor_log2(torch.where(sub, torch.ones_like(q), q))
+    mag = torch.where(sub, (q * 2.0 ** (bias - 1 + mbits)).to(torch.int64),
+                      ((qe + bias) << mbits) + ((q * _exp2_f64(mbits - qe)).to(torch.int64) - (1 << mbits)))
+    code = mag + (torch.signbit(v).to(torch.int64) << (ebits + mbits))
+    code = torch.where(bad, torch.zeros_like(code), code)
+    scale = torch.where(bad, torch.full_like(e, 255), e + 127).squeeze(-1)
+    return out, unblock(code).to(torch.uint8).contiguous(), scale.movedim(-1, dim).to(torch.uint8).contiguous()
+
+
+class MXQuantization(torch.autograd.Function):
+    """MX block-scaled quantization with a straight-through backward: the gradient passes unchanged (no clamp, no kernel)."""
+
+    @staticmethod
+    def forward(ctx, input: torch.Tensor, fmt: str = "mxfp8_e4m3", block_dim: int = -1, return_codes: bool = False):
+        _mx_format(fmt)
+        if input.dim() == 0:
+            raise ValueError("MX quantization needs a tensor with at least one dimension (blocks of 32 run along `block_dim`)")
+        if not -input.dim() <= block_dim < input.dim():
+            raise IndexError(f"block_dim {block_dim} out of range for a tensor of {input.dim()} dimensions")
+        dim = block_dim % input.dim()
+        if _hip.on_hip(input):
+            y, codes, scales = _hip.mx_quant_fwd(input, fmt, dim, _out_dtype(input), return_codes)
+        else:
+            y, codes, scales = _mx_aten(input, fmt, dim, _out_dtype(input), return_codes)
+        if not return_codes:
+            return y
+        ctx.mark_non_differentiable(codes, scales)
+        return y, codes, scales
+
+    @staticmethod
+    def backward(ctx, grad_output, grad_codes=None, grad_scales=None):
+        return grad_output, None, None, None
+
+
+def quantize_with_mx(input: torch.Tensor, fmt: str = "mxfp8_e4m3", block_dim: int = -1, return_codes: bool = False):
+    """OCP microscaling (MX) quantization: elements in ``fmt`` (``MX_FORMATS``), one power-of-two scale per block of 32
+    consecutive elements along ``block_dim`` (the last block of a line is shorter when the length is no multiple of 32).
+    Returns the de-quantized tensor -- float32, or the input dtype under ``preserve_dtype`` -- or, with ``return_codes``,
+    ``(y, codes, scales)``: ``codes`` uint8 of the input's shape (the element format's own bit encoding in the low bits),
+    ``scales`` uint8 E8M0 bytes (``X = 2^(scale - 127)``, 0xFF for a block that holds a NaN / Inf, whose outputs are all NaN)
+    of the input's shape with ``block_dim`` shrunk to ``ceil(n / 32)``."""
+    return MXQuantization.apply(input, fmt, block_dim, return_codes)
+
+
+def mx_dequantize(codes: torch.Tensor, scales: torch.Tensor, fmt: str, block_dim: int = -1,
+                  dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """the values of MX ``codes`` / ``scales`` (as ``quantize_with_mx(..., return_codes=True)`` returns them) from the two byte
+    tensors alone: a 256-entry table of the element format times ``2^(scale - 127)``, exact in float64, rounded once to ``dtype``"""
+    bits, ebits, mbits, bias, emax, max_normal = _mx_format(fmt)
+    c = torch.arange(256, dtype=torch.int64)
+    E, M = (c >> mbits) & ((1 << ebits) - 1), c & ((1 << mbits) - 1)
+    mag = torch.where(E == 0, M.double() * 2.0 ** (1 - bias - mbits), (1 + M.double() * 2.0 ** -mbits) * _exp2_f64(E - bias))
+    table = torch.where(((c >> (ebits + mbits)) & 1) == 1, -mag, mag).to(codes.device)
+    dim = block_dim % codes.dim()
+    X = torch.where(scales == 255, torch.full((), float("nan"), dtype=torch.float64, device=scales.device),
+                    _exp2_f64(scales.to(torch.int64) - 127))
+    X = X.repeat_interleave(MX_BLOCK, dim=dim).narrow(dim, 0, codes.shape[dim])
+    return (table[codes.to(torch.int64)] * X).to(dtype)
+
+
+class MXQuantizer(BaseQuantizer):
+    """``quantize(callback=...)`` callback for the MX block-scaled formats.  Stateless: the scale of a block comes from the data
+    of each step, so ``optimize`` returns the layer's weight unchanged (nothing to average, nothing to exchange between ranks).
+    ``bits`` of the layer must equal the element format's width.  ``block_dim`` names the axis the blocks run along; a tensor
+    with fewer dimensions than that (a bias next to a weight quantized along dim 1) takes its last one."""
+
+    weight_size = 1
+
+    def __init__(self, fmt: str = "mxfp8_e4m3", block_dim: int = -1):
+        super().__init__()
+        _mx_format(fmt)
+        self.fmt = fmt
+        self.block_dim = block_dim
+        self.t = 0              # (no running statistic: stays 0; `extra_state_dict` records every callback's count)
+
+    def _check_bits(self, bits):
+        width = _mx_format(self.fmt)[0]
+        if bits != width:
+            raise ValueError(f"MXQuantizer({self.fmt!r}) has {width}-bit elements but the layer asks for bits={bits}")
+
+    def _dim(self, tensor) -> int:
+        return self.block_dim if -tensor.dim() <= self.block_dim < tensor.dim() else -1
+
+    def optimize(self, tensor, bits, weight=None, batched=False, channel_index=-1, **kwargs):
+        self._check_bits(bits)
+        return weight
+
+    def forward(self, tensor, bits, weight=None, channel_index=-1, **kwargs):
+        self._check_bits(bits)
+        return quantize_with_mx(tensor, self.fmt, self._dim(tensor))
+
+    def export(self, tensor, bits, weight=None, channel_index=-1) -> dict:
+        """byte form of ``self(tensor, bits, weight)`` (qsparse_amd/export.py): codes and block scales are the second and third
+        output of the very call ``forward`` makes"""
+        self._check_bits(bits)
+        with torch.no_grad():
+            dim = self._dim(tensor) % tensor.dim()
+            y, codes, scales = quantize_with_mx(tensor, self.fmt, dim, return_codes=True)
+        return dict(kind="mx", codes=codes, values=y, block_scale=scales, fmt=self.fmt, block_dim=dim)
+
+
 class AdaptiveQuantizer(DecimalQuantizer):
     """min/max statistics + asymmetric lines (algorithm 2 of the MDPI paper; reference
     quantize.py:381-430)."""

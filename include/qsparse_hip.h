@@ -857,6 +857,46 @@ int qs_mx_quant_fwd_v(const qs_mx_quant_args* args);
 #define QS_MX_ROUTE_STRIDED 3
 int qs_mx_quant_route(const qs_mx_quant_args* args);
 
+/* ---- MX matrix product (block-scaled MFMA) -----------------------------------------------------------------------------------
+ * Added without raising QS_ABI_VERSION (27): by the rule above prototypes are frozen and symbols are only ever added, so a
+ * binding written against v27 is served unchanged; a binding that needs these two symbols resolves them when it loads the
+ * library and fails there against a library that lacks them.
+ *
+ * y[m, n] = round_once_to_ydt( sum_k val_a(a_codes[m, k]) * 2^(a_scales[m, k / 32] - 127)
+ *                                  * val_b(b_codes[n, k]) * 2^(b_scales[n, k / 32] - 127)  +  bias[n] )
+ * i.e. A . B^T with B laid out as an nn.Linear weight.  val_*: the value of the element format's code (sign, exponent, mantissa in
+ * the low bits of the byte, as qs_mx_quant_fwd_v writes them).  Products are exact, the sum is accumulated in float32 by
+ * v_mfma_scale_f32_16x16x128_f8f6f4 in steps of 128 along K (the order inside a step is the instruction's), the bias is added in
+ * float32, the result rounded once to ydt.  The two formats may differ.
+ *   - Any M, N >= 0 (M == 0 or N == 0: nothing is enqueued) and K >= 1.  K % 32 != 0: the last block is short, the missing
+ *     elements count as zero.  Nothing outside the five operands and y is read or written.
+ *   - A scale byte 0xFF (the quantizer's mark of a block that held NaN / Inf) makes every output whose dot product reads that
+ *     block NaN: row m of y for a byte of A's row m, column n for a byte of B's row n.
+ *   - Code bytes the quantizer never writes (E5M2 Inf / NaN patterns, E4M3 0x7F / 0xFF, bits above the format's width) give an
+ *     unspecified value in the outputs that read them, never a fault.
+ *   - a_codes / b_codes / scales: any address.  y: aligned to its element; bias: to 4 bytes (QS_ERR_ALIGN otherwise).
+ *     K % 16 == 0 with both code bases 16-byte aligned takes the 16-bytes-per-load kernel (QS_MX_GEMM_ROUTE_VEC), anything else
+ *     the same kernel with predicated byte loads (QS_MX_GEMM_ROUTE_PLAIN).  No workspace. */
+typedef struct qs_mx_matmul_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_matmul_args) as the caller compiled it */
+    int32_t a_format, b_format;      /* enum qs_mx_format, may differ */
+    const uint8_t* a_codes;          /* [M, K], one code per byte, row-major */
+    const uint8_t* a_scales;         /* [M, ceil(K / 32)] E8M0 bytes */
+    const uint8_t* b_codes;          /* [N, K] */
+    const uint8_t* b_scales;         /* [N, ceil(K / 32)] */
+    const float* bias;               /* nullable, [N] float32 */
+    void* y;                         /* [M, N] row-major */
+    int32_t ydt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    int64_t M, N, K;
+    qs_stream_t stream;
+} qs_mx_matmul_args;
+int qs_mx_matmul_v(const qs_mx_matmul_args* args);
+/* the kernel qs_mx_matmul_v launches for these operands, nothing enqueued: QS_MX_GEMM_ROUTE_*, 0 for an empty product, or the
+ * QS_ERR_* the call would return */
+#define QS_MX_GEMM_ROUTE_VEC 1
+#define QS_MX_GEMM_ROUTE_PLAIN 2
+int qs_mx_matmul_route(const qs_mx_matmul_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,8 @@ SIGNATURES = {
     "qs_stats_combine": (c_int, [_P, _I, _L, _P, _P, _L, _P]),
     "qs_mx_quant_fwd_v": (c_int, [_P]),
     "qs_mx_quant_route": (c_int, [_P]),
+    "qs_mx_matmul_v": (c_int, [_P]),
+    "qs_mx_matmul_route": (c_int, [_P]),
 }
 
 
@@ -171,6 +173,13 @@ class MxQuantArgs(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("format", c_int32), ("x", c_void_p), ("y", c_void_p), ("codes", c_void_p),
                 ("scales", c_void_p), ("xdt", c_int32), ("ydt", c_int32), ("outer", c_int64), ("n", c_int64), ("inner", c_int64),
                 ("stream", c_void_p)]
+
+
+class MxMatmulArgs(ctypes.Structure):
+    """`qs_mx_matmul_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("a_format", c_int32), ("b_format", c_int32), ("a_codes", c_void_p),
+                ("a_scales", c_void_p), ("b_codes", c_void_p), ("b_scales", c_void_p), ("bias", c_void_p), ("y", c_void_p),
+                ("ydt", c_int32), ("M", c_int64), ("N", c_int64), ("K", c_int64), ("stream", c_void_p)]
 
 
 class MultiRow(ctypes.Structure):
@@ -805,6 +814,35 @@ def mx_quant_fwd(x: torch.Tensor, fmt: str, block_dim: int, out_dtype: torch.dty
     if copied:
         y = laid_out_like(y, x)
     return y, codes, scales
+
+
+MX_GEMM_ROUTE_VEC, MX_GEMM_ROUTE_PLAIN = 1, 2
+mx_gemm_last_route = None     # the QS_MX_GEMM_ROUTE_* of the last `mx_matmul` launch (None: an empty product), for tests and tools
+
+
+def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
+              bias: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """y[M, N] = A . B^T on MX codes (qs_mx_matmul_v): `a_codes` [M, K], `b_codes` [N, K] uint8, scales [*, ceil(K / 32)] uint8,
+    all contiguous GPU tensors (qsparse_amd/mx_gemm.py checks and flattens); `bias` float32 [N] or None.  ONE launch."""
+    global mx_gemm_last_route
+    lib = load()
+    (M, K), N = a_codes.shape, b_codes.shape[0]
+    y = torch.empty((M, N), dtype=out_dtype, device=a_codes.device)
+    mx_gemm_last_route = None
+    if M and N:
+        a = MxMatmulArgs()
+        a.struct_size = ctypes.sizeof(a)
+        a.a_format, a.b_format = MX_FORMATS.index(a_fmt), MX_FORMATS.index(b_fmt)
+        a.a_codes, a.a_scales, a.b_codes, a.b_scales = _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales)
+        a.bias, a.y, a.ydt = _ptr(bias), _ptr(y), _DT[out_dtype]
+        a.M, a.N, a.K = M, N, K
+        a.stream = _stream(a_codes)
+        route = lib.qs_mx_matmul_route(ctypes.byref(a))
+        with _timed(f"mx_matmul[{route}]", a_codes, a_scales, b_codes, b_scales, bias, y):
+            st = lib.qs_mx_matmul_v(ctypes.byref(a))
+        _check(st, "qs_mx_matmul_v")
+        mx_gemm_last_route = route
+    return y
 
 
 def quant_line_fwd(x: torch.Tensor, lines: torch.Tensor, bits: int, channel_index: int, float_zero_point: bool,

@@ -897,6 +897,43 @@ int qs_mx_matmul_v(const qs_mx_matmul_args* args);
 #define QS_MX_GEMM_ROUTE_PLAIN 2
 int qs_mx_matmul_route(const qs_mx_matmul_args* args);
 
+/* ---- MX two-way quantizer (codes only) -----------------------------------------------------------------------------------------
+ * Added without raising QS_ABI_VERSION (27), by the same rule as qs_mx_matmul_v above: symbols are only added.
+ *
+ * x is CONTIGUOUS [R, C] (float32, bf16 or fp16) and is read once.  Two output pairs, each nullable as a whole, at least one given:
+ *   row pair  row_codes uint8 [R, C], row_scales uint8 [R, ceil(C / 32)], format row_format, blocks along C: the codes and scales
+ *             qs_mx_quant_fwd_v writes for x seen as [R, C, 1]
+ *   col pair  col_codes uint8 [C, R], row-major, col_scales uint8 [C, ceil(R / 32)], format col_format, blocks along R: the codes and
+ *             scales qs_mx_quant_fwd_v writes for the transpose of x, stored as that transpose
+ * bit for bit by the definition of the MX block-scaled quantizer above (short last blocks, zero blocks, float32 subnormals, the sign
+ * of a zero, a NaN / Inf block: scale 0xFF, codes 0).  The two formats may differ; the format of a pair that is not given is ignored.
+ * No de-quantized tensor is written, nothing but the four outputs is written, no workspace.
+ *   - x needs the alignment of its element (QS_ERR_ALIGN otherwise); codes and scales: any address.
+ *   - R == 0 or C == 0: nothing is enqueued, 0 is returned.
+ *   - QS_MX_Q2_ROUTE_TILE_VEC (16-byte loads of x, 16-byte stores of col_codes): C % 8 == 0 (two-byte x) or C % 4 == 0 (float32), x
+ *     16-byte aligned and, when the col pair is written, R % 16 == 0 and col_codes 16-byte aligned.  Anything else takes
+ *     QS_MX_Q2_ROUTE_TILE_PLAIN, the same tiling with element accesses: any R, C >= 1.
+ *   - QS_ERR_ARG: a null or too short descriptor, x null, both pairs null, codes without scales or the reverse, a format outside
+ *     enum qs_mx_format, a negative extent.  QS_ERR_DTYPE: xdt is none of the three. */
+typedef struct qs_mx_quant2_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_quant2_args) as the caller compiled it */
+    int32_t row_format, col_format;  /* enum qs_mx_format, may differ */
+    const void* x;                   /* [R, C] row-major */
+    int32_t xdt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    uint8_t* row_codes;              /* nullable with row_scales; [R, C] */
+    uint8_t* row_scales;             /* [R, ceil(C / 32)] */
+    uint8_t* col_codes;              /* nullable with col_scales; [C, R] */
+    uint8_t* col_scales;             /* [C, ceil(R / 32)] */
+    int64_t R, C;
+    qs_stream_t stream;
+} qs_mx_quant2_args;
+int qs_mx_quant2_v(const qs_mx_quant2_args* args);
+/* the kernel qs_mx_quant2_v launches for these operands, nothing enqueued: QS_MX_Q2_ROUTE_*, 0 for an empty tensor, or the QS_ERR_*
+ * the call would return */
+#define QS_MX_Q2_ROUTE_TILE_VEC 1
+#define QS_MX_Q2_ROUTE_TILE_PLAIN 2
+int qs_mx_quant2_route(const qs_mx_quant2_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,8 @@ SIGNATURES = {
     "qs_mx_quant_route": (c_int, [_P]),
     "qs_mx_matmul_v": (c_int, [_P]),
     "qs_mx_matmul_route": (c_int, [_P]),
+    "qs_mx_quant2_v": (c_int, [_P]),
+    "qs_mx_quant2_route": (c_int, [_P]),
 }
 
 
@@ -180,6 +182,13 @@ class MxMatmulArgs(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("a_format", c_int32), ("b_format", c_int32), ("a_codes", c_void_p),
                 ("a_scales", c_void_p), ("b_codes", c_void_p), ("b_scales", c_void_p), ("bias", c_void_p), ("y", c_void_p),
                 ("ydt", c_int32), ("M", c_int64), ("N", c_int64), ("K", c_int64), ("stream", c_void_p)]
+
+
+class MxQuant2Args(ctypes.Structure):
+    """`qs_mx_quant2_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("row_format", c_int32), ("col_format", c_int32), ("x", c_void_p), ("xdt", c_int32),
+                ("row_codes", c_void_p), ("row_scales", c_void_p), ("col_codes", c_void_p), ("col_scales", c_void_p),
+                ("R", c_int64), ("C", c_int64), ("stream", c_void_p)]
 
 
 class MultiRow(ctypes.Structure):
@@ -843,6 +852,39 @@ def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes
         _check(st, "qs_mx_matmul_v")
         mx_gemm_last_route = route
     return y
+
+
+MX_Q2_ROUTE_TILE_VEC, MX_Q2_ROUTE_TILE_PLAIN = 1, 2
+mx_quant2_last_route = None   # the QS_MX_Q2_ROUTE_* of the last `mx_quant2` launch (None: an empty tensor), for tests and tools
+
+
+def mx_quant2(x: torch.Tensor, row_fmt: Optional[str], col_fmt: Optional[str]):
+    """the two-way, codes-only MX quantizer (qs_mx_quant2_v) on a contiguous GPU tensor `x` [R, C]: returns (row_codes [R, C],
+    row_scales [R, ceil(C / 32)], col_codes [C, R], col_scales [C, ceil(R / 32)]), uint8, a pair None where its format is None --
+    from ONE launch that reads x once."""
+    global mx_quant2_last_route
+    lib = load()
+    R, C = x.shape
+    nb = lambda n: (n + MX_BLOCK - 1) // MX_BLOCK
+    new = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=x.device)
+    rc, rs = (new(R, C), new(R, nb(C))) if row_fmt is not None else (None, None)
+    cc, cs = (new(C, R), new(C, nb(R))) if col_fmt is not None else (None, None)
+    mx_quant2_last_route = None
+    if R and C:
+        a = MxQuant2Args()
+        a.struct_size = ctypes.sizeof(a)
+        a.row_format = MX_FORMATS.index(row_fmt) if row_fmt is not None else 0
+        a.col_format = MX_FORMATS.index(col_fmt) if col_fmt is not None else 0
+        a.x, a.xdt = _ptr(x), dt(x)
+        a.row_codes, a.row_scales, a.col_codes, a.col_scales = _ptr(rc), _ptr(rs), _ptr(cc), _ptr(cs)
+        a.R, a.C = R, C
+        a.stream = _stream(x)
+        route = lib.qs_mx_quant2_route(ctypes.byref(a))
+        with _timed(f"mx_quant2[{route}]", x, rc, rs, cc, cs):
+            st = lib.qs_mx_quant2_v(ctypes.byref(a))
+        _check(st, "qs_mx_quant2_v")
+        mx_quant2_last_route = route
+    return rc, rs, cc, cs
 
 
 def quant_line_fwd(x: torch.Tensor, lines: torch.Tensor, bits: int, channel_index: int, float_zero_point: bool,

@@ -6,32 +6,6 @@
 
 namespace {
 
-// ebits, mbits, bias, emax, largest normal
-struct MxSpec {
-    int ebits, mbits, bias, emax;
-    float max_normal;
-};
-constexpr MxSpec kMxSpecs[5] = {
-    {4, 3, 7, 8, 448.0f},       // QS_MX_FP8_E4M3
-    {5, 2, 15, 15, 57344.0f},   // QS_MX_FP8_E5M2
-    {2, 3, 1, 2, 7.5f},         // QS_MX_FP6_E2M3
-    {3, 2, 3, 4, 28.0f},        // QS_MX_FP6_E3M2
-    {2, 1, 1, 2, 6.0f},         // QS_MX_FP4_E2M1
-};
-
-inline MxFormat mx_format(int format) {
-    const MxSpec& sp = kMxSpecs[format];
-    MxFormat f;
-    f.emax = sp.emax;
-    f.mbits = sp.mbits;
-    f.min_exp_biased = 1 - sp.bias + 127;
-    f.code_bias = (uint32_t)(127 - sp.bias) << sp.mbits;
-    f.sign_shift = 31u - (uint32_t)(sp.ebits + sp.mbits);
-    f.max_normal = sp.max_normal;
-    f.sub_scale = (float)(1 << (sp.bias - 1 + sp.mbits));
-    return f;
-}
-
 inline size_t dt_size(int dt) { return dt == QS_F32 ? 4 : 2; }
 inline bool aligned_to(const void* p, size_t a) { return (((uintptr_t)p) & (a - 1)) == 0; }
 constexpr int64_t kMaxGrid = 0x7fffffff;

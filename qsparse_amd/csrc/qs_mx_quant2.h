@@ -1,0 +1,162 @@
+// Two-way, codes-only MX quantizer (include/qsparse_hip.h, "MX two-way quantizer"): x [R, C] is read ONCE and leaves as
+//   row pair  codes [R, C] / scales [R, ceil(C / 32)], blocks along C, format `fr`
+//   col pair  codes [C, R] / scales [C, ceil(R / 32)], blocks along R, format `fc`, stored transposed
+// -- the operands the three matrix products of a linear layer's training step need.  The per-element arithmetic is
+// qs_mx.h's (mx_scale / mx_round_abs / mx_code); nothing of it is restated here.
+//
+// A work-group of 256 lanes owns a tile of 128 rows x 64 columns (both multiples of 32: every block of either direction lies
+// inside one tile).
+//   Phase 1, lanes along C: a lane holds V = 8 (two-byte inputs) or 4 (float32) consecutive elements of a row -- one 16-byte load
+//     on the VEC route -- in 128 * 64 / (256 * V) passes whose loads are all issued before the first use.  The raw elements go to
+//     the LDS tile [128][64] unchanged (one 16-byte store per lane and pass: 8 contiguous lanes cover 32 consecutive dwords, no
+//     bank is hit twice); a row block is 32 / V adjacent lanes, its maximum two or three __shfl_xor steps, as mx_inner_vec_kernel.
+//   Phase 2, lanes along C again, a lane WALKS along R: lane (c = tid & 63, b = tid >> 6) reads the 32 elements tile[32 b + j][c],
+//     j = 0..31 -- a whole column block, so its maximum needs no exchange.  Each read instruction of a 32-lane half addresses 32
+//     consecutive columns of one tile row: 32 consecutive dwords (float32) or 16 (two-byte: two lanes per dword), conflict-free with
+//     the UNPADDED row pitch, because the transposition happens in registers, not in the addressing.  The lane packs its 32 codes
+//     into two 16-byte stores at col_codes[c][r0 + 32 b ..]: the four waves of the group write 128 contiguous bytes per output row.
+// No atomics, no workspace; a null pair skips its phase (wave-uniform), a null col pair also the LDS traffic and the barrier.
+// VEC = false is the same tiling with element accesses, each predicated on its own index: any R, C >= 1, any element-aligned base.
+#pragma once
+#include "qs_mx.h"
+
+namespace qs {
+
+constexpr int kMxq2Rows = 128, kMxq2Cols = 64, kMxq2Threads = 256;
+
+template <int XDT>
+struct Mxq2Raw {
+    using type = uint16_t;
+};
+template <>
+struct Mxq2Raw<QS_F32> {
+    using type = uint32_t;
+};
+
+template <int XDT>
+__device__ __forceinline__ float mxq2_widen(typename Mxq2Raw<XDT>::type raw) {
+    if constexpr (XDT == QS_F32) return __uint_as_float(raw);
+    if constexpr (XDT == QS_BF16) return bf16_bits_to_f32(raw);
+    return f16_bits_to_f32(raw);
+}
+
+__device__ __forceinline__ uint32_t mxq2_pack4(const uint32_t* c) { return c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24); }
+
+// `row_vec`: row_codes is aligned to the V bytes a lane stores at once (VEC only; otherwise byte stores)
+template <int XDT, bool VEC>
+__global__ __launch_bounds__(kMxq2Threads) void mx_quant2_kernel(MxFormat fr, MxFormat fc, const void* __restrict__ x,
+                                                                 uint8_t* __restrict__ row_codes, uint8_t* __restrict__ row_scales,
+                                                                 uint8_t* __restrict__ col_codes, uint8_t* __restrict__ col_scales,
+                                                                 int64_t R, int64_t C, int tiles_c, int row_vec) {
+    using raw_t = typename Mxq2Raw<XDT>::type;
+    constexpr int V = XDT == QS_F32 ? 4 : 8;              // elements per lane and pass: 16 bytes
+    constexpr int LPB = QS_MX_BLOCK / V;                  // lanes per row block
+    constexpr int LPR = kMxq2Cols / V;                    // lanes per tile row
+    constexpr int RPP = kMxq2Threads / LPR;               // tile rows per pass
+    constexpr int PASSES = kMxq2Rows / RPP;
+    __shared__ __attribute__((aligned(16))) raw_t tile[kMxq2Rows * kMxq2Cols];
+
+    const int tid = threadIdx.x;
+    const int64_t r0 = (int64_t)(blockIdx.x / tiles_c) * kMxq2Rows;
+    const int64_t c0 = (int64_t)(blockIdx.x % tiles_c) * kMxq2Cols;
+    const int64_t nbc = (C + QS_MX_BLOCK - 1) / QS_MX_BLOCK, nbr = (R + QS_MX_BLOCK - 1) / QS_MX_BLOCK;
+
+    // ---- phase 1: load, stage, row pair --------------------------------------------------------------------------------------
+    const int lrow = tid / LPR, lcol = (tid % LPR) * V;
+    const int64_t gc = c0 + lcol;
+    raw_t raw[PASSES][V];
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+        const int64_t gr = r0 + p * RPP + lrow;
+        if constexpr (VEC) {                              // (C % V == 0: the lane's V elements are inside or outside together)
+            u32x4 a = {0u, 0u, 0u, 0u};
+            if (gr < R && gc < C) a = ld16<true>((const u32x4*)((const raw_t*)x + gr * C + gc));
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                if constexpr (XDT == QS_F32) raw[p][j] = a[j];
+                else raw[p][j] = (raw_t)(a[j >> 1] >> ((j & 1) * 16));
+            }
+            if (col_codes) *(u32x4*)(tile + (p * RPP + lrow) * kMxq2Cols + lcol) = a;
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                raw[p][j] = (gr < R && gc + j < C) ? ((const raw_t*)x)[gr * C + gc + j] : (raw_t)0;
+                if (col_codes) tile[(p * RPP + lrow) * kMxq2Cols + lcol + j] = raw[p][j];
+            }
+        }
+    }
+    if (row_codes) {
+#pragma unroll
+        for (int p = 0; p < PASSES; ++p) {
+            const int64_t gr = r0 + p * RPP + lrow;
+            float v[V];
+            uint32_t am = 0;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                v[j] = mxq2_widen<XDT>(raw[p][j]);
+                const uint32_t a = mx_abs_bits(v[j]);
+                am = a > am ? a : am;
+            }
+#pragma unroll
+            for (int off = 1; off < LPB; off <<= 1) {
+                const uint32_t o = (uint32_t)__shfl_xor((int)am, off, 64);
+                am = o > am ? o : am;
+            }
+            const MxScale s = mx_scale(am, fr);
+            uint32_t c[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                uint32_t sg;
+                const float r = mx_round_abs(v[j], s, fr, sg);
+                c[j] = mx_code(r, sg, s, fr);
+            }
+            if (gr < R && gc < C) {
+                if ((tid % LPB) == 0) row_scales[gr * nbc + (gc >> 5)] = (uint8_t)s.byte;
+                uint8_t* out = row_codes + gr * C + gc;
+                if (VEC && row_vec) {
+                    if constexpr (V == 8) *(u32x2*)out = u32x2{mxq2_pack4(c), mxq2_pack4(c + 4)};
+                    else *(uint32_t*)out = mxq2_pack4(c);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < V; ++j)
+                        if (VEC || gc + j < C) out[j] = (uint8_t)c[j];
+                }
+            }
+        }
+    }
+    if (!col_codes) return;                               // (kernel-uniform)
+    __syncthreads();
+
+    // ---- phase 2: col pair ---------------------------------------------------------------------------------------------------
+    const int cc = tid & (kMxq2Cols - 1), cb = tid / kMxq2Cols;
+    const int64_t oc = c0 + cc, orow = r0 + cb * QS_MX_BLOCK;
+    float w[QS_MX_BLOCK];
+    uint32_t am = 0;
+#pragma unroll
+    for (int j = 0; j < QS_MX_BLOCK; ++j) {
+        w[j] = mxq2_widen<XDT>(tile[(cb * QS_MX_BLOCK + j) * kMxq2Cols + cc]);
+        const uint32_t a = mx_abs_bits(w[j]);
+        am = a > am ? a : am;
+    }
+    if (oc >= C || orow >= R) return;
+    const MxScale s = mx_scale(am, fc);
+    col_scales[oc * nbr + (orow >> 5)] = (uint8_t)s.byte;
+    uint32_t c[QS_MX_BLOCK];
+#pragma unroll
+    for (int j = 0; j < QS_MX_BLOCK; ++j) {
+        uint32_t sg;
+        const float r = mx_round_abs(w[j], s, fc, sg);
+        c[j] = mx_code(r, sg, s, fc);
+    }
+    uint8_t* out = col_codes + oc * R + orow;
+    if constexpr (VEC) {                                  // (R % 16 == 0: each half of the block is inside or outside as a whole)
+        *(u32x4*)out = u32x4{mxq2_pack4(c), mxq2_pack4(c + 4), mxq2_pack4(c + 8), mxq2_pack4(c + 12)};
+        if (orow + 16 < R) *(u32x4*)(out + 16) = u32x4{mxq2_pack4(c + 16), mxq2_pack4(c + 20), mxq2_pack4(c + 24), mxq2_pack4(c + 28)};
+    } else {
+#pragma unroll
+        for (int j = 0; j < QS_MX_BLOCK; ++j)
+            if (orow + j < R) out[j] = (uint8_t)c[j];
+    }
+}
+
+}  // namespace qs

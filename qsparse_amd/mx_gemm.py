@@ -3,15 +3,20 @@
 ``quantize_with_mx(..., block_dim=-1, return_codes=True)`` and ``export_integer`` hand out the bytes of an MX tensor -- one code
 per element, one E8M0 scale per block of 32 along K.  ``mx_matmul`` computes ``A . B^T`` directly on those bytes: on the GPU
 through the block-scaled MFMA of gfx950 (``qs_mx_matmul_v``: FP8 / FP6 / FP4 operands of either format on either side, float32
-accumulation), on the CPU by evaluating the definition in float64.  Training keeps using the simulated layers
-(``quantize(nn.Linear(...), callback=MXQuantizer(...))``); ``MXLinear`` is what such a layer becomes for inference."""
+accumulation), on the CPU by evaluating the definition in float64.  ``MXLinear`` is what a simulated layer
+(``quantize(nn.Linear(...), callback=MXQuantizer(...))``) becomes for inference.
+
+Training through the product: ``mx_linear`` / ``MXTrainLinear`` run all three matrix products of a linear layer's step -- forward,
+input gradient, weight gradient -- through ``mx_matmul``; their operands come from ``mx_quantize_2way``, which reads a tensor once
+and writes its codes with blocks along the rows and, transposed, with blocks along the columns (``qs_mx_quant2_v``)."""
 from typing import Optional
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from qsparse_amd import _hip
-from qsparse_amd.quantize import MX_BLOCK, MX_FORMATS, MXQuantizer, _mx_format, mx_dequantize, quantize_with_mx
+from qsparse_amd.quantize import MX_BLOCK, MX_FORMATS, MXQuantizer, _mx_aten, _mx_format, mx_dequantize, quantize_with_mx
 
 _OUT_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
@@ -151,4 +156,150 @@ class MXLinear(nn.Module):
             return mx_matmul(codes, scales, self.act_fmt, self.weight_codes, self.weight_scales, self.weight_fmt, self.bias, self.out_dtype)
 
 
-__all__ = ["mx_matmul", "MXLinear", "MX_FORMATS"]
+def mx_quantize_2way(x: torch.Tensor, row_fmt: Optional[str] = None, col_fmt: Optional[str] = None):
+    """MX codes of a 2-d float32 / bfloat16 / float16 tensor ``x [R, C]`` both ways from one read: returns ``(row_codes [R, C],
+    row_scales [R, ceil(C / 32)], col_codes [C, R], col_scales [C, ceil(R / 32)])`` -- the row pair is the codes and scales of
+    ``quantize_with_mx(x, row_fmt, -1, return_codes=True)``, the col pair those of ``quantize_with_mx(x.t().contiguous(), col_fmt,
+    -1, return_codes=True)``, bit for bit.  A pair whose format is ``None`` is not computed and comes back as ``(None, None)``; at
+    least one format must be given.  No de-quantized tensor is produced and the outputs are never differentiable.  GPU tensors take
+    the HIP kernel (one launch; no fallback), CPU tensors two evaluations of the definition."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"x must be a tensor, got {type(x).__name__}")
+    if x.dim() != 2:
+        raise ValueError(f"mx_quantize_2way needs a 2-d tensor [R, C], got shape {tuple(x.shape)}")
+    if x.dtype not in _OUT_DTYPES:
+        raise TypeError(f"x must be one of {_OUT_DTYPES}, got {x.dtype}")
+    if row_fmt is None and col_fmt is None:
+        raise ValueError("mx_quantize_2way needs row_fmt, col_fmt or both")
+    for fmt in (row_fmt, col_fmt):
+        if fmt is not None:
+            _mx_format(fmt)
+    x = x.detach()
+    if x.is_cuda:
+        return _hip.mx_quant2(x.contiguous(), row_fmt, col_fmt)
+    rc = rs = cc = cs = None
+    if row_fmt is not None:
+        _, rc, rs = _mx_aten(x, row_fmt, 1, torch.float32, True)
+    if col_fmt is not None:
+        _, cc, cs = _mx_aten(x.t(), col_fmt, 1, torch.float32, True)
+    return rc, rs, cc, cs
+
+
+class _MXLinearFunction(torch.autograd.Function):
+    """y = Q(x) Q(W)^T + b, dx = Q(dy) Q(W^T)^T, dW = Q(dy^T) Q(x^T)^T on MX codes; every quantizer straight-through"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, x_fmt, w_fmt, grad_fmt, need_col):
+        # `need_col`: a weight gradient can be asked for -- decided by mx_linear, where the grad mode is still the caller's (it is
+        # always off in here, and needs_input_grad is requires_grad whatever the mode)
+        N, K = weight.shape
+        x2 = x.reshape(-1, K)
+        x_row, x_rs, x_col, x_cs = mx_quantize_2way(x2, x_fmt, x_fmt if need_col else None)
+        w_row, w_rs, _, _ = mx_quantize_2way(weight, w_fmt, None)
+        b32 = None if bias is None else bias.detach().to(torch.float32)
+        y = mx_matmul(x_row, x_rs, x_fmt, w_row, w_rs, w_fmt, b32, x.dtype)
+        # the weight itself (autograd's version counter guards it), and x as its transposed codes: 1 + 1/32 bytes per element
+        ctx.save_for_backward(weight, x_col, x_cs)
+        ctx.fmts = (x_fmt, w_fmt, grad_fmt)
+        ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        return y.reshape(x.shape[:-1] + (N,))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        weight, x_col, x_cs = ctx.saved_tensors
+        x_fmt, w_fmt, grad_fmt = ctx.fmts
+        need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
+        N = weight.shape[0]
+        dy2 = dy.reshape(-1, N).contiguous()
+        dx = dw = db = None
+        if need_dx or need_dw:
+            g_row, g_rs, g_col, g_cs = mx_quantize_2way(dy2, grad_fmt if need_dx else None, grad_fmt if need_dw else None)
+        if need_dx:
+            _, _, w_col, w_cs = mx_quantize_2way(weight, None, w_fmt)
+            dx = mx_matmul(g_row, g_rs, grad_fmt, w_col, w_cs, w_fmt, None, ctx.x_dtype).reshape(ctx.x_shape)
+        if need_dw:
+            dw = mx_matmul(g_col, g_cs, grad_fmt, x_col, x_cs, x_fmt, None, weight.dtype)
+        if need_db:
+            db = dy2.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
+        return dx, dw, db, None, None, None, None
+
+
+def mx_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, x_fmt: str = "mxfp8_e4m3",
+              w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2") -> torch.Tensor:
+    """``F.linear`` whose three matrix products run on MX codes (``mx_matmul``), differentiable in ``x``, ``weight`` and ``bias``.
+    ``x`` is ``[..., K]`` in float32 / bfloat16 / float16, ``weight`` ``[N, K]`` and ``bias`` ``[N]`` in any of the three (float32
+    parameters next to a bfloat16 ``x`` are fine); the result is ``[..., N]`` in ``x.dtype``.  With ``Q_f(t)`` the MX quantization of
+    ``t`` in format ``f`` with blocks of 32 along its LAST axis, ``M`` the number of rows of ``x`` and ``dy`` the incoming gradient:
+
+        y  = Q_x(x) Q_w(W)^T + bias            blocks along K
+        dx = Q_g(dy) Q_w(W^T)^T                blocks along N
+        dW = Q_g(dy^T) Q_x(x^T)^T              blocks along M
+        db = sum over rows of dy (float32)
+
+    -- the straight-through rule of ``quantize_with_mx`` applied to all six quantizers.  ``mx_quantize_2way`` prepares the operands:
+    one call on ``x`` yields ``Q_x(x)`` and ``Q_x(x^T)`` (the latter is what the backward keeps instead of ``x``), one on ``dy``
+    both forms of the gradient.  Gradients nobody asks for are not computed, and without grad the transposed codes of ``x`` are
+    not either.  GPU tensors run HIP kernels only (no host synchronisation: a step can be graph-captured); CPU tensors evaluate
+    the same formulas in float64."""
+    for name, fmt in (("x_fmt", x_fmt), ("w_fmt", w_fmt), ("grad_fmt", grad_fmt)):
+        _mx_format(fmt)
+    for name, t in (("x", x), ("weight", weight)) + ((("bias", bias),) if bias is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+        if t.dtype not in _OUT_DTYPES:
+            raise TypeError(f"{name} must be one of {_OUT_DTYPES}, got {t.dtype}")
+        if t.device != x.device:
+            raise ValueError(f"x is on {x.device} but {name} on {t.device}")
+    if weight.dim() != 2:
+        raise ValueError(f"weight must be [N, K], got shape {tuple(weight.shape)}")
+    if x.dim() < 1 or x.shape[-1] != weight.shape[1]:
+        raise ValueError(f"x {tuple(x.shape)} and weight {tuple(weight.shape)} disagree on K (their last dimensions)")
+    if weight.shape[1] < 1:
+        raise ValueError("mx_linear needs K >= 1")
+    if bias is not None and tuple(bias.shape) != (weight.shape[0],):
+        raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({weight.shape[0]},)")
+    need_col = torch.is_grad_enabled() and weight.requires_grad
+    return _MXLinearFunction.apply(x, weight, bias, x_fmt, w_fmt, grad_fmt, need_col)
+
+
+class MXTrainLinear(nn.Linear):
+    """Drop-in ``nn.Linear`` that trains through MX matrix products: float ``weight`` / ``bias`` parameters (``nn.Linear``'s own
+    ``state_dict``), ``forward`` is ``mx_linear`` in the formats ``x_fmt`` / ``w_fmt`` / ``grad_fmt``.  Under ``torch.autocast``
+    the input is cast to the autocast dtype, as ``nn.Linear``'s would be, and the output has that dtype."""
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=None, x_fmt: str = "mxfp8_e4m3",
+                 w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2"):
+        super().__init__(in_features, out_features, bias=bias, device=device, dtype=dtype)
+        for fmt in (x_fmt, w_fmt, grad_fmt):
+            _mx_format(fmt)
+        self.x_fmt, self.w_fmt, self.grad_fmt = x_fmt, w_fmt, grad_fmt
+
+    @classmethod
+    def from_linear(cls, layer: nn.Linear, x_fmt: str = "mxfp8_e4m3", w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2"):
+        """a layer on ``layer``'s own parameters (shared, not copied)"""
+        if not isinstance(layer, nn.Linear):
+            raise TypeError(f"MXTrainLinear.from_linear needs an nn.Linear, got {type(layer).__name__}")
+        new = cls(layer.in_features, layer.out_features, bias=layer.bias is not None, device="meta", x_fmt=x_fmt, w_fmt=w_fmt,
+                  grad_fmt=grad_fmt)
+        new.weight, new.bias = layer.weight, layer.bias
+        new.train(layer.training)
+        return new
+
+    def extra_repr(self) -> str:
+        return f"{super().extra_repr()}, x_fmt={self.x_fmt!r}, w_fmt={self.w_fmt!r}, grad_fmt={self.grad_fmt!r}"
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        dev = x.device.type
+        if torch.is_autocast_enabled(dev):
+            x = x.to(torch.get_autocast_dtype(dev))
+        return mx_linear(x, self.weight, self.bias, self.x_fmt, self.w_fmt, self.grad_fmt)
+
+    def to_inference(self, act_fmt: Optional[str] = None, out_dtype: torch.dtype = torch.float32) -> MXLinear:
+        """the ``MXLinear`` on the current weight: its weight bytes are the row pair the training forward multiplies with"""
+        codes, scales, _, _ = mx_quantize_2way(self.weight, self.w_fmt, None)
+        return MXLinear(codes, scales, self.w_fmt, None if self.bias is None else self.bias.detach(), act_fmt or self.x_fmt, out_dtype)
+
+
+__all__ = ["mx_matmul", "MXLinear", "mx_quantize_2way", "mx_linear", "MXTrainLinear", "MX_FORMATS"]

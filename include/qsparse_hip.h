@@ -934,6 +934,70 @@ int qs_mx_quant2_v(const qs_mx_quant2_args* args);
 #define QS_MX_Q2_ROUTE_TILE_PLAIN 2
 int qs_mx_quant2_route(const qs_mx_quant2_args* args);
 
+/* ---- Stochastic rounding of the MX quantizers --------------------------------------------------------------------------------
+ * Added without raising QS_ABI_VERSION (27), by the same rule: four symbols are added, qs_mx_quant_args / qs_mx_quant2_args and their
+ * entry points stay as they are.  Each descriptor below is its predecessor, field for field, followed by the rounding operands.
+ *
+ * rounding == QS_MX_ROUND_NEAREST: the call is qs_mx_quant_fwd_v / qs_mx_quant2_v (same checks, routes, kernels, bytes).
+ * rounding == QS_MX_ROUND_STOCHASTIC changes ONE step of the definition above: how q_i is chosen between the two grid values that
+ * enclose v = x_i * 2^-e (float32, as before).  abs-max, scale byte, X, the NaN / Inf block, the clamp and the codes are unchanged.
+ *   ab = bits of |v|;  E = max(ab >> 23, 1);  m = (ab & 0x7FFFFF) | (ab >> 23 ? 0x800000 : 0)          (|v| = m 2^(E - 150))
+ *   ex = max(E, float32-biased exponent of the format's smallest normal);  sh = (23 - mbits) + (ex - E)   (>= 20)
+ *   T  = sh <= 56 ? floor(m 2^32 / 2^sh) : 0  in 64 bits;  n = (T + w) >> 32  with w the element's 32-bit random word
+ *   |q| = min(n 2^(ex - 127 - mbits), largest normal), the sign of v kept (a negative value that rounds to zero is -0)
+ * A value on the grid is returned unchanged for every w; w = 0 truncates toward zero; E[q] = v for every v that is not clamped.
+ * Random words, one per code, a pure function of the operands below (counter-based, no generator state):
+ *   j = index_base + the row-major linear index of the code in ITS OWN output tensor (codes / x for qs_mx_quant_sr_v; row_codes
+ *       [R, C] for the row pair, col_codes [C, R] for the col pair), 64 bits
+ *   k = seed + (step ? (uint64_t)*step : 0)  mod 2^64 -- *step is read by the KERNEL when it runs, never written: a launch captured
+ *       in a graph draws new words on every replay once the owner advances the counter on the stream
+ *   (o0, o1, o2, o3) = Philox4x32-10(counter = (lo32(j >> 2), hi32(j >> 2), rng_stream, 0), key = (lo32(k), hi32(k)))
+ *       (Random123's constants: multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85);  w = o[j & 3]
+ *   rng_stream: the descriptor's for qs_mx_quant_sr_v; 0 for the row pair and 1 for the col pair of qs_mx_quant2_sr_v -- so the col
+ *       pair is what qs_mx_quant_sr_v writes for the transpose of x with rng_stream = 1, the row pair what it writes for x with 0.
+ * Routes and alignment rules are those of the predecessor.  QS_ERR_ARG in addition: a rounding that is neither mode, a step pointer
+ * that is not 8-byte aligned, an index_base that is no multiple of 4 (checked in both modes).  No workspace, no atomics. */
+#define QS_MX_ROUND_NEAREST 0
+#define QS_MX_ROUND_STOCHASTIC 1
+typedef struct qs_mx_quant_sr_args {
+    uint32_t struct_size;        /* sizeof(qs_mx_quant_sr_args) as the caller compiled it */
+    int32_t format;              /* -- the fields of qs_mx_quant_args -- */
+    const void* x;
+    void* y;
+    uint8_t* codes;              /* nullable */
+    uint8_t* scales;             /* nullable */
+    int32_t xdt, ydt;
+    int64_t outer, n, inner;
+    qs_stream_t stream;
+    int32_t rounding;            /* QS_MX_ROUND_* */
+    int32_t rng_stream;          /* third counter word (`stream` above is the HIP stream) */
+    uint64_t seed;
+    const int64_t* step;         /* nullable (= 0); device memory, one int64, read by the kernel */
+    uint64_t index_base;         /* a multiple of 4 */
+} qs_mx_quant_sr_args;
+int qs_mx_quant_sr_v(const qs_mx_quant_sr_args* args);
+int qs_mx_quant_sr_route(const qs_mx_quant_sr_args* args);      /* QS_MX_ROUTE_*, 0, or the QS_ERR_* the call would return */
+
+typedef struct qs_mx_quant2_sr_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_quant2_sr_args) as the caller compiled it */
+    int32_t row_format, col_format;  /* -- the fields of qs_mx_quant2_args -- */
+    const void* x;
+    int32_t xdt;
+    uint8_t* row_codes;
+    uint8_t* row_scales;
+    uint8_t* col_codes;
+    uint8_t* col_scales;
+    int64_t R, C;
+    qs_stream_t stream;
+    int32_t rounding;                /* QS_MX_ROUND_* */
+    int32_t reserved0;
+    uint64_t seed;
+    const int64_t* step;             /* nullable (= 0); device memory, one int64, read by the kernel */
+    uint64_t index_base;             /* a multiple of 4; added to the indices of both pairs */
+} qs_mx_quant2_sr_args;
+int qs_mx_quant2_sr_v(const qs_mx_quant2_sr_args* args);
+int qs_mx_quant2_sr_route(const qs_mx_quant2_sr_args* args);    /* QS_MX_Q2_ROUTE_*, 0, or the QS_ERR_* the call would return */
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,6 @@
 // libqsparse_hip.so -- C ABI (include/qsparse_hip.h), the MX block-scaled quantizer forward (qs_mx.h): FP8 / FP6 / FP4 elements
-// with one E8M0 scale per block of 32 (OCP Microscaling Formats v1.0).
+// with one E8M0 scale per block of 32 (OCP Microscaling Formats v1.0), rounded to nearest-even (qs_mx_quant_fwd_v) or stochastically
+// (qs_mx_quant_sr_v: the same routes and kernels, instantiated with SR = true).
 // Host side: argument checks, route, launch configuration.  No allocation, no synchronisation.
 #include "qs_host.h"
 #include "qs_mx.h"
@@ -23,6 +24,48 @@ int mx_route(const qs_mx_quant_args& a) {
     return QS_MX_ROUTE_INNER_PLAIN;
 }
 
+template <bool SR>
+int mx_launch(const qs_mx_quant_args& a, int route, const MxSr& sr) {
+    const int64_t numel = a.outer * a.n * a.inner;
+    const int64_t nb = (a.n + QS_MX_BLOCK - 1) / QS_MX_BLOCK;
+    const MxFormat f = mx_format(a.format);
+    hipStream_t s = (hipStream_t)a.stream;
+    return with_dtype(a.xdt, [&](auto X) {
+        constexpr int XD = decltype(X)::value;
+        if (route == QS_MX_ROUTE_INNER_VEC) {
+            constexpr int64_t per_wg = (int64_t)kMxBlock * (XD == QS_F32 ? 4 : 8);
+            const int64_t grid = (numel + per_wg - 1) / per_wg;
+            if (grid > kMaxGrid) return (int)QS_ERR_ARG;
+            hipLaunchKernelGGL((mx_inner_vec_kernel<XD, SR>), dim3((unsigned)grid), dim3(kMxBlock), 0, s, f, a.x, a.y, a.codes, a.scales,
+                               numel, a.ydt, sr);
+            return launch_status();
+        }
+        if (route == QS_MX_ROUTE_INNER_PLAIN) {
+            const int64_t nblocks = a.outer * nb;
+            const int64_t grid = (nblocks + kMxBlock / 32 - 1) / (kMxBlock / 32);
+            if (grid > kMaxGrid) return (int)QS_ERR_ARG;
+            hipLaunchKernelGGL((mx_inner_plain_kernel<XD, SR>), dim3((unsigned)grid), dim3(kMxBlock), 0, s, f, a.x, a.y, a.codes, a.scales,
+                               nblocks, a.n, nb, a.ydt, sr);
+            return launch_status();
+        }
+        const int64_t total = a.outer * nb * a.inner;
+        const int64_t grid = (total + kMxBlock - 1) / kMxBlock;
+        if (grid > kMaxGrid) return (int)QS_ERR_ARG;
+        hipLaunchKernelGGL((mx_strided_kernel<XD, SR>), dim3((unsigned)grid), dim3(kMxBlock), 0, s, f, a.x, a.y, a.codes, a.scales, total, a.n,
+                           a.inner, nb, a.ydt, sr);
+        return launch_status();
+    });
+}
+
+// the descriptor of the stochastic entry points begins with its predecessor's fields, in place
+static_assert(offsetof(qs_mx_quant_sr_args, rounding) == sizeof(qs_mx_quant_args), "qs_mx_quant_sr_args must extend qs_mx_quant_args");
+inline qs_mx_quant_args base_of(const qs_mx_quant_sr_args& a) {
+    qs_mx_quant_args b;
+    memcpy(&b, &a, sizeof(b));
+    b.struct_size = sizeof(b);
+    return b;
+}
+
 }  // namespace
 
 extern "C" {
@@ -38,35 +81,26 @@ int qs_mx_quant_fwd_v(const qs_mx_quant_args* args) {
     if (!take_args(args, &a)) return QS_ERR_ARG;
     const int route = mx_route(a);
     if (route <= 0) return route;
-    const int64_t numel = a.outer * a.n * a.inner;
-    const int64_t nb = (a.n + QS_MX_BLOCK - 1) / QS_MX_BLOCK;
-    const MxFormat f = mx_format(a.format);
-    hipStream_t s = (hipStream_t)a.stream;
-    return with_dtype(a.xdt, [&](auto X) {
-        constexpr int XD = decltype(X)::value;
-        if (route == QS_MX_ROUTE_INNER_VEC) {
-            constexpr int64_t per_wg = (int64_t)kMxBlock * (XD == QS_F32 ? 4 : 8);
-            const int64_t grid = (numel + per_wg - 1) / per_wg;
-            if (grid > kMaxGrid) return (int)QS_ERR_ARG;
-            hipLaunchKernelGGL((mx_inner_vec_kernel<XD>), dim3((unsigned)grid), dim3(kMxBlock), 0, s, f, a.x, a.y, a.codes, a.scales,
-                               numel, a.ydt);
-            return launch_status();
-        }
-        if (route == QS_MX_ROUTE_INNER_PLAIN) {
-            const int64_t nblocks = a.outer * nb;
-            const int64_t grid = (nblocks + kMxBlock / 32 - 1) / (kMxBlock / 32);
-            if (grid > kMaxGrid) return (int)QS_ERR_ARG;
-            hipLaunchKernelGGL((mx_inner_plain_kernel<XD>), dim3((unsigned)grid), dim3(kMxBlock), 0, s, f, a.x, a.y, a.codes, a.scales,
-                               nblocks, a.n, nb, a.ydt);
-            return launch_status();
-        }
-        const int64_t total = a.outer * nb * a.inner;
-        const int64_t grid = (total + kMxBlock - 1) / kMxBlock;
-        if (grid > kMaxGrid) return (int)QS_ERR_ARG;
-        hipLaunchKernelGGL((mx_strided_kernel<XD>), dim3((unsigned)grid), dim3(kMxBlock), 0, s, f, a.x, a.y, a.codes, a.scales, total, a.n,
-                           a.inner, nb, a.ydt);
-        return launch_status();
-    });
+    return mx_launch<false>(a, route, MxSr{});
+}
+
+int qs_mx_quant_sr_route(const qs_mx_quant_sr_args* args) {
+    qs_mx_quant_sr_args a;
+    if (!take_args(args, &a)) return QS_ERR_ARG;
+    const int st = mx_sr_check(a.rounding, a.step, a.index_base);
+    return st ? st : mx_route(base_of(a));
+}
+
+int qs_mx_quant_sr_v(const qs_mx_quant_sr_args* args) {
+    qs_mx_quant_sr_args a;
+    if (!take_args(args, &a)) return QS_ERR_ARG;
+    const int st = mx_sr_check(a.rounding, a.step, a.index_base);
+    if (st) return st;
+    const qs_mx_quant_args b = base_of(a);
+    const int route = mx_route(b);
+    if (route <= 0) return route;
+    if (a.rounding == QS_MX_ROUND_NEAREST) return mx_launch<false>(b, route, MxSr{});
+    return mx_launch<true>(b, route, MxSr{a.seed, a.step, a.index_base, (uint32_t)a.rng_stream});
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // libqsparse_hip.so -- C ABI (include/qsparse_hip.h), the two-way, codes-only MX quantizer (qs_mx_quant2.h): one read of x [R, C],
-// codes and E8M0 scales with blocks along C and -- stored transposed -- with blocks along R.
+// codes and E8M0 scales with blocks along C and -- stored transposed -- with blocks along R; qs_mx_quant2_sr_v is the same call with a
+// rounding mode (nearest-even or stochastic: the kernel instantiated with SR = true).
 // Host side: argument checks, route, launch configuration.  No allocation, no synchronisation.
 #include "qs_host.h"
 #include "qs_mx_quant2.h"
@@ -28,6 +29,35 @@ int mx_quant2_route(const qs_mx_quant2_args& a) {
     return vec ? QS_MX_Q2_ROUTE_TILE_VEC : QS_MX_Q2_ROUTE_TILE_PLAIN;
 }
 
+template <bool SR>
+int mx_quant2_launch(const qs_mx_quant2_args& a, int route, const MxSr& sr) {
+    // a pair that is not asked for keeps a valid descriptor the kernel never reads
+    const MxFormat fr = mx_format(a.row_codes ? a.row_format : 0), fc = mx_format(a.col_codes ? a.col_format : 0);
+    const int tiles_c = (int)((a.C + kMxq2Cols - 1) / kMxq2Cols);
+    const int64_t grid = ((a.R + kMxq2Rows - 1) / kMxq2Rows) * tiles_c;
+    hipStream_t s = (hipStream_t)a.stream;
+    return with_dtype(a.xdt, [&](auto X) {
+        constexpr int XD = decltype(X)::value;
+        // a lane stores 8 (two-byte inputs) or 4 (float32) row codes at once where row_codes keeps that alignment in every row
+        const int row_vec = a.row_codes && (((uintptr_t)a.row_codes) & (XD == QS_F32 ? 3u : 7u)) == 0;
+        if (route == QS_MX_Q2_ROUTE_TILE_VEC)
+            hipLaunchKernelGGL((mx_quant2_kernel<XD, true, SR>), dim3((unsigned)grid), dim3(kMxq2Threads), 0, s, fr, fc, a.x, a.row_codes,
+                               a.row_scales, a.col_codes, a.col_scales, a.R, a.C, tiles_c, row_vec, sr);
+        else
+            hipLaunchKernelGGL((mx_quant2_kernel<XD, false, SR>), dim3((unsigned)grid), dim3(kMxq2Threads), 0, s, fr, fc, a.x, a.row_codes,
+                               a.row_scales, a.col_codes, a.col_scales, a.R, a.C, tiles_c, 0, sr);
+        return launch_status();
+    });
+}
+
+static_assert(offsetof(qs_mx_quant2_sr_args, rounding) == sizeof(qs_mx_quant2_args), "qs_mx_quant2_sr_args must extend qs_mx_quant2_args");
+inline qs_mx_quant2_args base_of(const qs_mx_quant2_sr_args& a) {
+    qs_mx_quant2_args b;
+    memcpy(&b, &a, sizeof(b));
+    b.struct_size = sizeof(b);
+    return b;
+}
+
 }  // namespace
 
 extern "C" {
@@ -43,23 +73,26 @@ int qs_mx_quant2_v(const qs_mx_quant2_args* args) {
     if (!take_args(args, &a)) return QS_ERR_ARG;
     const int route = mx_quant2_route(a);
     if (route <= 0) return route;
-    // a pair that is not asked for keeps a valid descriptor the kernel never reads
-    const MxFormat fr = mx_format(a.row_codes ? a.row_format : 0), fc = mx_format(a.col_codes ? a.col_format : 0);
-    const int tiles_c = (int)((a.C + kMxq2Cols - 1) / kMxq2Cols);
-    const int64_t grid = ((a.R + kMxq2Rows - 1) / kMxq2Rows) * tiles_c;
-    hipStream_t s = (hipStream_t)a.stream;
-    return with_dtype(a.xdt, [&](auto X) {
-        constexpr int XD = decltype(X)::value;
-        // a lane stores 8 (two-byte inputs) or 4 (float32) row codes at once where row_codes keeps that alignment in every row
-        const int row_vec = a.row_codes && (((uintptr_t)a.row_codes) & (XD == QS_F32 ? 3u : 7u)) == 0;
-        if (route == QS_MX_Q2_ROUTE_TILE_VEC)
-            hipLaunchKernelGGL((mx_quant2_kernel<XD, true>), dim3((unsigned)grid), dim3(kMxq2Threads), 0, s, fr, fc, a.x, a.row_codes,
-                               a.row_scales, a.col_codes, a.col_scales, a.R, a.C, tiles_c, row_vec);
-        else
-            hipLaunchKernelGGL((mx_quant2_kernel<XD, false>), dim3((unsigned)grid), dim3(kMxq2Threads), 0, s, fr, fc, a.x, a.row_codes,
-                               a.row_scales, a.col_codes, a.col_scales, a.R, a.C, tiles_c, 0);
-        return launch_status();
-    });
+    return mx_quant2_launch<false>(a, route, MxSr{});
+}
+
+int qs_mx_quant2_sr_route(const qs_mx_quant2_sr_args* args) {
+    qs_mx_quant2_sr_args a;
+    if (!take_args(args, &a)) return QS_ERR_ARG;
+    const int st = mx_sr_check(a.rounding, a.step, a.index_base);
+    return st ? st : mx_quant2_route(base_of(a));
+}
+
+int qs_mx_quant2_sr_v(const qs_mx_quant2_sr_args* args) {
+    qs_mx_quant2_sr_args a;
+    if (!take_args(args, &a)) return QS_ERR_ARG;
+    const int st = mx_sr_check(a.rounding, a.step, a.index_base);
+    if (st) return st;
+    const qs_mx_quant2_args b = base_of(a);
+    const int route = mx_quant2_route(b);
+    if (route <= 0) return route;
+    if (a.rounding == QS_MX_ROUND_NEAREST) return mx_quant2_launch<false>(b, route, MxSr{});
+    return mx_quant2_launch<true>(b, route, MxSr{a.seed, a.step, a.index_base, 0u});      // (the kernel sets the stream per phase)
 }
 
 }  // extern "C"

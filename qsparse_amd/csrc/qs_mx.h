@@ -12,8 +12,14 @@
 //   q * X  a multiplication by 2^e (2^-127 is the float32 subnormal 0x00400000), exact
 // The element format is a RUN-TIME descriptor (wave-uniform scalars: shift counts, two constants), so the kernels are templated on
 // the input dtype alone: 3 kernels x 3 dtypes for the five formats.  Output dtype and `codes != nullptr` branch wave-uniformly.
+//
+// Stochastic rounding (include/qsparse_hip.h, "Stochastic rounding of the MX quantizers") replaces the RNE step alone, by
+// mx_round_abs_sr: the 32-bit word of code j of an output tensor is word j & 3 of Philox4x32-10 (qs_philox.h) at counter
+// (j >> 2, stream), key = seed + *step -- `step` is read from device memory by the kernel, so a captured launch draws fresh words on
+// every replay.  The mode is the template parameter SR of every kernel: the SR = false instantiations are the kernels as they were.
 #pragma once
 #include "qs_common.h"
+#include "qs_philox.h"
 
 namespace qs {
 
@@ -60,6 +66,14 @@ inline MxFormat mx_format(int format) {
     return f;
 }
 
+// the stochastic operands of a descriptor (host side): QS_ERR_ARG for an unknown mode or -- in either mode -- a `step` pointer off
+// its 8-byte alignment or an index_base that is no multiple of 4
+inline int mx_sr_check(int rounding, const int64_t* step, uint64_t index_base) {
+    if (rounding != QS_MX_ROUND_NEAREST && rounding != QS_MX_ROUND_STOCHASTIC) return QS_ERR_ARG;
+    if ((((uintptr_t)step) & 7u) != 0 || (index_base & 3u) != 0) return QS_ERR_ARG;
+    return 0;
+}
+
 __device__ __forceinline__ uint32_t mx_abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
 
 // `am`: the maximum of the block's |x| bit patterns
@@ -86,6 +100,57 @@ __device__ __forceinline__ float mx_round_abs(float x, const MxScale& s, const M
     return r > f.max_normal ? f.max_normal : r;
 }
 
+// ---- stochastic rounding ---------------------------------------------------------------------------------------------------
+// what a launch carries (kernel argument); `step` is nullable (= 0) and only ever read
+struct MxSr {
+    uint64_t seed;
+    const int64_t* step;
+    uint64_t base;           // index_base, a multiple of 4
+    uint32_t stream;         // third counter word: 0 one-way / row pair, 1 col pair (the two-way kernel sets it per phase)
+};
+
+struct MxSrKey {
+    uint32_t k0, k1;
+};
+
+__device__ __forceinline__ MxSrKey mx_sr_key(const MxSr& sr) {
+    const uint64_t k = sr.seed + (sr.step ? (uint64_t)*sr.step : 0ull);        // (wave-uniform load)
+    return MxSrKey{(uint32_t)k, (uint32_t)(k >> 32)};
+}
+
+// the words of the four codes j .. j + 3, j % 4 == 0
+__device__ __forceinline__ void mx_sr_words4(const MxSrKey& k, uint32_t stream, uint64_t j, uint32_t (&w)[4]) {
+    const uint64_t q = j >> 2;
+    const uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), stream, 0u};
+    philox4x32_10(c, k.k0, k.k1, w);
+}
+
+// the word of code j, any j (one call per element: the routes that are correct, not tuned)
+__device__ __forceinline__ uint32_t mx_sr_word(const MxSrKey& k, uint32_t stream, uint64_t j) {
+    uint32_t w[4];
+    mx_sr_words4(k, stream, j & ~3ull, w);
+    const uint32_t i = (uint32_t)j & 3u;
+    return i == 0 ? w[0] : i == 1 ? w[1] : i == 2 ? w[2] : w[3];
+}
+
+// mx_round_abs with the rounding step drawn from the word `w`: |v| = m 2^(E - 150) lies n = floor(m / 2^sh) grid steps of
+// 2^(ex - 127 - mbits) above zero plus a remainder; T holds m / 2^sh with 32 fractional bits, so (T + w) >> 32 adds one step with
+// probability remainder / step.  sh >= 20 always; with sh > 56 the value is below 2^-32 of a step and stays where it is (zero).
+__device__ __forceinline__ float mx_round_abs_sr(float x, const MxScale& s, const MxFormat& f, uint32_t w, uint32_t& sign) {
+    const uint32_t vb = __float_as_uint(x * s.inv);
+    sign = vb & 0x80000000u;
+    const uint32_t ab = vb & 0x7fffffffu;
+    const uint32_t field = ab >> 23;
+    const int E = field ? (int)field : 1;
+    const uint32_t m = (ab & 0x7fffffu) | (field ? 0x800000u : 0u);
+    const int ex = E < f.min_exp_biased ? f.min_exp_biased : E;
+    const int sh = (23 - f.mbits) + (ex - E);
+    const uint64_t T = sh <= 56 ? (((uint64_t)m << 32) >> sh) : 0ull;
+    const uint32_t n = (uint32_t)((T + w) >> 32);                               // <= 2^(mbits + 1): exact as a float32
+    const float r = (float)n * __uint_as_float((uint32_t)(ex - f.mbits) << 23); // n 2^(ex - 127 - mbits), exact
+    return r > f.max_normal ? f.max_normal : r;
+}
+
 __device__ __forceinline__ float mx_value(float r, uint32_t sign, const MxScale& s) {
     return s.nan ? __uint_as_float(0x7fc00000u) : __uint_as_float(__float_as_uint(r * s.X) | sign);
 }
@@ -105,10 +170,10 @@ __device__ __forceinline__ uint32_t mx_code(float r, uint32_t sign, const MxScal
 // ------------------------------------------------------------------------------------------------
 constexpr int kMxBlock = 256;
 
-template <int XDT>
+template <int XDT, bool SR>
 __global__ __launch_bounds__(kMxBlock) void mx_inner_vec_kernel(MxFormat f, const void* __restrict__ x, void* __restrict__ y,
                                                                 uint8_t* __restrict__ codes, uint8_t* __restrict__ scales,
-                                                                int64_t numel, int ydt) {
+                                                                int64_t numel, int ydt, MxSr sr) {
     constexpr int V = XDT == QS_F32 ? 4 : 8;      // elements per lane
     constexpr int LPB = QS_MX_BLOCK / V;          // lanes per block
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -144,8 +209,19 @@ __global__ __launch_bounds__(kMxBlock) void mx_inner_vec_kernel(MxFormat f, cons
     const MxScale s = mx_scale(am, f);
     float r[V];
     uint32_t sg[V];
+    if constexpr (SR) {                           // e % V == 0 and sr.base % 4 == 0: one Philox call per 4 of the lane's codes
+        const MxSrKey key = mx_sr_key(sr);
 #pragma unroll
-    for (int j = 0; j < V; ++j) r[j] = mx_round_abs(v[j], s, f, sg[j]);
+        for (int q = 0; q < V; q += 4) {
+            uint32_t w[4];
+            mx_sr_words4(key, sr.stream, sr.base + (uint64_t)e + q, w);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r[q + j] = mx_round_abs_sr(v[q + j], s, f, w[j], sg[q + j]);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j) r[j] = mx_round_abs(v[j], s, f, sg[j]);
+    }
     if (scales && in && (lane & (LPB - 1)) == 0) scales[e >> 5] = (uint8_t)s.byte;
     if (codes && in) {
         uint32_t c[V];
@@ -195,10 +271,10 @@ __global__ __launch_bounds__(kMxBlock) void mx_inner_vec_kernel(MxFormat f, cons
 // Innermost axis, any line length and any element-aligned base: one element per lane, a block is half a wave (five __shfl_xor
 // steps), every access coalesced.  `nb` = ceil(n / 32) blocks per line; lanes past the end of a line load nothing and store nothing.
 // ------------------------------------------------------------------------------------------------
-template <int XDT>
+template <int XDT, bool SR>
 __global__ __launch_bounds__(kMxBlock) void mx_inner_plain_kernel(MxFormat f, const void* __restrict__ x, void* __restrict__ y,
                                                                   uint8_t* __restrict__ codes, uint8_t* __restrict__ scales,
-                                                                  int64_t nblocks, int64_t n, int64_t nb, int ydt) {
+                                                                  int64_t nblocks, int64_t n, int64_t nb, int ydt, MxSr sr) {
     const int64_t b = ((int64_t)blockIdx.x * kMxBlock + threadIdx.x) >> 5;       // block index = line * nb + kb
     const int sub = threadIdx.x & 31;
     const bool okb = b < nblocks;
@@ -215,7 +291,9 @@ __global__ __launch_bounds__(kMxBlock) void mx_inner_plain_kernel(MxFormat f, co
     }
     const MxScale s = mx_scale(am, f);
     uint32_t sg;
-    const float r = mx_round_abs(v, s, f, sg);
+    float r;
+    if constexpr (SR) r = mx_round_abs_sr(v, s, f, mx_sr_word(mx_sr_key(sr), sr.stream, sr.base + (uint64_t)e), sg);
+    else r = mx_round_abs(v, s, f, sg);
     if (scales && okb && sub == 0) scales[b] = (uint8_t)s.byte;
     if (!in) return;
     if (codes) codes[e] = (uint8_t)mx_code(r, sg, s, f);
@@ -229,10 +307,10 @@ __global__ __launch_bounds__(kMxBlock) void mx_inner_plain_kernel(MxFormat f, co
 // load and store of a wave is coalesced; a thread walks the <= 32 elements of its block at stride `inner` and keeps them in
 // registers.  Thread t = (o * nb + kb) * inner + i, which is also the index of its scale byte.
 // ------------------------------------------------------------------------------------------------
-template <int XDT>
+template <int XDT, bool SR>
 __global__ __launch_bounds__(kMxBlock) void mx_strided_kernel(MxFormat f, const void* __restrict__ x, void* __restrict__ y,
                                                               uint8_t* __restrict__ codes, uint8_t* __restrict__ scales,
-                                                              int64_t total, int64_t n, int64_t inner, int64_t nb, int ydt) {
+                                                              int64_t total, int64_t n, int64_t inner, int64_t nb, int ydt, MxSr sr) {
     const int64_t t = (int64_t)blockIdx.x * kMxBlock + threadIdx.x;
     if (t >= total) return;
     const int64_t ob = t / inner, i = t - ob * inner;
@@ -250,12 +328,16 @@ __global__ __launch_bounds__(kMxBlock) void mx_strided_kernel(MxFormat f, const 
     }
     const MxScale s = mx_scale(am, f);
     if (scales) scales[t] = (uint8_t)s.byte;
+    MxSrKey key = {0u, 0u};
+    if constexpr (SR) key = mx_sr_key(sr);
 #pragma unroll
     for (int j = 0; j < QS_MX_BLOCK; ++j) {
         if (j < cnt) {
             uint32_t sg;
-            const float r = mx_round_abs(v[j], s, f, sg);
             const int64_t e = base + j * inner;
+            float r;
+            if constexpr (SR) r = mx_round_abs_sr(v[j], s, f, mx_sr_word(key, sr.stream, sr.base + (uint64_t)e), sg);
+            else r = mx_round_abs(v[j], s, f, sg);
             if (codes) codes[e] = (uint8_t)mx_code(r, sg, s, f);
             const float out = mx_value(r, sg, s);
             if (ydt == QS_F32) store1<QS_F32>(y, e, out);

@@ -17,6 +17,9 @@
 //     into two 16-byte stores at col_codes[c][r0 + 32 b ..]: the four waves of the group write 128 contiguous bytes per output row.
 // No atomics, no workspace; a null pair skips its phase (wave-uniform), a null col pair also the LDS traffic and the barrier.
 // VEC = false is the same tiling with element accesses, each predicated on its own index: any R, C >= 1, any element-aligned base.
+// SR = true rounds stochastically (qs_mx.h): the row pair draws its words at stream 0 and index gr * C + gc of row_codes, the col pair
+// at stream 1 and index oc * R + orow of col_codes.  On the VEC route both indices are multiples of 4 at a lane's first code, so a
+// Philox call serves four codes: V / 4 calls per lane and pass in phase 1, eight per lane in phase 2.  PLAIN spends a call per code.
 #pragma once
 #include "qs_mx.h"
 
@@ -43,11 +46,11 @@ __device__ __forceinline__ float mxq2_widen(typename Mxq2Raw<XDT>::type raw) {
 __device__ __forceinline__ uint32_t mxq2_pack4(const uint32_t* c) { return c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24); }
 
 // `row_vec`: row_codes is aligned to the V bytes a lane stores at once (VEC only; otherwise byte stores)
-template <int XDT, bool VEC>
+template <int XDT, bool VEC, bool SR>
 __global__ __launch_bounds__(kMxq2Threads) void mx_quant2_kernel(MxFormat fr, MxFormat fc, const void* __restrict__ x,
                                                                  uint8_t* __restrict__ row_codes, uint8_t* __restrict__ row_scales,
                                                                  uint8_t* __restrict__ col_codes, uint8_t* __restrict__ col_scales,
-                                                                 int64_t R, int64_t C, int tiles_c, int row_vec) {
+                                                                 int64_t R, int64_t C, int tiles_c, int row_vec, MxSr sr) {
     using raw_t = typename Mxq2Raw<XDT>::type;
     constexpr int V = XDT == QS_F32 ? 4 : 8;              // elements per lane and pass: 16 bytes
     constexpr int LPB = QS_MX_BLOCK / V;                  // lanes per row block
@@ -60,6 +63,8 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_quant2_kernel(MxFormat fr, Mx
     const int64_t r0 = (int64_t)(blockIdx.x / tiles_c) * kMxq2Rows;
     const int64_t c0 = (int64_t)(blockIdx.x % tiles_c) * kMxq2Cols;
     const int64_t nbc = (C + QS_MX_BLOCK - 1) / QS_MX_BLOCK, nbr = (R + QS_MX_BLOCK - 1) / QS_MX_BLOCK;
+    MxSrKey key = {0u, 0u};
+    if constexpr (SR) key = mx_sr_key(sr);
 
     // ---- phase 1: load, stage, row pair --------------------------------------------------------------------------------------
     const int lrow = tid / LPR, lcol = (tid % LPR) * V;
@@ -104,11 +109,27 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_quant2_kernel(MxFormat fr, Mx
             }
             const MxScale s = mx_scale(am, fr);
             uint32_t c[V];
+            if constexpr (SR && VEC) {                    // (C % V == 0, gc % V == 0: the lane's first index is a multiple of 4)
 #pragma unroll
-            for (int j = 0; j < V; ++j) {
-                uint32_t sg;
-                const float r = mx_round_abs(v[j], s, fr, sg);
-                c[j] = mx_code(r, sg, s, fr);
+                for (int q = 0; q < V; q += 4) {
+                    uint32_t w[4];
+                    mx_sr_words4(key, 0u, sr.base + (uint64_t)(gr * C + gc) + q, w);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        uint32_t sg;
+                        const float r = mx_round_abs_sr(v[q + j], s, fr, w[j], sg);
+                        c[q + j] = mx_code(r, sg, s, fr);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    uint32_t sg;
+                    float r;
+                    if constexpr (SR) r = mx_round_abs_sr(v[j], s, fr, mx_sr_word(key, 0u, sr.base + (uint64_t)(gr * C + gc + j)), sg);
+                    else r = mx_round_abs(v[j], s, fr, sg);
+                    c[j] = mx_code(r, sg, s, fr);
+                }
             }
             if (gr < R && gc < C) {
                 if ((tid % LPB) == 0) row_scales[gr * nbc + (gc >> 5)] = (uint8_t)s.byte;
@@ -142,11 +163,27 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_quant2_kernel(MxFormat fr, Mx
     const MxScale s = mx_scale(am, fc);
     col_scales[oc * nbr + (orow >> 5)] = (uint8_t)s.byte;
     uint32_t c[QS_MX_BLOCK];
+    if constexpr (SR && VEC) {                            // (R % 16 == 0, orow % 32 == 0: eight calls for the lane's 32 codes)
 #pragma unroll
-    for (int j = 0; j < QS_MX_BLOCK; ++j) {
-        uint32_t sg;
-        const float r = mx_round_abs(w[j], s, fc, sg);
-        c[j] = mx_code(r, sg, s, fc);
+        for (int q = 0; q < QS_MX_BLOCK; q += 4) {
+            uint32_t rw[4];
+            mx_sr_words4(key, 1u, sr.base + (uint64_t)(oc * R + orow) + q, rw);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint32_t sg;
+                const float r = mx_round_abs_sr(w[q + j], s, fc, rw[j], sg);
+                c[q + j] = mx_code(r, sg, s, fc);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < QS_MX_BLOCK; ++j) {
+            uint32_t sg;
+            float r;
+            if constexpr (SR) r = mx_round_abs_sr(w[j], s, fc, mx_sr_word(key, 1u, sr.base + (uint64_t)(oc * R + orow + j)), sg);
+            else r = mx_round_abs(w[j], s, fc, sg);
+            c[j] = mx_code(r, sg, s, fc);
+        }
     }
     uint8_t* out = col_codes + oc * R + orow;
     if constexpr (VEC) {                                  // (R % 16 == 0: each half of the block is inside or outside as a whole)

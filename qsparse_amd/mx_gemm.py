@@ -16,7 +16,8 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from qsparse_amd import _hip
-from qsparse_amd.quantize import MX_BLOCK, MX_FORMATS, MXQuantizer, _mx_aten, _mx_format, mx_dequantize, quantize_with_mx
+from qsparse_amd.quantize import (MX_BLOCK, MX_FORMATS, MXQuantizer, _mx_aten, _mx_check_rounding, _mx_format, _mx_sr_words,
+                                  mx_dequantize, quantize_with_mx)
 
 _OUT_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
@@ -156,13 +157,18 @@ class MXLinear(nn.Module):
             return mx_matmul(codes, scales, self.act_fmt, self.weight_codes, self.weight_scales, self.weight_fmt, self.bias, self.out_dtype)
 
 
-def mx_quantize_2way(x: torch.Tensor, row_fmt: Optional[str] = None, col_fmt: Optional[str] = None):
+def mx_quantize_2way(x: torch.Tensor, row_fmt: Optional[str] = None, col_fmt: Optional[str] = None, rounding: str = "nearest",
+                     seed: int = 0, step: Optional[torch.Tensor] = None):
     """MX codes of a 2-d float32 / bfloat16 / float16 tensor ``x [R, C]`` both ways from one read: returns ``(row_codes [R, C],
     row_scales [R, ceil(C / 32)], col_codes [C, R], col_scales [C, ceil(R / 32)])`` -- the row pair is the codes and scales of
     ``quantize_with_mx(x, row_fmt, -1, return_codes=True)``, the col pair those of ``quantize_with_mx(x.t().contiguous(), col_fmt,
     -1, return_codes=True)``, bit for bit.  A pair whose format is ``None`` is not computed and comes back as ``(None, None)``; at
     least one format must be given.  No de-quantized tensor is produced and the outputs are never differentiable.  GPU tensors take
-    the HIP kernel (one launch; no fallback), CPU tensors two evaluations of the definition."""
+    the HIP kernel (one launch; no fallback), CPU tensors two evaluations of the definition.
+
+    ``rounding="stochastic"`` (``seed``, ``step`` as in ``quantize_with_mx``): the row pair is the stochastic one-way quantizer on
+    ``x`` with ``stream=0``, the col pair the one on ``x.t().contiguous()`` with ``stream=1`` -- the two forms of a tensor are
+    rounded independently, each indexed in its own output."""
     if not isinstance(x, torch.Tensor):
         raise TypeError(f"x must be a tensor, got {type(x).__name__}")
     if x.dim() != 2:
@@ -174,14 +180,19 @@ def mx_quantize_2way(x: torch.Tensor, row_fmt: Optional[str] = None, col_fmt: Op
     for fmt in (row_fmt, col_fmt):
         if fmt is not None:
             _mx_format(fmt)
+    _mx_check_rounding(rounding, step, x)
     x = x.detach()
+    sr = rounding == "stochastic"
     if x.is_cuda:
-        return _hip.mx_quant2(x.contiguous(), row_fmt, col_fmt)
+        if not sr:
+            return _hip.mx_quant2(x.contiguous(), row_fmt, col_fmt)
+        return _hip.mx_quant2(x.contiguous(), row_fmt, col_fmt, rounding, seed, step)
     rc = rs = cc = cs = None
     if row_fmt is not None:
-        _, rc, rs = _mx_aten(x, row_fmt, 1, torch.float32, True)
+        _, rc, rs = _mx_aten(x, row_fmt, 1, torch.float32, True, _mx_sr_words(x.shape, seed, step, 0) if sr else None)
     if col_fmt is not None:
-        _, cc, cs = _mx_aten(x.t(), col_fmt, 1, torch.float32, True)
+        xt = x.t()
+        _, cc, cs = _mx_aten(xt, col_fmt, 1, torch.float32, True, _mx_sr_words(xt.shape, seed, step, 1) if sr else None)
     return rc, rs, cc, cs
 
 
@@ -189,7 +200,7 @@ class _MXLinearFunction(torch.autograd.Function):
     """y = Q(x) Q(W)^T + b, dx = Q(dy) Q(W^T)^T, dW = Q(dy^T) Q(x^T)^T on MX codes; every quantizer straight-through"""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, x_fmt, w_fmt, grad_fmt, need_col):
+    def forward(ctx, x, weight, bias, x_fmt, w_fmt, grad_fmt, need_col, grad_rounding="nearest", seed=0, step=None):
         # `need_col`: a weight gradient can be asked for -- decided by mx_linear, where the grad mode is still the caller's (it is
         # always off in here, and needs_input_grad is requires_grad whatever the mode)
         N, K = weight.shape
@@ -201,6 +212,8 @@ class _MXLinearFunction(torch.autograd.Function):
         # the weight itself (autograd's version counter guards it), and x as its transposed codes: 1 + 1/32 bytes per element
         ctx.save_for_backward(weight, x_col, x_cs)
         ctx.fmts = (x_fmt, w_fmt, grad_fmt)
+        # `step` is advanced in place by the backward: an attribute, not a saved tensor (no version check, nothing to differentiate)
+        ctx.sr = (seed, step) if grad_rounding == "stochastic" else None
         ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
         ctx.bias_dtype = None if bias is None else bias.dtype
         return y.reshape(x.shape[:-1] + (N,))
@@ -214,8 +227,16 @@ class _MXLinearFunction(torch.autograd.Function):
         N = weight.shape[0]
         dy2 = dy.reshape(-1, N).contiguous()
         dx = dw = db = None
-        if need_dx or need_dw:
+        if (need_dx or need_dw) and ctx.sr is None:
             g_row, g_rs, g_col, g_cs = mx_quantize_2way(dy2, grad_fmt if need_dx else None, grad_fmt if need_dw else None)
+        elif need_dx or need_dw:
+            # the two forms of dy alone are rounded stochastically (row pair: stream 0, for dx; col pair: stream 1, for dW); then
+            # the counter moves on, on the stream: the next backward -- or the next replay of this one -- draws new words
+            seed, step = ctx.sr
+            g_row, g_rs, g_col, g_cs = mx_quantize_2way(dy2, grad_fmt if need_dx else None, grad_fmt if need_dw else None,
+                                                        "stochastic", seed, step)
+            if step is not None:
+                step.add_(1)
         if need_dx:
             _, _, w_col, w_cs = mx_quantize_2way(weight, None, w_fmt)
             dx = mx_matmul(g_row, g_rs, grad_fmt, w_col, w_cs, w_fmt, None, ctx.x_dtype).reshape(ctx.x_shape)
@@ -223,11 +244,12 @@ class _MXLinearFunction(torch.autograd.Function):
             dw = mx_matmul(g_col, g_cs, grad_fmt, x_col, x_cs, x_fmt, None, weight.dtype)
         if need_db:
             db = dy2.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
-        return dx, dw, db, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None
 
 
 def mx_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, x_fmt: str = "mxfp8_e4m3",
-              w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2") -> torch.Tensor:
+              w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2", grad_rounding: str = "nearest", seed: int = 0,
+              step: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``F.linear`` whose three matrix products run on MX codes (``mx_matmul``), differentiable in ``x``, ``weight`` and ``bias``.
     ``x`` is ``[..., K]`` in float32 / bfloat16 / float16, ``weight`` ``[N, K]`` and ``bias`` ``[N]`` in any of the three (float32
     parameters next to a bfloat16 ``x`` are fine); the result is ``[..., N]`` in ``x.dtype``.  With ``Q_f(t)`` the MX quantization of
@@ -242,9 +264,17 @@ def mx_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
     one call on ``x`` yields ``Q_x(x)`` and ``Q_x(x^T)`` (the latter is what the backward keeps instead of ``x``), one on ``dy``
     both forms of the gradient.  Gradients nobody asks for are not computed, and without grad the transposed codes of ``x`` are
     not either.  GPU tensors run HIP kernels only (no host synchronisation: a step can be graph-captured); CPU tensors evaluate
-    the same formulas in float64."""
+    the same formulas in float64.
+
+    ``grad_rounding="stochastic"`` rounds the two forms of ``dy`` -- and nothing else: ``x`` and ``W`` stay round-to-nearest-even, ``y``
+    is the nearest mode's bit for bit -- stochastically (``mx_quantize_2way(dy, ..., "stochastic", seed, step)``), which makes
+    ``Q_g(dy)`` an unbiased estimate of ``dy`` also in the FP6 / FP4 formats, where nearest rounding zeroes every element below half
+    its block's smallest step.  ``step`` (a one-element int64 tensor on ``x``'s device, or None) is part of the key and is advanced
+    by one in place after each backward that quantizes ``dy``, without a host synchronisation: successive steps, and successive
+    replays of a captured step, draw different words."""
     for name, fmt in (("x_fmt", x_fmt), ("w_fmt", w_fmt), ("grad_fmt", grad_fmt)):
         _mx_format(fmt)
+    _mx_check_rounding(grad_rounding, step, x)
     for name, t in (("x", x), ("weight", weight)) + ((("bias", bias),) if bias is not None else ()):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
@@ -261,40 +291,55 @@ def mx_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
     if bias is not None and tuple(bias.shape) != (weight.shape[0],):
         raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({weight.shape[0]},)")
     need_col = torch.is_grad_enabled() and weight.requires_grad
-    return _MXLinearFunction.apply(x, weight, bias, x_fmt, w_fmt, grad_fmt, need_col)
+    return _MXLinearFunction.apply(x, weight, bias, x_fmt, w_fmt, grad_fmt, need_col, grad_rounding, seed, step)
 
 
 class MXTrainLinear(nn.Linear):
     """Drop-in ``nn.Linear`` that trains through MX matrix products: float ``weight`` / ``bias`` parameters (``nn.Linear``'s own
     ``state_dict``), ``forward`` is ``mx_linear`` in the formats ``x_fmt`` / ``w_fmt`` / ``grad_fmt``.  Under ``torch.autocast``
-    the input is cast to the autocast dtype, as ``nn.Linear``'s would be, and the output has that dtype."""
+    the input is cast to the autocast dtype, as ``nn.Linear``'s would be, and the output has that dtype.
+
+    ``grad_rounding="stochastic"`` rounds the gradient operands stochastically (``mx_linear``).  The layer then owns ``sr_seed`` --
+    ``seed``, or a draw from torch's default CPU generator when that is None, so ``torch.manual_seed`` makes a model reproducible
+    and no two layers share their noise -- and a non-persistent int64 buffer ``sr_step`` that counts its backwards on the device.
+    With ``"nearest"`` neither exists and the ``state_dict`` is ``nn.Linear``'s."""
 
     def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=None, x_fmt: str = "mxfp8_e4m3",
-                 w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2"):
+                 w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2", grad_rounding: str = "nearest", seed: Optional[int] = None):
         super().__init__(in_features, out_features, bias=bias, device=device, dtype=dtype)
         for fmt in (x_fmt, w_fmt, grad_fmt):
             _mx_format(fmt)
-        self.x_fmt, self.w_fmt, self.grad_fmt = x_fmt, w_fmt, grad_fmt
+        _mx_check_rounding(grad_rounding, None, self.weight)
+        self.x_fmt, self.w_fmt, self.grad_fmt, self.grad_rounding = x_fmt, w_fmt, grad_fmt, grad_rounding
+        if grad_rounding == "stochastic":
+            self.sr_seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if seed is None else int(seed)
+            self.register_buffer("sr_step", torch.zeros(1, dtype=torch.int64, device=self.weight.device), persistent=False)
 
     @classmethod
-    def from_linear(cls, layer: nn.Linear, x_fmt: str = "mxfp8_e4m3", w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2"):
+    def from_linear(cls, layer: nn.Linear, x_fmt: str = "mxfp8_e4m3", w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2",
+                    grad_rounding: str = "nearest", seed: Optional[int] = None):
         """a layer on ``layer``'s own parameters (shared, not copied)"""
         if not isinstance(layer, nn.Linear):
             raise TypeError(f"MXTrainLinear.from_linear needs an nn.Linear, got {type(layer).__name__}")
         new = cls(layer.in_features, layer.out_features, bias=layer.bias is not None, device="meta", x_fmt=x_fmt, w_fmt=w_fmt,
-                  grad_fmt=grad_fmt)
+                  grad_fmt=grad_fmt, grad_rounding=grad_rounding, seed=seed)
         new.weight, new.bias = layer.weight, layer.bias
+        if grad_rounding == "stochastic":
+            new.sr_step = torch.zeros(1, dtype=torch.int64, device=layer.weight.device)
         new.train(layer.training)
         return new
 
     def extra_repr(self) -> str:
-        return f"{super().extra_repr()}, x_fmt={self.x_fmt!r}, w_fmt={self.w_fmt!r}, grad_fmt={self.grad_fmt!r}"
+        sr = f", grad_rounding={self.grad_rounding!r}" if self.grad_rounding != "nearest" else ""
+        return f"{super().extra_repr()}, x_fmt={self.x_fmt!r}, w_fmt={self.w_fmt!r}, grad_fmt={self.grad_fmt!r}{sr}"
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         dev = x.device.type
         if torch.is_autocast_enabled(dev):
             x = x.to(torch.get_autocast_dtype(dev))
-        return mx_linear(x, self.weight, self.bias, self.x_fmt, self.w_fmt, self.grad_fmt)
+        if self.grad_rounding == "nearest":
+            return mx_linear(x, self.weight, self.bias, self.x_fmt, self.w_fmt, self.grad_fmt)
+        return mx_linear(x, self.weight, self.bias, self.x_fmt, self.w_fmt, self.grad_fmt, self.grad_rounding, self.sr_seed, self.sr_step)
 
     def to_inference(self, act_fmt: Optional[str] = None, out_dtype: torch.dtype = torch.float32) -> MXLinear:
         """the ``MXLinear`` on the current weight: its weight bytes are the row pair the training forward multiplies with"""

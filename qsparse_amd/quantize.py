@@ -12,7 +12,7 @@ quantize.py:56-62/110-116 acts on a temporary), scaler rounds half-to-even after
 decimal truncates, the backward clamps gradient *values* into ``[(-L+notch)*s, (L-1+notch)*s]``.
 """
 import math
-from typing import List, Tuple, Union
+from typing import List, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -519,9 +519,70 @@ def _mx_blocks(x: torch.Tensor, dim: int):
     return v.reshape(v.shape[:-1] + (nb, MX_BLOCK)), n
 
 
-def _mx_aten(x: torch.Tensor, fmt: str, dim: int, out_dtype: torch.dtype, want_codes: bool):
+MX_ROUNDINGS = ("nearest", "stochastic")
+_M32 = 0xFFFFFFFF
+_PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+_PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+
+
+def _mulhilo32(a: int, b: torch.Tensor):
+    """(high, low) 32-bit halves of a * b for a 32-bit constant `a` and an int64 tensor `b` of 32-bit values: the product does not
+    fit a signed int64, so `b` is split into 16-bit halves (a bh 2^16 + a bl, each partial product below 2^48)"""
+    p, q = a * (b >> 16), a * (b & 0xFFFF)
+    return (p + (q >> 16)) >> 16, (((p & 0xFFFF) << 16) + q) & _M32
+
+
+def _philox4x32_10(c0, c1, c2, c3, k0: int, k1: int):
+    """Philox4x32-10 on int64 tensors holding 32-bit counter words, key (k0, k1) Python ints: the four output words"""
+    for _ in range(10):
+        hi0, lo0 = _mulhilo32(_PHILOX_M[0], c0)
+        hi1, lo1 = _mulhilo32(_PHILOX_M[1], c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + _PHILOX_W[0]) & _M32, (k1 + _PHILOX_W[1]) & _M32
+    return c0, c1, c2, c3
+
+
+def _mx_sr_key(seed: int, step) -> int:
+    """k = (seed + step) mod 2^64; `step` None, an int or a one-element int64 tensor"""
+    t = 0 if step is None else int(step.item()) if isinstance(step, torch.Tensor) else int(step)
+    return (int(seed) + t) & 0xFFFFFFFFFFFFFFFF
+
+
+def _mx_sr_words(shape, seed: int, step=None, stream: int = 0, index_base: int = 0, device=None) -> torch.Tensor:
+    """the 32-bit random word (as int64) of every code of a tensor of `shape`: word j & 3 of Philox4x32-10 at counter
+    (j >> 2, stream, 0) and key seed + step, j = index_base + the code's row-major linear index (include/qsparse_hip.h)"""
+    numel = 1
+    for d in shape:
+        numel *= int(d)
+    k = _mx_sr_key(seed, step)
+    calls = (numel + 3) // 4 + 1
+    base = int(index_base) & 0xFFFFFFFFFFFFFFFF
+    lo0, hi0 = (base >> 2) & _M32, base >> 34                                 # the first counter, then carries by hand: q < 2^62
+    q = torch.arange(calls, dtype=torch.int64, device=device) + lo0
+    c0, c1 = q & _M32, (hi0 + (q >> 32)) & _M32
+    sw = torch.full_like(q, int(stream) & _M32)
+    o = torch.stack(_philox4x32_10(c0, c1, sw, torch.zeros_like(q), k & _M32, k >> 32), -1).reshape(-1)
+    off = base & 3
+    return o[off:off + numel].reshape(tuple(shape))
+
+
+def _mx_round_sr(a: torch.Tensor, w: torch.Tensor, mbits: int, bias: int, max_normal: float) -> torch.Tensor:
+    """|q| of |v| = `a` (float64 holding float32 values) under the words `w`, by the integer definition of the header"""
+    ab = a.to(torch.float32).contiguous().view(torch.int32).to(torch.int64)
+    field = ab >> 23
+    E = field.clamp(min=1)
+    m = (ab & 0x7FFFFF) | torch.where(field > 0, 0x800000, 0)
+    ex = E.clamp(min=1 - bias + 127)
+    sh = (23 - mbits) + (ex - E)
+    T = torch.where(sh <= 56, (m << 32) >> sh.clamp(max=56), torch.zeros_like(m))
+    n = (T + w) >> 32
+    return (n.to(torch.float64) * _exp2_f64(ex - 127 - mbits)).clamp(max=max_normal)
+
+
+def _mx_aten(x: torch.Tensor, fmt: str, dim: int, out_dtype: torch.dtype, want_codes: bool, words: Optional[torch.Tensor] = None):
     """the definition as an ATen expression (CPU tensors, float64 GPU tensors): exact float64 arithmetic on the float32 widening of
-    x -- exponents from frexp, powers of two from their bits, one rounding (torch.round: half to even) per element"""
+    x -- exponents from frexp, powers of two from their bits, one rounding (torch.round: half to even) per element.  `words`
+    (int64, x's shape: `_mx_sr_words`) rounds stochastically instead: the same blocks, scales and codes around `_mx_round_sr`"""
     bits, ebits, mbits, bias, emax, max_normal = _mx_format(fmt)
     blk, n = _mx_blocks(x, dim)
     amax = blk.abs().amax(-1, keepdim=True)
@@ -534,7 +595,14 @@ def _mx_aten(x: torch.Tensor, fmt: str, dim: int, out_dtype: torch.dtype, want_c
     ex = _floor_log2(torch.where(a == 0, torch.ones_like(a), a)).clamp(min=1 - bias)
     ex = torch.where(a == 0, torch.full_like(ex, 1 - bias), ex)
     quantum = _exp2_f64(ex - mbits)
-    q = (torch.round(a / quantum) * quantum).clamp(max=max_normal)             # (a / quantum is exact: a power of two)
+    if words is None:
+        q = (torch.round(a / quantum) * quantum).clamp(max=max_normal)         # (a / quantum is exact: a power of two)
+    else:
+        # v in float32, as the kernels form it (a product that leaves float32's normal range lies below 2^-32 of a grid step: T = 0)
+        v32 = (torch.where(bad, torch.zeros_like(blk), blk).to(torch.float32) * _exp2_f64(-e).to(torch.float32)).to(torch.float64)
+        wb = words.movedim(dim, -1)
+        wb = torch.nn.functional.pad(wb, (0, blk.shape[-2] * MX_BLOCK - n)).reshape(blk.shape)
+        q = _mx_round_sr(v32.abs(), wb, mbits, bias, max_normal)
     y = torch.copysign(q, v) * _exp2_f64(e)
     y = torch.where(bad, torch.full_like(y, float("nan")), y)
 
@@ -559,17 +627,25 @@ class MXQuantization(torch.autograd.Function):
     """MX block-scaled quantization with a straight-through backward: the gradient passes unchanged (no clamp, no kernel)."""
 
     @staticmethod
-    def forward(ctx, input: torch.Tensor, fmt: str = "mxfp8_e4m3", block_dim: int = -1, return_codes: bool = False):
+    def forward(ctx, input: torch.Tensor, fmt: str = "mxfp8_e4m3", block_dim: int = -1, return_codes: bool = False,
+                rounding: str = "nearest", seed: int = 0, step: Optional[torch.Tensor] = None, stream: int = 0):
         _mx_format(fmt)
+        _mx_check_rounding(rounding, step, input)
         if input.dim() == 0:
             raise ValueError("MX quantization needs a tensor with at least one dimension (blocks of 32 run along `block_dim`)")
         if not -input.dim() <= block_dim < input.dim():
             raise IndexError(f"block_dim {block_dim} out of range for a tensor of {input.dim()} dimensions")
         dim = block_dim % input.dim()
-        if _hip.on_hip(input):
-            y, codes, scales = _hip.mx_quant_fwd(input, fmt, dim, _out_dtype(input), return_codes)
+        if rounding == "nearest":               # the entry point and the expression as they were
+            if _hip.on_hip(input):
+                y, codes, scales = _hip.mx_quant_fwd(input, fmt, dim, _out_dtype(input), return_codes)
+            else:
+                y, codes, scales = _mx_aten(input, fmt, dim, _out_dtype(input), return_codes)
+        elif _hip.on_hip(input):
+            y, codes, scales = _hip.mx_quant_fwd(input, fmt, dim, _out_dtype(input), return_codes, rounding, seed, step, stream)
         else:
-            y, codes, scales = _mx_aten(input, fmt, dim, _out_dtype(input), return_codes)
+            words = _mx_sr_words(input.shape, seed, step, stream, device=input.device)
+            y, codes, scales = _mx_aten(input, fmt, dim, _out_dtype(input), return_codes, words)
         if not return_codes:
             return y
         ctx.mark_non_differentiable(codes, scales)
@@ -577,17 +653,35 @@ class MXQuantization(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_output, grad_codes=None, grad_scales=None):
-        return grad_output, None, None, None
+        return grad_output, None, None, None, None, None, None, None
 
 
-def quantize_with_mx(input: torch.Tensor, fmt: str = "mxfp8_e4m3", block_dim: int = -1, return_codes: bool = False):
+def _mx_check_rounding(rounding: str, step, like: torch.Tensor):
+    if rounding not in MX_ROUNDINGS:
+        raise ValueError(f"unknown rounding {rounding!r}: one of {MX_ROUNDINGS}")
+    if step is not None:
+        if not isinstance(step, torch.Tensor) or step.dtype != torch.int64 or step.numel() != 1:
+            raise TypeError("step must be a one-element int64 tensor (or None)")
+        if step.device != like.device:
+            raise ValueError(f"the tensor is on {like.device} but step on {step.device}")
+
+
+def quantize_with_mx(input: torch.Tensor, fmt: str = "mxfp8_e4m3", block_dim: int = -1, return_codes: bool = False,
+                     rounding: str = "nearest", seed: int = 0, step: Optional[torch.Tensor] = None, stream: int = 0):
     """OCP microscaling (MX) quantization: elements in ``fmt`` (``MX_FORMATS``), one power-of-two scale per block of 32
     consecutive elements along ``block_dim`` (the last block of a line is shorter when the length is no multiple of 32).
     Returns the de-quantized tensor -- float32, or the input dtype under ``preserve_dtype`` -- or, with ``return_codes``,
     ``(y, codes, scales)``: ``codes`` uint8 of the input's shape (the element format's own bit encoding in the low bits),
     ``scales`` uint8 E8M0 bytes (``X = 2^(scale - 127)``, 0xFF for a block that holds a NaN / Inf, whose outputs are all NaN)
-    of the input's shape with ``block_dim`` shrunk to ``ceil(n / 32)``."""
-    return MXQuantization.apply(input, fmt, block_dim, return_codes)
+    of the input's shape with ``block_dim`` shrunk to ``ceil(n / 32)``.
+
+    ``rounding="stochastic"`` replaces round-to-nearest-even by an unbiased choice between the two enclosing grid values (values
+    beyond the largest normal still saturate): the element at row-major index ``j`` draws word ``j & 3`` of Philox4x32-10 at counter
+    ``(j >> 2, stream)`` and key ``seed + step`` -- a pure function of its arguments, the same bits on the GPU and on the CPU.
+    ``step`` is an optional one-element int64 tensor on the input's device that the GPU kernel reads when it runs, so a call captured
+    in a graph draws fresh words on every replay once the caller advances it; ``stream`` separates calls that share seed and step.
+    The backward is straight-through in either mode."""
+    return MXQuantization.apply(input, fmt, block_dim, return_codes, rounding, seed, step, stream)
 
 
 def mx_dequantize(codes: torch.Tensor, scales: torch.Tensor, fmt: str, block_dim: int = -1,

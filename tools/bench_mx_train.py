@@ -20,6 +20,10 @@ Layer step: forward + backward of one linear, (M, N, K) = the two ViT-B MLP shap
       MX-quantized input, forward + backward.  THE BAR: the MXTrainLinear step no slower than (a)
   (b) a plain bf16 nn.Linear, forward + backward -- for information
   and the step's launches one by one (HIP events around each): the four two-way calls and the three GEMMs.
+Stochastic rounding (commits that have it; `--no-stochastic` skips): the two-way call on a gradient-like bf16 tensor of the three
+  quantizer shapes, E5M2 and FP4, both pairs, stochastic with a device step counter, next to the nearest-mode call and to the
+  yardstick (t) / (s) above in that format.  THE BAR: the stochastic call no slower than the yardstick.  And the layer step with
+  grad_fmt FP4 in nearest and in stochastic mode, with the dy call of each timed on its own.
 Needs a GPU: there is no fallback.  `--small` shrinks the shapes for a functional rehearsal (its numbers mean nothing)."""
 import argparse
 import json
@@ -162,6 +166,83 @@ def bench_layer(args, out, save):
         save()
 
 
+def bench_stochastic(args, out, save):
+    import torch
+    import qsparse_amd as qs
+    from qsparse_amd import _hip
+    from qsparse_amd.quantize import quantize_with_mx
+    dev = "cuda:0"
+    g = torch.Generator(device=dev).manual_seed(1)
+    step_t = torch.zeros(1, dtype=torch.int64, device=dev)
+    shapes = [(50432, 768), (50432, 3072), (4096, 4096)] if not args.small else [(512, 256), (256, 384)]
+    for R, C in shapes:
+        x = torch.randn(R, C, device=dev, generator=g, dtype=torch.bfloat16) / C
+        for fmt in ("mxfp8_e5m2", "mxfp4_e2m1"):
+            rec = {"R": R, "C": C, "fmt": fmt, "dtype": "bfloat16"}
+
+            def via_transpose():
+                _, rc, rs = quantize_with_mx(x, fmt, -1, return_codes=True)
+                _, cc, cs = quantize_with_mx(x.t().contiguous(), fmt, -1, return_codes=True)
+                return rc, rs, cc, cs
+
+            def via_strided():
+                _, rc, rs = quantize_with_mx(x, fmt, -1, return_codes=True)
+                _, c, s = quantize_with_mx(x, fmt, 0, return_codes=True)
+                return rc, rs, c.t().contiguous(), s.t().contiguous()
+
+            with torch.no_grad():
+                ms_t, reps_t = timed(via_transpose, args.iters, args.warmup)
+                ms_s, reps_s = timed(via_strided, args.iters, args.warmup)
+                yard, yreps = (ms_t, reps_t) if ms_t <= ms_s else (ms_s, reps_s)
+                rec["yardstick"] = {"which": "via_transpose" if ms_t <= ms_s else "via_strided", "ms": yard, "reps_ms": yreps,
+                                    "spread": (max(yreps) - min(yreps)) / yard}
+                ms_n, reps_n = timed(lambda: qs.mx_quantize_2way(x, fmt, fmt), args.iters, args.warmup)
+                rec["two_way_nearest"] = {"ms": ms_n, "reps_ms": reps_n}
+                # the stochastic call is its own one-way composition, bit for bit (streams 0 / 1), before it is timed
+                got = qs.mx_quantize_2way(x, fmt, fmt, "stochastic", 7, step_t)
+                assert _hip.mx_quant2_last_route == _hip.MX_Q2_ROUTE_TILE_VEC
+                want = (quantize_with_mx(x, fmt, -1, True, "stochastic", 7, step_t, 0)[1:]
+                        + quantize_with_mx(x.t().contiguous(), fmt, -1, True, "stochastic", 7, step_t, 1)[1:])
+                assert all(torch.equal(a, b) for a, b in zip(got, want)), "the stochastic two-way call and its one-way composition disagree"
+                ms, reps = timed(lambda: qs.mx_quantize_2way(x, fmt, fmt, "stochastic", 7, step_t), args.iters, args.warmup)
+                nbytes = R * C * (2 + 1 + 1 + 2 / 32)
+                rec["two_way_stochastic"] = {"ms": ms, "reps_ms": reps, "ratio_to_nearest": ms / ms_n, "ratio_to_yardstick": ms / yard,
+                                             "no_slower_than_yardstick": bool(ms <= max(yreps)),
+                                             "roofline_fraction": nbytes / (ms * 1e-3) / HBM_BYTES_PER_S}
+            out["stochastic_quantizer"].append(rec)
+            print(json.dumps(rec), flush=True)
+            save()
+    import torch.nn as nn
+    shapes = [(50432, 3072, 768), (50432, 768, 3072), (4096, 4096, 4096)] if not args.small else [(512, 384, 256), (256, 256, 512)]
+    for M, N, K in shapes:
+        rec = {"M": M, "N": N, "K": K, "x_dtype": "bfloat16", "fmts": ["mxfp8_e4m3", "mxfp8_e4m3", "mxfp4_e2m1"]}
+        x = torch.randn(M, K, device=dev, generator=g, dtype=torch.bfloat16).requires_grad_(True)
+        dy = torch.randn(M, N, device=dev, generator=g, dtype=torch.bfloat16) / N
+        torch.manual_seed(0)
+        base = nn.Linear(K, N).to(dev)
+        for mode in ("nearest", "stochastic"):
+            layer = qs.MXTrainLinear.from_linear(base, grad_fmt="mxfp4_e2m1", grad_rounding=mode, seed=3)
+
+            def step():
+                x.grad = None
+                for p in layer.parameters():
+                    p.grad = None
+                layer(x).backward(dy)
+
+            ms, reps = timed(step, args.iters, args.warmup)
+            _hip.start_event_log()
+            for _ in range(5):
+                step()
+            log = _hip.stop_event_log()
+            q2 = [t for k, v in log.items() if k.startswith("mx_quant2") for t in v]
+            assert len(q2) == 20
+            rec[mode] = {"ms": ms, "reps_ms": reps, "quant2_dy_both_ms": statistics.median(q2[2::4])}
+        rec["stochastic"]["ratio_to_nearest"] = rec["stochastic"]["ms"] / rec["nearest"]["ms"]
+        out["stochastic_layer_step"].append(rec)
+        print(json.dumps(rec), flush=True)
+        save()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -169,6 +250,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--small", action="store_true")
     ap.add_argument("--commit", default="", help="recorded in the output: the commit the figures were measured on")
+    ap.add_argument("--no-stochastic", action="store_true", help="skip the stochastic-rounding cases")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -188,6 +270,10 @@ def main():
 
     bench_quantizer(args, out, save)
     bench_layer(args, out, save)
+    import inspect
+    if out["has_two_way"] and "rounding" in inspect.signature(qs.mx_quantize_2way).parameters and not args.no_stochastic:
+        out["stochastic_quantizer"], out["stochastic_layer_step"] = [], []
+        bench_stochastic(args, out, save)
     print("wrote", args.out)
 
 

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define QS_ABI_VERSION 27
+#define QS_ABI_VERSION 28
 /* ABI compatibility (from v25 on).
  *   - Every positional prototype in this header is FROZEN as of v25: a later version never changes the argument list of an
  *     existing symbol.  qs_abi_floor() returns the oldest version whose prototypes this library still honours (25); a binding
@@ -822,20 +822,44 @@ int qs_mailbox_wait(void* box, int world, int64_t n, uint32_t step, int32_t* sta
                     qs_stream_t stream);
 int qs_records_max(const float* records, int world, int64_t n, float* out, qs_stream_t stream);
 
-/* ---- MX block-scaled quantizer (OCP Microscaling Formats v1.0), ABI v27 ------------------------------------------------------
+/* ---- MX block-scaled quantizer (OCP Microscaling Formats v1.0), ABI v27; rounding modes v28 ------------------------------------
  * The tensor is CONTIGUOUS memory seen as [outer, n, inner]; a block is 32 consecutive elements along `n` (the last block of a
  * line is shorter when n % 32 != 0), nb = ceil(n / 32) blocks per line.  Per block, on the float32 widening of x:
  *   amax = max |x_i|.  NaN or Inf: every y_i of the block is NaN, the scale byte 0xFF, every code 0.
  *   e = clamp(floor(log2(amax)) - emax, -127, 127), -127 for amax == 0 (the exponent is taken from the bits, float32 subnormals
  *   included);  scale byte = e + 127 (E8M0);  X = 2^e
- *   q_i = x_i / X rounded to nearest, ties to even, onto the element format's value grid (its subnormals included), then clamped
- *   to +- the largest normal; a zero keeps its sign; no format's own NaN / Inf code is ever produced
+ *   q_i = x_i / X rounded to nearest, ties to even (`rounding` == QS_MX_ROUND_NEAREST, the default; stochastic: below), onto the
+ *   element format's value grid (its subnormals included), then clamped to +- the largest normal; a zero keeps its sign; no
+ *   format's own NaN / Inf code is ever produced
  *   y_i = q_i * X (exact in float32, subnormals kept), rounded once to ydt
  *   codes[i] (nullable; uint8, x's geometry) = the format's encoding of q_i -- sign, exponent, mantissa -- in the low bits
  *   (QS_MX_FP8_E4M3 / _E5M2: the bytes of OCP e4m3fn / e5m2);  scales (nullable; uint8 [outer, nb, inner]) = the scale bytes.
  * ydt is QS_F32 or xdt.  inner == 1 selects the innermost-axis kernels: with n % 32 == 0 and x, y (and codes: 8 bytes) 16-byte
  * aligned the 16-bytes-per-lane form, otherwise one element per lane; inner > 1 the strided-axis kernel (lanes along `inner`).
- * x, y need the alignment of their element type only (QS_ERR_ALIGN otherwise).  One pass over the data, no workspace. */
+ * x, y need the alignment of their element type only (QS_ERR_ALIGN otherwise).  One pass over the data, no workspace.
+ *
+ * (v28) `rounding` == QS_MX_ROUND_STOCHASTIC changes ONE step of the definition above: how q_i is chosen between the two grid
+ * values that enclose v = x_i * 2^-e (float32, as before).  abs-max, scale byte, X, the NaN / Inf block, the clamp and the codes
+ * are unchanged.
+ *   ab = bits of |v|;  E = max(ab >> 23, 1);  m = (ab & 0x7FFFFF) | (ab >> 23 ? 0x800000 : 0)          (|v| = m 2^(E - 150))
+ *   ex = max(E, float32-biased exponent of the format's smallest normal);  sh = (23 - mbits) + (ex - E)   (>= 20)
+ *   T  = sh <= 56 ? floor(m 2^32 / 2^sh) : 0  in 64 bits;  n = (T + w) >> 32  with w the element's 32-bit random word
+ *   |q| = min(n 2^(ex - 127 - mbits), largest normal), the sign of v kept (a negative value that rounds to zero is -0)
+ * A value on the grid is returned unchanged for every w; w = 0 truncates toward zero; E[q] = v for every v that is not clamped.
+ * Random words, one per code, a pure function of the operands below (counter-based, no generator state):
+ *   j = index_base + the row-major linear index of the code in ITS OWN output tensor (codes / x for qs_mx_quant_fwd_v; row_codes
+ *       [R, C] for the row pair, col_codes [C, R] for the col pair), 64 bits
+ *   k = seed + (step ? (uint64_t)*step : 0)  mod 2^64 -- *step is read by the KERNEL when it runs, never written: a launch captured
+ *       in a graph draws new words on every replay once the owner advances the counter on the stream
+ *   (o0, o1, o2, o3) = Philox4x32-10(counter = (lo32(j >> 2), hi32(j >> 2), rng_stream, 0), key = (lo32(k), hi32(k)))
+ *       (Random123's constants: multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85);  w = o[j & 3]
+ *   rng_stream: the descriptor's for qs_mx_quant_fwd_v; 0 for the row pair and 1 for the col pair of qs_mx_quant2_v -- so the col
+ *       pair is what qs_mx_quant_fwd_v writes for the transpose of x with rng_stream = 1, the row pair what it writes for x with 0.
+ * Routes and alignment rules do not depend on the mode.  QS_ERR_ARG, checked first and in both modes: a rounding that is neither
+ * mode, a step pointer that is not 8-byte aligned, an index_base that is no multiple of 4.  No atomics.  A caller that passes the
+ * v27 struct_size leaves the five rounding fields 0 / NULL: nearest. */
+#define QS_MX_ROUND_NEAREST 0
+#define QS_MX_ROUND_STOCHASTIC 1
 enum qs_mx_format { QS_MX_FP8_E4M3 = 0, QS_MX_FP8_E5M2 = 1, QS_MX_FP6_E2M3 = 2, QS_MX_FP6_E3M2 = 3, QS_MX_FP4_E2M1 = 4 };
 #define QS_MX_BLOCK 32
 typedef struct qs_mx_quant_args {
@@ -848,6 +872,11 @@ typedef struct qs_mx_quant_args {
     int32_t xdt, ydt;
     int64_t outer, n, inner;
     qs_stream_t stream;
+    int32_t rounding;            /* (v28) QS_MX_ROUND_* */
+    int32_t rng_stream;          /* (v28) third counter word (`stream` above is the HIP stream) */
+    uint64_t seed;               /* (v28) */
+    const int64_t* step;         /* (v28) nullable (= 0); device memory, one int64, read by the kernel */
+    uint64_t index_base;         /* (v28) a multiple of 4 */
 } qs_mx_quant_args;
 int qs_mx_quant_fwd_v(const qs_mx_quant_args* args);
 /* the kernel qs_mx_quant_fwd_v launches for these operands, decided by the code that launches it and without enqueuing anything:
@@ -907,14 +936,16 @@ int qs_mx_matmul_route(const qs_mx_matmul_args* args);
  *             scales qs_mx_quant_fwd_v writes for the transpose of x, stored as that transpose
  * bit for bit by the definition of the MX block-scaled quantizer above (short last blocks, zero blocks, float32 subnormals, the sign
  * of a zero, a NaN / Inf block: scale 0xFF, codes 0).  The two formats may differ; the format of a pair that is not given is ignored.
- * No de-quantized tensor is written, nothing but the four outputs is written, no workspace.
+ * No de-quantized tensor is written, nothing but the four outputs is written, no workspace.  (v28) `rounding`, `seed`, `step` and
+ * `index_base` are the rounding operands of qs_mx_quant_fwd_v above; the row pair draws its words with rng_stream 0, the col pair with 1.
  *   - x needs the alignment of its element (QS_ERR_ALIGN otherwise); codes and scales: any address.
  *   - R == 0 or C == 0: nothing is enqueued, 0 is returned.
  *   - QS_MX_Q2_ROUTE_TILE_VEC (16-byte loads of x, 16-byte stores of col_codes): C % 8 == 0 (two-byte x) or C % 4 == 0 (float32), x
  *     16-byte aligned and, when the col pair is written, R % 16 == 0 and col_codes 16-byte aligned.  Anything else takes
  *     QS_MX_Q2_ROUTE_TILE_PLAIN, the same tiling with element accesses: any R, C >= 1.
  *   - QS_ERR_ARG: a null or too short descriptor, x null, both pairs null, codes without scales or the reverse, a format outside
- *     enum qs_mx_format, a negative extent.  QS_ERR_DTYPE: xdt is none of the three. */
+ *     enum qs_mx_format, a negative extent; the rounding operands as for qs_mx_quant_fwd_v, checked before the others.
+ *     QS_ERR_DTYPE: xdt is none of the three. */
 typedef struct qs_mx_quant2_args {
     uint32_t struct_size;            /* sizeof(qs_mx_quant2_args) as the caller compiled it */
     int32_t row_format, col_format;  /* enum qs_mx_format, may differ */
@@ -926,6 +957,11 @@ typedef struct qs_mx_quant2_args {
     uint8_t* col_scales;             /* [C, ceil(R / 32)] */
     int64_t R, C;
     qs_stream_t stream;
+    int32_t rounding;                /* (v28) QS_MX_ROUND_*, as for qs_mx_quant_fwd_v */
+    int32_t reserved0;               /* (v28) */
+    uint64_t seed;                   /* (v28) */
+    const int64_t* step;             /* (v28) nullable (= 0); device memory, one int64, read by the kernel */
+    uint64_t index_base;             /* (v28) a multiple of 4; added to the indices of both pairs */
 } qs_mx_quant2_args;
 int qs_mx_quant2_v(const qs_mx_quant2_args* args);
 /* the kernel qs_mx_quant2_v launches for these operands, nothing enqueued: QS_MX_Q2_ROUTE_*, 0 for an empty tensor, or the QS_ERR_*
@@ -934,69 +970,15 @@ int qs_mx_quant2_v(const qs_mx_quant2_args* args);
 #define QS_MX_Q2_ROUTE_TILE_PLAIN 2
 int qs_mx_quant2_route(const qs_mx_quant2_args* args);
 
-/* ---- Stochastic rounding of the MX quantizers --------------------------------------------------------------------------------
- * Added without raising QS_ABI_VERSION (27), by the same rule: four symbols are added, qs_mx_quant_args / qs_mx_quant2_args and their
- * entry points stay as they are.  Each descriptor below is its predecessor, field for field, followed by the rounding operands.
- *
- * rounding == QS_MX_ROUND_NEAREST: the call is qs_mx_quant_fwd_v / qs_mx_quant2_v (same checks, routes, kernels, bytes).
- * rounding == QS_MX_ROUND_STOCHASTIC changes ONE step of the definition above: how q_i is chosen between the two grid values that
- * enclose v = x_i * 2^-e (float32, as before).  abs-max, scale byte, X, the NaN / Inf block, the clamp and the codes are unchanged.
- *   ab = bits of |v|;  E = max(ab >> 23, 1);  m = (ab & 0x7FFFFF) | (ab >> 23 ? 0x800000 : 0)          (|v| = m 2^(E - 150))
- *   ex = max(E, float32-biased exponent of the format's smallest normal);  sh = (23 - mbits) + (ex - E)   (>= 20)
- *   T  = sh <= 56 ? floor(m 2^32 / 2^sh) : 0  in 64 bits;  n = (T + w) >> 32  with w the element's 32-bit random word
- *   |q| = min(n 2^(ex - 127 - mbits), largest normal), the sign of v kept (a negative value that rounds to zero is -0)
- * A value on the grid is returned unchanged for every w; w = 0 truncates toward zero; E[q] = v for every v that is not clamped.
- * Random words, one per code, a pure function of the operands below (counter-based, no generator state):
- *   j = index_base + the row-major linear index of the code in ITS OWN output tensor (codes / x for qs_mx_quant_sr_v; row_codes
- *       [R, C] for the row pair, col_codes [C, R] for the col pair), 64 bits
- *   k = seed + (step ? (uint64_t)*step : 0)  mod 2^64 -- *step is read by the KERNEL when it runs, never written: a launch captured
- *       in a graph draws new words on every replay once the owner advances the counter on the stream
- *   (o0, o1, o2, o3) = Philox4x32-10(counter = (lo32(j >> 2), hi32(j >> 2), rng_stream, 0), key = (lo32(k), hi32(k)))
- *       (Random123's constants: multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85);  w = o[j & 3]
- *   rng_stream: the descriptor's for qs_mx_quant_sr_v; 0 for the row pair and 1 for the col pair of qs_mx_quant2_sr_v -- so the col
- *       pair is what qs_mx_quant_sr_v writes for the transpose of x with rng_stream = 1, the row pair what it writes for x with 0.
- * Routes and alignment rules are those of the predecessor.  QS_ERR_ARG in addition: a rounding that is neither mode, a step pointer
- * that is not 8-byte aligned, an index_base that is no multiple of 4 (checked in both modes).  No workspace, no atomics. */
-#define QS_MX_ROUND_NEAREST 0
-#define QS_MX_ROUND_STOCHASTIC 1
-typedef struct qs_mx_quant_sr_args {
-    uint32_t struct_size;        /* sizeof(qs_mx_quant_sr_args) as the caller compiled it */
-    int32_t format;              /* -- the fields of qs_mx_quant_args -- */
-    const void* x;
-    void* y;
-    uint8_t* codes;              /* nullable */
-    uint8_t* scales;             /* nullable */
-    int32_t xdt, ydt;
-    int64_t outer, n, inner;
-    qs_stream_t stream;
-    int32_t rounding;            /* QS_MX_ROUND_* */
-    int32_t rng_stream;          /* third counter word (`stream` above is the HIP stream) */
-    uint64_t seed;
-    const int64_t* step;         /* nullable (= 0); device memory, one int64, read by the kernel */
-    uint64_t index_base;         /* a multiple of 4 */
-} qs_mx_quant_sr_args;
-int qs_mx_quant_sr_v(const qs_mx_quant_sr_args* args);
-int qs_mx_quant_sr_route(const qs_mx_quant_sr_args* args);      /* QS_MX_ROUTE_*, 0, or the QS_ERR_* the call would return */
-
-typedef struct qs_mx_quant2_sr_args {
-    uint32_t struct_size;            /* sizeof(qs_mx_quant2_sr_args) as the caller compiled it */
-    int32_t row_format, col_format;  /* -- the fields of qs_mx_quant2_args -- */
-    const void* x;
-    int32_t xdt;
-    uint8_t* row_codes;
-    uint8_t* row_scales;
-    uint8_t* col_codes;
-    uint8_t* col_scales;
-    int64_t R, C;
-    qs_stream_t stream;
-    int32_t rounding;                /* QS_MX_ROUND_* */
-    int32_t reserved0;
-    uint64_t seed;
-    const int64_t* step;             /* nullable (= 0); device memory, one int64, read by the kernel */
-    uint64_t index_base;             /* a multiple of 4; added to the indices of both pairs */
-} qs_mx_quant2_sr_args;
-int qs_mx_quant2_sr_v(const qs_mx_quant2_sr_args* args);
-int qs_mx_quant2_sr_route(const qs_mx_quant2_sr_args* args);    /* QS_MX_Q2_ROUTE_*, 0, or the QS_ERR_* the call would return */
+/* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
+ * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
+ * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */
+typedef qs_mx_quant_args qs_mx_quant_sr_args;
+typedef qs_mx_quant2_args qs_mx_quant2_sr_args;
+int qs_mx_quant_sr_v(const qs_mx_quant_sr_args* args);          /* qs_mx_quant_fwd_v */
+int qs_mx_quant_sr_route(const qs_mx_quant_sr_args* args);      /* qs_mx_quant_route */
+int qs_mx_quant2_sr_v(const qs_mx_quant2_sr_args* args);        /* qs_mx_quant2_v */
+int qs_mx_quant2_sr_route(const qs_mx_quant2_sr_args* args);    /* qs_mx_quant2_route */
 
 #ifdef __cplusplus
 }

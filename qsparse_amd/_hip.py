@@ -18,7 +18,7 @@ MEAN_ABS, MEAN_L0, MEAN_RELU = 1, 2, 4
 WS_KTH_VALUE = 1
 MAX_DIMS = 6
 
-ABI_VERSION = 27          # QS_ABI_VERSION of include/qsparse_hip.h this binding was written against: the version it NEEDS
+ABI_VERSION = 28          # QS_ABI_VERSION of include/qsparse_hip.h this binding was written against: the version it NEEDS
 _LIB_NAME = "libqsparse_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 
@@ -178,7 +178,9 @@ class MxQuantArgs(ctypes.Structure):
     """`qs_mx_quant_args` of include/qsparse_hip.h"""
     _fields_ = [("struct_size", ctypes.c_uint32), ("format", c_int32), ("x", c_void_p), ("y", c_void_p), ("codes", c_void_p),
                 ("scales", c_void_p), ("xdt", c_int32), ("ydt", c_int32), ("outer", c_int64), ("n", c_int64), ("inner", c_int64),
-                ("stream", c_void_p)]
+                ("stream", c_void_p),
+                ("rounding", c_int32), ("rng_stream", c_int32), ("seed", ctypes.c_uint64), ("step", c_void_p),
+                ("index_base", ctypes.c_uint64)]                                                # v28
 
 
 class MxMatmulArgs(ctypes.Structure):
@@ -192,19 +194,9 @@ class MxQuant2Args(ctypes.Structure):
     """`qs_mx_quant2_args` of include/qsparse_hip.h"""
     _fields_ = [("struct_size", ctypes.c_uint32), ("row_format", c_int32), ("col_format", c_int32), ("x", c_void_p), ("xdt", c_int32),
                 ("row_codes", c_void_p), ("row_scales", c_void_p), ("col_codes", c_void_p), ("col_scales", c_void_p),
-                ("R", c_int64), ("C", c_int64), ("stream", c_void_p)]
-
-
-class MxQuantSrArgs(ctypes.Structure):
-    """`qs_mx_quant_sr_args` of include/qsparse_hip.h: `qs_mx_quant_args` followed by the rounding operands"""
-    _fields_ = MxQuantArgs._fields_ + [("rounding", c_int32), ("rng_stream", c_int32), ("seed", ctypes.c_uint64), ("step", c_void_p),
-                                       ("index_base", ctypes.c_uint64)]
-
-
-class MxQuant2SrArgs(ctypes.Structure):
-    """`qs_mx_quant2_sr_args` of include/qsparse_hip.h: `qs_mx_quant2_args` followed by the rounding operands"""
-    _fields_ = MxQuant2Args._fields_ + [("rounding", c_int32), ("reserved0", c_int32), ("seed", ctypes.c_uint64), ("step", c_void_p),
-                                        ("index_base", ctypes.c_uint64)]
+                ("R", c_int64), ("C", c_int64), ("stream", c_void_p),
+                ("rounding", c_int32), ("reserved0", c_int32), ("seed", ctypes.c_uint64), ("step", c_void_p),
+                ("index_base", ctypes.c_uint64)]                                                # v28
 
 
 class MultiRow(ctypes.Structure):
@@ -789,7 +781,7 @@ MX_ROUNDINGS = ("nearest", "stochastic")      # QS_MX_ROUND_*, in order
 
 
 def _mx_sr_operands(a, x: torch.Tensor, rounding: str, seed: int, step: Optional[torch.Tensor], index_base: int):
-    """fill the rounding operands of a `qs_mx_quant_sr_args` / `qs_mx_quant2_sr_args`"""
+    """fill the rounding operands of a `qs_mx_quant_args` / `qs_mx_quant2_args`"""
     a.rounding = MX_ROUNDINGS.index(rounding)
     a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     if step is not None:
@@ -814,12 +806,12 @@ def _mx_memory_view(x: torch.Tensor, block_dim: int):
 
 
 def mx_quant_fwd(x: torch.Tensor, fmt: str, block_dim: int, out_dtype: torch.dtype = torch.float32, want_codes: bool = False,
-                 rounding: Optional[str] = None, seed: int = 0, step: Optional[torch.Tensor] = None, stream: int = 0,
+                 rounding: str = "nearest", seed: int = 0, step: Optional[torch.Tensor] = None, stream: int = 0,
                  index_base: int = 0):
     """MX block-scaled quantization of a GPU tensor (qs_mx_quant_fwd_v): returns (y, codes|None, scales|None) -- `codes` uint8 of
-    x's shape, `scales` uint8 (E8M0) of x's shape with `block_dim` shrunk to ceil(n / 32) -- from ONE launch.  With a `rounding`
-    ("nearest" / "stochastic") the call goes through qs_mx_quant_sr_v; the random word of an element is indexed by its row-major
-    position in x's SHAPE, so a stochastic call on a tensor that is not contiguous runs on a contiguous copy."""
+    x's shape, `scales` uint8 (E8M0) of x's shape with `block_dim` shrunk to ceil(n / 32) -- from ONE launch.  `rounding` is
+    "nearest" or "stochastic"; the random word of an element is indexed by its row-major position in x's SHAPE, so a stochastic
+    call on a tensor that is not contiguous runs on a contiguous copy."""
     global mx_last_route
     lib = load()
     block_dim = block_dim % x.dim()
@@ -838,23 +830,19 @@ def mx_quant_fwd(x: torch.Tensor, fmt: str, block_dim: int, out_dtype: torch.dty
         scales = torch.empty(sshape, dtype=torch.uint8, device=x.device)
     mx_last_route = None
     if numel:
-        a = MxQuantArgs() if rounding is None else MxQuantSrArgs()
+        a = MxQuantArgs()
         a.struct_size = ctypes.sizeof(a)
         a.format = MX_FORMATS.index(fmt)
         a.x, a.y, a.codes, a.scales = _ptr(xm), _ptr(y), _ptr(codes), _ptr(scales)
         a.xdt, a.ydt = dt(xm), _DT[out_dtype]
         a.outer, a.n, a.inner = outer, n, inner
         a.stream = _stream(xm)
-        if rounding is None:
-            route_fn, run_fn, name = lib.qs_mx_quant_route, lib.qs_mx_quant_fwd_v, "qs_mx_quant_fwd_v"
-        else:
-            _mx_sr_operands(a, xm, rounding, seed, step, index_base)
-            a.rng_stream = int(stream)
-            route_fn, run_fn, name = lib.qs_mx_quant_sr_route, lib.qs_mx_quant_sr_v, "qs_mx_quant_sr_v"
-        route = route_fn(ctypes.byref(a))
+        _mx_sr_operands(a, xm, rounding, seed, step, index_base)
+        a.rng_stream = int(stream)
+        route = lib.qs_mx_quant_route(ctypes.byref(a))
         with _timed(f"mx_quant_fwd[{route}]", xm, y, codes, scales):
-            st = run_fn(ctypes.byref(a))
-        _check(st, name)
+            st = lib.qs_mx_quant_fwd_v(ctypes.byref(a))
+        _check(st, "qs_mx_quant_fwd_v")
         mx_last_route = route
     if scales is not None and xm is not like:         # (memory-order view of a channels_last tensor: back to the logical dim order)
         inv = [0] * xm.dim()
@@ -899,11 +887,11 @@ MX_Q2_ROUTE_TILE_VEC, MX_Q2_ROUTE_TILE_PLAIN = 1, 2
 mx_quant2_last_route = None   # the QS_MX_Q2_ROUTE_* of the last `mx_quant2` launch (None: an empty tensor), for tests and tools
 
 
-def mx_quant2(x: torch.Tensor, row_fmt: Optional[str], col_fmt: Optional[str], rounding: Optional[str] = None, seed: int = 0,
+def mx_quant2(x: torch.Tensor, row_fmt: Optional[str], col_fmt: Optional[str], rounding: str = "nearest", seed: int = 0,
               step: Optional[torch.Tensor] = None, index_base: int = 0):
     """the two-way, codes-only MX quantizer (qs_mx_quant2_v) on a contiguous GPU tensor `x` [R, C]: returns (row_codes [R, C],
     row_scales [R, ceil(C / 32)], col_codes [C, R], col_scales [C, ceil(R / 32)]), uint8, a pair None where its format is None --
-    from ONE launch that reads x once.  With a `rounding` ("nearest" / "stochastic") the call goes through qs_mx_quant2_sr_v."""
+    from ONE launch that reads x once.  `rounding` is "nearest" or "stochastic"."""
     global mx_quant2_last_route
     lib = load()
     R, C = x.shape
@@ -913,7 +901,7 @@ def mx_quant2(x: torch.Tensor, row_fmt: Optional[str], col_fmt: Optional[str], r
     cc, cs = (new(C, R), new(C, nb(R))) if col_fmt is not None else (None, None)
     mx_quant2_last_route = None
     if R and C:
-        a = MxQuant2Args() if rounding is None else MxQuant2SrArgs()
+        a = MxQuant2Args()
         a.struct_size = ctypes.sizeof(a)
         a.row_format = MX_FORMATS.index(row_fmt) if row_fmt is not None else 0
         a.col_format = MX_FORMATS.index(col_fmt) if col_fmt is not None else 0
@@ -921,15 +909,11 @@ def mx_quant2(x: torch.Tensor, row_fmt: Optional[str], col_fmt: Optional[str], r
         a.row_codes, a.row_scales, a.col_codes, a.col_scales = _ptr(rc), _ptr(rs), _ptr(cc), _ptr(cs)
         a.R, a.C = R, C
         a.stream = _stream(x)
-        if rounding is None:
-            route_fn, run_fn, name = lib.qs_mx_quant2_route, lib.qs_mx_quant2_v, "qs_mx_quant2_v"
-        else:
-            _mx_sr_operands(a, x, rounding, seed, step, index_base)
-            route_fn, run_fn, name = lib.qs_mx_quant2_sr_route, lib.qs_mx_quant2_sr_v, "qs_mx_quant2_sr_v"
-        route = route_fn(ctypes.byref(a))
+        _mx_sr_operands(a, x, rounding, seed, step, index_base)
+        route = lib.qs_mx_quant2_route(ctypes.byref(a))
         with _timed(f"mx_quant2[{route}]", x, rc, rs, cc, cs):
-            st = run_fn(ctypes.byref(a))
-        _check(st, name)
+            st = lib.qs_mx_quant2_v(ctypes.byref(a))
+        _check(st, "qs_mx_quant2_v")
         mx_quant2_last_route = route
     return rc, rs, cc, cs
 

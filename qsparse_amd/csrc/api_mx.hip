@@ -1,19 +1,18 @@
 // libqsparse_hip.so -- C ABI (include/qsparse_hip.h), the MX block-scaled quantizer forward (qs_mx.h): FP8 / FP6 / FP4 elements
-// with one E8M0 scale per block of 32 (OCP Microscaling Formats v1.0), rounded to nearest-even (qs_mx_quant_fwd_v) or stochastically
-// (qs_mx_quant_sr_v: the same routes and kernels, instantiated with SR = true).
+// with one E8M0 scale per block of 32 (OCP Microscaling Formats v1.0), rounded to nearest-even or stochastically (the descriptor's
+// `rounding`: the same routes and kernels, instantiated with SR = true).
 // Host side: argument checks, route, launch configuration.  No allocation, no synchronisation.
 #include "qs_host.h"
 #include "qs_mx.h"
 
 namespace {
 
-inline size_t dt_size(int dt) { return dt == QS_F32 ? 4 : 2; }
 inline bool aligned_to(const void* p, size_t a) { return (((uintptr_t)p) & (a - 1)) == 0; }
-constexpr int64_t kMaxGrid = 0x7fffffff;
 
 // the checks of qs_mx_quant_fwd_v and the kernel it launches for these operands: QS_MX_ROUTE_*, 0 for an empty tensor, QS_ERR_*
 int mx_route(const qs_mx_quant_args& a) {
-    if (!a.x || !a.y || a.format < 0 || a.format > QS_MX_FP4_E2M1) return QS_ERR_ARG;
+    if (const int st = mx_sr_check(a.rounding, a.step, a.index_base)) return st;
+    if (!a.x || !a.y || !mx_format_ok(a.format)) return QS_ERR_ARG;
     if (a.outer < 0 || a.n < 0 || a.inner < 0) return QS_ERR_ARG;
     if (!dt_ok(a.xdt) || !dt_ok(a.ydt) || !(a.ydt == QS_F32 || a.ydt == a.xdt)) return QS_ERR_DTYPE;
     if (!aligned_to(a.x, dt_size(a.xdt)) || !aligned_to(a.y, dt_size(a.ydt))) return QS_ERR_ALIGN;
@@ -25,7 +24,8 @@ int mx_route(const qs_mx_quant_args& a) {
 }
 
 template <bool SR>
-int mx_launch(const qs_mx_quant_args& a, int route, const MxSr& sr) {
+int mx_launch(const qs_mx_quant_args& a, int route) {
+    const MxSr sr = SR ? MxSr{a.seed, a.step, a.index_base, (uint32_t)a.rng_stream} : MxSr{};
     const int64_t numel = a.outer * a.n * a.inner;
     const int64_t nb = (a.n + QS_MX_BLOCK - 1) / QS_MX_BLOCK;
     const MxFormat f = mx_format(a.format);
@@ -57,15 +57,6 @@ int mx_launch(const qs_mx_quant_args& a, int route, const MxSr& sr) {
     });
 }
 
-// the descriptor of the stochastic entry points begins with its predecessor's fields, in place
-static_assert(offsetof(qs_mx_quant_sr_args, rounding) == sizeof(qs_mx_quant_args), "qs_mx_quant_sr_args must extend qs_mx_quant_args");
-inline qs_mx_quant_args base_of(const qs_mx_quant_sr_args& a) {
-    qs_mx_quant_args b;
-    memcpy(&b, &a, sizeof(b));
-    b.struct_size = sizeof(b);
-    return b;
-}
-
 }  // namespace
 
 extern "C" {
@@ -81,26 +72,11 @@ int qs_mx_quant_fwd_v(const qs_mx_quant_args* args) {
     if (!take_args(args, &a)) return QS_ERR_ARG;
     const int route = mx_route(a);
     if (route <= 0) return route;
-    return mx_launch<false>(a, route, MxSr{});
+    return a.rounding == QS_MX_ROUND_STOCHASTIC ? mx_launch<true>(a, route) : mx_launch<false>(a, route);
 }
 
-int qs_mx_quant_sr_route(const qs_mx_quant_sr_args* args) {
-    qs_mx_quant_sr_args a;
-    if (!take_args(args, &a)) return QS_ERR_ARG;
-    const int st = mx_sr_check(a.rounding, a.step, a.index_base);
-    return st ? st : mx_route(base_of(a));
-}
-
-int qs_mx_quant_sr_v(const qs_mx_quant_sr_args* args) {
-    qs_mx_quant_sr_args a;
-    if (!take_args(args, &a)) return QS_ERR_ARG;
-    const int st = mx_sr_check(a.rounding, a.step, a.index_base);
-    if (st) return st;
-    const qs_mx_quant_args b = base_of(a);
-    const int route = mx_route(b);
-    if (route <= 0) return route;
-    if (a.rounding == QS_MX_ROUND_NEAREST) return mx_launch<false>(b, route, MxSr{});
-    return mx_launch<true>(b, route, MxSr{a.seed, a.step, a.index_base, (uint32_t)a.rng_stream});
-}
+// the v27 names of the two entry points above
+int qs_mx_quant_sr_route(const qs_mx_quant_sr_args* args) { return qs_mx_quant_route(args); }
+int qs_mx_quant_sr_v(const qs_mx_quant_sr_args* args) { return qs_mx_quant_fwd_v(args); }
 
 }  // extern "C"

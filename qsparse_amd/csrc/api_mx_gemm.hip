@@ -6,13 +6,10 @@
 
 namespace {
 
-inline size_t dt_size(int dt) { return dt == QS_F32 ? 4 : 2; }
-constexpr int64_t kMaxGrid = 0x7fffffff;
-
 // the checks of qs_mx_matmul_v and the kernel it launches for these operands: QS_MX_GEMM_ROUTE_*, 0 for an empty product, QS_ERR_*
 int mx_gemm_route(const qs_mx_matmul_args& a) {
     if (!a.a_codes || !a.a_scales || !a.b_codes || !a.b_scales || !a.y) return QS_ERR_ARG;
-    if (a.a_format < 0 || a.a_format > QS_MX_FP4_E2M1 || a.b_format < 0 || a.b_format > QS_MX_FP4_E2M1) return QS_ERR_ARG;
+    if (!mx_format_ok(a.a_format) || !mx_format_ok(a.b_format)) return QS_ERR_ARG;
     if (a.M < 0 || a.N < 0 || a.K < 0) return QS_ERR_ARG;
     if (!dt_ok(a.ydt)) return QS_ERR_DTYPE;
     if ((((uintptr_t)a.y) & (dt_size(a.ydt) - 1)) != 0 || (a.bias && (((uintptr_t)a.bias) & 3u) != 0)) return QS_ERR_ALIGN;

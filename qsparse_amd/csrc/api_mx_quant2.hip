@@ -1,22 +1,19 @@
 // libqsparse_hip.so -- C ABI (include/qsparse_hip.h), the two-way, codes-only MX quantizer (qs_mx_quant2.h): one read of x [R, C],
-// codes and E8M0 scales with blocks along C and -- stored transposed -- with blocks along R; qs_mx_quant2_sr_v is the same call with a
-// rounding mode (nearest-even or stochastic: the kernel instantiated with SR = true).
+// codes and E8M0 scales with blocks along C and -- stored transposed -- with blocks along R, rounded to nearest-even or stochastically
+// (the descriptor's `rounding`: the kernel instantiated with SR = true).
 // Host side: argument checks, route, launch configuration.  No allocation, no synchronisation.
 #include "qs_host.h"
 #include "qs_mx_quant2.h"
 
 namespace {
 
-inline size_t dt_size(int dt) { return dt == QS_F32 ? 4 : 2; }
-inline bool fmt_ok(int f) { return f >= 0 && f <= QS_MX_FP4_E2M1; }
-constexpr int64_t kMaxGrid = 0x7fffffff;
-
 // the checks of qs_mx_quant2_v and the kernel it launches for these operands: QS_MX_Q2_ROUTE_*, 0 for an empty tensor, QS_ERR_*
 int mx_quant2_route(const qs_mx_quant2_args& a) {
+    if (const int st = mx_sr_check(a.rounding, a.step, a.index_base)) return st;
     const bool row = a.row_codes && a.row_scales, col = a.col_codes && a.col_scales;
     if (!a.x || (!row && !col)) return QS_ERR_ARG;
     if ((!a.row_codes) != (!a.row_scales) || (!a.col_codes) != (!a.col_scales)) return QS_ERR_ARG;      // half a pair
-    if ((row && !fmt_ok(a.row_format)) || (col && !fmt_ok(a.col_format))) return QS_ERR_ARG;
+    if ((row && !mx_format_ok(a.row_format)) || (col && !mx_format_ok(a.col_format))) return QS_ERR_ARG;
     if (a.R < 0 || a.C < 0) return QS_ERR_ARG;
     if (!dt_ok(a.xdt)) return QS_ERR_DTYPE;
     if ((((uintptr_t)a.x) & (dt_size(a.xdt) - 1)) != 0) return QS_ERR_ALIGN;
@@ -30,7 +27,8 @@ int mx_quant2_route(const qs_mx_quant2_args& a) {
 }
 
 template <bool SR>
-int mx_quant2_launch(const qs_mx_quant2_args& a, int route, const MxSr& sr) {
+int mx_quant2_launch(const qs_mx_quant2_args& a, int route) {
+    const MxSr sr = SR ? MxSr{a.seed, a.step, a.index_base, 0u} : MxSr{};      // (the kernel sets the stream per phase)
     // a pair that is not asked for keeps a valid descriptor the kernel never reads
     const MxFormat fr = mx_format(a.row_codes ? a.row_format : 0), fc = mx_format(a.col_codes ? a.col_format : 0);
     const int tiles_c = (int)((a.C + kMxq2Cols - 1) / kMxq2Cols);
@@ -50,14 +48,6 @@ int mx_quant2_launch(const qs_mx_quant2_args& a, int route, const MxSr& sr) {
     });
 }
 
-static_assert(offsetof(qs_mx_quant2_sr_args, rounding) == sizeof(qs_mx_quant2_args), "qs_mx_quant2_sr_args must extend qs_mx_quant2_args");
-inline qs_mx_quant2_args base_of(const qs_mx_quant2_sr_args& a) {
-    qs_mx_quant2_args b;
-    memcpy(&b, &a, sizeof(b));
-    b.struct_size = sizeof(b);
-    return b;
-}
-
 }  // namespace
 
 extern "C" {
@@ -73,26 +63,11 @@ int qs_mx_quant2_v(const qs_mx_quant2_args* args) {
     if (!take_args(args, &a)) return QS_ERR_ARG;
     const int route = mx_quant2_route(a);
     if (route <= 0) return route;
-    return mx_quant2_launch<false>(a, route, MxSr{});
+    return a.rounding == QS_MX_ROUND_STOCHASTIC ? mx_quant2_launch<true>(a, route) : mx_quant2_launch<false>(a, route);
 }
 
-int qs_mx_quant2_sr_route(const qs_mx_quant2_sr_args* args) {
-    qs_mx_quant2_sr_args a;
-    if (!take_args(args, &a)) return QS_ERR_ARG;
-    const int st = mx_sr_check(a.rounding, a.step, a.index_base);
-    return st ? st : mx_quant2_route(base_of(a));
-}
-
-int qs_mx_quant2_sr_v(const qs_mx_quant2_sr_args* args) {
-    qs_mx_quant2_sr_args a;
-    if (!take_args(args, &a)) return QS_ERR_ARG;
-    const int st = mx_sr_check(a.rounding, a.step, a.index_base);
-    if (st) return st;
-    const qs_mx_quant2_args b = base_of(a);
-    const int route = mx_quant2_route(b);
-    if (route <= 0) return route;
-    if (a.rounding == QS_MX_ROUND_NEAREST) return mx_quant2_launch<false>(b, route, MxSr{});
-    return mx_quant2_launch<true>(b, route, MxSr{a.seed, a.step, a.index_base, 0u});      // (the kernel sets the stream per phase)
-}
+// the v27 names of the two entry points above
+int qs_mx_quant2_sr_route(const qs_mx_quant2_sr_args* args) { return qs_mx_quant2_route(args); }
+int qs_mx_quant2_sr_v(const qs_mx_quant2_sr_args* args) { return qs_mx_quant2_v(args); }
 
 }  // extern "C"

@@ -102,6 +102,9 @@ inline int mean_lanes(int64_t total) {
 constexpr size_t kLast2MaxLds = 63 * 1024;    // qs_mean_last2's [H*W + W + 8] float tile (a workgroup may hold 64 KiB)
 
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+inline size_t dt_size(int dt) { return dt == QS_F32 ? 4 : 2; }
+inline bool mx_format_ok(int f) { return f >= 0 && f <= QS_MX_FP4_E2M1; }      // enum qs_mx_format
+constexpr int64_t kMaxGrid = 0x7fffffff;
 inline int dt_ok(int dt) { return dt == QS_F32 || dt == QS_BF16 || dt == QS_F16; }
 inline int hip_status(hipError_t e) { return (int)e; }
 inline int launch_status() { return hip_status(hipGetLastError()); }

@@ -184,8 +184,6 @@ def mx_quantize_2way(x: torch.Tensor, row_fmt: Optional[str] = None, col_fmt: Op
     x = x.detach()
     sr = rounding == "stochastic"
     if x.is_cuda:
-        if not sr:
-            return _hip.mx_quant2(x.contiguous(), row_fmt, col_fmt)
         return _hip.mx_quant2(x.contiguous(), row_fmt, col_fmt, rounding, seed, step)
     rc = rs = cc = cs = None
     if row_fmt is not None:
@@ -213,7 +211,7 @@ class _MXLinearFunction(torch.autograd.Function):
         ctx.save_for_backward(weight, x_col, x_cs)
         ctx.fmts = (x_fmt, w_fmt, grad_fmt)
         # `step` is advanced in place by the backward: an attribute, not a saved tensor (no version check, nothing to differentiate)
-        ctx.sr = (seed, step) if grad_rounding == "stochastic" else None
+        ctx.sr = (grad_rounding, seed, step)
         ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
         ctx.bias_dtype = None if bias is None else bias.dtype
         return y.reshape(x.shape[:-1] + (N,))
@@ -227,15 +225,13 @@ class _MXLinearFunction(torch.autograd.Function):
         N = weight.shape[0]
         dy2 = dy.reshape(-1, N).contiguous()
         dx = dw = db = None
-        if (need_dx or need_dw) and ctx.sr is None:
-            g_row, g_rs, g_col, g_cs = mx_quantize_2way(dy2, grad_fmt if need_dx else None, grad_fmt if need_dw else None)
-        elif need_dx or need_dw:
-            # the two forms of dy alone are rounded stochastically (row pair: stream 0, for dx; col pair: stream 1, for dW); then
-            # the counter moves on, on the stream: the next backward -- or the next replay of this one -- draws new words
-            seed, step = ctx.sr
+        if need_dx or need_dw:
+            # the two forms of dy alone take `grad_rounding` (row pair: stream 0, for dx; col pair: stream 1, for dW); after a
+            # stochastic one the counter moves on, on the stream: the next backward -- or the next replay of this one -- draws new words
+            rounding, seed, step = ctx.sr
             g_row, g_rs, g_col, g_cs = mx_quantize_2way(dy2, grad_fmt if need_dx else None, grad_fmt if need_dw else None,
-                                                        "stochastic", seed, step)
-            if step is not None:
+                                                        rounding, seed, step)
+            if rounding == "stochastic" and step is not None:
                 step.add_(1)
         if need_dx:
             _, _, w_col, w_cs = mx_quantize_2way(weight, None, w_fmt)
@@ -337,9 +333,8 @@ class MXTrainLinear(nn.Linear):
         dev = x.device.type
         if torch.is_autocast_enabled(dev):
             x = x.to(torch.get_autocast_dtype(dev))
-        if self.grad_rounding == "nearest":
-            return mx_linear(x, self.weight, self.bias, self.x_fmt, self.w_fmt, self.grad_fmt)
-        return mx_linear(x, self.weight, self.bias, self.x_fmt, self.w_fmt, self.grad_fmt, self.grad_rounding, self.sr_seed, self.sr_step)
+        seed, step = (self.sr_seed, self.sr_step) if self.grad_rounding == "stochastic" else (0, None)
+        return mx_linear(x, self.weight, self.bias, self.x_fmt, self.w_fmt, self.grad_fmt, self.grad_rounding, seed, step)
 
     def to_inference(self, act_fmt: Optional[str] = None, out_dtype: torch.dtype = torch.float32) -> MXLinear:
         """the ``MXLinear`` on the current weight: its weight bytes are the row pair the training forward multiplies with"""

@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from qsparse_amd import _hip
+from qsparse_amd._hip import MX_BLOCK, MX_ROUNDINGS
 from qsparse_amd import distributed as qdist
 from qsparse_amd.common import (HostMirror, TensorOrFloat, TensorOrInt, adopt_state_parameters, ensure_tensor,
                                 state_parameter)
@@ -489,7 +490,7 @@ MX_FORMATS = {
     "mxfp6_e3m2": (6, 3, 2, 3, 4, 28.0),
     "mxfp4_e2m1": (4, 2, 1, 1, 2, 6.0),
 }
-MX_BLOCK = 32
+assert tuple(MX_FORMATS) == _hip.MX_FORMATS, "MX_FORMATS must list the formats in the order of enum qs_mx_format"
 
 
 def _mx_format(fmt: str):
@@ -519,7 +520,6 @@ def _mx_blocks(x: torch.Tensor, dim: int):
     return v.reshape(v.shape[:-1] + (nb, MX_BLOCK)), n
 
 
-MX_ROUNDINGS = ("nearest", "stochastic")
 _M32 = 0xFFFFFFFF
 _PHILOX_M = (0xD2511F53, 0xCD9E8D57)
 _PHILOX_W = (0x9E3779B9, 0xBB67AE85)
@@ -636,15 +636,10 @@ class MXQuantization(torch.autograd.Function):
         if not -input.dim() <= block_dim < input.dim():
             raise IndexError(f"block_dim {block_dim} out of range for a tensor of {input.dim()} dimensions")
         dim = block_dim % input.dim()
-        if rounding == "nearest":               # the entry point and the expression as they were
-            if _hip.on_hip(input):
-                y, codes, scales = _hip.mx_quant_fwd(input, fmt, dim, _out_dtype(input), return_codes)
-            else:
-                y, codes, scales = _mx_aten(input, fmt, dim, _out_dtype(input), return_codes)
-        elif _hip.on_hip(input):
+        if _hip.on_hip(input):
             y, codes, scales = _hip.mx_quant_fwd(input, fmt, dim, _out_dtype(input), return_codes, rounding, seed, step, stream)
         else:
-            words = _mx_sr_words(input.shape, seed, step, stream, device=input.device)
+            words = _mx_sr_words(input.shape, seed, step, stream, device=input.device) if rounding == "stochastic" else None
             y, codes, scales = _mx_aten(input, fmt, dim, _out_dtype(input), return_codes, words)
         if not return_codes:
             return y

@@ -264,7 +264,7 @@ def _scaler_net():
 def test_entry_point_is_declared_bound_and_validates_without_a_gpu(tmp_path):
     from qsparse_amd import _hip
     lib = _hip.load()
-    assert lib.qs_version() >= 27 and _hip.ABI_VERSION == 27
+    assert lib.qs_version() >= 28 and _hip.ABI_VERSION == 28
     assert lib.qs_mx_quant_fwd_v(None) == -2
     a = _hip.MxQuantArgs()
     a.struct_size = ctypes.sizeof(a)

@@ -1,7 +1,7 @@
 """Stochastic rounding of the MX quantizers, CPU side: the Philox known answers, the package's CPU path against the independent
 reference tests/mx_sr_ref.py (bit for bit), the properties the definition promises (grid values fixed, the stream and step rules,
-unbiasedness), ``mx_linear`` with stochastically rounded gradient operands, and the two new C entry points (layout, validation,
-routes) -- none of which needs a GPU."""
+unbiasedness), ``mx_linear`` with stochastically rounded gradient operands, and the rounding operands of the two C descriptors
+(layout, validation, routes; the v27 struct_size and the v27 alias symbols) -- none of which needs a GPU."""
 import ctypes
 import os
 import subprocess
@@ -20,6 +20,8 @@ from qsparse_amd.quantize import _mx_sr_words, _philox4x32_10, quantize_with_mx
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FMTS = list(R.FORMATS)
 SHAPES = [((5, 45), -1), ((4, 64), -1), ((3, 40, 5), 1)]
+# sizeof(qs_mx_quant_args) / sizeof(qs_mx_quant2_args) as ABI v27 had them: where the fields appended in v28 begin
+V27_SIZE_1, V27_SIZE_2 = _hip.MxQuantArgs.rounding.offset, _hip.MxQuant2Args.rounding.offset
 
 
 def randn(shape, dtype, seed=0, spread=3.0):
@@ -232,6 +234,7 @@ def test_mxtrainlinear_owns_seed_and_step_only_in_stochastic_mode():
 
 
 def _layout(tmp_path, cname, ct):
+    """sizeof and every offsetof of the header's `cname` by gcc, against the ctypes struct `ct`; returns the field names"""
     fields = [f for f, _ in ct._fields_]
     src = tmp_path / f"{cname}.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(void) { printf("%%zu", sizeof(%s));\n%s\nreturn 0; }\n'
@@ -239,41 +242,51 @@ def _layout(tmp_path, cname, ct):
     subprocess.run(["gcc", "-std=c11", "-o", str(tmp_path / cname), str(src)], check=True)
     size, *offs = subprocess.run([str(tmp_path / cname)], check=True, capture_output=True, text=True).stdout.split()
     assert int(size) == ctypes.sizeof(ct) and [int(o) for o in offs] == [getattr(ct, f).offset for f in fields], cname
-    return fields
+    return fields, dict(zip(fields, map(int, offs)))
 
 
 def test_descriptors_extend_their_predecessors_and_match_the_header(tmp_path):
-    one = _layout(tmp_path, "qs_mx_quant_sr_args", _hip.MxQuantSrArgs)
-    two = _layout(tmp_path, "qs_mx_quant2_sr_args", _hip.MxQuant2SrArgs)
-    old1, old2 = [f for f, _ in _hip.MxQuantArgs._fields_], [f for f, _ in _hip.MxQuant2Args._fields_]
-    assert one == old1 + ["rounding", "rng_stream", "seed", "step", "index_base"]
-    assert two == old2 + ["rounding", "reserved0", "seed", "step", "index_base"]
-    for new, old in ((_hip.MxQuantSrArgs, _hip.MxQuantArgs), (_hip.MxQuant2SrArgs, _hip.MxQuant2Args)):
-        assert all(getattr(new, f).offset == getattr(old, f).offset for f, _ in old._fields_)
-        assert new.rounding.offset == ctypes.sizeof(old)
+    one, off1 = _layout(tmp_path, "qs_mx_quant_args", _hip.MxQuantArgs)
+    two, off2 = _layout(tmp_path, "qs_mx_quant2_args", _hip.MxQuant2Args)
+    # the v27 type names are the same structs: same size, same offsets
+    assert _layout(tmp_path, "qs_mx_quant_sr_args", _hip.MxQuantArgs) == (one, off1)
+    assert _layout(tmp_path, "qs_mx_quant2_sr_args", _hip.MxQuant2Args) == (two, off2)
+    assert one[-5:] == ["rounding", "rng_stream", "seed", "step", "index_base"] and one[-6] == "stream"
+    assert two[-5:] == ["rounding", "reserved0", "seed", "step", "index_base"] and two[-6] == "stream"
+    # the appended fields begin where the v27 structs ended (8-byte aligned, so nothing moves): sizeof as gcc laid v27 out
+    assert (off1["rounding"], off2["rounding"]) == (V27_SIZE_1, V27_SIZE_2) == (80, 88)
     lib = _hip.load()
-    assert lib.qs_version() == _hip.ABI_VERSION == 27                          # symbols were added, the version was not raised
+    assert lib.qs_version() == _hip.ABI_VERSION == 28                          # fields were appended: the version was raised
     for name in ("qs_mx_quant_sr_v", "qs_mx_quant_sr_route", "qs_mx_quant2_sr_v", "qs_mx_quant2_sr_route"):
         assert name in _hip.SIGNATURES and hasattr(lib, name)
 
 
+def _entry_points(lib):
+    """(run, route) of the one-way and of the two-way call: the entry points and their v27 aliases"""
+    return (((lib.qs_mx_quant_fwd_v, lib.qs_mx_quant_route), (lib.qs_mx_quant2_v, lib.qs_mx_quant2_route)),
+            ((lib.qs_mx_quant_sr_v, lib.qs_mx_quant_sr_route), (lib.qs_mx_quant2_sr_v, lib.qs_mx_quant2_sr_route)))
+
+
 def test_stochastic_entry_points_validate_without_a_gpu():
-    lib = _hip.load()
-    for fn in (lib.qs_mx_quant_sr_v, lib.qs_mx_quant_sr_route, lib.qs_mx_quant2_sr_v, lib.qs_mx_quant2_sr_route):
+    """the whole table by the entry points and again by their v27 aliases: the same answers"""
+    for (v1, r1), (v2, r2) in _entry_points(_hip.load()):
+        _validation_table(v1, r1, v2, r2)
+
+
+def _validation_table(v1, r1, v2, r2):
+    for fn in (v1, r1, v2, r2):
         assert fn(None) == -2
-    for ct, fns in ((_hip.MxQuantSrArgs, (lib.qs_mx_quant_sr_v, lib.qs_mx_quant_sr_route)),
-                    (_hip.MxQuant2SrArgs, (lib.qs_mx_quant2_sr_v, lib.qs_mx_quant2_sr_route))):
+    for ct, fns in ((_hip.MxQuantArgs, (v1, r1)), (_hip.MxQuant2Args, (v2, r2))):
         short = ct()
         short.struct_size = 2
         assert [fn(ctypes.byref(short)) for fn in fns] == [-2, -2]             # too short to carry its own size
-    a = _hip.MxQuantSrArgs()
+    a = _hip.MxQuantArgs()
     a.struct_size = ctypes.sizeof(a)
     a.x, a.y, a.codes, a.scales, a.outer, a.n, a.inner = 4096, 8192, 16384, 32768, 4, 64, 1
-    b = _hip.MxQuant2SrArgs()
+    b = _hip.MxQuant2Args()
     b.struct_size = ctypes.sizeof(b)
     b.x, b.R, b.C, b.row_codes, b.row_scales, b.col_codes, b.col_scales = 4096, 64, 64, 8192, 16384, 32768, 65536
-    for d, v, r, ok in ((a, lib.qs_mx_quant_sr_v, lib.qs_mx_quant_sr_route, _hip.MX_ROUTE_INNER_VEC),
-                        (b, lib.qs_mx_quant2_sr_v, lib.qs_mx_quant2_sr_route, _hip.MX_Q2_ROUTE_TILE_VEC)):
+    for d, v, r, ok in ((a, v1, r1, _hip.MX_ROUTE_INNER_VEC), (b, v2, r2, _hip.MX_Q2_ROUTE_TILE_VEC)):
         call = lambda: (v(ctypes.byref(d)), r(ctypes.byref(d)))
         for rounding in (0, 1):
             d.rounding = rounding
@@ -290,9 +303,11 @@ def test_stochastic_entry_points_validate_without_a_gpu():
         for rounding in (2, -1):
             d.rounding = rounding
             assert call() == (-2, -2)                                          # unknown rounding
+        # ... which answers before the other checks do
+        d.rounding, d.xdt = 2, 7
+        assert call() == (-2, -2)
         d.rounding = 1
-        # the predecessor's own checks still answer
-        d.xdt = 7
+        # the other checks still answer
         assert call() == (-1, -1)
         d.xdt, d.x = 0, 4098
         assert call() == (-3, -3)
@@ -300,16 +315,21 @@ def test_stochastic_entry_points_validate_without_a_gpu():
         assert call() == (-2, -2)
         d.x = 4096
     a.outer = 0
-    assert (lib.qs_mx_quant_sr_v(ctypes.byref(a)), lib.qs_mx_quant_sr_route(ctypes.byref(a))) == (0, 0)     # empty: nothing enqueued
+    assert (v1(ctypes.byref(a)), r1(ctypes.byref(a))) == (0, 0)                # empty: nothing enqueued
     b.C = 0
-    assert (lib.qs_mx_quant2_sr_v(ctypes.byref(b)), lib.qs_mx_quant2_sr_route(ctypes.byref(b))) == (0, 0)
-    # a caller that knows the predecessor only (its struct_size): the rounding operands read as zero, which is nearest mode
-    b.C, b.rounding = 64, 9
-    b.struct_size = ctypes.sizeof(_hip.MxQuant2Args)
-    assert lib.qs_mx_quant2_sr_route(ctypes.byref(b)) == _hip.MX_Q2_ROUTE_TILE_VEC
+    assert (v2(ctypes.byref(b)), r2(ctypes.byref(b))) == (0, 0)
+    # a caller that knows the v27 fields only (its struct_size): the rounding operands read as zero, which is nearest mode --
+    # whatever lies behind the struct it passed
+    a.outer, a.rounding, a.step, a.index_base = 4, 9, 4100, 6
+    a.struct_size = V27_SIZE_1
+    assert r1(ctypes.byref(a)) == _hip.MX_ROUTE_INNER_VEC
+    b.C, b.rounding, b.step, b.index_base = 64, 9, 4100, 6
+    b.struct_size = V27_SIZE_2
+    assert r2(ctypes.byref(b)) == _hip.MX_Q2_ROUTE_TILE_VEC
 
 
 def test_routes_are_the_predecessors_in_both_modes():
+    """the route of a v27-sized descriptor ("old") is the route of the full one ("new") in either mode, by either symbol"""
     lib = _hip.load()
     # two-way: the operands tests/test_mx_train.py walks -- R, C, xdt, x, row pair, col pair
     P = (16384, 8192, 65536, 32768)
@@ -320,29 +340,31 @@ def test_routes_are_the_predecessors_in_both_modes():
              (64, 64, 0, 4098, P[:2], P[2:]), (64, 64, 7, 4096, P[:2], P[2:]), (64, 64, 1, 4096, (16384, None), P[2:])]
     seen = set()
     for R_, C, xdt, x, row, col in cases:
-        old, new = _hip.MxQuant2Args(), _hip.MxQuant2SrArgs()
-        for d in (old, new):
-            d.struct_size = ctypes.sizeof(d)
+        old, new = _hip.MxQuant2Args(), _hip.MxQuant2Args()
+        for d, size in ((old, V27_SIZE_2), (new, ctypes.sizeof(new))):
+            d.struct_size = size
             d.R, d.C, d.xdt, d.x, d.row_format, d.col_format = R_, C, xdt, x, 4, 1
             (d.row_codes, d.row_scales), (d.col_codes, d.col_scales) = row, col
         want = lib.qs_mx_quant2_route(ctypes.byref(old))
         seen.add(want)
         for rounding in (0, 1):
             new.rounding, new.seed, new.index_base = rounding, 99, 8
-            assert lib.qs_mx_quant2_sr_route(ctypes.byref(new)) == want, (R_, C, xdt, x, row, col, rounding)
+            for route in (lib.qs_mx_quant2_route, lib.qs_mx_quant2_sr_route):
+                assert route(ctypes.byref(new)) == want, (R_, C, xdt, x, row, col, rounding)
     assert {_hip.MX_Q2_ROUTE_TILE_VEC, _hip.MX_Q2_ROUTE_TILE_PLAIN, 0, -1, -2, -3} <= seen
     # one-way: outer, n, inner, xdt, x, y, codes
     seen = set()
     for outer, n, inner, xdt, x, y, codes in ((4, 64, 1, 0, 4096, 8192, 16384), (4, 64, 1, 1, 4096, 8192, None), (4, 45, 1, 0, 4096, 8192, 16384),
                                               (4, 64, 1, 0, 4100, 8192, 16384), (4, 64, 1, 0, 4096, 8192, 16388), (3, 40, 5, 2, 4096, 8192, 16384),
                                               (0, 64, 1, 0, 4096, 8192, 16384), (4, 64, 1, 0, 4098, 8192, 16384), (4, 64, 1, 5, 4096, 8192, 16384)):
-        old, new = _hip.MxQuantArgs(), _hip.MxQuantSrArgs()
-        for d in (old, new):
-            d.struct_size = ctypes.sizeof(d)
+        old, new = _hip.MxQuantArgs(), _hip.MxQuantArgs()
+        for d, size in ((old, V27_SIZE_1), (new, ctypes.sizeof(new))):
+            d.struct_size = size
             d.outer, d.n, d.inner, d.xdt, d.ydt, d.x, d.y, d.codes, d.scales, d.format = outer, n, inner, xdt, 0, x, y, codes, 32768 if codes else None, 2
         want = lib.qs_mx_quant_route(ctypes.byref(old))
         seen.add(want)
         for rounding in (0, 1):
             new.rounding, new.rng_stream = rounding, 1
-            assert lib.qs_mx_quant_sr_route(ctypes.byref(new)) == want, (outer, n, inner, xdt, x, y, codes, rounding)
+            for route in (lib.qs_mx_quant_route, lib.qs_mx_quant_sr_route):
+                assert route(ctypes.byref(new)) == want, (outer, n, inner, xdt, x, y, codes, rounding)
     assert {_hip.MX_ROUTE_INNER_VEC, _hip.MX_ROUTE_INNER_PLAIN, _hip.MX_ROUTE_STRIDED, 0, -1, -3} <= seen

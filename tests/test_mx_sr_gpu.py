@@ -50,7 +50,7 @@ def test_one_way_equals_the_cpu_path_on_every_route(fmt, dtype):
         assert same_all(got, want), (shape, fmt, dtype)
         assert int(dstep) == 5                                                # read, never written
         nearest = quantize_with_mx(x.to(DEV), fmt, dim, True)
-        # the new entry point in nearest mode: the old entry point's bytes
+        # nearest mode asked for by name, with rounding operands it must ignore: the same bytes
         again = _hip.mx_quant_fwd(x.to(DEV), fmt, dim % x.dim(), torch.float32, True, "nearest", 11, dstep, 1)
         assert _hip.mx_last_route == route and same_all(again, nearest)
 
@@ -124,7 +124,7 @@ def test_margins_and_step_survive_the_stochastic_entry_points(dtype):
         nbr, nbc = -(-R_ // 32), -(-C // 32)
         sizes = dict(row_codes=R_ * C, row_scales=R_ * nbc, col_codes=C * R_, col_scales=C * nbr)
         out = {n: _guarded(sz, ooff) for n, sz in sizes.items()}
-        a = _hip.MxQuant2SrArgs()
+        a = _hip.MxQuant2Args()
         a.struct_size = ctypes.sizeof(a)
         a.row_format, a.col_format = _hip.MX_FORMATS.index(rf), _hip.MX_FORMATS.index(cf)
         a.x, a.xdt, a.R, a.C = xbody.data_ptr(), _hip._DT[dtype], R_, C
@@ -133,8 +133,8 @@ def test_margins_and_step_survive_the_stochastic_entry_points(dtype):
         a.stream = _hip._stream(xbody)
         a.rounding, a.seed, a.step, a.index_base = 1, seed, sbody.data_ptr(), 4
         what = (dtype, R_, C, xoff, ooff)
-        assert lib.qs_mx_quant2_sr_route(ctypes.byref(a)) == route, what
-        assert lib.qs_mx_quant2_sr_v(ctypes.byref(a)) == 0, what
+        assert lib.qs_mx_quant2_route(ctypes.byref(a)) == route, what
+        assert lib.qs_mx_quant2_v(ctypes.byref(a)) == 0, what
         torch.cuda.synchronize()
         assert _intact(xraw, R_ * C * esz, xoff * esz) and torch.equal(xbody.cpu(), x.view(torch.uint8).reshape(-1)), ("x", what)
         assert _intact(sraw, 8) and torch.equal(sbody.cpu(), step.view(torch.uint8)), ("step", what)
@@ -153,7 +153,7 @@ def test_margins_and_step_survive_the_stochastic_entry_points(dtype):
         yraw, ybody = _guarded(numel * 4, off * 4)
         craw, cbody = _guarded(numel, off)
         scraw, scbody = _guarded(outer * nb * inner, off)
-        a = _hip.MxQuantSrArgs()
+        a = _hip.MxQuantArgs()
         a.struct_size = ctypes.sizeof(a)
         a.format = _hip.MX_FORMATS.index(rf)
         a.x, a.y, a.codes, a.scales = xbody.data_ptr(), ybody.data_ptr(), cbody.data_ptr(), scbody.data_ptr()
@@ -161,8 +161,8 @@ def test_margins_and_step_survive_the_stochastic_entry_points(dtype):
         a.stream = _hip._stream(xbody)
         a.rounding, a.rng_stream, a.seed, a.step, a.index_base = 1, 3, seed, sbody.data_ptr(), 8
         what = (dtype, outer, n, inner)
-        assert lib.qs_mx_quant_sr_route(ctypes.byref(a)) == route, what
-        assert lib.qs_mx_quant_sr_v(ctypes.byref(a)) == 0, what
+        assert lib.qs_mx_quant_route(ctypes.byref(a)) == route, what
+        assert lib.qs_mx_quant_fwd_v(ctypes.byref(a)) == 0, what
         torch.cuda.synchronize()
         assert _intact(xraw, numel * esz, off * esz) and torch.equal(xbody.cpu(), x.view(torch.uint8).reshape(-1)), ("x", what)
         assert _intact(sraw, 8) and torch.equal(sbody.cpu(), step.view(torch.uint8)), ("step", what)
@@ -176,6 +176,90 @@ def _cpu_pair(x, fmt, seed, step, stream, base):
     """codes and scales of the package's CPU path with an index base (which the public call does not take)"""
     from qsparse_amd.quantize import _mx_aten, _mx_sr_words
     return _mx_aten(x, fmt, x.dim() - 1, torch.float32, True, _mx_sr_words(x.shape, seed, step, stream, base))[1:]
+
+
+# sizeof(qs_mx_quant_args) / sizeof(qs_mx_quant2_args) as ABI v27 had them: where the fields appended in v28 begin
+V27_SIZE_1, V27_SIZE_2 = _hip.MxQuantArgs.rounding.offset, _hip.MxQuant2Args.rounding.offset
+
+
+def _raw_one_way(run, route, x, dim, fmt, size=None, **rounding_operands):
+    """(y, codes, scales), route: one call of the C entry point `run` on a contiguous GPU tensor, outputs pre-filled with a pattern"""
+    outer, n, inner, numel = _hip.split3(x.shape, dim)
+    y = torch.zeros(x.shape, dtype=torch.float32, device=DEV)
+    codes = torch.full(x.shape, PATTERN, dtype=torch.uint8, device=DEV)
+    sshape = list(x.shape)
+    sshape[dim] = -(-n // 32)
+    scales = torch.full(sshape, PATTERN, dtype=torch.uint8, device=DEV)
+    a = _hip.MxQuantArgs()
+    a.struct_size = ctypes.sizeof(a) if size is None else size
+    a.format = _hip.MX_FORMATS.index(fmt)
+    a.x, a.y, a.codes, a.scales = x.data_ptr(), y.data_ptr(), codes.data_ptr(), scales.data_ptr()
+    a.xdt, a.ydt, a.outer, a.n, a.inner = _hip._DT[x.dtype], _hip.F32, outer, n, inner
+    a.stream = _hip._stream(x)
+    for k, v in rounding_operands.items():
+        setattr(a, k, v)
+    r = route(ctypes.byref(a))
+    assert run(ctypes.byref(a)) == 0
+    torch.cuda.synchronize()
+    return (y, codes, scales), r
+
+
+def _raw_two_way(run, route, x, rf, cf, size=None, **rounding_operands):
+    """(row_codes, row_scales, col_codes, col_scales), route: one call of the C entry point `run` on a contiguous GPU tensor [R, C]"""
+    R_, C = x.shape
+    out = [torch.full(shape, PATTERN, dtype=torch.uint8, device=DEV) for shape in ((R_, C), (R_, -(-C // 32)), (C, R_), (C, -(-R_ // 32)))]
+    a = _hip.MxQuant2Args()
+    a.struct_size = ctypes.sizeof(a) if size is None else size
+    a.row_format, a.col_format = _hip.MX_FORMATS.index(rf), _hip.MX_FORMATS.index(cf)
+    a.x, a.xdt, a.R, a.C = x.data_ptr(), _hip._DT[x.dtype], R_, C
+    a.row_codes, a.row_scales, a.col_codes, a.col_scales = (t.data_ptr() for t in out)
+    a.stream = _hip._stream(x)
+    for k, v in rounding_operands.items():
+        setattr(a, k, v)
+    r = route(ctypes.byref(a))
+    assert run(ctypes.byref(a)) == 0
+    torch.cuda.synchronize()
+    return tuple(out), r
+
+
+@pytest.mark.parametrize("fmt", FMTS)
+def test_a_v27_sized_descriptor_is_nearest_rounding(fmt):
+    """a caller compiled against the v27 header passes the v27 struct_size; what lies behind it -- here rounding = 1, seed = 5 -- is
+    never read: the bytes of the full descriptor with rounding = 0, and those of tests/mx_ref.py"""
+    lib = _hip.load()
+    for shape, dim, route in (((4, 64), 1, IV), ((3, 45), 1, IP), ((2, 40, 5), 1, ST)):
+        x = randn(shape, torch.bfloat16, seed=len(shape))
+        xd = x.to(DEV)
+        old, r_old = _raw_one_way(lib.qs_mx_quant_fwd_v, lib.qs_mx_quant_route, xd, dim, fmt, V27_SIZE_1, rounding=1, seed=5)
+        new, r_new = _raw_one_way(lib.qs_mx_quant_fwd_v, lib.qs_mx_quant_route, xd, dim, fmt, rounding=0, seed=5)
+        assert r_old == r_new == route, (shape, r_old, r_new)
+        assert same_all(old, new) and same_all(old, R.reference(x, fmt, dim)), (shape, fmt)
+    other = FMTS[(FMTS.index(fmt) + 2) % 5]
+    for shape, route in (((128, 64), VEC), ((33, 45), PLAIN)):
+        x = randn(shape, torch.bfloat16, seed=shape[0])
+        xd = x.to(DEV)
+        old, r_old = _raw_two_way(lib.qs_mx_quant2_v, lib.qs_mx_quant2_route, xd, fmt, other, V27_SIZE_2, rounding=1, seed=5)
+        new, r_new = _raw_two_way(lib.qs_mx_quant2_v, lib.qs_mx_quant2_route, xd, fmt, other, rounding=0, seed=5)
+        assert r_old == r_new == route, (shape, r_old, r_new)
+        want = R.reference(x, fmt, -1)[1:] + R.reference(x.t().contiguous(), other, -1)[1:]
+        assert same_all(old, new) and same_all(old, want), (shape, fmt, other)
+
+
+def test_the_v27_alias_symbols_are_the_call():
+    lib = _hip.load()
+    step = torch.tensor([9], device=DEV)
+    sr = dict(rounding=1, seed=21, step=step.data_ptr(), index_base=8)
+    x = randn((4, 64), torch.bfloat16, seed=1).to(DEV)
+    alias, r_alias = _raw_one_way(lib.qs_mx_quant_sr_v, lib.qs_mx_quant_sr_route, x, 1, "mxfp4_e2m1", **sr)
+    call, r_call = _raw_one_way(lib.qs_mx_quant_fwd_v, lib.qs_mx_quant_route, x, 1, "mxfp4_e2m1", **sr)
+    assert r_alias == r_call == IV and same_all(alias, call)
+    assert same_all(call, S.reference(x.cpu(), "mxfp4_e2m1", -1, torch.float32, 21, 9, 0, 8))      # (the operands were read)
+    x = randn((128, 64), torch.bfloat16, seed=2).to(DEV)
+    alias, r_alias = _raw_two_way(lib.qs_mx_quant2_sr_v, lib.qs_mx_quant2_sr_route, x, "mxfp4_e2m1", "mxfp6_e3m2", **sr)
+    call, r_call = _raw_two_way(lib.qs_mx_quant2_v, lib.qs_mx_quant2_route, x, "mxfp4_e2m1", "mxfp6_e3m2", **sr)
+    assert r_alias == r_call == VEC and same_all(alias, call)
+    assert R.same(call[0], S.reference(x.cpu(), "mxfp4_e2m1", -1, torch.float32, 21, 9, 0, 8)[1])
+    assert int(step) == 9
 
 
 ALIGNED, RAGGED = (512, 576, 640), (530, 522, 542)        # the shapes of tests/test_mx_train_gpu.py

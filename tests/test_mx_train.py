@@ -27,7 +27,7 @@ VEC, PLAIN = _hip.MX_Q2_ROUTE_TILE_VEC, _hip.MX_Q2_ROUTE_TILE_PLAIN
 
 def test_entry_point_is_declared_bound_and_validates_without_a_gpu(tmp_path):
     lib = _hip.load()
-    assert lib.qs_version() == _hip.ABI_VERSION == 27                          # symbols were added, the version was not raised
+    assert lib.qs_version() == _hip.ABI_VERSION == 28                          # the version this binding needs
     assert "qs_mx_quant2_v" in _hip.SIGNATURES and "qs_mx_quant2_route" in _hip.SIGNATURES
     assert lib.qs_mx_quant2_v(None) == -2 and lib.qs_mx_quant2_route(None) == -2
     short = _hip.MxQuant2Args()
@@ -96,7 +96,8 @@ def test_entry_point_is_declared_bound_and_validates_without_a_gpu(tmp_path):
     subprocess.run(["gcc", "-std=c11", "-o", str(tmp_path / "layout"), str(src)], check=True)
     size, *offs = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.split()
     assert int(size) == ctypes.sizeof(_hip.MxQuant2Args) and [int(o) for o in offs] == [getattr(_hip.MxQuant2Args, f).offset for f in fields]
-    assert fields == ["struct_size", "row_format", "col_format", "x", "xdt", "row_codes", "row_scales", "col_codes", "col_scales", "R", "C", "stream"]
+    assert fields == ["struct_size", "row_format", "col_format", "x", "xdt", "row_codes", "row_scales", "col_codes", "col_scales", "R", "C", "stream",
+                      "rounding", "reserved0", "seed", "step", "index_base"]
 
 
 def randn(shape, dtype, seed=0, spread=3.0):
@@ -234,7 +235,7 @@ def test_col_pair_of_x_only_where_a_weight_gradient_can_be_asked_for(monkeypatch
     import qsparse_amd.mx_gemm as M
     calls = []
     real = M.mx_quantize_2way
-    monkeypatch.setattr(M, "mx_quantize_2way", lambda x, row_fmt=None, col_fmt=None: calls.append((tuple(x.shape), row_fmt, col_fmt)) or real(x, row_fmt, col_fmt))
+    monkeypatch.setattr(M, "mx_quantize_2way", lambda x, row_fmt=None, col_fmt=None, *sr: calls.append((tuple(x.shape), row_fmt, col_fmt)) or real(x, row_fmt, col_fmt, *sr))
     layer, x = MXTrainLinear(64, 32), torch.randn(6, 64)
     X, W, F = (6, 64), (32, 64), "mxfp8_e4m3"
 

@@ -1,0 +1,196 @@
+"""Convolutions on MX codes: ``mx_conv2d`` and the inference-side layer ``MXConv2d`` -- the counterparts of ``mx_matmul`` and
+``MXLinear`` for ``nn.Conv2d``.
+
+Layouts are channels-last, so that the MX blocks of 32 run along the input channels: the contraction axis, innermost in memory,
+as the matrix instruction needs.  ``quantize_with_mx(x.permute(0, 2, 3, 1), fmt, -1, return_codes=True)`` hands out the
+activation's bytes (zero-copy for a ``torch.channels_last`` tensor), a ``quantize(nn.Conv2d(...), callback=MXQuantizer(fmt,
+block_dim=1))`` layer exports the weight's.  On the GPU ``mx_conv2d`` is one HIP kernel (``qs_mx_conv2d_v``): an implicit GEMM
+on the block-scaled MFMA of gfx950 that gathers the windows while it stages them -- no im2col matrix is ever written -- and
+accumulates in float32; on the CPU it evaluates the definition in float64.  Inference only: training through convolutions (the
+input- and weight-gradient products) is not implemented; train with the simulated layers."""
+from typing import Optional
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from qsparse_amd import _hip
+from qsparse_amd.mx_gemm import _OUT_DTYPES
+from qsparse_amd.quantize import MX_BLOCK, MX_FORMATS, MXQuantizer, _mx_format, mx_dequantize, quantize_with_mx
+
+
+def _pair(name: str, v, least: int):
+    """`v` as a pair of ints, each >= `least`"""
+    if isinstance(v, str):
+        raise ValueError(f"{name} must be an int or a pair of ints, got the string {v!r} (padding modes such as 'same' are not supported: "
+                         "give the padding as numbers)")
+    if isinstance(v, bool) or not isinstance(v, (int, tuple, list)):
+        raise TypeError(f"{name} must be an int or a pair of ints, got {type(v).__name__}")
+    p = (v, v) if isinstance(v, int) else tuple(v)
+    if len(p) != 2 or any(isinstance(e, bool) or not isinstance(e, int) for e in p):
+        raise ValueError(f"{name} must be an int or a pair of ints, got {v!r}")
+    if min(p) < least:
+        raise ValueError(f"{name} must be >= {least}, got {v!r}")
+    return p
+
+
+def _check_operand(name: str, what: str, codes: torch.Tensor, scales: torch.Tensor, fmt: str):
+    _mx_format(fmt)
+    for label, t in ((f"{name}_codes", codes), (f"{name}_scales", scales)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{label} must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.uint8:
+            raise TypeError(f"{label} must be uint8 (the bytes quantize_with_mx(..., return_codes=True) returns), got {t.dtype}")
+    if codes.dim() != 4:
+        raise ValueError(f"{name}_codes needs 4 dimensions {what}, got shape {tuple(codes.shape)}")
+    C = codes.shape[-1]
+    want = tuple(codes.shape[:-1]) + ((C + MX_BLOCK - 1) // MX_BLOCK,)
+    if tuple(scales.shape) != want:
+        raise ValueError(f"{name}_scales has shape {tuple(scales.shape)}, expected {want}: one E8M0 byte per block of {MX_BLOCK} "
+                         f"along the last dimension (the channels) of {name}_codes {tuple(codes.shape)}")
+    if scales.device != codes.device:
+        raise ValueError(f"{name}_codes is on {codes.device} but {name}_scales on {scales.device}")
+
+
+def mx_conv2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_codes: torch.Tensor, w_scales: torch.Tensor, w_fmt: str,
+              bias: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """``conv2d(x, w) (+ bias)`` on MX codes, channels-last.  ``x_codes`` ``[B, H, W, C]`` and ``w_codes`` ``[Cout, KH, KW, C]`` are
+    uint8 codes of the formats ``x_fmt`` / ``w_fmt`` (``MX_FORMATS``; they may differ) with blocks along C, ``x_scales`` ``[B, H, W,
+    ceil(C / 32)]`` and ``w_scales`` ``[Cout, KH, KW, ceil(C / 32)]`` their E8M0 bytes, ``bias`` float32 ``[Cout]``; ``stride``,
+    ``padding`` (zeros) and ``dilation`` an int or a pair each; ``groups`` is 1.  Returns ``[B, OH, OW, Cout]``, contiguous, in
+    ``out_dtype`` (float32, bfloat16 or float16):
+
+        y[b, oh, ow, n] = round( sum_{kh, kw, c} val(x[b, ih, iw, c]) 2^(sx[b, ih, iw, c / 32] - 127)
+                                               * val(w[n, kh, kw, c]) 2^(sw[n, kh, kw, c / 32] - 127) + bias[n] )
+        ih = oh * stride_h - pad_h + kh * dil_h,    iw = ow * stride_w - pad_w + kw * dil_w
+
+    with ``val`` the value of a code as ``mx_dequantize`` decodes it; a tap outside the image contributes zero.  A scale byte 0xFF
+    makes every output whose window reads that block NaN.  GPU tensors take the HIP kernel -- float32 accumulation in the order of
+    ``mx_matmul`` on the im2col operands, to which the result is bit-identical; there is no fallback: without the library the call
+    raises -- CPU tensors evaluate the expression above in float64 and round once.  Input channels are padded to a multiple of 32
+    per tap inside the kernel, so a stem (C = 3) spends most of its products on zeros and is slow."""
+    _check_operand("x", "[B, H, W, C]", x_codes, x_scales, x_fmt)
+    _check_operand("w", "[Cout, KH, KW, C]", w_codes, w_scales, w_fmt)
+    (B, H, W, C), (Cout, KH, KW, Cw) = x_codes.shape, w_codes.shape
+    if Cw != C:
+        raise ValueError(f"x_codes {tuple(x_codes.shape)} and w_codes {tuple(w_codes.shape)} disagree on C (their last dimensions)")
+    if C < 1 or KH < 1 or KW < 1 or H < 1 or W < 1:
+        raise ValueError(f"mx_conv2d needs C, H, W, KH, KW >= 1, got x_codes {tuple(x_codes.shape)}, w_codes {tuple(w_codes.shape)}")
+    if w_codes.device != x_codes.device:
+        raise ValueError(f"x_codes is on {x_codes.device} but w_codes on {w_codes.device}")
+    if out_dtype not in _OUT_DTYPES:
+        raise TypeError(f"out_dtype must be one of {_OUT_DTYPES}, got {out_dtype}")
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
+            raise TypeError("bias must be a float32 tensor")
+        if tuple(bias.shape) != (Cout,):
+            raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({Cout},)")
+        if bias.device != x_codes.device:
+            raise ValueError(f"x_codes is on {x_codes.device} but bias on {bias.device}")
+    stride, padding, dilation = _pair("stride", stride, 1), _pair("padding", padding, 0), _pair("dilation", dilation, 1)
+    OH = _hip.mx_conv_out_size(H, KH, stride[0], padding[0], dilation[0])
+    OW = _hip.mx_conv_out_size(W, KW, stride[1], padding[1], dilation[1])
+    if OH < 1 or OW < 1:
+        raise ValueError(f"the kernel {KH}x{KW} (dilation {dilation}) does not fit the padded image {H + 2 * padding[0]}x{W + 2 * padding[1]}: "
+                         f"the output would be {OH}x{OW}")
+    if x_codes.is_cuda:
+        return _hip.mx_conv2d(x_codes.contiguous(), x_scales.contiguous(), x_fmt, w_codes.contiguous(), w_scales.contiguous(), w_fmt,
+                              None if bias is None else bias.contiguous(), stride, padding, dilation, out_dtype)
+    x = mx_dequantize(x_codes, x_scales, x_fmt, -1, torch.float64).permute(0, 3, 1, 2)
+    w = mx_dequantize(w_codes, w_scales, w_fmt, -1, torch.float64).permute(0, 3, 1, 2)
+    # a 0xFF block is NaN in every window that reads it, also against a zero (NaN * 0 is NaN): the convolution's own propagation
+    y = F.conv2d(x, w, None if bias is None else bias.to(torch.float64), stride, padding, dilation)
+    return y.permute(0, 2, 3, 1).to(out_dtype).contiguous()
+
+
+class MXConv2d(nn.Module):
+    """``nn.Conv2d`` (``groups == 1``, zero padding) for inference on MX codes: the weight is held channels-last as uint8 codes
+    ``weight_codes [Cout, KH, KW, C]`` and E8M0 scales ``weight_scales [Cout, KH, KW, ceil(C / 32)]`` of the format ``weight_fmt``
+    (buffers, with the optional float32 ``bias``).  ``forward`` takes ``[B, C, H, W]`` in float32 / bfloat16 / float16, quantizes it
+    to ``act_fmt`` along the channels with the MX quantizer and convolves the two sets of codes with ``mx_conv2d``; it returns a
+    ``torch.channels_last`` ``[B, Cout, OH, OW]`` tensor in ``out_dtype`` that never requires grad.  An input that requires grad
+    while gradients are enabled is refused -- training runs on the simulated layers this one is built from.
+
+    Memory format: a ``torch.channels_last`` input is quantized where it lies (its ``[B, H, W, C]`` view is contiguous and takes
+    the quantizer's innermost-axis route).  An NCHW-contiguous input pays one extra layout pass over the activation before the
+    quantizer; keep the network channels_last to avoid it."""
+
+    def __init__(self, weight_codes: torch.Tensor, weight_scales: torch.Tensor, weight_fmt: str, bias: Optional[torch.Tensor] = None,
+                 stride=1, padding=0, dilation=1, act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32):
+        super().__init__()
+        _mx_format(act_fmt)
+        _check_operand("w", "[Cout, KH, KW, C]", weight_codes, weight_scales, weight_fmt)
+        if out_dtype not in _OUT_DTYPES:
+            raise TypeError(f"out_dtype must be one of {_OUT_DTYPES}, got {out_dtype}")
+        if bias is not None and tuple(bias.shape) != (weight_codes.shape[0],):
+            raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({weight_codes.shape[0]},)")
+        self.weight_fmt, self.act_fmt, self.out_dtype = weight_fmt, act_fmt, out_dtype
+        self.stride, self.padding, self.dilation = _pair("stride", stride, 1), _pair("padding", padding, 0), _pair("dilation", dilation, 1)
+        self.out_channels, self.in_channels = weight_codes.shape[0], weight_codes.shape[3]
+        self.kernel_size = (weight_codes.shape[1], weight_codes.shape[2])
+        self.register_buffer("weight_codes", weight_codes.detach().clone().contiguous())
+        self.register_buffer("weight_scales", weight_scales.detach().clone().contiguous())
+        self.register_buffer("bias", None if bias is None else bias.detach().to(torch.float32).clone().contiguous())
+
+    def extra_repr(self) -> str:
+        return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, "
+                f"dilation={self.dilation}, bias={self.bias is not None}, weight_fmt={self.weight_fmt!r}, act_fmt={self.act_fmt!r}")
+
+    @classmethod
+    def from_exported(cls, qt, bias: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1, act_fmt: str = "mxfp8_e4m3",
+                      out_dtype: torch.dtype = torch.float32):
+        """from the ``QuantizedTensor(kind="mx")`` ``export_integer`` returns for a conv layer's weight ``[Cout, C, KH, KW]`` with
+        blocks along dim 1; codes and scales are permuted to channels-last once, here"""
+        if getattr(qt, "kind", None) != "mx":
+            raise ValueError(f"MXConv2d needs an MX weight (QuantizedTensor.kind == 'mx'), got kind {getattr(qt, 'kind', None)!r}")
+        if qt.codes.dim() != 4:
+            raise ValueError(f"MXConv2d needs a 4-d weight [Cout, C, KH, KW], got shape {tuple(qt.codes.shape)}")
+        if qt.block_dim % qt.codes.dim() != 1:
+            raise ValueError(f"the weight's MX blocks run along dim {qt.block_dim}, not along the input channels (dim 1): such blocks "
+                             "cannot feed the matrix instruction -- quantize the layer with MXQuantizer(fmt, block_dim=1)")
+        return cls(qt.codes.permute(0, 2, 3, 1).contiguous(), qt.block_scale.permute(0, 2, 3, 1).contiguous(), qt.fmt, bias, stride,
+                   padding, dilation, act_fmt, out_dtype)
+
+    @classmethod
+    def from_quantized(cls, layer: nn.Module, act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32):
+        """from a ``quantize(nn.Conv2d(...), bits=w, callback=MXQuantizer(fmt, block_dim=1))`` layer that is past its timeout: the
+        weight codes are the export's, stride / padding / dilation the layer's, the bias what its evaluation-mode forward adds"""
+        from qsparse_amd.export import export_integer
+        q = layer.__dict__.get("_modules", {}).get("quantize")
+        if not isinstance(layer, nn.Conv2d) or q is None or not isinstance(q.callback, MXQuantizer):
+            raise ValueError("MXConv2d.from_quantized needs an nn.Conv2d wrapped by quantize(..., callback=MXQuantizer(...))")
+        if layer.groups != 1:
+            raise ValueError(f"MXConv2d supports groups == 1 only, the layer has groups={layer.groups}")
+        if layer.padding_mode != "zeros":
+            raise ValueError(f"MXConv2d supports zero padding only, the layer has padding_mode={layer.padding_mode!r}")
+        if isinstance(layer.padding, str):
+            raise ValueError(f"MXConv2d needs the padding as numbers, the layer has padding={layer.padding!r}")
+        rec = export_integer(nn.Sequential(layer)).get("0")
+        if rec is None or rec.weight is None:
+            raise ValueError("the layer has not quantized its weight yet (still inside its timeout): nothing to build an MXConv2d from")
+        was = layer.training
+        layer.eval()
+        try:
+            with torch.no_grad():
+                b = layer.bias
+                bias = None if b is None else b.detach().to(torch.float32)
+        finally:
+            layer.train(was)
+        return cls.from_exported(rec.weight, bias, tuple(layer.stride), tuple(layer.padding), tuple(layer.dilation), act_fmt, out_dtype)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError("MXConv2d is an inference layer: its input requires grad.  Train with the simulated layer "
+                               "(quantize(nn.Conv2d(...), callback=MXQuantizer(...))) or call it under torch.no_grad()")
+        if x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise ValueError(f"MXConv2d expects [B, {self.in_channels}, H, W], got shape {tuple(x.shape)}")
+        with torch.no_grad():
+            _, codes, scales = quantize_with_mx(x.permute(0, 2, 3, 1), self.act_fmt, -1, return_codes=True)
+            if not codes.is_contiguous():      # an input that was not channels_last: one layout pass
+                codes, scales = codes.contiguous(), scales.contiguous()
+            y = mx_conv2d(codes, scales, self.act_fmt, self.weight_codes, self.weight_scales, self.weight_fmt, self.bias, self.stride,
+                          self.padding, self.dilation, self.out_dtype)
+            return y.permute(0, 3, 1, 2)
+
+
+__all__ = ["mx_conv2d", "MXConv2d", "MX_FORMATS"]

@@ -926,6 +926,58 @@ int qs_mx_matmul_v(const qs_mx_matmul_args* args);
 #define QS_MX_GEMM_ROUTE_PLAIN 2
 int qs_mx_matmul_route(const qs_mx_matmul_args* args);
 
+/* ---- MX matrix product, split along K (deterministic split-K) ----------------------------------------------------------------------
+ * Added without raising QS_ABI_VERSION (28), by the same rule as qs_mx_matmul_v above: symbols are only added.
+ *
+ * For products with a small output and a long contraction (a linear layer's weight gradient): qs_mx_matmul_v has one work-group per
+ * 128 x 128 tile of y, each walking all of K; here the walk is cut into slices that run side by side.  With steps = ceil(K / 128)
+ * and a requested slice count S >= 1:
+ *   per = ceil(steps / S),  S' = ceil(steps / per)  (no slice is empty; S' <= S, and S' requested again gives S' again)
+ *   slice s covers the K-steps [s per, min((s + 1) per, steps)), i.e. the codes k in [128 s per, min(128 (s + 1) per, K)): slice
+ *   boundaries are multiples of 128, hence of the MX block
+ *   p_s[m, n] = the float32 value qs_mx_matmul_v computes for the operands restricted to slice s, without bias, ydt = QS_F32
+ *   y[m, n]   = round_once_to_ydt( ((p_0 + p_1) + p_2 + ... + p_{S'-1}) + bias[n] )
+ * All adds are float32, in ascending s; the bias is added last.  S' == 1 IS qs_mx_matmul_v: the call is forwarded to it and the
+ * result is bit-identical.  The result is a pure function of the operands and S -- the same on every run and every device: there are
+ * no atomics of any kind and no synchronisation between work-groups.  0xFF scale bytes keep their meaning: a NaN partial makes the
+ * sum NaN.  Two launches (partial products into the workspace: tiles x S' work-groups; the reduction), graph-capturable, no
+ * allocation, no synchronisation.
+ *   - workspace: caller-provided, S' * M * N * 4 bytes (qs_mx_matmul_splitk_plan tells), 16-byte aligned (QS_ERR_ALIGN otherwise);
+ *     too small: QS_ERR_WORKSPACE; NULL with S' > 1: QS_ERR_ARG.  Not needed, and not looked at, when S' == 1.  Its contents on
+ *     entry do not matter; on return it holds the partials, and nothing past S' * M * N * 4 bytes was written.
+ *   - Every check of qs_mx_matmul_v applies unchanged and comes first; then split_k < 1: QS_ERR_ARG.  M == 0 or N == 0: nothing is
+ *     enqueued.  tiles * S' beyond 2^31 - 1 or a byte count beyond 64 bits: QS_ERR_ARG.
+ *   - Routes are those of qs_mx_matmul_v, decided by the same conditions (K % 16 == 0, 16-byte aligned code bases). */
+typedef struct qs_mx_matmul_splitk_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_matmul_splitk_args) as the caller compiled it */
+    int32_t a_format, b_format;      /* the fields of qs_mx_matmul_args, with their meaning ... */
+    const uint8_t* a_codes;
+    const uint8_t* a_scales;
+    const uint8_t* b_codes;
+    const uint8_t* b_scales;
+    const float* bias;
+    void* y;
+    int32_t ydt;
+    int64_t M, N, K;
+    qs_stream_t stream;
+    int32_t split_k;                 /* ... and: S >= 1, the requested number of slices */
+    int32_t reserved0;
+    void* workspace;                 /* S' * M * N float32; nullable when S' == 1 */
+    uint64_t workspace_bytes;
+} qs_mx_matmul_splitk_args;
+int qs_mx_matmul_splitk_v(const qs_mx_matmul_splitk_args* args);
+/* the kernel the first launch of qs_mx_matmul_splitk_v runs for these operands (S' == 1: the one qs_mx_matmul_v runs), nothing
+ * enqueued: QS_MX_GEMM_ROUTE_*, 0 for an empty product, or the QS_ERR_* the call would return */
+int qs_mx_matmul_splitk_route(const qs_mx_matmul_splitk_args* args);
+/* writes S' and the workspace bytes (0 when S' == 1) of a request; either pointer may be NULL.  split_k == 0 asks for the library's
+ * automatic choice, a pure function of (M, N, K) on compile-time constants (no query of the device) and the single place the rule
+ * lives.  With tiles = ceil(M / 128) ceil(N / 128) and steps = ceil(K / 128):
+ *     S = 1                                                 when steps < 32 or tiles >= 256
+ *     S = max(1, min(floor(512 / tiles), floor(steps / 8), 16))   otherwise
+ * -- 256 tiles already give every CU a work-group; 512 work-groups are two co-resident ones per CU; a slice keeps at least 8 steps.
+ * QS_ERR_ARG: a negative extent or request, K == 0 with M, N > 0, a byte count beyond 64 bits.  M == 0 or N == 0: S' = 1, 0 bytes. */
+int qs_mx_matmul_splitk_plan(int64_t M, int64_t N, int64_t K, int32_t split_k, int32_t* slices, uint64_t* workspace_bytes);
+
 /* ---- MX two-way quantizer (codes only) -----------------------------------------------------------------------------------------
  * Added without raising QS_ABI_VERSION (27), by the same rule as qs_mx_matmul_v above: symbols are only added.
  *

@@ -97,6 +97,9 @@ SIGNATURES = {
     "qs_mx_quant_route": (c_int, [_P]),
     "qs_mx_matmul_v": (c_int, [_P]),
     "qs_mx_matmul_route": (c_int, [_P]),
+    "qs_mx_matmul_splitk_v": (c_int, [_P]),
+    "qs_mx_matmul_splitk_route": (c_int, [_P]),
+    "qs_mx_matmul_splitk_plan": (c_int, [_L, _L, _L, c_int32, _P, _P]),
     "qs_mx_quant2_v": (c_int, [_P]),
     "qs_mx_quant2_route": (c_int, [_P]),
     "qs_mx_quant_sr_v": (c_int, [_P]),
@@ -190,6 +193,12 @@ class MxMatmulArgs(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("a_format", c_int32), ("b_format", c_int32), ("a_codes", c_void_p),
                 ("a_scales", c_void_p), ("b_codes", c_void_p), ("b_scales", c_void_p), ("bias", c_void_p), ("y", c_void_p),
                 ("ydt", c_int32), ("M", c_int64), ("N", c_int64), ("K", c_int64), ("stream", c_void_p)]
+
+
+class MxMatmulSplitkArgs(ctypes.Structure):
+    """`qs_mx_matmul_splitk_args` of include/qsparse_hip.h"""
+    _fields_ = MxMatmulArgs._fields_ + [("split_k", c_int32), ("reserved0", c_int32), ("workspace", c_void_p),
+                                        ("workspace_bytes", ctypes.c_uint64)]
 
 
 class MxQuant2Args(ctypes.Structure):
@@ -867,30 +876,49 @@ def mx_quant_fwd(x: torch.Tensor, fmt: str, block_dim: int, out_dtype: torch.dty
 
 MX_GEMM_ROUTE_VEC, MX_GEMM_ROUTE_PLAIN = 1, 2
 mx_gemm_last_route = None     # the QS_MX_GEMM_ROUTE_* of the last `mx_matmul` launch (None: an empty product), for tests and tools
+mx_gemm_last_split = 1        # the S' of the last `mx_matmul` launch: 1 for an unsplit one
+
+
+def mx_split_plan(M: int, N: int, K: int, split_k: int):
+    """(S', workspace bytes) of `qs_mx_matmul_splitk_plan` for a request of `split_k` slices; 0 asks for the library's automatic choice"""
+    slices, nbytes = c_int32(0), ctypes.c_uint64(0)
+    _check(load().qs_mx_matmul_splitk_plan(M, N, K, split_k, ctypes.byref(slices), ctypes.byref(nbytes)), "qs_mx_matmul_splitk_plan")
+    return slices.value, nbytes.value
 
 
 def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
-              bias: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+              bias: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32, split_k: int = 1) -> torch.Tensor:
     """y[M, N] = A . B^T on MX codes (qs_mx_matmul_v): `a_codes` [M, K], `b_codes` [N, K] uint8, scales [*, ceil(K / 32)] uint8,
-    all contiguous GPU tensors (qsparse_amd/mx_gemm.py checks and flattens); `bias` float32 [N] or None.  ONE launch."""
-    global mx_gemm_last_route
+    all contiguous GPU tensors (qsparse_amd/mx_gemm.py checks and flattens); `bias` float32 [N] or None.  ONE launch -- or, when
+    `split_k` (0: the library's choice) plans S' > 1 slices of K, the two of qs_mx_matmul_splitk_v, with a workspace from torch's
+    caching allocator (no hipMalloc in a warmed-up step: capture stays possible)."""
+    global mx_gemm_last_route, mx_gemm_last_split
     lib = load()
     (M, K), N = a_codes.shape, b_codes.shape[0]
     y = torch.empty((M, N), dtype=out_dtype, device=a_codes.device)
-    mx_gemm_last_route = None
+    mx_gemm_last_route, mx_gemm_last_split = None, 1
     if M and N:
-        a = MxMatmulArgs()
+        slices, nbytes = mx_split_plan(M, N, K, split_k)
+        a = MxMatmulSplitkArgs() if slices > 1 else MxMatmulArgs()
         a.struct_size = ctypes.sizeof(a)
         a.a_format, a.b_format = MX_FORMATS.index(a_fmt), MX_FORMATS.index(b_fmt)
         a.a_codes, a.a_scales, a.b_codes, a.b_scales = _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales)
         a.bias, a.y, a.ydt = _ptr(bias), _ptr(y), _DT[out_dtype]
         a.M, a.N, a.K = M, N, K
         a.stream = _stream(a_codes)
-        route = lib.qs_mx_matmul_route(ctypes.byref(a))
-        with _timed(f"mx_matmul[{route}]", a_codes, a_scales, b_codes, b_scales, bias, y):
-            st = lib.qs_mx_matmul_v(ctypes.byref(a))
-        _check(st, "qs_mx_matmul_v")
-        mx_gemm_last_route = route
+        if slices > 1:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=a_codes.device)
+            a.split_k, a.workspace, a.workspace_bytes = slices, _ptr(ws), nbytes
+            route = lib.qs_mx_matmul_splitk_route(ctypes.byref(a))
+            with _timed(f"mx_matmul_splitk[{route}]", a_codes, a_scales, b_codes, b_scales, bias, y, 2 * nbytes):
+                st = lib.qs_mx_matmul_splitk_v(ctypes.byref(a))
+            _check(st, "qs_mx_matmul_splitk_v")
+        else:
+            route = lib.qs_mx_matmul_route(ctypes.byref(a))
+            with _timed(f"mx_matmul[{route}]", a_codes, a_scales, b_codes, b_scales, bias, y):
+                st = lib.qs_mx_matmul_v(ctypes.byref(a))
+            _check(st, "qs_mx_matmul_v")
+        mx_gemm_last_route, mx_gemm_last_split = route, slices
     return y
 
 

@@ -41,8 +41,21 @@ def _check_operand(name: str, codes: torch.Tensor, scales: torch.Tensor, fmt: st
         raise ValueError(f"{name}_codes is on {codes.device} but {name}_scales on {scales.device}")
 
 
+def _split_request(split_k, name: str = "split_k") -> int:
+    """the slice count the C ABI takes for `split_k`: an int >= 1 as it is, "auto" as 0 (the library's rule)"""
+    if isinstance(split_k, str):
+        if split_k != "auto":
+            raise ValueError(f'{name} must be an int >= 1 or "auto", got {split_k!r}')
+        return 0
+    if isinstance(split_k, bool) or not isinstance(split_k, int):
+        raise TypeError(f'{name} must be an int >= 1 or "auto", got {type(split_k).__name__}')
+    if not 1 <= split_k < 2 ** 31:
+        raise ValueError(f'{name} must be an int >= 1 or "auto", got {split_k}')
+    return split_k
+
+
 def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
-              bias: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+              bias: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32, *, split_k=1) -> torch.Tensor:
     """``A . B^T (+ bias)`` on MX codes.  ``a_codes`` ``[..., K]`` and ``b_codes`` ``[N, K]`` (an ``nn.Linear`` weight) are uint8
     codes of the formats ``a_fmt`` / ``b_fmt`` (``MX_FORMATS``; they may differ) with blocks along K, ``a_scales`` ``[..., ceil(K /
     32)]`` and ``b_scales`` ``[N, ceil(K / 32)]`` their E8M0 bytes, ``bias`` float32 ``[N]``.  Returns ``[..., N]`` in ``out_dtype``
@@ -52,7 +65,16 @@ def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes
 
     with ``val`` the value of a code as ``mx_dequantize`` decodes it.  A scale byte 0xFF (a block that held NaN / Inf) makes every
     output that reads it NaN.  GPU tensors take the HIP kernel (float32 accumulation; there is no fallback: without the library
-    the call raises), CPU tensors evaluate the expression above in float64 and round once."""
+    the call raises), CPU tensors evaluate the expression above in float64 and round once.
+
+    ``split_k`` (keyword; an int ``>= 1`` or ``"auto"``) cuts the walk along K into that many slices of whole steps of 128 codes
+    (``qs_mx_matmul_splitk_v``): the slices run side by side, their float32 partial sums go to a workspace and are added in ascending
+    order, then the bias, then the one rounding -- no atomics, so the result is a pure function of the operands and ``split_k``,
+    the same on every run.  It is for products with a small output and a long K (a weight gradient), which otherwise occupy a
+    fraction of the GPU.  ``1`` (the default) is the unsplit kernel, bit for bit; ``"auto"`` lets the library choose from the shape
+    (1 whenever ``ceil(K / 128) < 32`` or the output has 256 tiles of 128 x 128 or more).  A request that leaves one slice is the
+    unsplit call.  The CPU path checks the argument and evaluates the float64 definition, which has no order to cut."""
+    request = _split_request(split_k)
     _check_operand("a", a_codes, a_scales, a_fmt)
     _check_operand("b", b_codes, b_scales, b_fmt)
     if b_codes.dim() != 2:
@@ -77,7 +99,7 @@ def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes
     a2, sa2 = a_codes.reshape(-1, K), a_scales.reshape(-1, a_scales.shape[-1])
     if a_codes.is_cuda:
         y = _hip.mx_matmul(a2.contiguous(), sa2.contiguous(), a_fmt, b_codes.contiguous(), b_scales.contiguous(), b_fmt,
-                           None if bias is None else bias.contiguous(), out_dtype)
+                           None if bias is None else bias.contiguous(), out_dtype, request)
     else:
         a = mx_dequantize(a2, sa2, a_fmt, -1, torch.float64)
         b = mx_dequantize(b_codes, b_scales, b_fmt, -1, torch.float64)
@@ -198,7 +220,7 @@ class _MXLinearFunction(torch.autograd.Function):
     """y = Q(x) Q(W)^T + b, dx = Q(dy) Q(W^T)^T, dW = Q(dy^T) Q(x^T)^T on MX codes; every quantizer straight-through"""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, x_fmt, w_fmt, grad_fmt, need_col, grad_rounding="nearest", seed=0, step=None):
+    def forward(ctx, x, weight, bias, x_fmt, w_fmt, grad_fmt, need_col, grad_rounding="nearest", seed=0, step=None, wgrad_split_k=1):
         # `need_col`: a weight gradient can be asked for -- decided by mx_linear, where the grad mode is still the caller's (it is
         # always off in here, and needs_input_grad is requires_grad whatever the mode)
         N, K = weight.shape
@@ -212,6 +234,7 @@ class _MXLinearFunction(torch.autograd.Function):
         ctx.fmts = (x_fmt, w_fmt, grad_fmt)
         # `step` is advanced in place by the backward: an attribute, not a saved tensor (no version check, nothing to differentiate)
         ctx.sr = (grad_rounding, seed, step)
+        ctx.wgrad_split_k = wgrad_split_k
         ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
         ctx.bias_dtype = None if bias is None else bias.dtype
         return y.reshape(x.shape[:-1] + (N,))
@@ -237,15 +260,15 @@ class _MXLinearFunction(torch.autograd.Function):
             _, _, w_col, w_cs = mx_quantize_2way(weight, None, w_fmt)
             dx = mx_matmul(g_row, g_rs, grad_fmt, w_col, w_cs, w_fmt, None, ctx.x_dtype).reshape(ctx.x_shape)
         if need_dw:
-            dw = mx_matmul(g_col, g_cs, grad_fmt, x_col, x_cs, x_fmt, None, weight.dtype)
+            dw = mx_matmul(g_col, g_cs, grad_fmt, x_col, x_cs, x_fmt, None, weight.dtype, split_k=ctx.wgrad_split_k)
         if need_db:
             db = dy2.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
-        return dx, dw, db, None, None, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None, None
 
 
 def mx_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, x_fmt: str = "mxfp8_e4m3",
               w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2", grad_rounding: str = "nearest", seed: int = 0,
-              step: Optional[torch.Tensor] = None) -> torch.Tensor:
+              step: Optional[torch.Tensor] = None, wgrad_split_k="auto") -> torch.Tensor:
     """``F.linear`` whose three matrix products run on MX codes (``mx_matmul``), differentiable in ``x``, ``weight`` and ``bias``.
     ``x`` is ``[..., K]`` in float32 / bfloat16 / float16, ``weight`` ``[N, K]`` and ``bias`` ``[N]`` in any of the three (float32
     parameters next to a bfloat16 ``x`` are fine); the result is ``[..., N]`` in ``x.dtype``.  With ``Q_f(t)`` the MX quantization of
@@ -267,7 +290,14 @@ def mx_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
     ``Q_g(dy)`` an unbiased estimate of ``dy`` also in the FP6 / FP4 formats, where nearest rounding zeroes every element below half
     its block's smallest step.  ``step`` (a one-element int64 tensor on ``x``'s device, or None) is part of the key and is advanced
     by one in place after each backward that quantizes ``dy``, without a host synchronisation: successive steps, and successive
-    replays of a captured step, draw different words."""
+    replays of a captured step, draw different words.
+
+    ``wgrad_split_k`` (an int ``>= 1`` or ``"auto"``) is ``mx_matmul``'s ``split_k`` for the weight-gradient product alone -- the one
+    with a small output ``[N, K]`` and the contraction over the ``M`` rows; ``y`` and ``dx`` are untouched by it.  The default
+    ``"auto"`` lets the library split that product when its shape leaves most of the GPU idle: ``dW`` then differs from
+    ``wgrad_split_k=1`` in the order of its float32 additions only (deterministically: same bits on every run), and only for shapes
+    the rule splits -- none with fewer than 3969 rows ``M``, none whose weight has 256 tiles of 128 x 128 or more."""
+    _split_request(wgrad_split_k, "wgrad_split_k")
     for name, fmt in (("x_fmt", x_fmt), ("w_fmt", w_fmt), ("grad_fmt", grad_fmt)):
         _mx_format(fmt)
     _mx_check_rounding(grad_rounding, step, x)
@@ -287,7 +317,7 @@ def mx_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
     if bias is not None and tuple(bias.shape) != (weight.shape[0],):
         raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({weight.shape[0]},)")
     need_col = torch.is_grad_enabled() and weight.requires_grad
-    return _MXLinearFunction.apply(x, weight, bias, x_fmt, w_fmt, grad_fmt, need_col, grad_rounding, seed, step)
+    return _MXLinearFunction.apply(x, weight, bias, x_fmt, w_fmt, grad_fmt, need_col, grad_rounding, seed, step, wgrad_split_k)
 
 
 class MXTrainLinear(nn.Linear):
@@ -298,14 +328,20 @@ class MXTrainLinear(nn.Linear):
     ``grad_rounding="stochastic"`` rounds the gradient operands stochastically (``mx_linear``).  The layer then owns ``sr_seed`` --
     ``seed``, or a draw from torch's default CPU generator when that is None, so ``torch.manual_seed`` makes a model reproducible
     and no two layers share their noise -- and a non-persistent int64 buffer ``sr_step`` that counts its backwards on the device.
-    With ``"nearest"`` neither exists and the ``state_dict`` is ``nn.Linear``'s."""
+    With ``"nearest"`` neither exists and the ``state_dict`` is ``nn.Linear``'s.
+
+    ``wgrad_split_k`` is ``mx_linear``'s: ``"auto"`` (the default) lets the library split the weight-gradient product along the batch
+    rows where that fills the GPU, which changes ``weight.grad`` in float32 summation order only (never below 3969 rows)."""
 
     def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=None, x_fmt: str = "mxfp8_e4m3",
-                 w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2", grad_rounding: str = "nearest", seed: Optional[int] = None):
+                 w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2", grad_rounding: str = "nearest", seed: Optional[int] = None,
+                 wgrad_split_k="auto"):
         super().__init__(in_features, out_features, bias=bias, device=device, dtype=dtype)
         for fmt in (x_fmt, w_fmt, grad_fmt):
             _mx_format(fmt)
         _mx_check_rounding(grad_rounding, None, self.weight)
+        _split_request(wgrad_split_k, "wgrad_split_k")
+        self.wgrad_split_k = wgrad_split_k
         self.x_fmt, self.w_fmt, self.grad_fmt, self.grad_rounding = x_fmt, w_fmt, grad_fmt, grad_rounding
         if grad_rounding == "stochastic":
             self.sr_seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if seed is None else int(seed)
@@ -313,12 +349,12 @@ class MXTrainLinear(nn.Linear):
 
     @classmethod
     def from_linear(cls, layer: nn.Linear, x_fmt: str = "mxfp8_e4m3", w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2",
-                    grad_rounding: str = "nearest", seed: Optional[int] = None):
+                    grad_rounding: str = "nearest", seed: Optional[int] = None, wgrad_split_k="auto"):
         """a layer on ``layer``'s own parameters (shared, not copied)"""
         if not isinstance(layer, nn.Linear):
             raise TypeError(f"MXTrainLinear.from_linear needs an nn.Linear, got {type(layer).__name__}")
         new = cls(layer.in_features, layer.out_features, bias=layer.bias is not None, device="meta", x_fmt=x_fmt, w_fmt=w_fmt,
-                  grad_fmt=grad_fmt, grad_rounding=grad_rounding, seed=seed)
+                  grad_fmt=grad_fmt, grad_rounding=grad_rounding, seed=seed, wgrad_split_k=wgrad_split_k)
         new.weight, new.bias = layer.weight, layer.bias
         if grad_rounding == "stochastic":
             new.sr_step = torch.zeros(1, dtype=torch.int64, device=layer.weight.device)
@@ -327,14 +363,16 @@ class MXTrainLinear(nn.Linear):
 
     def extra_repr(self) -> str:
         sr = f", grad_rounding={self.grad_rounding!r}" if self.grad_rounding != "nearest" else ""
-        return f"{super().extra_repr()}, x_fmt={self.x_fmt!r}, w_fmt={self.w_fmt!r}, grad_fmt={self.grad_fmt!r}{sr}"
+        split = f", wgrad_split_k={self.wgrad_split_k!r}" if self.wgrad_split_k != "auto" else ""
+        return f"{super().extra_repr()}, x_fmt={self.x_fmt!r}, w_fmt={self.w_fmt!r}, grad_fmt={self.grad_fmt!r}{sr}{split}"
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         dev = x.device.type
         if torch.is_autocast_enabled(dev):
             x = x.to(torch.get_autocast_dtype(dev))
         seed, step = (self.sr_seed, self.sr_step) if self.grad_rounding == "stochastic" else (0, None)
-        return mx_linear(x, self.weight, self.bias, self.x_fmt, self.w_fmt, self.grad_fmt, self.grad_rounding, seed, step)
+        return mx_linear(x, self.weight, self.bias, self.x_fmt, self.w_fmt, self.grad_fmt, self.grad_rounding, seed, step,
+                         self.wgrad_split_k)
 
     def to_inference(self, act_fmt: Optional[str] = None, out_dtype: torch.dtype = torch.float32) -> MXLinear:
         """the ``MXLinear`` on the current weight: its weight bytes are the row pair the training forward multiplies with"""

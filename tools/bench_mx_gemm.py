@@ -3,6 +3,7 @@
 
     python3 tools/bench_mx_gemm.py [--out profiles/mx_gemm.json] [--iters 50] [--warmup 10] [--small]
     python3 tools/bench_mx_gemm.py --errors [--out profiles/mx_gemm_error.json]
+    python3 tools/bench_mx_gemm.py --splitk [--out profiles/mx_splitk_gemm.json]
 
 One process.  Per case and operation: `warmup` launches, then HIP events around `iters` back-to-back launches, three times, the
 median kept (all three recorded).  Shapes: [50432, 768] x [3072, 768] and [50432, 3072] x [768, 3072] (the ViT-B MLP of bench.py's
@@ -13,7 +14,12 @@ same values, in the same process:
   (b) F.linear on their bf16 images -- for orientation, no target
 and the end-to-end figure quantize_with_mx(x) + mx_matmul (bf16 activations in).  `--errors`: the largest |y - y64| / S per format
 pair (S = sum_k |a_k b_k|, float64 on the CPU) on quantizer-produced inputs, K = 4096 -- the slack under the tests' bound
-2 K 2^-23.  Needs a GPU: there is no fallback.  `--small` shrinks the shapes for a functional rehearsal (its numbers mean nothing)."""
+2 K 2^-23.  `--splitk`: the three products of a linear layer's step on the same three layer shapes, in the formats and output
+dtypes `mx_linear` uses (forward E4M3 x E4M3 and dgrad E5M2 x E4M3 to bf16, wgrad E5M2 x E4M3 to float32): each unsplit, and the
+weight-gradient products also through `mx_matmul(..., split_k=S)` for S = "auto", 2, 3, 4, 6, 8 -- both launches of the split call
+inside the timed window.  On a commit without split-K the tool finds no split call and times the unsplit products alone: that run is
+the yardstick (THE BARS: the split call at the automatic S no slower than the yardstick's unsplit weight-gradient product; the unsplit
+products no slower than the yardstick's by more than the larger of its repeat-to-repeat spread and 2 %).  Needs a GPU: there is no fallback.  `--small` shrinks the shapes for a functional rehearsal (its numbers mean nothing)."""
 import argparse
 import json
 import os
@@ -88,6 +94,49 @@ def bench(args):
     print("wrote", args.out)
 
 
+def splitk(args):
+    import torch
+    from qsparse_amd import _hip
+    from qsparse_amd.mx_gemm import mx_matmul
+    from qsparse_amd.quantize import quantize_with_mx
+    dev = "cuda:0"
+    layers = [(50432, 3072, 768), (50432, 768, 3072), (4096, 4096, 4096)] if not args.small else [(4224, 384, 256), (256, 256, 512)]
+    has_split = hasattr(_hip, "mx_split_plan")
+    out = {"device": torch.cuda.get_device_name(0), "commit": args.commit, "iters": args.iters, "warmup": args.warmup,
+           "split_k_available": has_split, "cases": []}
+    g = torch.Generator(device=dev).manual_seed(0)
+    e4, e5 = "mxfp8_e4m3", "mxfp8_e5m2"
+    for Ml, Nl, Kl in layers:
+        # product, (rows of A, rows of B, contraction), formats, output dtype
+        for name, (M, N, K), fa, fb, dt in (("forward", (Ml, Nl, Kl), e4, e4, torch.bfloat16), ("dgrad", (Ml, Kl, Nl), e5, e4, torch.bfloat16),
+                                            ("wgrad", (Nl, Kl, Ml), e5, e4, torch.float32)):
+            _, ac, asc = quantize_with_mx(torch.randn(M, K, device=dev, generator=g, dtype=torch.bfloat16), fa, -1, return_codes=True)
+            _, bc, bsc = quantize_with_mx(torch.randn(N, K, device=dev, generator=g, dtype=torch.bfloat16), fb, -1, return_codes=True)
+            flop = 2.0 * M * N * K
+            rec = {"layer": [Ml, Nl, Kl], "product": name, "M": M, "N": N, "K": K, "a_fmt": fa, "b_fmt": fb, "out": str(dt).split(".")[1]}
+            ms, reps = timed(lambda: mx_matmul(ac, asc, fa, bc, bsc, fb, None, dt), args.iters, args.warmup)
+            assert _hip.mx_gemm_last_route == _hip.MX_GEMM_ROUTE_VEC
+            rec["unsplit"] = {"ms": ms, "reps_ms": reps, "tflops": flop / ms * 1e-9, "spread": (max(reps) - min(reps)) / ms}
+            if has_split:
+                rec["auto_slices"] = _hip.mx_split_plan(M, N, K, 0)[0]
+                if name == "wgrad":
+                    y1 = mx_matmul(ac, asc, fa, bc, bsc, fb, None, dt)
+                    for S in ("auto", 2, 3, 4, 6, 8):
+                        y = mx_matmul(ac, asc, fa, bc, bsc, fb, None, dt, split_k=S)
+                        slices = _hip.mx_gemm_last_split
+                        err = float((y - y1).abs().max() / y1.abs().max())          # summation order only: a few float32 ulps
+                        ms_s, reps_s = timed(lambda: mx_matmul(ac, asc, fa, bc, bsc, fb, None, dt, split_k=S), args.iters, args.warmup)
+                        rec[f"split_{S}"] = {"slices": slices, "ms": ms_s, "reps_ms": reps_s, "tflops": flop / ms_s * 1e-9,
+                                             "ratio_to_unsplit": ms_s / ms, "max_abs_diff_over_max_abs": err}
+            out["cases"].append(rec)
+            print(json.dumps(rec), flush=True)
+            with open(args.out, "w") as f:
+                json.dump(out, f, indent=1)
+                f.write("\n")
+            del ac, asc, bc, bsc
+    print("wrote", args.out)
+
+
 def errors(args):
     import torch
     from qsparse_amd.mx_gemm import mx_matmul
@@ -119,14 +168,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--small", action="store_true")
     ap.add_argument("--errors", action="store_true")
+    ap.add_argument("--splitk", action="store_true")
     ap.add_argument("--commit", default="", help="recorded in the output: the commit the figures were measured on")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_mx_gemm.py measures on the GPU: none found")
-    args.out = args.out or os.path.join(ROOT, "profiles", "mx_gemm_error.json" if args.errors else "mx_gemm.json")
+    args.out = args.out or os.path.join(ROOT, "profiles", "mx_gemm_error.json" if args.errors else "mx_splitk_gemm.json" if args.splitk else "mx_gemm.json")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    (errors if args.errors else bench)(args)
+    (errors if args.errors else splitk if args.splitk else bench)(args)
 
 
 if __name__ == "__main__":

@@ -19,7 +19,10 @@ Layer step: forward + backward of one linear, (M, N, K) = the two ViT-B MLP shap
   (a) the simulated layer, quantize(nn.Linear, callback=MXQuantizer("mxfp8_e4m3", block_dim=1)) past its timeout, on an
       MX-quantized input, forward + backward.  THE BAR: the MXTrainLinear step no slower than (a)
   (b) a plain bf16 nn.Linear, forward + backward -- for information
-  and the step's launches one by one (HIP events around each): the four two-way calls and the three GEMMs.
+  and the step's launches one by one (HIP events around each): the four two-way calls and the three GEMMs.  On commits with
+  split-K (`wgrad_split_k`) the step is the default one ("auto": the weight gradient of the two ViT shapes is split), the step with
+  wgrad_split_k=1 is timed next to it, and the weight-gradient entry of the launch list is the split call, both launches.
+  `--no-quantizer` skips the two-way quantizer section.
 Stochastic rounding (commits that have it; `--no-stochastic` skips): the two-way call on a gradient-like bf16 tensor of the three
   quantizer shapes, E5M2 and FP4, both pairs, stochastic with a device step counter, next to the nearest-mode call and to the
   yardstick (t) / (s) above in that format.  THE BAR: the stochastic call no slower than the yardstick.  And the layer step with
@@ -145,6 +148,10 @@ def bench_layer(args, out, save):
             ms, reps = timed(step, args.iters, args.warmup)
             rec["mx_train_linear"] = {"ms": ms, "reps_ms": reps, "ratio_to_simulated": ms / ms_a, "ratio_to_linear_bf16": ms / ms_b,
                                       "no_slower_than_simulated": bool(ms <= max(reps_a))}
+            if hasattr(layer, "wgrad_split_k"):
+                rec["mx_train_linear"]["wgrad_slices"] = _hip.mx_split_plan(N, K, M, 0)[0]
+                ms_1, reps_1 = timed(step_of(qs.MXTrainLinear.from_linear(base, wgrad_split_k=1), x, dy), args.iters, args.warmup)
+                rec["mx_train_linear_wgrad_unsplit"] = {"ms": ms_1, "reps_ms": reps_1, "ratio_to_linear_bf16": ms_1 / ms_b}
             # the launches of a step one by one, in order: quantizer calls x (both pairs), W (row), dy (both), W (col); GEMMs
             # forward, dgrad, wgrad
             _hip.start_event_log()
@@ -153,7 +160,11 @@ def bench_layer(args, out, save):
                 step()
             log = _hip.stop_event_log()
             q2 = [t for k, v in log.items() if k.startswith("mx_quant2") for t in v]
-            mm = [t for k, v in log.items() if k.startswith("mx_matmul") for t in v]
+            mm = [t for k, v in log.items() if k.startswith("mx_matmul[") for t in v]
+            wg = [t for k, v in log.items() if k.startswith("mx_matmul_splitk[") for t in v]
+            if wg:                                  # a split weight gradient is logged under its own name: back into launch order
+                assert len(mm) == 2 * n and len(wg) == n
+                mm = [t for i in range(n) for t in (mm[2 * i], mm[2 * i + 1], wg[i])]
             assert len(q2) == 4 * n and len(mm) == 3 * n and len([k for k in log if k.startswith("mx_quant2")]) == 1
             for names, ts in ((("quant2_x_both", "quant2_w_row", "quant2_dy_both", "quant2_w_col"), q2), (("gemm_forward", "gemm_dgrad", "gemm_wgrad"), mm)):
                 for i, name in enumerate(names):
@@ -251,6 +262,7 @@ def main():
     ap.add_argument("--small", action="store_true")
     ap.add_argument("--commit", default="", help="recorded in the output: the commit the figures were measured on")
     ap.add_argument("--no-stochastic", action="store_true", help="skip the stochastic-rounding cases")
+    ap.add_argument("--no-quantizer", action="store_true", help="skip the two-way quantizer cases")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -268,7 +280,8 @@ def main():
             json.dump(out, f, indent=1)
             f.write("\n")
 
-    bench_quantizer(args, out, save)
+    if not args.no_quantizer:
+        bench_quantizer(args, out, save)
     bench_layer(args, out, save)
     import inspect
     if out["has_two_way"] and "rounding" in inspect.signature(qs.mx_quantize_2way).parameters and not args.no_stochastic:

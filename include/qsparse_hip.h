@@ -901,6 +901,14 @@ int qs_mx_quant_route(const qs_mx_quant_args* args);
  *     elements count as zero.  Nothing outside the five operands and y is read or written.
  *   - A scale byte 0xFF (the quantizer's mark of a block that held NaN / Inf) makes every output whose dot product reads that
  *     block NaN: row m of y for a byte of A's row m, column n for a byte of B's row n.
+ *   - Range.  Every scale byte 0..254 is honoured, 0 (2^-127, itself a float32 subnormal) and 254 included: a product whose
+ *     exact magnitude lies in [2^-126, 2^128) enters the sum exactly whatever the two bytes are.  Outside that range, as measured
+ *     on the MI355X and the same for all 25 format pairs (tests/test_mx_one_term_gpu.py pins it): underflow is GRADUAL -- a
+ *     product below 2^-126 is rounded to the nearest float32 subnormal, ties to even, not flushed; a product of magnitude
+ *     >= 2^128 gives Inf of its sign.  The float32 sum is +0 both for an exact zero (a -0 product included) and for a product
+ *     of either sign that rounds to zero in float32: the sum starts at +0.  So y = round_dt(+0 + bias) there, which is +0 for
+ *     a -0 bias too.  The fp16 / bf16 rounding of y is a plain IEEE cast of the float32 acc + bias (nearest even, subnormals
+ *     kept, Inf on overflow) and keeps the sign: a negative sum too small for the dtype gives -0.
  *   - Code bytes the quantizer never writes (E5M2 Inf / NaN patterns, E4M3 0x7F / 0xFF, bits above the format's width) give an
  *     unspecified value in the outputs that read them, never a fault.
  *   - a_codes / b_codes / scales: any address.  y: aligned to its element; bias: to 4 bytes (QS_ERR_ALIGN otherwise).

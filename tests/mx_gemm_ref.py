@@ -107,3 +107,63 @@ def exact_operand(g, rows, K, fmt, r, base=None):
     base = int(torch.randint(100, 150, (1,), generator=g)) if base is None else base
     scales = (base + torch.randint(0, r, (rows, -(-K // BLOCK)), generator=g)).to(torch.uint8)
     return codes, scales
+
+
+# ---- one-term products: every valid code of a format crossed with scale bytes over the whole E8M0 range ---------------------------
+ONE_TERM_SCALES = (0, 1, 64, 126, 127, 128, 190, 253, 254)
+
+
+def valid_codes(fmt):
+    """every code of `fmt` that has a value (E4M3 254, E5M2 248, FP6 64, FP4 16): the special patterns are left out"""
+    return (~table(fmt)[: 1 << WIDTH[fmt]].isnan()).nonzero().reshape(-1)
+
+
+def one_term_operand(g, fmt, K, k0):
+    """(codes [rows, K], scales [rows, ceil(K / 32)], value [rows] in float64): row r holds ONE code that may be nonzero, at column
+    k0, and runs over every valid code of `fmt` crossed with ONE_TERM_SCALES at the block of k0.  Every other code is the zero code
+    and every other block carries a random scale byte 0..254, which must not matter."""
+    codes = valid_codes(fmt)
+    c = codes.repeat_interleave(len(ONE_TERM_SCALES))
+    s = torch.tensor(ONE_TERM_SCALES).repeat(len(codes))
+    rows = len(c)
+    cm = torch.zeros(rows, K, dtype=torch.uint8)
+    cm[:, k0] = c.to(torch.uint8)
+    sm = torch.randint(0, 255, (rows, -(-K // BLOCK)), generator=g).to(torch.uint8)
+    sm[:, k0 // BLOCK] = s.to(torch.uint8)
+    return cm, sm, table(fmt)[c] * torch.pow(torch.tensor(2.0, dtype=torch.float64), (s - 127).double())
+
+
+class OneTerm:
+    """the outputs of the one-term product of two operands of one_term_operand (row values va, vb), worked out once per format pair:
+    they depend on neither K, k0 nor the kernel.
+    p: the product in float64, exact (at most 8 significant bits, exponents within +-300).
+    strict: the exact value is zero or has a magnitude in [2^-126, 2^128), where float32 holds it; under: 0 < magnitude < 2^-126;
+    over: magnitude >= 2^128."""
+
+    def __init__(self, va, vb):
+        self.p = va.reshape(-1, 1) * vb.reshape(1, -1)
+        mag = self.p.abs()
+        self.under, self.over = (mag > 0) & (mag < 2.0 ** -126), mag >= 2.0 ** 128
+        self.strict = ~(self.under | self.over)
+        self.y64 = self.p + 0.0            # the sum over K of the definition: every other term is +0, so a -0 product sums to +0
+        self.p32 = self.p.float() + 0.0
+
+    def expected(self, bias, dt):
+        """(strict_want, measured_want).  `bias` holds zeros of either sign only, so the classes are those of the product.
+        `strict_want` is the float64 value of the definition cast once to float32 and from there to `dt` -- binding on the strict
+        class.  `measured_want` states every output, as the MI355X was measured to give them for all 25 format pairs alike
+        (include/qsparse_hip.h, "MX matrix product"): the product rounded to float32 to nearest-even with GRADUAL underflow
+        (subnormal results are kept), Inf of the product's sign from 2^128 on, and a product that rounds to zero in float32 sums
+        to +0 whatever its sign, as an exact zero does -- the accumulator starts at +0 and the other terms are +0; then the bias,
+        in float32 (+0 + -0 = +0); then one IEEE cast to `dt`, which keeps the sign (a small negative sum is -0 in fp16 / bf16)."""
+        assert bias is None or bool((bias == 0).all())
+        strict_want = (self.y64 if bias is None else self.y64 + bias.double()).float().to(dt)
+        measured = (self.p32 if bias is None else self.p32 + bias.float()).to(dt)
+        assert bool(bits_equal(strict_want, measured)[self.strict].all())    # the measured behaviour is one reading of the definition
+        return strict_want, measured
+
+
+def bits_equal(a, b):
+    """elementwise bit-for-bit equality of two tensors of one floating dtype (all NaNs alike), on their device"""
+    assert a.dtype == b.dtype and a.shape == b.shape
+    return (a.isnan() & b.isnan()) | ((a == b) & (torch.signbit(a) == torch.signbit(b)))

@@ -92,6 +92,7 @@ def check_against_im2col(g, case, fx, fw, dtypes=DTYPES, shift=False):
         for b in (None, bias):
             y = conv(ops, fx, fw, route, b, stride, padding, dilation, dt)
             want = mx_matmul(A, SA, fx, Wp, SWp, fw, b, dt)
+            assert _hip.mx_gemm_last_route == _hip.MX_GEMM_ROUTE_VEC and _hip.mx_gemm_last_split == 1      # K' % 32 == 0, fresh operands
             assert y.shape == (B, R.out_size(H, KH, R.pair(stride)[0], R.pair(padding)[0], R.pair(dilation)[0]),
                                R.out_size(W, KW, R.pair(stride)[1], R.pair(padding)[1], R.pair(dilation)[1]), Cout)
             assert G.same(y.reshape(-1, Cout), want), (case, fx, fw, dt, b is not None, shift)
@@ -112,19 +113,34 @@ def test_bit_identical_to_matmul_on_im2col_every_geometry(fx, fw):
     check_against_im2col(g, CASES[2], fx, fw, (torch.bfloat16,), shift=True)
 
 
+# B, H, W, C, Cout, (KH, KW), stride, padding, dilation, route: the last two are dilated, the second of them with OH == OW == 1
+EXACT_GEOMETRIES = ((2, 9, 7, 32, 130, (3, 3), 1, 1, 1, VEC), (2, 9, 7, 40, 20, (3, 3), 1, 1, 1, PLAIN), (2, 9, 7, 64, 17, (1, 1), 2, 0, 1, VEC),
+                    (2, 11, 10, 32, 20, (3, 3), 1, 2, 2, VEC), (2, 9, 9, 32, 17, (3, 3), 1, 1, 5, VEC))
+
+
+def check_against_conv64(g, geometry, fx, fw):
+    """the comparison that does not pass through mx_matmul: exact-class operands against torch's float64 convolution of their values"""
+    B, H, W, C, Cout, (KH, KW), stride, padding, dilation, route = geometry
+    ops = exact_conv_case(g, B, H, W, C, Cout, KH, KW, fx, fw)
+    bias = torch.randint(-16, 16, (Cout,), generator=g).float()
+    y64 = R.conv64(G.values(ops[0], ops[1], fx), G.values(ops[2], ops[3], fw), bias, stride, padding, dilation)
+    dev = tuple(t.to(DEV) for t in ops)
+    for dt in DTYPES:
+        y = conv(dev, fx, fw, route, bias.to(DEV), stride, padding, dilation, dt)
+        assert G.same(y, y64.to(dt)), (geometry, dt)
+        assert torch.equal(y.cpu(), mx_conv2d(*ops[:2], fx, *ops[2:], fw, bias, stride, padding, dilation, dt))      # the CPU path
+
+
 @pytest.mark.parametrize("fx,fw", PAIRS)
 def test_exact_class_bit_for_bit_against_the_float64_convolution(fx, fw):
     g = torch.Generator().manual_seed(400 + G.FMTS.index(fx) * 5 + G.FMTS.index(fw))
-    for B, H, W, C, Cout, (KH, KW), stride, padding, route in ((2, 9, 7, 32, 130, (3, 3), 1, 1, VEC), (2, 9, 7, 40, 20, (3, 3), 1, 1, PLAIN),
-                                                                (2, 9, 7, 64, 17, (1, 1), 2, 0, VEC)):
-        ops = exact_conv_case(g, B, H, W, C, Cout, KH, KW, fx, fw)
-        bias = torch.randint(-16, 16, (Cout,), generator=g).float()
-        y64 = R.conv64(G.values(ops[0], ops[1], fx), G.values(ops[2], ops[3], fw), bias, stride, padding, 1)
-        dev = tuple(t.to(DEV) for t in ops)
-        for dt in DTYPES:
-            y = conv(dev, fx, fw, route, bias.to(DEV), stride, padding, 1, dt)
-            assert G.same(y, y64.to(dt)), (C, KH, dt)
-            assert torch.equal(y.cpu(), mx_conv2d(*ops[:2], fx, *ops[2:], fw, bias, stride, padding, 1, dt))      # the CPU path
+    for geometry in EXACT_GEOMETRIES:
+        check_against_conv64(g, geometry, fx, fw)
+
+
+@pytest.mark.parametrize("fx,fw", ALL_PAIRS)
+def test_exact_class_against_the_float64_convolution_every_format_pair(fx, fw):
+    check_against_conv64(torch.Generator().manual_seed(450 + G.FMTS.index(fx) * 5 + G.FMTS.index(fw)), EXACT_GEOMETRIES[0], fx, fw)
 
 
 @pytest.mark.parametrize("fx,fw", PAIRS)

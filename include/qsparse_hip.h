@@ -1081,6 +1081,63 @@ int qs_mx_conv2d_v(const qs_mx_conv2d_args* args);
 #define QS_MX_CONV_ROUTE_PLAIN 3
 int qs_mx_conv2d_route(const qs_mx_conv2d_args* args);
 
+/* ---- MX transposed convolution (fractionally-strided implicit GEMM) ----------------------------------------------------------
+ * Added without raising QS_ABI_VERSION (28): symbols are only added.  Also the input gradient (dgrad) of qs_mx_conv2d_v's
+ * convolution: dx is the transposed convolution of dy with the same weight, contracted over (kh, kw, cout).
+ *
+ * Channels-last operands, MX blocks of 32 along the contraction channels C (the innermost axis):
+ *   x_codes [B, H, W, C], x_scales [B, H, W, ceil(C / 32)];  w_codes [Cout, KH, KW, C], w_scales [Cout, KH, KW, ceil(C / 32)]
+ *   (w is nn.ConvTranspose2d.weight [C, Cout, KH, KW] permuted (1, 2, 3, 0); for dgrad conv.weight [Cout_fwd, Cin, KH, KW] permuted
+ *   (1, 2, 3, 0), so Cout := Cin and C := Cout_fwd.  The kernel indices are the weight's own, un-flipped.)
+ *   OH = (H - 1) stride_h - 2 pad_h + dil_h (KH - 1) + out_pad_h + 1, OW likewise;  y is [B, OH, OW, Cout]
+ *   y[b, oh, ow, n] = round_once_to_ydt( sum over (kh, kw, c) of
+ *                         val_x(x[b, ih, iw, c]) * 2^(x_scales[b, ih, iw, c / 32] - 127)
+ *                       * val_w(w[n, kh, kw, c]) * 2^(w_scales[n, kh, kw, c / 32] - 127)  +  bias[n] )
+ *   ih = (oh + pad_h - kh * dil_h) / stride_h,  iw = (ow + pad_w - kw * dil_w) / stride_w;  a tap exists only where both divisions
+ *   are exact and 0 <= ih < H, 0 <= iw < W.  A tap that does not exist contributes zero codes with scale byte 127, as do codes
+ *   with c >= C.
+ * Order of the sum: with Cp = 32 ceil(C / 32) and k' = (kh * KW + kw) * Cp + c the sum is accumulated in float32 from zero along k'
+ * in steps of 128, one v_mfma_scale_f32_16x16x128_f8f6f4 per step -- the order of qs_mx_matmul_v on the gathered operands
+ * A [B OH OW, KH KW Cp] and Wp [Cout, KH KW Cp], whose result it equals bit for bit.  The bias is added in float32 at the end.  No
+ * gathered matrix is written; no workspace; groups == 1.
+ *   - No tap is skipped.  A scale byte 0xFF in w's row n makes channel n NaN at every (b, oh, ow), also where no tap exists (the
+ *     block meets zero codes there); a byte 0xFF of x makes NaN exactly the outputs that have an existing tap on that pixel.
+ *   - An output that no tap reaches (a stride larger than the kernel's reach) is bias[n], or +0.0 without a bias.
+ *   - A stride s spends stride_h stride_w - 1 of every stride_h stride_w products on zero codes: correct, not tuned -- there is no
+ *     sub-pixel (per-phase) decomposition.
+ *   - Code bytes the quantizer never writes give an unspecified value in the outputs that read them, never a fault.
+ *   - Codes and scales: any address.  y: aligned to its element; bias: to 4 bytes (QS_ERR_ALIGN otherwise).
+ *   - B == 0 or Cout == 0: nothing is enqueued, 0 is returned.
+ *   - QS_ERR_ARG: a null or too short descriptor, a null operand, a format outside enum qs_mx_format, B or Cout < 0, H, W, C, KH,
+ *     KW, a stride or a dilation < 1, a negative padding, an output padding < 0 or >= max(stride, dilation) of its axis, OH < 1 or
+ *     OW < 1, OH + pad_h, OW + pad_w or dil (K - 1) beyond INT32_MAX, B, Cout or C + 32 beyond INT32_MAX.  QS_ERR_DTYPE: ydt is
+ *     none of the three.
+ * Routes (the values of qs_mx_conv2d_route):
+ *   QS_MX_CONV_ROUTE_GEMM   KH == KW == 1, strides 1, paddings 0, output paddings 0 and C % 32 == 0: the operands ARE [B H W, C] and
+ *                           [Cout, C]; the call is forwarded to qs_mx_matmul_v on the same bytes
+ *   QS_MX_CONV_ROUTE_VEC    C % 16 == 0 and both code bases 16-byte aligned: 16 bytes per load
+ *   QS_MX_CONV_ROUTE_PLAIN  anything else (any C >= 1, any base): the same kernel with predicated byte loads */
+typedef struct qs_mx_conv_transpose2d_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_conv_transpose2d_args) as the caller compiled it */
+    int32_t x_format, w_format;      /* enum qs_mx_format, may differ */
+    const uint8_t* x_codes;          /* [B, H, W, C], one code per byte */
+    const uint8_t* x_scales;         /* [B, H, W, ceil(C / 32)] E8M0 bytes */
+    const uint8_t* w_codes;          /* [Cout, KH, KW, C] */
+    const uint8_t* w_scales;         /* [Cout, KH, KW, ceil(C / 32)] */
+    const float* bias;               /* nullable, [Cout] float32 */
+    void* y;                         /* [B, OH, OW, Cout] */
+    int32_t ydt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    int64_t B, H, W, C, Cout;
+    int32_t KH, KW;
+    int32_t stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
+    int32_t out_pad_h, out_pad_w;    /* 0 <= out_pad < max(stride, dil) of the axis */
+    qs_stream_t stream;
+} qs_mx_conv_transpose2d_args;
+int qs_mx_conv_transpose2d_v(const qs_mx_conv_transpose2d_args* args);
+/* the route qs_mx_conv_transpose2d_v takes for these operands, nothing enqueued: QS_MX_CONV_ROUTE_*, 0 for an empty problem, or the
+ * QS_ERR_* the call would return */
+int qs_mx_conv_transpose2d_route(const qs_mx_conv_transpose2d_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

@@ -108,6 +108,8 @@ SIGNATURES = {
     "qs_mx_quant2_sr_route": (c_int, [_P]),
     "qs_mx_conv2d_v": (c_int, [_P]),
     "qs_mx_conv2d_route": (c_int, [_P]),
+    "qs_mx_conv_transpose2d_v": (c_int, [_P]),
+    "qs_mx_conv_transpose2d_route": (c_int, [_P]),
 }
 
 
@@ -217,6 +219,11 @@ class MxConv2dArgs(ctypes.Structure):
                 ("ydt", c_int32), ("B", c_int64), ("H", c_int64), ("W", c_int64), ("C", c_int64), ("Cout", c_int64),
                 ("KH", c_int32), ("KW", c_int32), ("stride_h", c_int32), ("stride_w", c_int32), ("pad_h", c_int32), ("pad_w", c_int32),
                 ("dil_h", c_int32), ("dil_w", c_int32), ("stream", c_void_p)]
+
+
+class MxConvTranspose2dArgs(ctypes.Structure):
+    """`qs_mx_conv_transpose2d_args` of include/qsparse_hip.h"""
+    _fields_ = MxConv2dArgs._fields_[:-1] + [("out_pad_h", c_int32), ("out_pad_w", c_int32), ("stream", c_void_p)]
 
 
 class MultiRow(ctypes.Structure):
@@ -957,6 +964,45 @@ def mx_conv2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_codes
             st = lib.qs_mx_conv2d_v(ctypes.byref(a))
         _check(st, "qs_mx_conv2d_v")
         mx_conv_last_route = route
+    return y
+
+
+mx_conv_transpose_last_route = None   # likewise of the last `mx_conv_transpose2d` launch
+
+
+def mx_conv_transpose_out_size(n: int, k: int, stride: int, pad: int, dil: int, out_pad: int) -> int:
+    """output extent of one axis of a transposed convolution (the header's formula; < 1: no output)"""
+    return (n - 1) * stride - 2 * pad + dil * (k - 1) + out_pad + 1
+
+
+def mx_conv_transpose2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_codes: torch.Tensor, w_scales: torch.Tensor,
+                        w_fmt: str, bias: Optional[torch.Tensor], stride, padding, output_padding, dilation,
+                        out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """y[B, OH, OW, Cout] on MX codes (qs_mx_conv_transpose2d_v): `x_codes` [B, H, W, C], `w_codes` [Cout, KH, KW, C] uint8, scales
+    [..., ceil(C / 32)] uint8, all contiguous GPU tensors (qsparse_amd/mx_conv_transpose.py checks); `bias` float32 [Cout] or None;
+    `stride`, `padding`, `output_padding`, `dilation` pairs of ints.  ONE launch, no gathered matrix."""
+    global mx_conv_transpose_last_route
+    lib = load()
+    (B, H, W, C), (Cout, KH, KW, _) = x_codes.shape, w_codes.shape
+    OH = mx_conv_transpose_out_size(H, KH, stride[0], padding[0], dilation[0], output_padding[0])
+    OW = mx_conv_transpose_out_size(W, KW, stride[1], padding[1], dilation[1], output_padding[1])
+    y = torch.empty((B, OH, OW, Cout), dtype=out_dtype, device=x_codes.device)
+    mx_conv_transpose_last_route = None
+    if B and Cout:
+        a = MxConvTranspose2dArgs()
+        a.struct_size = ctypes.sizeof(a)
+        a.x_format, a.w_format = MX_FORMATS.index(x_fmt), MX_FORMATS.index(w_fmt)
+        a.x_codes, a.x_scales, a.w_codes, a.w_scales = _ptr(x_codes), _ptr(x_scales), _ptr(w_codes), _ptr(w_scales)
+        a.bias, a.y, a.ydt = _ptr(bias), _ptr(y), _DT[out_dtype]
+        a.B, a.H, a.W, a.C, a.Cout, a.KH, a.KW = B, H, W, C, Cout, KH, KW
+        (a.stride_h, a.stride_w), (a.pad_h, a.pad_w), (a.dil_h, a.dil_w) = stride, padding, dilation
+        a.out_pad_h, a.out_pad_w = output_padding
+        a.stream = _stream(x_codes)
+        route = lib.qs_mx_conv_transpose2d_route(ctypes.byref(a))
+        with _timed(f"mx_conv_transpose2d[{route}]", x_codes, x_scales, w_codes, w_scales, bias, y):
+            st = lib.qs_mx_conv_transpose2d_v(ctypes.byref(a))
+        _check(st, "qs_mx_conv_transpose2d_v")
+        mx_conv_transpose_last_route = route
     return y
 
 

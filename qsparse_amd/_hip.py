@@ -938,32 +938,38 @@ def mx_conv_out_size(n: int, k: int, stride: int, pad: int, dil: int) -> int:
     return (n + 2 * pad - dil * (k - 1) - 1) // stride + 1
 
 
+def _mx_conv_launch(name: str, a, x_codes, x_scales, x_fmt, w_codes, w_scales, w_fmt, bias, size, stride, padding, dilation, out_dtype):
+    """fill the descriptor `a` (`MxConv2dArgs` or, with its output padding already set, `MxConvTranspose2dArgs`) and run
+    `qs_<name>_v` into a new y [B, *size, Cout]; returns y and the route taken (None: an empty problem, nothing enqueued)"""
+    lib = load()
+    (B, H, W, C), (Cout, KH, KW, _) = x_codes.shape, w_codes.shape
+    y = torch.empty((B,) + tuple(size) + (Cout,), dtype=out_dtype, device=x_codes.device)
+    if not (B and Cout):
+        return y, None
+    a.struct_size = ctypes.sizeof(a)
+    a.x_format, a.w_format = MX_FORMATS.index(x_fmt), MX_FORMATS.index(w_fmt)
+    a.x_codes, a.x_scales, a.w_codes, a.w_scales = _ptr(x_codes), _ptr(x_scales), _ptr(w_codes), _ptr(w_scales)
+    a.bias, a.y, a.ydt = _ptr(bias), _ptr(y), _DT[out_dtype]
+    a.B, a.H, a.W, a.C, a.Cout, a.KH, a.KW = B, H, W, C, Cout, KH, KW
+    (a.stride_h, a.stride_w), (a.pad_h, a.pad_w), (a.dil_h, a.dil_w) = stride, padding, dilation
+    a.stream = _stream(x_codes)
+    route = getattr(lib, f"qs_{name}_route")(ctypes.byref(a))
+    with _timed(f"{name}[{route}]", x_codes, x_scales, w_codes, w_scales, bias, y):
+        st = getattr(lib, f"qs_{name}_v")(ctypes.byref(a))
+    _check(st, f"qs_{name}_v")
+    return y, route
+
+
 def mx_conv2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_codes: torch.Tensor, w_scales: torch.Tensor, w_fmt: str,
               bias: Optional[torch.Tensor], stride, padding, dilation, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """y[B, OH, OW, Cout] on MX codes (qs_mx_conv2d_v): `x_codes` [B, H, W, C], `w_codes` [Cout, KH, KW, C] uint8, scales
     [..., ceil(C / 32)] uint8, all contiguous GPU tensors (qsparse_amd/mx_conv.py checks); `bias` float32 [Cout] or None; `stride`,
     `padding`, `dilation` pairs of ints.  ONE launch, no im2col matrix."""
     global mx_conv_last_route
-    lib = load()
-    (B, H, W, C), (Cout, KH, KW, _) = x_codes.shape, w_codes.shape
-    OH = mx_conv_out_size(H, KH, stride[0], padding[0], dilation[0])
-    OW = mx_conv_out_size(W, KW, stride[1], padding[1], dilation[1])
-    y = torch.empty((B, OH, OW, Cout), dtype=out_dtype, device=x_codes.device)
     mx_conv_last_route = None
-    if B and Cout:
-        a = MxConv2dArgs()
-        a.struct_size = ctypes.sizeof(a)
-        a.x_format, a.w_format = MX_FORMATS.index(x_fmt), MX_FORMATS.index(w_fmt)
-        a.x_codes, a.x_scales, a.w_codes, a.w_scales = _ptr(x_codes), _ptr(x_scales), _ptr(w_codes), _ptr(w_scales)
-        a.bias, a.y, a.ydt = _ptr(bias), _ptr(y), _DT[out_dtype]
-        a.B, a.H, a.W, a.C, a.Cout, a.KH, a.KW = B, H, W, C, Cout, KH, KW
-        (a.stride_h, a.stride_w), (a.pad_h, a.pad_w), (a.dil_h, a.dil_w) = stride, padding, dilation
-        a.stream = _stream(x_codes)
-        route = lib.qs_mx_conv2d_route(ctypes.byref(a))
-        with _timed(f"mx_conv2d[{route}]", x_codes, x_scales, w_codes, w_scales, bias, y):
-            st = lib.qs_mx_conv2d_v(ctypes.byref(a))
-        _check(st, "qs_mx_conv2d_v")
-        mx_conv_last_route = route
+    size = [mx_conv_out_size(n, k, s, p, d) for n, k, s, p, d in zip(x_codes.shape[1:3], w_codes.shape[1:3], stride, padding, dilation)]
+    y, mx_conv_last_route = _mx_conv_launch("mx_conv2d", MxConv2dArgs(), x_codes, x_scales, x_fmt, w_codes, w_scales, w_fmt, bias, size,
+                                            stride, padding, dilation, out_dtype)
     return y
 
 
@@ -982,27 +988,13 @@ def mx_conv_transpose2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: st
     [..., ceil(C / 32)] uint8, all contiguous GPU tensors (qsparse_amd/mx_conv_transpose.py checks); `bias` float32 [Cout] or None;
     `stride`, `padding`, `output_padding`, `dilation` pairs of ints.  ONE launch, no gathered matrix."""
     global mx_conv_transpose_last_route
-    lib = load()
-    (B, H, W, C), (Cout, KH, KW, _) = x_codes.shape, w_codes.shape
-    OH = mx_conv_transpose_out_size(H, KH, stride[0], padding[0], dilation[0], output_padding[0])
-    OW = mx_conv_transpose_out_size(W, KW, stride[1], padding[1], dilation[1], output_padding[1])
-    y = torch.empty((B, OH, OW, Cout), dtype=out_dtype, device=x_codes.device)
     mx_conv_transpose_last_route = None
-    if B and Cout:
-        a = MxConvTranspose2dArgs()
-        a.struct_size = ctypes.sizeof(a)
-        a.x_format, a.w_format = MX_FORMATS.index(x_fmt), MX_FORMATS.index(w_fmt)
-        a.x_codes, a.x_scales, a.w_codes, a.w_scales = _ptr(x_codes), _ptr(x_scales), _ptr(w_codes), _ptr(w_scales)
-        a.bias, a.y, a.ydt = _ptr(bias), _ptr(y), _DT[out_dtype]
-        a.B, a.H, a.W, a.C, a.Cout, a.KH, a.KW = B, H, W, C, Cout, KH, KW
-        (a.stride_h, a.stride_w), (a.pad_h, a.pad_w), (a.dil_h, a.dil_w) = stride, padding, dilation
-        a.out_pad_h, a.out_pad_w = output_padding
-        a.stream = _stream(x_codes)
-        route = lib.qs_mx_conv_transpose2d_route(ctypes.byref(a))
-        with _timed(f"mx_conv_transpose2d[{route}]", x_codes, x_scales, w_codes, w_scales, bias, y):
-            st = lib.qs_mx_conv_transpose2d_v(ctypes.byref(a))
-        _check(st, "qs_mx_conv_transpose2d_v")
-        mx_conv_transpose_last_route = route
+    size = [mx_conv_transpose_out_size(n, k, s, p, d, op)
+            for n, k, s, p, d, op in zip(x_codes.shape[1:3], w_codes.shape[1:3], stride, padding, dilation, output_padding)]
+    a = MxConvTranspose2dArgs()
+    a.out_pad_h, a.out_pad_w = output_padding
+    y, mx_conv_transpose_last_route = _mx_conv_launch("mx_conv_transpose2d", a, x_codes, x_scales, x_fmt, w_codes, w_scales, w_fmt, bias,
+                                                      size, stride, padding, dilation, out_dtype)
     return y
 
 

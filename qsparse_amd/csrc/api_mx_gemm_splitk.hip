@@ -2,7 +2,7 @@
 // products of slices of K into a caller-provided workspace, then an ordered float32 reduction.  A translation unit of its own: the
 // 50 instantiations of the partial kernel compile next to the 50 of api_mx_gemm.hip, not after them.
 // Host side: argument checks, the slicing and the automatic slice count, launch configuration.  No allocation, no synchronisation.
-#include "qs_host.h"
+#include "qs_mx_host.h"
 #include "qs_mx_gemm_splitk.h"
 
 namespace {
@@ -46,14 +46,7 @@ int split_plan(int64_t M, int64_t N, int64_t K, int32_t split_k, SplitPlan* p) {
 }
 
 qs_mx_matmul_args unsplit_args(const qs_mx_matmul_splitk_args& a) {
-    qs_mx_matmul_args m = {};
-    m.struct_size = sizeof(m);
-    m.a_format = a.a_format, m.b_format = a.b_format;
-    m.a_codes = a.a_codes, m.a_scales = a.a_scales, m.b_codes = a.b_codes, m.b_scales = a.b_scales;
-    m.bias = a.bias, m.y = a.y, m.ydt = a.ydt;
-    m.M = a.M, m.N = a.N, m.K = a.K;
-    m.stream = a.stream;
-    return m;
+    return mx_matmul_args(a.a_format, a.b_format, a.a_codes, a.a_scales, a.b_codes, a.b_scales, a.bias, a.y, a.ydt, a.M, a.N, a.K, a.stream);
 }
 
 // the checks of qs_mx_matmul_splitk_v and the kernel its first launch runs: every check of qs_mx_matmul_v (by asking it), then the
@@ -75,39 +68,26 @@ int splitk_route(const qs_mx_matmul_splitk_args& a, SplitPlan* p) {
     return route;
 }
 
-template <int FA, int FB>
-int launch_pair(const qs_mx_matmul_splitk_args& a, const SplitPlan& p, int route) {
+// the two launches: the partial products of every slice, then their ordered sum
+int launch_split(const qs_mx_matmul_splitk_args& a, const SplitPlan& p, int route) {
     const int tiles_n = (int)cdiv(a.N, kMxgTile);
     const int tiles = (int)cdiv(a.M, kMxgTile) * tiles_n;
     const int64_t grid = (int64_t)tiles * p.slices;
     const int ws_vec = a.N % 4 == 0;               // every row of every slice then keeps the workspace's 16-byte alignment
     float* ws = (float*)a.workspace;
     hipStream_t s = (hipStream_t)a.stream;
-    if (route == QS_MX_GEMM_ROUTE_VEC)
-        hipLaunchKernelGGL((mx_gemm_partial_kernel<FA, FB, true>), dim3((unsigned)grid), dim3(kMxgThreads), 0, s, a.a_codes, a.a_scales,
-                           a.b_codes, a.b_scales, ws, a.M, a.N, a.K, tiles_n, tiles, p.per, ws_vec);
-    else
-        hipLaunchKernelGGL((mx_gemm_partial_kernel<FA, FB, false>), dim3((unsigned)grid), dim3(kMxgThreads), 0, s, a.a_codes, a.a_scales,
-                           a.b_codes, a.b_scales, ws, a.M, a.N, a.K, tiles_n, tiles, p.per, ws_vec);
-    const int st = launch_status();
+    const int st = mx_dispatch(a.a_format, a.b_format, route == QS_MX_GEMM_ROUTE_VEC, [&](auto FA, auto FB, auto VEC) {
+        hipLaunchKernelGGL((mx_gemm_partial_kernel<decltype(FA)::value, decltype(FB)::value, decltype(VEC)::value>), dim3((unsigned)grid),
+                           dim3(kMxgThreads), 0, s, a.a_codes, a.a_scales, a.b_codes, a.b_scales, ws, a.M, a.N, a.K, tiles_n, tiles, p.per,
+                           ws_vec);
+        return launch_status();
+    });
     if (st != 0) return st;
-    const int y_vec = a.N % 4 == 0 && (((uintptr_t)a.y) & (4 * dt_size(a.ydt) - 1)) == 0;
     const int64_t groups_n = cdiv(a.N, 4), groups = a.M * groups_n;
     const int64_t blocks = std::min<int64_t>(cdiv(groups, kBlock), kMaxGrid);       // the kernel strides over the rest
     hipLaunchKernelGGL(mx_gemm_reduce_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s, ws, a.bias, a.y, a.ydt, a.M, a.N, (int)p.slices,
-                       groups_n, ws_vec, y_vec);
+                       groups_n, ws_vec, mx_y_vec(a.y, a.ydt, a.N));
     return launch_status();
-}
-
-template <int FA>
-int launch_a(const qs_mx_matmul_splitk_args& a, const SplitPlan& p, int route) {
-    switch (a.b_format) {
-        case QS_MX_FP8_E4M3: return launch_pair<FA, QS_MX_FP8_E4M3>(a, p, route);
-        case QS_MX_FP8_E5M2: return launch_pair<FA, QS_MX_FP8_E5M2>(a, p, route);
-        case QS_MX_FP6_E2M3: return launch_pair<FA, QS_MX_FP6_E2M3>(a, p, route);
-        case QS_MX_FP6_E3M2: return launch_pair<FA, QS_MX_FP6_E3M2>(a, p, route);
-        default: return launch_pair<FA, QS_MX_FP4_E2M1>(a, p, route);
-    }
 }
 
 }  // namespace
@@ -140,13 +120,7 @@ int qs_mx_matmul_splitk_v(const qs_mx_matmul_splitk_args* args) {
         const qs_mx_matmul_args m = unsplit_args(a);
         return qs_mx_matmul_v(&m);
     }
-    switch (a.a_format) {
-        case QS_MX_FP8_E4M3: return launch_a<QS_MX_FP8_E4M3>(a, p, route);
-        case QS_MX_FP8_E5M2: return launch_a<QS_MX_FP8_E5M2>(a, p, route);
-        case QS_MX_FP6_E2M3: return launch_a<QS_MX_FP6_E2M3>(a, p, route);
-        case QS_MX_FP6_E3M2: return launch_a<QS_MX_FP6_E3M2>(a, p, route);
-        default: return launch_a<QS_MX_FP4_E2M1>(a, p, route);
-    }
+    return launch_split(a, p, route);
 }
 
 }  // extern "C"

@@ -101,6 +101,162 @@ struct MxgLds {
     }
 };
 
+// 16 codes from codes + off if `in`, else zeros; `left` (1..16) of them exist (!VEC: the bytes past it are not read)
+template <bool VEC>
+__device__ __forceinline__ u32x4 mx_load16(const uint8_t* __restrict__ codes, bool in, int64_t off, int left) {
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if constexpr (VEC) {                           // an unconditional load from a clamped address, then a select: no branch per piece
+        const u32x4 w = *(const u32x4*)(codes + (in ? off : 0));
+        v = in ? w : v;
+    } else if (in) {
+        const uint8_t* p = codes + off;
+#pragma unroll
+        for (int b = 0; b < 16; ++b)
+            if (b < left) v[b >> 2] |= (uint32_t)p[b] << (8 * (b & 3));
+    }
+    return v;
+}
+
+// the scale byte at scales + off if `in`, else 127 (2^0); clamped address + select, as the pieces
+__device__ __forceinline__ uint32_t mx_scale(const uint8_t* __restrict__ scales, bool in, int64_t off) {
+    const uint32_t b = scales[in ? off : 0];
+    return in ? b : 127u;
+}
+
+// the four pieces a thread stages per step: piece q = thread + 256 i is piece (q & 7) of tile row (q >> 3) = (thread >> 3) + 32 i
+template <int BITS>
+__device__ __forceinline__ void mxg_stage(uint8_t* tile, const u32x4 (&reg)[4], int tid) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int q = tid + kMxgThreads * i;
+        MxgLds<BITS>::put(tile, q >> 3, q & 7, reg[i]);
+    }
+}
+
+template <int FA, int FB>
+constexpr int kMxTileLds = 2 * (MxgLds<mxg_bits(FA)>::kBytes + MxgLds<mxg_bits(FB)>::kBytes);       // two buffers of both operands
+
+// The K loop of the implicit-GEMM products on MX codes, parameterised by its operands (the loop of mx_gemm_kernel below, which
+// keeps a statement of its own).  An OPERAND is one side of the product seen through the tile; it has
+//   fetch<VEC>(reg, step)   the four 16-code pieces this thread stages at K-step `step`: piece (thread & 7) of the tile rows
+//                           (thread >> 3) + 32 i
+//   scales(s, step)         the scale bytes of block (lane >> 4) of that step for this lane's four fragments: the tile rows
+//                           w + 16 j + (lane & 15), w the wave's corner
+//   advance()               called once before the fetch of each step after the first, in ascending order
+// Models: MxcOperand (qs_mx_conv.h; an image or a weight under a convolution's window), MxctOperand (qs_mx_conv_t.h; an image under
+// a transposed convolution's).  A is the activation (SrcB of the instruction, tile
+// rows m, corner wm), B the weight (SrcA, rows n, corner wn).  The loop walks the steps [t0, t1), t0 < t1, from whatever `acc`
+// holds: the loads of step t + 1 are issued before the 16 MFMAs of step t and staged into the other buffer after them, one barrier
+// per step; the buffer of step t is (t - t0) & 1.
+template <int FA, int FB, bool VEC, class OpA, class OpB>
+__device__ __forceinline__ void mx_tile_loop(f32x4 (&acc)[4][4], OpA& A, OpB& B, int64_t t0, int64_t t1, uint8_t* lds, int tid, int wm,
+                                             int wn) {
+    using LA = MxgLds<mxg_bits(FA)>;
+    using LB = MxgLds<mxg_bits(FB)>;
+    constexpr int kBuf = LA::kBytes + LB::kBytes;
+    const int lane = tid & 63;
+
+    u32x4 ra[4], rb[4];
+    uint32_t sa[4], sb[4], sa_next[4], sb_next[4];
+    A.template fetch<VEC>(ra, t0);
+    B.template fetch<VEC>(rb, t0);
+    A.scales(sa, t0);
+    B.scales(sb, t0);
+    mxg_stage<mxg_bits(FA)>(lds, ra, tid);
+    mxg_stage<mxg_bits(FB)>(lds + LA::kBytes, rb, tid);
+    __syncthreads();
+
+    for (int64_t t = t0; t < t1; ++t) {
+        const bool more = t + 1 < t1;
+        if (more) {
+            A.advance();
+            B.advance();
+            A.template fetch<VEC>(ra, t + 1);
+            B.template fetch<VEC>(rb, t + 1);
+            A.scales(sa_next, t + 1);
+            B.scales(sb_next, t + 1);
+        }
+        const uint8_t* cur = lds + ((t - t0) & 1) * kBuf;
+        i32x8 fa[4], fb[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            fa[j] = LA::get(cur, wm + 16 * j + (lane & 15), lane >> 4);
+            fb[j] = LB::get(cur + LA::kBytes, wn + 16 * j + (lane & 15), lane >> 4);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb[i], fa[j], acc[i][j], FB, FA, 0, (int)sb[i], 0, (int)sa[j]);
+        if (more) {
+            uint8_t* nxt = lds + ((t + 1 - t0) & 1) * kBuf;
+            mxg_stage<mxg_bits(FA)>(nxt, ra, tid);
+            mxg_stage<mxg_bits(FB)>(nxt + LA::kBytes, rb, tid);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sa[j] = sa_next[j], sb[j] = sb_next[j];
+        }
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ void mx_zero(f32x4 (&acc)[4][4]) {       // [i: 16 n][j: 16 m]
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+}
+
+// v[0..3] rounded once to ydt at y[e .. e + 3], the elements (m, n .. n + 3) of y [M, N]; those with n + r >= N are not written.
+// y_vec: N % 4 == 0 and y 16-byte (float32) / 8-byte aligned, so n + 3 < N and one aligned store takes the four
+__device__ __forceinline__ void mx_store4(void* __restrict__ y, int ydt, int64_t e, const float (&v)[4], int64_t n, int64_t N, int y_vec) {
+    if (y_vec) {
+        if (ydt == QS_F32) {
+            *(u32x4*)((float*)y + e) = u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+        } else if (ydt == QS_BF16) {
+            *(u32x2*)((uint16_t*)y + e) = u32x2{f32_to_bf16_bits(v[0]) | (f32_to_bf16_bits(v[1]) << 16),
+                                                f32_to_bf16_bits(v[2]) | (f32_to_bf16_bits(v[3]) << 16)};
+        } else {
+            *(u32x2*)((uint16_t*)y + e) = u32x2{f32_to_f16_bits(v[0]) | (f32_to_f16_bits(v[1]) << 16),
+                                                f32_to_f16_bits(v[2]) | (f32_to_f16_bits(v[3]) << 16)};
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (n + r >= N) break;
+            if (ydt == QS_F32) ((float*)y)[e + r] = v[r];
+            else if (ydt == QS_BF16) ((uint16_t*)y)[e + r] = (uint16_t)f32_to_bf16_bits(v[r]);
+            else ((uint16_t*)y)[e + r] = (uint16_t)f32_to_f16_bits(v[r]);
+        }
+    }
+}
+
+// bias in float32, one rounding to ydt, the stores of a wave's 64 (m, from mw) x 64 (n, from nw) corner of y [M, N]
+__device__ __forceinline__ void mx_epilogue(const f32x4 (&acc)[4][4], const float* __restrict__ bias, void* __restrict__ y, int ydt,
+                                            int64_t M, int64_t N, int64_t mw, int64_t nw, int lane, int y_vec) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int64_t n = nw + 16 * i + 4 * (lane >> 4);
+        float bv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (bias) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (n + r < N) bv[r] = bias[n + r];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t m = mw + 16 * j + (lane & 15);
+            float v[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = bias ? acc[i][j][r] + bv[r] : acc[i][j][r];
+            if (m >= M || n >= N) continue;
+            mx_store4(y, ydt, m * N + n, v, n, N, y_vec);
+        }
+    }
+}
+
+// mx_gemm_kernel and mx_gemm_partial_kernel (qs_mx_gemm_splitk.h) state the fetch, the loop and the epilogue themselves, statement
+// for statement what mx_load16 / mx_scale / mx_tile_loop / mx_epilogue say: built on those, with a row-major operand of their own,
+// they gave the same bits from fewer registers but were 3-17 % slower where K is short or the tiles are few.
 // the four 16-code pieces this thread stages per step: piece q = thread + 256 i is piece (q & 7) of tile row (q >> 3)
 template <bool VEC>
 __device__ __forceinline__ void mxg_fetch(u32x4 (&reg)[4], const uint8_t* __restrict__ codes, int64_t row0, int64_t rows, int64_t K,
@@ -122,15 +278,6 @@ __device__ __forceinline__ void mxg_fetch(u32x4 (&reg)[4], const uint8_t* __rest
                 if (b < left) v[b >> 2] |= (uint32_t)p[b] << (8 * (b & 3));
         }
         reg[i] = v;
-    }
-}
-
-template <int BITS>
-__device__ __forceinline__ void mxg_stage(uint8_t* tile, const u32x4 (&reg)[4], int tid) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int q = tid + kMxgThreads * i;
-        MxgLds<BITS>::put(tile, q >> 3, q & 7, reg[i]);
     }
 }
 

@@ -7,7 +7,7 @@
 //                           without bias, to workspace[s][M][N].
 //   mx_gemm_reduce_kernel   y = round_once(((p_0 + p_1) + ... + p_{S-1}) + bias): plain float32 adds in ascending s (the library is
 //                           built with -ffp-contract=off and without any fast-math flag, so nothing re-associates them), four
-//                           consecutive n per thread, the store rule of mx_gemm_kernel's epilogue.
+//                           consecutive n per thread, stored by the epilogue's mx_store4.
 // Every (m < M, n < N) of every slice is written by exactly one lane of the first launch, so the second reads nothing stale and the
 // workspace needs no clearing.  Nothing past slices * M * N floats of the workspace is touched.
 #pragma once
@@ -130,25 +130,7 @@ __global__ __launch_bounds__(kBlock) void mx_gemm_reduce_kernel(const float* __r
             for (int r = 0; r < 4; ++r)
                 if (n + r < N) v[r] = v[r] + bias[n + r];
         }
-        if (y_vec) {                               // as mx_gemm_kernel: N % 4 == 0 and y 16-byte (float32) / 8-byte aligned
-            if (ydt == QS_F32) {
-                *(u32x4*)((float*)y + e) = u32x4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
-            } else if (ydt == QS_BF16) {
-                *(u32x2*)((uint16_t*)y + e) = u32x2{f32_to_bf16_bits(v[0]) | (f32_to_bf16_bits(v[1]) << 16),
-                                                    f32_to_bf16_bits(v[2]) | (f32_to_bf16_bits(v[3]) << 16)};
-            } else {
-                *(u32x2*)((uint16_t*)y + e) = u32x2{f32_to_f16_bits(v[0]) | (f32_to_f16_bits(v[1]) << 16),
-                                                    f32_to_f16_bits(v[2]) | (f32_to_f16_bits(v[3]) << 16)};
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (n + r >= N) break;
-                if (ydt == QS_F32) ((float*)y)[e + r] = v[r];
-                else if (ydt == QS_BF16) ((uint16_t*)y)[e + r] = (uint16_t)f32_to_bf16_bits(v[r]);
-                else ((uint16_t*)y)[e + r] = (uint16_t)f32_to_f16_bits(v[r]);
-            }
-        }
+        mx_store4(y, ydt, e, v, n, N, y_vec);
     }
 }
 

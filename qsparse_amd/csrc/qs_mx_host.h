@@ -1,0 +1,99 @@
+// Host-side helpers shared by the four translation units of the products on MX codes (api_mx_gemm.hip, api_mx_gemm_splitk.hip,
+// api_mx_conv.hip, api_mx_conv_t.hip): the dispatch over the 5 x 5 format pairs, the store rule of y, the descriptor of a product
+// forwarded to qs_mx_matmul_v, and the checks the two convolutions share.  Internal linkage, as qs_host.h.
+#pragma once
+#include "qs_host.h"
+#include "qs_mx_gemm.h"
+
+namespace {
+
+template <typename F>
+int mx_with_format(int format, F&& f) {
+    switch (format) {
+        case QS_MX_FP8_E4M3: return f(IC<QS_MX_FP8_E4M3>{});
+        case QS_MX_FP8_E5M2: return f(IC<QS_MX_FP8_E5M2>{});
+        case QS_MX_FP6_E2M3: return f(IC<QS_MX_FP6_E2M3>{});
+        case QS_MX_FP6_E3M2: return f(IC<QS_MX_FP6_E3M2>{});
+        default: return f(IC<QS_MX_FP4_E2M1>{});
+    }
+}
+
+// f(FA, FB, VEC) with the two formats (checked by the caller: mx_format_ok) and `vec` as integral constants
+template <typename F>
+int mx_dispatch(int fa, int fb, bool vec, F&& f) {
+    return mx_with_format(fa, [&](auto FA) {
+        return mx_with_format(fb, [&](auto FB) { return vec ? f(FA, FB, std::true_type{}) : f(FA, FB, std::false_type{}); });
+    });
+}
+
+inline int64_t mx_tiles(int64_t n) { return (n + kMxgTile - 1) / kMxgTile; }
+
+// four consecutive n per lane in one store: every row of y [., N] must keep the store's alignment
+inline int mx_y_vec(const void* y, int ydt, int64_t N) { return N % 4 == 0 && (((uintptr_t)y) & (4 * dt_size(ydt) - 1)) == 0; }
+
+// y = A [M, K] . B [N, K]^T as qs_mx_matmul_v takes it
+inline qs_mx_matmul_args mx_matmul_args(int fa, int fb, const uint8_t* a_codes, const uint8_t* a_scales, const uint8_t* b_codes,
+                                        const uint8_t* b_scales, const float* bias, void* y, int ydt, int64_t M, int64_t N, int64_t K,
+                                        qs_stream_t stream) {
+    qs_mx_matmul_args m = {};
+    m.struct_size = sizeof(m);
+    m.a_format = fa, m.b_format = fb;
+    m.a_codes = a_codes, m.a_scales = a_scales, m.b_codes = b_codes, m.b_scales = b_scales;
+    m.bias = bias, m.y = y, m.ydt = ydt;
+    m.M = M, m.N = N, m.K = K;
+    m.stream = stream;
+    return m;
+}
+
+// ---- what qs_mx_conv2d_v and qs_mx_conv_transpose2d_v check alike (Args: either descriptor) -----------------------------------------
+struct MxConvPlan {
+    int64_t OH, OW, M;
+};
+
+// before the output size: QS_OK or the error.  `own_ok`: the caller's own conditions on the arguments, which fail before the dtype's
+template <class Args>
+int mx_conv_check_args(const Args& a, bool own_ok) {
+    if (!a.x_codes || !a.x_scales || !a.w_codes || !a.w_scales || !a.y) return QS_ERR_ARG;
+    if (!mx_format_ok(a.x_format) || !mx_format_ok(a.w_format)) return QS_ERR_ARG;
+    if (a.B < 0 || a.Cout < 0 || a.H < 1 || a.W < 1 || a.C < 1 || a.KH < 1 || a.KW < 1) return QS_ERR_ARG;
+    if (a.stride_h < 1 || a.stride_w < 1 || a.dil_h < 1 || a.dil_w < 1 || a.pad_h < 0 || a.pad_w < 0) return QS_ERR_ARG;
+    if (!own_ok) return QS_ERR_ARG;
+    if (!dt_ok(a.ydt)) return QS_ERR_DTYPE;
+    if ((((uintptr_t)a.y) & (dt_size(a.ydt) - 1)) != 0 || (a.bias && (((uintptr_t)a.bias) & 3u) != 0)) return QS_ERR_ALIGN;
+    // the kernels keep coordinates inside one image in 32 bits (addresses: 64); H and W are the caller's to bound
+    if (a.C > INT32_MAX - QS_MX_BLOCK || a.B > INT32_MAX || a.Cout > INT32_MAX) return QS_ERR_ARG;
+    return QS_OK;
+}
+
+// after it (1 <= OH, OW; H, W <= INT32_MAX): the sizes, the plan and the kernel -- QS_MX_CONV_ROUTE_VEC or _PLAIN, 0 for an empty
+// problem, QS_ERR_ARG
+template <class Args>
+int mx_conv_plan(const Args& a, int64_t OH, int64_t OW, MxConvPlan* plan) {
+    const int64_t taps = (int64_t)a.KH * a.KW, Cp = (a.C + QS_MX_BLOCK - 1) / QS_MX_BLOCK * QS_MX_BLOCK;
+    if (taps > INT32_MAX || taps > INT64_MAX / Cp) return QS_ERR_ARG;
+    if (a.B == 0 || a.Cout == 0) return 0;
+    const int64_t Kp = taps * Cp;
+    if (OH > INT64_MAX / OW || a.B > INT64_MAX / (OH * OW)) return QS_ERR_ARG;
+    const int64_t M = a.B * OH * OW;
+    if (a.H > INT64_MAX / a.W || a.B > INT64_MAX / (a.H * a.W) || a.B * a.H * a.W > INT64_MAX / a.C) return QS_ERR_ARG;
+    if (M > INT64_MAX / a.Cout || M > INT64_MAX / Kp || a.Cout > INT64_MAX / Kp) return QS_ERR_ARG;
+    if (mx_tiles(M) * mx_tiles(a.Cout) > kMaxGrid) return QS_ERR_ARG;
+    if (plan) *plan = MxConvPlan{OH, OW, M};
+    return (a.C % 16 == 0 && aligned16(a.x_codes) && aligned16(a.w_codes)) ? QS_MX_CONV_ROUTE_VEC : QS_MX_CONV_ROUTE_PLAIN;
+}
+
+// a 1 x 1 kernel at stride 1 without padding over whole blocks: x IS A [B H W, C] and w IS B [Cout, C] as they lie
+template <class Args>
+bool mx_conv_is_gemm(const Args& a) {
+    return a.KH == 1 && a.KW == 1 && a.stride_h == 1 && a.stride_w == 1 && a.pad_h == 0 && a.pad_w == 0 && a.C % QS_MX_BLOCK == 0;
+}
+
+// QS_MX_CONV_ROUTE_GEMM: the call forwarded to qs_mx_matmul_v on the same bytes
+template <class Args>
+int mx_conv_as_matmul(const Args& a, int64_t M) {
+    const qs_mx_matmul_args m = mx_matmul_args(a.x_format, a.w_format, a.x_codes, a.x_scales, a.w_codes, a.w_scales, a.bias, a.y, a.ydt, M,
+                                               a.Cout, a.C, a.stream);
+    return qs_mx_matmul_v(&m);
+}
+
+}  // namespace

@@ -52,6 +52,28 @@ def _check_operand(name: str, what: str, codes: torch.Tensor, scales: torch.Tens
         raise ValueError(f"{name}_codes is on {codes.device} but {name}_scales on {scales.device}")
 
 
+def _check_product(fn: str, x_codes, x_scales, x_fmt: str, w_codes, w_scales, w_fmt: str, bias, out_dtype):
+    """the operand, C, device, out_dtype and bias checks of the public product `fn` (the name in its messages)"""
+    _check_operand("x", "[B, H, W, C]", x_codes, x_scales, x_fmt)
+    _check_operand("w", "[Cout, KH, KW, C]", w_codes, w_scales, w_fmt)
+    (B, H, W, C), (Cout, KH, KW, Cw) = x_codes.shape, w_codes.shape
+    if Cw != C:
+        raise ValueError(f"x_codes {tuple(x_codes.shape)} and w_codes {tuple(w_codes.shape)} disagree on C (their last dimensions)")
+    if C < 1 or KH < 1 or KW < 1 or H < 1 or W < 1:
+        raise ValueError(f"{fn} needs C, H, W, KH, KW >= 1, got x_codes {tuple(x_codes.shape)}, w_codes {tuple(w_codes.shape)}")
+    if w_codes.device != x_codes.device:
+        raise ValueError(f"x_codes is on {x_codes.device} but w_codes on {w_codes.device}")
+    if out_dtype not in _OUT_DTYPES:
+        raise TypeError(f"out_dtype must be one of {_OUT_DTYPES}, got {out_dtype}")
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
+            raise TypeError("bias must be a float32 tensor")
+        if tuple(bias.shape) != (Cout,):
+            raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({Cout},)")
+        if bias.device != x_codes.device:
+            raise ValueError(f"x_codes is on {x_codes.device} but bias on {bias.device}")
+
+
 def mx_conv2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_codes: torch.Tensor, w_scales: torch.Tensor, w_fmt: str,
               bias: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """``conv2d(x, w) (+ bias)`` on MX codes, channels-last.  ``x_codes`` ``[B, H, W, C]`` and ``w_codes`` ``[Cout, KH, KW, C]`` are
@@ -69,24 +91,8 @@ def mx_conv2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_codes
     ``mx_matmul`` on the im2col operands, to which the result is bit-identical; there is no fallback: without the library the call
     raises -- CPU tensors evaluate the expression above in float64 and round once.  Input channels are padded to a multiple of 32
     per tap inside the kernel, so a stem (C = 3) spends most of its products on zeros and is slow."""
-    _check_operand("x", "[B, H, W, C]", x_codes, x_scales, x_fmt)
-    _check_operand("w", "[Cout, KH, KW, C]", w_codes, w_scales, w_fmt)
-    (B, H, W, C), (Cout, KH, KW, Cw) = x_codes.shape, w_codes.shape
-    if Cw != C:
-        raise ValueError(f"x_codes {tuple(x_codes.shape)} and w_codes {tuple(w_codes.shape)} disagree on C (their last dimensions)")
-    if C < 1 or KH < 1 or KW < 1 or H < 1 or W < 1:
-        raise ValueError(f"mx_conv2d needs C, H, W, KH, KW >= 1, got x_codes {tuple(x_codes.shape)}, w_codes {tuple(w_codes.shape)}")
-    if w_codes.device != x_codes.device:
-        raise ValueError(f"x_codes is on {x_codes.device} but w_codes on {w_codes.device}")
-    if out_dtype not in _OUT_DTYPES:
-        raise TypeError(f"out_dtype must be one of {_OUT_DTYPES}, got {out_dtype}")
-    if bias is not None:
-        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
-            raise TypeError("bias must be a float32 tensor")
-        if tuple(bias.shape) != (Cout,):
-            raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({Cout},)")
-        if bias.device != x_codes.device:
-            raise ValueError(f"x_codes is on {x_codes.device} but bias on {bias.device}")
+    _check_product("mx_conv2d", x_codes, x_scales, x_fmt, w_codes, w_scales, w_fmt, bias, out_dtype)
+    (H, W), (KH, KW) = x_codes.shape[1:3], w_codes.shape[1:3]
     stride, padding, dilation = _pair("stride", stride, 1), _pair("padding", padding, 0), _pair("dilation", dilation, 1)
     OH = _hip.mx_conv_out_size(H, KH, stride[0], padding[0], dilation[0])
     OW = _hip.mx_conv_out_size(W, KW, stride[1], padding[1], dilation[1])
@@ -103,20 +109,17 @@ def mx_conv2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_codes
     return y.permute(0, 2, 3, 1).to(out_dtype).contiguous()
 
 
-class MXConv2d(nn.Module):
-    """``nn.Conv2d`` (``groups == 1``, zero padding) for inference on MX codes: the weight is held channels-last as uint8 codes
-    ``weight_codes [Cout, KH, KW, C]`` and E8M0 scales ``weight_scales [Cout, KH, KW, ceil(C / 32)]`` of the format ``weight_fmt``
-    (buffers, with the optional float32 ``bias``).  ``forward`` takes ``[B, C, H, W]`` in float32 / bfloat16 / float16, quantizes it
-    to ``act_fmt`` along the channels with the MX quantizer and convolves the two sets of codes with ``mx_conv2d``; it returns a
-    ``torch.channels_last`` ``[B, Cout, OH, OW]`` tensor in ``out_dtype`` that never requires grad.  An input that requires grad
-    while gradients are enabled is refused -- training runs on the simulated layers this one is built from.
+class _MXConvBase(nn.Module):
+    """what ``MXConv2d`` and ``MXConvTranspose2d`` share: the weight buffers and attributes, the checks of an exported weight and
+    ``forward``.  A subclass names the layer it stands for and the layout of that layer's weight, and supplies ``_product``."""
+    _layer = None                  # the torch layer
+    _weight_layout = ""            # of its weight, for messages
+    _perm = ()                     # that weight -> [Cout, KH, KW, C]
+    _block_dim = 0                 # the input channels in that weight
+    _block_dim_note = ""
 
-    Memory format: a ``torch.channels_last`` input is quantized where it lies (its ``[B, H, W, C]`` view is contiguous and takes
-    the quantizer's innermost-axis route).  An NCHW-contiguous input pays one extra layout pass over the activation before the
-    quantizer; keep the network channels_last to avoid it."""
-
-    def __init__(self, weight_codes: torch.Tensor, weight_scales: torch.Tensor, weight_fmt: str, bias: Optional[torch.Tensor] = None,
-                 stride=1, padding=0, dilation=1, act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32):
+    def __init__(self, weight_codes: torch.Tensor, weight_scales: torch.Tensor, weight_fmt: str, bias, stride, padding, dilation, act_fmt: str,
+                 out_dtype: torch.dtype):
         super().__init__()
         _mx_format(act_fmt)
         _check_operand("w", "[Cout, KH, KW, C]", weight_codes, weight_scales, weight_fmt)
@@ -132,24 +135,70 @@ class MXConv2d(nn.Module):
         self.register_buffer("weight_scales", weight_scales.detach().clone().contiguous())
         self.register_buffer("bias", None if bias is None else bias.detach().to(torch.float32).clone().contiguous())
 
+    def _extra_field(self) -> str:
+        """what ``extra_repr`` shows between the padding and the dilation"""
+        return ""
+
     def extra_repr(self) -> str:
         return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, "
-                f"dilation={self.dilation}, bias={self.bias is not None}, weight_fmt={self.weight_fmt!r}, act_fmt={self.act_fmt!r}")
+                f"{self._extra_field()}dilation={self.dilation}, bias={self.bias is not None}, weight_fmt={self.weight_fmt!r}, "
+                f"act_fmt={self.act_fmt!r}")
+
+    @classmethod
+    def _channels_last(cls, qt):
+        """the codes and scales ``[Cout, KH, KW, C]`` of an exported weight ``qt``, checked"""
+        name = f"MX{cls._layer.__name__}"
+        if getattr(qt, "kind", None) != "mx":
+            raise ValueError(f"{name} needs an MX weight (QuantizedTensor.kind == 'mx'), got kind {getattr(qt, 'kind', None)!r}")
+        if qt.codes.dim() != 4:
+            raise ValueError(f"{name} needs a 4-d weight {cls._weight_layout}, got shape {tuple(qt.codes.shape)}")
+        if qt.block_dim % qt.codes.dim() != cls._block_dim:
+            raise ValueError(f"the weight's MX blocks run along dim {qt.block_dim}, not along the input channels ({cls._block_dim_note}): "
+                             "such blocks cannot feed the matrix instruction -- quantize the layer with "
+                             f"MXQuantizer(fmt, block_dim={cls._block_dim})")
+        return qt.codes.permute(*cls._perm).contiguous(), qt.block_scale.permute(*cls._perm).contiguous()
+
+    def _product(self, codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+        raise NotImplementedError
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        layer = self._layer.__name__
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError(f"MX{layer} is an inference layer: its input requires grad.  Train with the simulated layer "
+                               f"(quantize(nn.{layer}(...), callback=MXQuantizer(...))) or call it under torch.no_grad()")
+        if x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise ValueError(f"MX{layer} expects [B, {self.in_channels}, H, W], got shape {tuple(x.shape)}")
+        with torch.no_grad():
+            _, codes, scales = quantize_with_mx(x.permute(0, 2, 3, 1), self.act_fmt, -1, return_codes=True)
+            if not codes.is_contiguous():      # an input that was not channels_last: one layout pass
+                codes, scales = codes.contiguous(), scales.contiguous()
+            return self._product(codes, scales).permute(0, 3, 1, 2)
+
+
+class MXConv2d(_MXConvBase):
+    """``nn.Conv2d`` (``groups == 1``, zero padding) for inference on MX codes: the weight is held channels-last as uint8 codes
+    ``weight_codes [Cout, KH, KW, C]`` and E8M0 scales ``weight_scales [Cout, KH, KW, ceil(C / 32)]`` of the format ``weight_fmt``
+    (buffers, with the optional float32 ``bias``).  ``forward`` takes ``[B, C, H, W]`` in float32 / bfloat16 / float16, quantizes it
+    to ``act_fmt`` along the channels with the MX quantizer and convolves the two sets of codes with ``mx_conv2d``; it returns a
+    ``torch.channels_last`` ``[B, Cout, OH, OW]`` tensor in ``out_dtype`` that never requires grad.  An input that requires grad
+    while gradients are enabled is refused -- training runs on the simulated layers this one is built from.
+
+    Memory format: a ``torch.channels_last`` input is quantized where it lies (its ``[B, H, W, C]`` view is contiguous and takes
+    the quantizer's innermost-axis route).  An NCHW-contiguous input pays one extra layout pass over the activation before the
+    quantizer; keep the network channels_last to avoid it."""
+
+    _layer, _weight_layout, _perm, _block_dim, _block_dim_note = nn.Conv2d, "[Cout, C, KH, KW]", (0, 2, 3, 1), 1, "dim 1"
+
+    def __init__(self, weight_codes: torch.Tensor, weight_scales: torch.Tensor, weight_fmt: str, bias: Optional[torch.Tensor] = None,
+                 stride=1, padding=0, dilation=1, act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32):
+        super().__init__(weight_codes, weight_scales, weight_fmt, bias, stride, padding, dilation, act_fmt, out_dtype)
 
     @classmethod
     def from_exported(cls, qt, bias: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1, act_fmt: str = "mxfp8_e4m3",
                       out_dtype: torch.dtype = torch.float32):
         """from the ``QuantizedTensor(kind="mx")`` ``export_integer`` returns for a conv layer's weight ``[Cout, C, KH, KW]`` with
         blocks along dim 1; codes and scales are permuted to channels-last once, here"""
-        if getattr(qt, "kind", None) != "mx":
-            raise ValueError(f"MXConv2d needs an MX weight (QuantizedTensor.kind == 'mx'), got kind {getattr(qt, 'kind', None)!r}")
-        if qt.codes.dim() != 4:
-            raise ValueError(f"MXConv2d needs a 4-d weight [Cout, C, KH, KW], got shape {tuple(qt.codes.shape)}")
-        if qt.block_dim % qt.codes.dim() != 1:
-            raise ValueError(f"the weight's MX blocks run along dim {qt.block_dim}, not along the input channels (dim 1): such blocks "
-                             "cannot feed the matrix instruction -- quantize the layer with MXQuantizer(fmt, block_dim=1)")
-        return cls(qt.codes.permute(0, 2, 3, 1).contiguous(), qt.block_scale.permute(0, 2, 3, 1).contiguous(), qt.fmt, bias, stride,
-                   padding, dilation, act_fmt, out_dtype)
+        return cls(*cls._channels_last(qt), qt.fmt, bias, stride, padding, dilation, act_fmt, out_dtype)
 
     @classmethod
     def from_quantized(cls, layer: nn.Module, act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32):
@@ -178,19 +227,9 @@ class MXConv2d(nn.Module):
             layer.train(was)
         return cls.from_exported(rec.weight, bias, tuple(layer.stride), tuple(layer.padding), tuple(layer.dilation), act_fmt, out_dtype)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if torch.is_grad_enabled() and x.requires_grad:
-            raise RuntimeError("MXConv2d is an inference layer: its input requires grad.  Train with the simulated layer "
-                               "(quantize(nn.Conv2d(...), callback=MXQuantizer(...))) or call it under torch.no_grad()")
-        if x.dim() != 4 or x.shape[1] != self.in_channels:
-            raise ValueError(f"MXConv2d expects [B, {self.in_channels}, H, W], got shape {tuple(x.shape)}")
-        with torch.no_grad():
-            _, codes, scales = quantize_with_mx(x.permute(0, 2, 3, 1), self.act_fmt, -1, return_codes=True)
-            if not codes.is_contiguous():      # an input that was not channels_last: one layout pass
-                codes, scales = codes.contiguous(), scales.contiguous()
-            y = mx_conv2d(codes, scales, self.act_fmt, self.weight_codes, self.weight_scales, self.weight_fmt, self.bias, self.stride,
-                          self.padding, self.dilation, self.out_dtype)
-            return y.permute(0, 3, 1, 2)
+    def _product(self, codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+        return mx_conv2d(codes, scales, self.act_fmt, self.weight_codes, self.weight_scales, self.weight_fmt, self.bias, self.stride,
+                         self.padding, self.dilation, self.out_dtype)
 
 
 __all__ = ["mx_conv2d", "MXConv2d", "MX_FORMATS"]

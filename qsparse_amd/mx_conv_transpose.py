@@ -8,7 +8,7 @@ Layouts are channels-last with the MX blocks of 32 along the contraction channel
 ...), callback=MXQuantizer(fmt, block_dim=0))`` layer exports.  For dgrad the contraction runs over the convolution's output
 channels: ``dy [B, OH, OW, Cout]`` quantized along its last axis and ``conv.weight [Cout, Cin, KH, KW].permute(1, 2, 3, 0)`` with
 blocks along ``Cout``.  On the GPU it is one HIP kernel (``qs_mx_conv_transpose2d_v``): the implicit GEMM of ``mx_conv2d`` with a
-fractionally-strided pixel functor, accumulating in float32; on the CPU the definition is evaluated in float64.  A stride ``s``
+fractionally-strided image operand, accumulating in float32; on the CPU the definition is evaluated in float64.  A stride ``s``
 spends ``sh sw - 1`` of every ``sh sw`` products on zero codes -- the kernel is correct and untuned, it has no sub-pixel
 decomposition.  The weight gradient of a convolution is not implemented."""
 from typing import Optional
@@ -18,9 +18,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from qsparse_amd import _hip
-from qsparse_amd.mx_conv import _check_operand, _pair
-from qsparse_amd.mx_gemm import _OUT_DTYPES
-from qsparse_amd.quantize import MX_FORMATS, MXQuantizer, _mx_format, mx_dequantize, quantize_with_mx
+from qsparse_amd.mx_conv import _check_operand, _check_product, _MXConvBase, _pair
+from qsparse_amd.quantize import MX_FORMATS, MXQuantizer, mx_dequantize
 
 
 def mx_conv_transpose2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_codes: torch.Tensor, w_scales: torch.Tensor, w_fmt: str,
@@ -42,24 +41,8 @@ def mx_conv_transpose2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: st
     pixel, one of the activation exactly the outputs with a tap on that pixel.  GPU tensors take the HIP kernel -- float32
     accumulation in the order of ``mx_matmul`` on the gathered operands, to which the result is bit-identical; there is no fallback:
     without the library the call raises -- CPU tensors evaluate the expression above in float64 and round once."""
-    _check_operand("x", "[B, H, W, C]", x_codes, x_scales, x_fmt)
-    _check_operand("w", "[Cout, KH, KW, C]", w_codes, w_scales, w_fmt)
-    (B, H, W, C), (Cout, KH, KW, Cw) = x_codes.shape, w_codes.shape
-    if Cw != C:
-        raise ValueError(f"x_codes {tuple(x_codes.shape)} and w_codes {tuple(w_codes.shape)} disagree on C (their last dimensions)")
-    if C < 1 or KH < 1 or KW < 1 or H < 1 or W < 1:
-        raise ValueError(f"mx_conv_transpose2d needs C, H, W, KH, KW >= 1, got x_codes {tuple(x_codes.shape)}, w_codes {tuple(w_codes.shape)}")
-    if w_codes.device != x_codes.device:
-        raise ValueError(f"x_codes is on {x_codes.device} but w_codes on {w_codes.device}")
-    if out_dtype not in _OUT_DTYPES:
-        raise TypeError(f"out_dtype must be one of {_OUT_DTYPES}, got {out_dtype}")
-    if bias is not None:
-        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
-            raise TypeError("bias must be a float32 tensor")
-        if tuple(bias.shape) != (Cout,):
-            raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({Cout},)")
-        if bias.device != x_codes.device:
-            raise ValueError(f"x_codes is on {x_codes.device} but bias on {bias.device}")
+    _check_product("mx_conv_transpose2d", x_codes, x_scales, x_fmt, w_codes, w_scales, w_fmt, bias, out_dtype)
+    (B, H, W, C), (KH, KW) = x_codes.shape, w_codes.shape[1:3]
     stride, padding, dilation = _pair("stride", stride, 1), _pair("padding", padding, 0), _pair("dilation", dilation, 1)
     output_padding = _pair("output_padding", output_padding, 0)
     if any(op >= max(s, d) for op, s, d in zip(output_padding, stride, dilation)):
@@ -111,7 +94,7 @@ def mx_conv2d_input_grad(dy_codes: torch.Tensor, dy_scales: torch.Tensor, dy_fmt
                                out_dtype)
 
 
-class MXConvTranspose2d(nn.Module):
+class MXConvTranspose2d(_MXConvBase):
     """``nn.ConvTranspose2d`` (``groups == 1``, zero padding) for inference on MX codes: the weight is held channels-last as uint8
     codes ``weight_codes [Cout, KH, KW, C]`` and E8M0 scales ``weight_scales [Cout, KH, KW, ceil(C / 32)]`` of the format
     ``weight_fmt`` (buffers, with the optional float32 ``bias``).  ``forward`` takes ``[B, C, H, W]`` in float32 / bfloat16 / float16,
@@ -120,44 +103,23 @@ class MXConvTranspose2d(nn.Module):
     requires grad while gradients are enabled is refused -- training runs on the simulated layers this one is built from.  As for
     ``MXConv2d``, a ``torch.channels_last`` input is quantized where it lies; an NCHW-contiguous one pays one layout pass."""
 
+    _layer, _weight_layout, _perm, _block_dim = nn.ConvTranspose2d, "[C, Cout, KH, KW]", (1, 2, 3, 0), 0
+    _block_dim_note = "dim 0 of a transposed convolution's weight"
+
     def __init__(self, weight_codes: torch.Tensor, weight_scales: torch.Tensor, weight_fmt: str, bias: Optional[torch.Tensor] = None,
                  stride=1, padding=0, output_padding=0, dilation=1, act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32):
-        super().__init__()
-        _mx_format(act_fmt)
-        _check_operand("w", "[Cout, KH, KW, C]", weight_codes, weight_scales, weight_fmt)
-        if out_dtype not in _OUT_DTYPES:
-            raise TypeError(f"out_dtype must be one of {_OUT_DTYPES}, got {out_dtype}")
-        if bias is not None and tuple(bias.shape) != (weight_codes.shape[0],):
-            raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({weight_codes.shape[0]},)")
-        self.weight_fmt, self.act_fmt, self.out_dtype = weight_fmt, act_fmt, out_dtype
-        self.stride, self.padding, self.dilation = _pair("stride", stride, 1), _pair("padding", padding, 0), _pair("dilation", dilation, 1)
+        super().__init__(weight_codes, weight_scales, weight_fmt, bias, stride, padding, dilation, act_fmt, out_dtype)
         self.output_padding = _pair("output_padding", output_padding, 0)
-        self.out_channels, self.in_channels = weight_codes.shape[0], weight_codes.shape[3]
-        self.kernel_size = (weight_codes.shape[1], weight_codes.shape[2])
-        self.register_buffer("weight_codes", weight_codes.detach().clone().contiguous())
-        self.register_buffer("weight_scales", weight_scales.detach().clone().contiguous())
-        self.register_buffer("bias", None if bias is None else bias.detach().to(torch.float32).clone().contiguous())
 
-    def extra_repr(self) -> str:
-        return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, "
-                f"output_padding={self.output_padding}, dilation={self.dilation}, bias={self.bias is not None}, "
-                f"weight_fmt={self.weight_fmt!r}, act_fmt={self.act_fmt!r}")
+    def _extra_field(self) -> str:
+        return f"output_padding={self.output_padding}, "
 
     @classmethod
     def from_exported(cls, qt, bias: Optional[torch.Tensor] = None, stride=1, padding=0, output_padding=0, dilation=1,
                       act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32):
         """from the ``QuantizedTensor(kind="mx")`` ``export_integer`` returns for a transposed conv layer's weight ``[C, Cout, KH,
         KW]`` with blocks along dim 0; codes and scales are permuted to channels-last once, here"""
-        if getattr(qt, "kind", None) != "mx":
-            raise ValueError(f"MXConvTranspose2d needs an MX weight (QuantizedTensor.kind == 'mx'), got kind {getattr(qt, 'kind', None)!r}")
-        if qt.codes.dim() != 4:
-            raise ValueError(f"MXConvTranspose2d needs a 4-d weight [C, Cout, KH, KW], got shape {tuple(qt.codes.shape)}")
-        if qt.block_dim % qt.codes.dim() != 0:
-            raise ValueError(f"the weight's MX blocks run along dim {qt.block_dim}, not along the input channels (dim 0 of a transposed "
-                             "convolution's weight): such blocks cannot feed the matrix instruction -- quantize the layer with "
-                             "MXQuantizer(fmt, block_dim=0)")
-        return cls(qt.codes.permute(1, 2, 3, 0).contiguous(), qt.block_scale.permute(1, 2, 3, 0).contiguous(), qt.fmt, bias, stride,
-                   padding, output_padding, dilation, act_fmt, out_dtype)
+        return cls(*cls._channels_last(qt), qt.fmt, bias, stride, padding, output_padding, dilation, act_fmt, out_dtype)
 
     @classmethod
     def from_quantized(cls, layer: nn.Module, act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32):
@@ -179,19 +141,9 @@ class MXConvTranspose2d(nn.Module):
         return cls.from_exported(rec.weight, bias, tuple(layer.stride), tuple(layer.padding), tuple(layer.output_padding),
                                  tuple(layer.dilation), act_fmt, out_dtype)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if torch.is_grad_enabled() and x.requires_grad:
-            raise RuntimeError("MXConvTranspose2d is an inference layer: its input requires grad.  Train with the simulated layer "
-                               "(quantize(nn.ConvTranspose2d(...), callback=MXQuantizer(...))) or call it under torch.no_grad()")
-        if x.dim() != 4 or x.shape[1] != self.in_channels:
-            raise ValueError(f"MXConvTranspose2d expects [B, {self.in_channels}, H, W], got shape {tuple(x.shape)}")
-        with torch.no_grad():
-            _, codes, scales = quantize_with_mx(x.permute(0, 2, 3, 1), self.act_fmt, -1, return_codes=True)
-            if not codes.is_contiguous():      # an input that was not channels_last: one layout pass
-                codes, scales = codes.contiguous(), scales.contiguous()
-            y = mx_conv_transpose2d(codes, scales, self.act_fmt, self.weight_codes, self.weight_scales, self.weight_fmt, self.bias,
-                                    self.stride, self.padding, self.output_padding, self.dilation, self.out_dtype)
-            return y.permute(0, 3, 1, 2)
+    def _product(self, codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+        return mx_conv_transpose2d(codes, scales, self.act_fmt, self.weight_codes, self.weight_scales, self.weight_fmt, self.bias,
+                                   self.stride, self.padding, self.output_padding, self.dilation, self.out_dtype)
 
 
 __all__ = ["mx_conv_transpose2d", "mx_conv2d_input_grad", "MXConvTranspose2d", "MX_FORMATS"]

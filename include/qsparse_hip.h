@@ -1138,6 +1138,71 @@ int qs_mx_conv_transpose2d_v(const qs_mx_conv_transpose2d_args* args);
  * QS_ERR_* the call would return */
 int qs_mx_conv_transpose2d_route(const qs_mx_conv_transpose2d_args* args);
 
+/* ---- MX convolution, weight gradient (batch-blocked implicit GEMM, deterministic split-K) ---------------------------------------
+ * Added without raising QS_ABI_VERSION (28): symbols are only added.  The weight gradient (wgrad) of qs_mx_conv2d_v's convolution,
+ * whose contraction runs over (b, oh, ow).
+ *
+ * Operands with MX blocks of 32 along the BATCH B, the innermost axis -- a block of 32 images at one pixel and channel is the same 32
+ * numbers under every tap (kh, kw), so one quantization of x serves all taps:
+ *   dyt_codes [OH, OW, Cout, B], dyt_scales [OH, OW, Cout, ceil(B / 32)];  xt_codes [H, W, C, B], xt_scales [H, W, C, ceil(B / 32)]
+ *   (the column pair qs_mx_quant2_v writes for the channels-last tensor seen as [B, OH OW Cout] / [B, H W C])
+ *   OH = (H + 2 pad_h - dil_h (KH - 1) - 1) / stride_h + 1, OW likewise (qs_mx_conv2d_v's; any other OH, OW: QS_ERR_ARG)
+ *   dw[n, kh, kw, c] = round_once_to_ydt( sum over (oh, ow, b) of
+ *                          val_g(dyt[oh, ow, n, b]) * 2^(dyt_scales[oh, ow, n, b / 32] - 127)
+ *                        * val_x(xt[ih, iw, c, b])  * 2^(xt_scales[ih, iw, c, b / 32] - 127) )
+ *   ih = oh * stride_h - pad_h + kh * dil_h,  iw = ow * stride_w - pad_w + kw * dil_w;  dw is [Cout, KH, KW, C], contiguous.
+ * Order of the sum: with Bp = 32 ceil(B / 32), k' = (oh * OW + ow) * Bp + b and K' = OH OW Bp the result equals, bit for bit, that of
+ * qs_mx_matmul_splitk_v (qs_mx_matmul_v when S' == 1) on the gathered operands G [Cout, K'] = dyt[oh, ow, n, b] and
+ * X' [KH KW C, K'] = xt[ih, iw, c, b] with the same S.  A code with b >= B, or an x tap outside the image, is the zero code; the
+ * scale byte of a block that does not exist at all (a tap outside the image) is 127.  No gathered matrix is written; groups == 1.
+ *   - Slicing: steps = ceil(K' / 128), per = ceil(steps / S), S' = ceil(steps / per); slice s covers the steps [s per, (s + 1) per);
+ *     the float32 partial sums are added in ascending s.  No atomics: the result is a pure function of the operands and S.
+ *     split_k == 0 asks for the automatic S of qs_mx_conv2d_wgrad_plan.
+ *   - No tap and no pixel is skipped.  A scale byte 0xFF of dyt at channel n makes dw[n] NaN everywhere; a byte 0xFF of xt at
+ *     (ih, iw, c) makes dw[:, kh, kw, c] NaN for exactly the taps (kh, kw) through which some output pixel reads (ih, iw).
+ *   - A batch below 32 pads its block with zero codes: B = 8 spends 3 / 4 of the products on zeros.
+ *   - workspace: caller-provided, S' * Cout * KH KW C * 4 bytes (qs_mx_conv2d_wgrad_plan tells), 16-byte aligned (QS_ERR_ALIGN
+ *     otherwise); too small: QS_ERR_WORKSPACE; NULL with S' > 1: QS_ERR_ARG.  Not looked at when S' == 1.  Nothing past those bytes
+ *     is written.  One launch, or two when S' > 1 (partials; their ordered sum); graph-capturable, no allocation, no synchronisation.
+ *   - Codes and scales: any address.  dw: aligned to its element (QS_ERR_ALIGN otherwise).
+ *   - Cout == 0 or C == 0: nothing is enqueued, 0 is returned.
+ *   - QS_ERR_ARG: a null or too short descriptor, a null operand, a format outside enum qs_mx_format, B < 1, Cout or C < 0, H, W, KH,
+ *     KW, a stride or a dilation < 1, a negative padding or split_k, OH or OW not the convolution's, H + 2 pad_h, W + 2 pad_w, B + 32,
+ *     Cout or C beyond INT32_MAX, a product of extents beyond 64 bits, tiles * S' beyond 2^31 - 1.  QS_ERR_DTYPE: ydt is none of the
+ *     three.
+ * Routes (the values of qs_mx_conv2d_route; there is no GEMM route: even a 1 x 1 operand is not row-major in k'):
+ *   QS_MX_CONV_ROUTE_VEC    B % 16 == 0 and both code bases 16-byte aligned: 16 bytes per load
+ *   QS_MX_CONV_ROUTE_PLAIN  anything else (any B >= 1, any base): the same kernel with predicated byte loads */
+typedef struct qs_mx_conv2d_wgrad_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_conv2d_wgrad_args) as the caller compiled it */
+    int32_t dy_format, x_format;     /* enum qs_mx_format, may differ */
+    const uint8_t* dyt_codes;        /* [OH, OW, Cout, B], one code per byte */
+    const uint8_t* dyt_scales;       /* [OH, OW, Cout, ceil(B / 32)] E8M0 bytes */
+    const uint8_t* xt_codes;         /* [H, W, C, B] */
+    const uint8_t* xt_scales;        /* [H, W, C, ceil(B / 32)] */
+    void* dw;                        /* [Cout, KH, KW, C] */
+    int32_t ydt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    int32_t split_k;                 /* S >= 1, the requested number of slices; 0: the library's choice */
+    int64_t B, H, W, C, Cout, OH, OW;
+    int32_t KH, KW;
+    int32_t stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
+    qs_stream_t stream;
+    void* workspace;                 /* S' * Cout * KH KW C float32; nullable when S' == 1 */
+    uint64_t workspace_bytes;
+} qs_mx_conv2d_wgrad_args;
+int qs_mx_conv2d_wgrad_v(const qs_mx_conv2d_wgrad_args* args);
+/* the route qs_mx_conv2d_wgrad_v takes for these operands, nothing enqueued: QS_MX_CONV_ROUTE_VEC or _PLAIN, 0 for an empty
+ * problem, or the QS_ERR_* the call would return */
+int qs_mx_conv2d_wgrad_route(const qs_mx_conv2d_wgrad_args* args);
+/* writes S' and the workspace bytes (0 when S' == 1) of a request on the product M = Cout, N = KH KW C, K = OH OW Bp; either pointer
+ * may be NULL.  split_k == 0 asks for the automatic choice, a pure function of (M, N, K): the rule of qs_mx_matmul_splitk_plan with a
+ * cap of 128 slices instead of 16 --
+ *     S = 1                                                        when steps < 32 or tiles >= 256
+ *     S = max(1, min(floor(512 / tiles), floor(steps / 8), 128))   otherwise
+ * -- because this product has few tiles (64 -> 64 channels, 3 x 3: 5) and thousands of steps.  Errors as
+ * qs_mx_matmul_splitk_plan. */
+int qs_mx_conv2d_wgrad_plan(int64_t M, int64_t N, int64_t K, int32_t split_k, int32_t* slices, uint64_t* workspace_bytes);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

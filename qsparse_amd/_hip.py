@@ -110,6 +110,9 @@ SIGNATURES = {
     "qs_mx_conv2d_route": (c_int, [_P]),
     "qs_mx_conv_transpose2d_v": (c_int, [_P]),
     "qs_mx_conv_transpose2d_route": (c_int, [_P]),
+    "qs_mx_conv2d_wgrad_v": (c_int, [_P]),
+    "qs_mx_conv2d_wgrad_route": (c_int, [_P]),
+    "qs_mx_conv2d_wgrad_plan": (c_int, [_L, _L, _L, c_int32, _P, _P]),
 }
 
 
@@ -224,6 +227,16 @@ class MxConv2dArgs(ctypes.Structure):
 class MxConvTranspose2dArgs(ctypes.Structure):
     """`qs_mx_conv_transpose2d_args` of include/qsparse_hip.h"""
     _fields_ = MxConv2dArgs._fields_[:-1] + [("out_pad_h", c_int32), ("out_pad_w", c_int32), ("stream", c_void_p)]
+
+
+class MxConv2dWgradArgs(ctypes.Structure):
+    """`qs_mx_conv2d_wgrad_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("dy_format", c_int32), ("x_format", c_int32), ("dyt_codes", c_void_p),
+                ("dyt_scales", c_void_p), ("xt_codes", c_void_p), ("xt_scales", c_void_p), ("dw", c_void_p), ("ydt", c_int32),
+                ("split_k", c_int32), ("B", c_int64), ("H", c_int64), ("W", c_int64), ("C", c_int64), ("Cout", c_int64),
+                ("OH", c_int64), ("OW", c_int64), ("KH", c_int32), ("KW", c_int32), ("stride_h", c_int32), ("stride_w", c_int32),
+                ("pad_h", c_int32), ("pad_w", c_int32), ("dil_h", c_int32), ("dil_w", c_int32), ("stream", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64)]
 
 
 class MultiRow(ctypes.Structure):
@@ -996,6 +1009,51 @@ def mx_conv_transpose2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: st
     y, mx_conv_transpose_last_route = _mx_conv_launch("mx_conv_transpose2d", a, x_codes, x_scales, x_fmt, w_codes, w_scales, w_fmt, bias,
                                                       size, stride, padding, dilation, out_dtype)
     return y
+
+
+mx_conv_wgrad_last_route = None     # the QS_MX_CONV_ROUTE_* of the last `mx_conv2d_wgrad` launch (None: an empty problem)
+mx_conv_wgrad_last_split = 1        # its S': 1 for an unsplit one
+
+
+def mx_conv_wgrad_plan(M: int, N: int, K: int, split_k: int):
+    """(S', workspace bytes) of `qs_mx_conv2d_wgrad_plan` for a request of `split_k` slices of the product M = Cout, N = KH KW C,
+    K = OH OW Bp; 0 asks for the library's automatic choice"""
+    slices, nbytes = c_int32(0), ctypes.c_uint64(0)
+    _check(load().qs_mx_conv2d_wgrad_plan(M, N, K, split_k, ctypes.byref(slices), ctypes.byref(nbytes)), "qs_mx_conv2d_wgrad_plan")
+    return slices.value, nbytes.value
+
+
+def mx_conv2d_wgrad(dyt_codes: torch.Tensor, dyt_scales: torch.Tensor, dy_fmt: str, xt_codes: torch.Tensor, xt_scales: torch.Tensor,
+                    x_fmt: str, kernel_size, stride, padding, dilation, out_dtype: torch.dtype = torch.float32,
+                    split_k: int = 0) -> torch.Tensor:
+    """dW[Cout, KH, KW, C] on batch-blocked MX codes (qs_mx_conv2d_wgrad_v): `dyt_codes` [OH, OW, Cout, B], `xt_codes` [H, W, C, B]
+    uint8, scales [..., ceil(B / 32)] uint8, all contiguous GPU tensors (qsparse_amd/mx_conv_train.py checks); `kernel_size`,
+    `stride`, `padding`, `dilation` pairs of ints; `split_k` slices of the contraction (0: the library's choice).  ONE launch -- two
+    when S' > 1, with a workspace from torch's caching allocator (no hipMalloc in a warmed-up step: capture stays possible)."""
+    global mx_conv_wgrad_last_route, mx_conv_wgrad_last_split
+    lib = load()
+    (OH, OW, Cout, B), (H, W, C, _), (KH, KW) = dyt_codes.shape, xt_codes.shape, kernel_size
+    dw = torch.empty((Cout, KH, KW, C), dtype=out_dtype, device=xt_codes.device)
+    mx_conv_wgrad_last_route, mx_conv_wgrad_last_split = None, 1
+    if Cout and C:
+        Bp = (B + MX_BLOCK - 1) // MX_BLOCK * MX_BLOCK
+        slices, nbytes = mx_conv_wgrad_plan(Cout, KH * KW * C, OH * OW * Bp, split_k)
+        a = MxConv2dWgradArgs()
+        a.struct_size = ctypes.sizeof(a)
+        a.dy_format, a.x_format = MX_FORMATS.index(dy_fmt), MX_FORMATS.index(x_fmt)
+        a.dyt_codes, a.dyt_scales, a.xt_codes, a.xt_scales = _ptr(dyt_codes), _ptr(dyt_scales), _ptr(xt_codes), _ptr(xt_scales)
+        a.dw, a.ydt, a.split_k = _ptr(dw), _DT[out_dtype], slices
+        a.B, a.H, a.W, a.C, a.Cout, a.OH, a.OW, a.KH, a.KW = B, H, W, C, Cout, OH, OW, KH, KW
+        (a.stride_h, a.stride_w), (a.pad_h, a.pad_w), (a.dil_h, a.dil_w) = stride, padding, dilation
+        a.stream = _stream(xt_codes)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=xt_codes.device) if slices > 1 else None
+        a.workspace, a.workspace_bytes = _ptr(ws), nbytes
+        route = lib.qs_mx_conv2d_wgrad_route(ctypes.byref(a))
+        with _timed(f"mx_conv2d_wgrad[{route}]", dyt_codes, dyt_scales, xt_codes, xt_scales, dw, 2 * nbytes):
+            st = lib.qs_mx_conv2d_wgrad_v(ctypes.byref(a))
+        _check(st, "qs_mx_conv2d_wgrad_v")
+        mx_conv_wgrad_last_route, mx_conv_wgrad_last_split = route, slices
+    return dw
 
 
 MX_Q2_ROUTE_TILE_VEC, MX_Q2_ROUTE_TILE_PLAIN = 1, 2

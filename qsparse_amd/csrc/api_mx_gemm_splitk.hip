@@ -7,43 +7,7 @@
 
 namespace {
 
-// ---- the automatic slice count (qs_mx_matmul_splitk_plan, split_k == 0): a pure function of (M, N, K) --------------------------------
-constexpr int64_t kSplitMinSteps = 32;     // fewer K-steps than this: never split
-constexpr int64_t kSplitFullTiles = 256;   // this many output tiles (one per CU) or more: never split
-constexpr int64_t kSplitGroups = 512;      // work-groups aimed at: two co-resident per CU at 64 KiB of LDS each
-constexpr int64_t kSplitStepsPerSlice = 8; // a slice keeps at least this many K-steps
-constexpr int64_t kSplitMax = 16;
-
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-int64_t auto_split(int64_t M, int64_t N, int64_t K) {
-    const int64_t tiles = cdiv(M, kMxgTile) * cdiv(N, kMxgTile), steps = cdiv(K, kMxgK);
-    if (steps < kSplitMinSteps || tiles >= kSplitFullTiles) return 1;
-    return std::max<int64_t>(1, std::min({kSplitGroups / tiles, steps / kSplitStepsPerSlice, kSplitMax}));
-}
-
-struct SplitPlan {
-    int64_t per;          // K-steps per slice
-    int32_t slices;       // S': no slice is empty
-    uint64_t bytes;       // of the workspace; 0 when slices == 1
-};
-
-// QS_OK and the plan, or QS_ERR_ARG (a negative extent or request, K == 0 of a non-empty product, a byte count beyond 64 bits)
-int split_plan(int64_t M, int64_t N, int64_t K, int32_t split_k, SplitPlan* p) {
-    if (M < 0 || N < 0 || K < 0 || split_k < 0) return QS_ERR_ARG;
-    *p = SplitPlan{0, 1, 0};
-    if (M == 0 || N == 0) return QS_OK;
-    if (K == 0 || M > INT64_MAX / N) return QS_ERR_ARG;
-    const int64_t steps = cdiv(K, kMxgK);
-    const int64_t S = split_k == 0 ? auto_split(M, N, K) : split_k;
-    p->per = cdiv(steps, S);
-    p->slices = (int32_t)cdiv(steps, p->per);      // <= S <= INT32_MAX
-    if (p->slices > 1) {
-        if ((uint64_t)(M * N) > UINT64_MAX / 4 / (uint64_t)p->slices) return QS_ERR_ARG;
-        p->bytes = (uint64_t)(M * N) * 4u * (uint64_t)p->slices;
-    }
-    return QS_OK;
-}
+constexpr int64_t kSplitMax = 16;    // the most slices the automatic rule asks for
 
 qs_mx_matmul_args unsplit_args(const qs_mx_matmul_splitk_args& a) {
     return mx_matmul_args(a.a_format, a.b_format, a.a_codes, a.a_scales, a.b_codes, a.b_scales, a.bias, a.y, a.ydt, a.M, a.N, a.K, a.stream);
@@ -57,7 +21,7 @@ int splitk_route(const qs_mx_matmul_splitk_args& a, SplitPlan* p) {
     if (route < 0) return route;
     if (a.split_k < 1) return QS_ERR_ARG;
     if (route == 0) return 0;
-    const int st = split_plan(a.M, a.N, a.K, a.split_k, p);
+    const int st = split_plan(a.M, a.N, a.K, a.split_k, kSplitMax, p);
     if (st != QS_OK) return st;
     if (p->slices == 1) return route;              // forwarded to qs_mx_matmul_v: no workspace
     if (!a.workspace) return QS_ERR_ARG;
@@ -96,7 +60,7 @@ extern "C" {
 
 int qs_mx_matmul_splitk_plan(int64_t M, int64_t N, int64_t K, int32_t split_k, int32_t* slices, uint64_t* workspace_bytes) {
     SplitPlan p;
-    const int st = split_plan(M, N, K, split_k, &p);
+    const int st = split_plan(M, N, K, split_k, kSplitMax, &p);
     if (st != QS_OK) return st;
     if (slices) *slices = p.slices;
     if (workspace_bytes) *workspace_bytes = p.bytes;

@@ -77,15 +77,20 @@ __device__ __forceinline__ int64_t mxc_pixel(const MxcRow& r, const MxcPos& p, c
 }
 
 // where this thread stands along k': the position of its pieces (codes) and of its lane's scale bytes (blocks).  One walk serves
-// both operands of a product -- they read the same k' -- and the activation's operand advances it: 128 codes (4 blocks) per step
+// both operands of a product -- they read the same k' -- and the activation's operand advances it: 128 codes (4 blocks) per step.
+// The walk is over any k' = (outer * wrap + middle) * period + inner: the weight gradient (qs_mx_conv_wgrad.h) walks (oh, ow, b)
 struct MxcWalk {
     MxcPos pc, ps;
     int Cp, nb, KW;
 
-    __device__ __forceinline__ MxcWalk(const MxcShape& g, int tid) : pc{0, 0, 0}, ps{0, 0, 0}, Cp(g.nb * QS_MX_BLOCK), nb(g.nb), KW(g.KW) {
+    // a period of `nb` blocks, the middle coordinate wrapping at `wrap`; `start` = where the first code of the first step lies (its c:
+    // a multiple of the block)
+    __device__ __forceinline__ MxcWalk(int nb, int wrap, const MxcPos& start, int tid)
+        : pc(start), ps{start.c / QS_MX_BLOCK, start.kh, start.kw}, Cp(nb * QS_MX_BLOCK), nb(nb), KW(wrap) {
         mxc_advance(pc, (tid & 7) * 16, Cp, KW);
         mxc_advance(ps, (tid & 63) >> 4, nb, KW);
     }
+    __device__ __forceinline__ MxcWalk(const MxcShape& g, int tid) : MxcWalk(g.nb, g.KW, MxcPos{0, 0, 0}, tid) {}
     __device__ __forceinline__ void advance() {
         mxc_advance(pc, kMxgK, Cp, KW);
         mxc_advance(ps, kMxgK / QS_MX_BLOCK, nb, KW);

@@ -102,8 +102,9 @@ __global__ __launch_bounds__(kMxgThreads) void mx_gemm_partial_kernel(const uint
     }
 }
 
-// one thread per group of four consecutive n of one row m; `groups_n` = ceil(N / 4) groups per row
-__global__ __launch_bounds__(kBlock) void mx_gemm_reduce_kernel(const float* __restrict__ ws, const float* __restrict__ bias,
+// one thread per group of four consecutive n of one row m; `groups_n` = ceil(N / 4) groups per row.  static: api_mx_gemm_splitk.hip and
+// api_mx_conv_wgrad.hip both launch it, each from a copy of its own
+static __global__ __launch_bounds__(kBlock) void mx_gemm_reduce_kernel(const float* __restrict__ ws, const float* __restrict__ bias,
                                                                  void* __restrict__ y, int ydt, int64_t M, int64_t N, int slices,
                                                                  int64_t groups_n, int ws_vec, int y_vec) {
     const int64_t groups = M * groups_n, plane = M * N;

@@ -1,6 +1,7 @@
-// Host-side helpers shared by the four translation units of the products on MX codes (api_mx_gemm.hip, api_mx_gemm_splitk.hip,
-// api_mx_conv.hip, api_mx_conv_t.hip): the dispatch over the 5 x 5 format pairs, the store rule of y, the descriptor of a product
-// forwarded to qs_mx_matmul_v, and the checks the two convolutions share.  Internal linkage, as qs_host.h.
+// Host-side helpers shared by the five translation units of the products on MX codes (api_mx_gemm.hip, api_mx_gemm_splitk.hip,
+// api_mx_conv.hip, api_mx_conv_t.hip, api_mx_conv_wgrad.hip): the dispatch over the 5 x 5 format pairs, the store rule of y, the
+// descriptor of a product forwarded to qs_mx_matmul_v, the slicing of a split product, and the checks the two convolutions share.
+// Internal linkage, as qs_host.h.
 #pragma once
 #include "qs_host.h"
 #include "qs_mx_gemm.h"
@@ -43,6 +44,45 @@ inline qs_mx_matmul_args mx_matmul_args(int fa, int fb, const uint8_t* a_codes, 
     m.M = M, m.N = N, m.K = K;
     m.stream = stream;
     return m;
+}
+
+// ---- the slicing of a product split along K and the automatic slice count (qs_mx_matmul_splitk_plan, qs_mx_conv2d_wgrad_plan;
+// split_k == 0): a pure function of (M, N, K) and the caller's cap ----------------------------------------------------------------
+constexpr int64_t kSplitMinSteps = 32;     // fewer K-steps than this: never split
+constexpr int64_t kSplitFullTiles = 256;   // this many output tiles (one per CU) or more: never split
+constexpr int64_t kSplitGroups = 512;      // work-groups aimed at: two co-resident per CU at 64 KiB of LDS each
+constexpr int64_t kSplitStepsPerSlice = 8; // a slice keeps at least this many K-steps
+
+inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+inline int64_t auto_split(int64_t M, int64_t N, int64_t K, int64_t cap) {
+    const int64_t tiles = cdiv(M, kMxgTile) * cdiv(N, kMxgTile), steps = cdiv(K, kMxgK);
+    if (steps < kSplitMinSteps || tiles >= kSplitFullTiles) return 1;
+    return std::max<int64_t>(1, std::min({kSplitGroups / tiles, steps / kSplitStepsPerSlice, cap}));
+}
+
+struct SplitPlan {
+    int64_t per;          // K-steps per slice
+    int32_t slices;       // S': no slice is empty
+    uint64_t bytes;       // of the workspace; 0 when slices == 1
+};
+
+// QS_OK and the plan, or QS_ERR_ARG (a negative extent or request, K == 0 of a non-empty product, a byte count beyond 64 bits).
+// `cap`: the most slices the automatic rule asks for
+inline int split_plan(int64_t M, int64_t N, int64_t K, int32_t split_k, int64_t cap, SplitPlan* p) {
+    if (M < 0 || N < 0 || K < 0 || split_k < 0) return QS_ERR_ARG;
+    *p = SplitPlan{0, 1, 0};
+    if (M == 0 || N == 0) return QS_OK;
+    if (K == 0 || M > INT64_MAX / N) return QS_ERR_ARG;
+    const int64_t steps = cdiv(K, kMxgK);
+    const int64_t S = split_k == 0 ? auto_split(M, N, K, cap) : split_k;
+    p->per = cdiv(steps, S);
+    p->slices = (int32_t)cdiv(steps, p->per);      // <= S <= INT32_MAX
+    if (p->slices > 1) {
+        if ((uint64_t)(M * N) > UINT64_MAX / 4 / (uint64_t)p->slices) return QS_ERR_ARG;
+        p->bytes = (uint64_t)(M * N) * 4u * (uint64_t)p->slices;
+    }
+    return QS_OK;
 }
 
 // ---- what qs_mx_conv2d_v and qs_mx_conv_transpose2d_v check alike (Args: either descriptor) -----------------------------------------

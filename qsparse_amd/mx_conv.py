@@ -6,8 +6,9 @@ as the matrix instruction needs.  ``quantize_with_mx(x.permute(0, 2, 3, 1), fmt,
 activation's bytes (zero-copy for a ``torch.channels_last`` tensor), a ``quantize(nn.Conv2d(...), callback=MXQuantizer(fmt,
 block_dim=1))`` layer exports the weight's.  On the GPU ``mx_conv2d`` is one HIP kernel (``qs_mx_conv2d_v``): an implicit GEMM
 on the block-scaled MFMA of gfx950 that gathers the windows while it stages them -- no im2col matrix is ever written -- and
-accumulates in float32; on the CPU it evaluates the definition in float64.  Inference only: training through convolutions (the
-input- and weight-gradient products) is not implemented; train with the simulated layers."""
+accumulates in float32; on the CPU it evaluates the definition in float64.  ``MXConv2d`` is an inference layer; training through
+the three products of a convolution (forward, input gradient, weight gradient) is ``mx_conv2d_train`` / ``MXTrainConv2d`` of
+``qsparse_amd/mx_conv_train.py``."""
 from typing import Optional
 
 import torch

@@ -10,7 +10,7 @@ channels: ``dy [B, OH, OW, Cout]`` quantized along its last axis and ``conv.weig
 blocks along ``Cout``.  On the GPU it is one HIP kernel (``qs_mx_conv_transpose2d_v``): the implicit GEMM of ``mx_conv2d`` with a
 fractionally-strided image operand, accumulating in float32; on the CPU the definition is evaluated in float64.  A stride ``s``
 spends ``sh sw - 1`` of every ``sh sw`` products on zero codes -- the kernel is correct and untuned, it has no sub-pixel
-decomposition.  The weight gradient of a convolution is not implemented."""
+decomposition.  The weight gradient of a convolution is ``mx_conv2d_weight_grad`` (``qsparse_amd/mx_conv_train.py``)."""
 from typing import Optional
 
 import torch

@@ -899,19 +899,28 @@ mx_gemm_last_route = None     # the QS_MX_GEMM_ROUTE_* of the last `mx_matmul` l
 mx_gemm_last_split = 1        # the S' of the last `mx_matmul` launch: 1 for an unsplit one
 
 
-def mx_split_plan(M: int, N: int, K: int, split_k: int):
-    """(S', workspace bytes) of `qs_mx_matmul_splitk_plan` for a request of `split_k` slices; 0 asks for the library's automatic choice"""
+def _mx_plan(symbol: str, M: int, N: int, K: int, split_k: int):
+    """(S', workspace bytes) of the plan export `symbol` for `split_k` slices of [M, K] . [N, K]^T; 0 asks for the library's choice"""
     slices, nbytes = c_int32(0), ctypes.c_uint64(0)
-    _check(load().qs_mx_matmul_splitk_plan(M, N, K, split_k, ctypes.byref(slices), ctypes.byref(nbytes)), "qs_mx_matmul_splitk_plan")
+    _check(getattr(load(), symbol)(M, N, K, split_k, ctypes.byref(slices), ctypes.byref(nbytes)), symbol)
     return slices.value, nbytes.value
+
+
+def _mx_workspace(nbytes: int, device):
+    """the workspace of a split product, from torch's caching allocator: no hipMalloc in a warmed-up step, capture stays possible"""
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def mx_split_plan(M: int, N: int, K: int, split_k: int):
+    """`_mx_plan` of `mx_matmul`'s split (`qs_mx_matmul_splitk_plan`)"""
+    return _mx_plan("qs_mx_matmul_splitk_plan", M, N, K, split_k)
 
 
 def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
               bias: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32, split_k: int = 1) -> torch.Tensor:
     """y[M, N] = A . B^T on MX codes (qs_mx_matmul_v): `a_codes` [M, K], `b_codes` [N, K] uint8, scales [*, ceil(K / 32)] uint8,
     all contiguous GPU tensors (qsparse_amd/mx_gemm.py checks and flattens); `bias` float32 [N] or None.  ONE launch -- or, when
-    `split_k` (0: the library's choice) plans S' > 1 slices of K, the two of qs_mx_matmul_splitk_v, with a workspace from torch's
-    caching allocator (no hipMalloc in a warmed-up step: capture stays possible)."""
+    `split_k` (0: the library's choice) plans S' > 1 slices of K, the two of qs_mx_matmul_splitk_v, with a workspace (`_mx_workspace`)."""
     global mx_gemm_last_route, mx_gemm_last_split
     lib = load()
     (M, K), N = a_codes.shape, b_codes.shape[0]
@@ -927,7 +936,7 @@ def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes
         a.M, a.N, a.K = M, N, K
         a.stream = _stream(a_codes)
         if slices > 1:
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=a_codes.device)
+            ws = _mx_workspace(nbytes, a_codes.device)
             a.split_k, a.workspace, a.workspace_bytes = slices, _ptr(ws), nbytes
             route = lib.qs_mx_matmul_splitk_route(ctypes.byref(a))
             with _timed(f"mx_matmul_splitk[{route}]", a_codes, a_scales, b_codes, b_scales, bias, y, 2 * nbytes):
@@ -1016,11 +1025,8 @@ mx_conv_wgrad_last_split = 1        # its S': 1 for an unsplit one
 
 
 def mx_conv_wgrad_plan(M: int, N: int, K: int, split_k: int):
-    """(S', workspace bytes) of `qs_mx_conv2d_wgrad_plan` for a request of `split_k` slices of the product M = Cout, N = KH KW C,
-    K = OH OW Bp; 0 asks for the library's automatic choice"""
-    slices, nbytes = c_int32(0), ctypes.c_uint64(0)
-    _check(load().qs_mx_conv2d_wgrad_plan(M, N, K, split_k, ctypes.byref(slices), ctypes.byref(nbytes)), "qs_mx_conv2d_wgrad_plan")
-    return slices.value, nbytes.value
+    """`_mx_plan` of the conv weight gradient (`qs_mx_conv2d_wgrad_plan`): the product M = Cout, N = KH KW C, K = OH OW Bp"""
+    return _mx_plan("qs_mx_conv2d_wgrad_plan", M, N, K, split_k)
 
 
 def mx_conv2d_wgrad(dyt_codes: torch.Tensor, dyt_scales: torch.Tensor, dy_fmt: str, xt_codes: torch.Tensor, xt_scales: torch.Tensor,
@@ -1029,7 +1035,7 @@ def mx_conv2d_wgrad(dyt_codes: torch.Tensor, dyt_scales: torch.Tensor, dy_fmt: s
     """dW[Cout, KH, KW, C] on batch-blocked MX codes (qs_mx_conv2d_wgrad_v): `dyt_codes` [OH, OW, Cout, B], `xt_codes` [H, W, C, B]
     uint8, scales [..., ceil(B / 32)] uint8, all contiguous GPU tensors (qsparse_amd/mx_conv_train.py checks); `kernel_size`,
     `stride`, `padding`, `dilation` pairs of ints; `split_k` slices of the contraction (0: the library's choice).  ONE launch -- two
-    when S' > 1, with a workspace from torch's caching allocator (no hipMalloc in a warmed-up step: capture stays possible)."""
+    when S' > 1, with a workspace (`_mx_workspace`)."""
     global mx_conv_wgrad_last_route, mx_conv_wgrad_last_split
     lib = load()
     (OH, OW, Cout, B), (H, W, C, _), (KH, KW) = dyt_codes.shape, xt_codes.shape, kernel_size
@@ -1046,7 +1052,7 @@ def mx_conv2d_wgrad(dyt_codes: torch.Tensor, dyt_scales: torch.Tensor, dy_fmt: s
         a.B, a.H, a.W, a.C, a.Cout, a.OH, a.OW, a.KH, a.KW = B, H, W, C, Cout, OH, OW, KH, KW
         (a.stride_h, a.stride_w), (a.pad_h, a.pad_w), (a.dil_h, a.dil_w) = stride, padding, dilation
         a.stream = _stream(xt_codes)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=xt_codes.device) if slices > 1 else None
+        ws = _mx_workspace(nbytes, xt_codes.device) if slices > 1 else None
         a.workspace, a.workspace_bytes = _ptr(ws), nbytes
         route = lib.qs_mx_conv2d_wgrad_route(ctypes.byref(a))
         with _timed(f"mx_conv2d_wgrad[{route}]", dyt_codes, dyt_scales, xt_codes, xt_scales, dw, 2 * nbytes):

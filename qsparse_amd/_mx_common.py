@@ -1,0 +1,147 @@
+"""What the products on MX codes (``mx_gemm.py``, ``mx_conv.py``, ``mx_conv_transpose.py``, ``mx_conv_train.py``) and their two training
+layers say alike, stated once: the argument checks of an operand, of ``out_dtype``, of a bias and of a training entry, the options /
+stochastic-rounding counter / ``repr`` of ``MXTrainLinear`` and ``MXTrainConv2d`` (``_MXTrainMixin``), and the two steps their autograd
+functions share.  Private: the public modules import from here and keep their own shape messages."""
+import torch
+
+from qsparse_amd.quantize import MX_BLOCK, _mx_check_rounding, _mx_format
+
+_OUT_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def _pair(name: str, v, least: int):
+    """`v` as a pair of ints, each >= `least`"""
+    if isinstance(v, str):
+        raise ValueError(f"{name} must be an int or a pair of ints, got the string {v!r} (padding modes such as 'same' are not supported: "
+                         "give the padding as numbers)")
+    if isinstance(v, bool) or not isinstance(v, (int, tuple, list)):
+        raise TypeError(f"{name} must be an int or a pair of ints, got {type(v).__name__}")
+    p = (v, v) if isinstance(v, int) else tuple(v)
+    if len(p) != 2 or any(isinstance(e, bool) or not isinstance(e, int) for e in p):
+        raise ValueError(f"{name} must be an int or a pair of ints, got {v!r}")
+    if min(p) < least:
+        raise ValueError(f"{name} must be >= {least}, got {v!r}")
+    return p
+
+
+def _split_request(split_k, name: str = "split_k") -> int:
+    """the slice count the C ABI takes for `split_k`: an int >= 1 as it is, "auto" as 0 (the library's rule)"""
+    if isinstance(split_k, str):
+        if split_k != "auto":
+            raise ValueError(f'{name} must be an int >= 1 or "auto", got {split_k!r}')
+        return 0
+    if isinstance(split_k, bool) or not isinstance(split_k, int):
+        raise TypeError(f'{name} must be an int >= 1 or "auto", got {type(split_k).__name__}')
+    if not 1 <= split_k < 2 ** 31:
+        raise ValueError(f'{name} must be an int >= 1 or "auto", got {split_k}')
+    return split_k
+
+
+def _check_operand(name: str, codes: torch.Tensor, scales: torch.Tensor, fmt: str, what: str, least: int = 4, most=4,
+                   needs: str = "4 dimensions", source: str = "quantize_with_mx(..., return_codes=True)", axis: str = ""):
+    """one MX operand `<name>_codes` / `<name>_scales` in the format `fmt`.  The codes have the layout `what`: `least` to `most` (None:
+    any number of) dimensions, `needs` in the message; `source`: who hands such bytes out; `axis`: a note on the last axis.  It
+    runs six times per training step, so a message is put together only where it is raised"""
+    _mx_format(fmt)
+    if not (isinstance(codes, torch.Tensor) and isinstance(scales, torch.Tensor) and codes.dtype == scales.dtype == torch.uint8):
+        for kind, t in (("codes", codes), ("scales", scales)):      # which of the two, and why
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name}_{kind} must be a tensor, got {type(t).__name__}")
+            if t.dtype != torch.uint8:
+                raise TypeError(f"{name}_{kind} must be uint8 (the bytes {source} returns), got {t.dtype}")
+    if codes.dim() < least or most is not None and codes.dim() > most:
+        raise ValueError(f"{name}_codes needs {needs} {what}, got shape {tuple(codes.shape)}")
+    shape = tuple(codes.shape)
+    want = shape[:-1] + ((shape[-1] + MX_BLOCK - 1) // MX_BLOCK,)
+    if tuple(scales.shape) != want:
+        raise ValueError(f"{name}_scales has shape {tuple(scales.shape)}, expected {want}: one E8M0 byte per block of {MX_BLOCK} "
+                         f"along the last dimension{axis} of {name}_codes {shape}")
+    if scales.device != codes.device:
+        raise ValueError(f"{name}_codes is on {codes.device} but {name}_scales on {scales.device}")
+
+
+def _check_dtype(name: str, dtype):
+    if dtype not in _OUT_DTYPES:
+        raise TypeError(f"{name} must be one of {_OUT_DTYPES}, got {dtype}")
+
+
+def _check_bias_shape(bias, n: int):
+    if bias is not None and tuple(bias.shape) != (n,):
+        raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({n},)")
+
+
+def _check_bias(bias, n: int, first: str, device):
+    """the float32 bias `[n]` of a product whose first operand `first` (its name in the message) is on `device`"""
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
+            raise TypeError("bias must be a float32 tensor")
+        _check_bias_shape(bias, n)
+        if bias.device != device:
+            raise ValueError(f"{first} is on {device} but bias on {bias.device}")
+
+
+def _check_train_entry(x, weight, bias, fmts, grad_rounding: str, step, wgrad_split_k):
+    """what `mx_linear` and `mx_conv2d_train` check before the shapes"""
+    _split_request(wgrad_split_k, "wgrad_split_k")
+    for fmt in fmts:
+        _mx_format(fmt)
+    for name, t in (("x", x), ("weight", weight)) + ((("bias", bias),) if bias is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+        _check_dtype(name, t.dtype)
+        if t.device != x.device:
+            raise ValueError(f"x is on {x.device} but {name} on {t.device}")
+    _mx_check_rounding(grad_rounding, step, x)
+
+
+class _MXTrainMixin:
+    """what ``MXTrainLinear`` and ``MXTrainConv2d`` share, mixed in before the torch layer they derive from"""
+
+    def _init_mx(self, x_fmt: str, w_fmt: str, grad_fmt: str, grad_rounding: str, seed, wgrad_split_k):
+        for fmt in (x_fmt, w_fmt, grad_fmt):
+            _mx_format(fmt)
+        _mx_check_rounding(grad_rounding, None, self.weight)
+        _split_request(wgrad_split_k, "wgrad_split_k")
+        self.wgrad_split_k = wgrad_split_k
+        self.x_fmt, self.w_fmt, self.grad_fmt, self.grad_rounding = x_fmt, w_fmt, grad_fmt, grad_rounding
+        if grad_rounding == "stochastic":
+            self.sr_seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if seed is None else int(seed)
+            self.register_buffer("sr_step", torch.zeros(1, dtype=torch.int64, device=self.weight.device), persistent=False)
+
+    def _adopt(self, layer):
+        """take `layer`'s parameters (shared, not copied), count on its device and follow its mode; returns self"""
+        self.weight, self.bias = layer.weight, layer.bias
+        if self.grad_rounding == "stochastic":
+            self.sr_step = torch.zeros(1, dtype=torch.int64, device=layer.weight.device)
+        self.train(layer.training)
+        return self
+
+    def extra_repr(self) -> str:
+        sr = f", grad_rounding={self.grad_rounding!r}" if self.grad_rounding != "nearest" else ""
+        split = f", wgrad_split_k={self.wgrad_split_k!r}" if self.wgrad_split_k != "auto" else ""
+        return f"{super().extra_repr()}, x_fmt={self.x_fmt!r}, w_fmt={self.w_fmt!r}, grad_fmt={self.grad_fmt!r}{sr}{split}"
+
+    def _mx_input(self, x: torch.Tensor):
+        """(x in the autocast dtype, seed, step) for the functional form"""
+        dev = x.device.type
+        if torch.is_autocast_enabled(dev):
+            x = x.to(torch.get_autocast_dtype(dev))
+        seed, step = (self.sr_seed, self.sr_step) if self.grad_rounding == "stochastic" else (0, None)
+        return x, seed, step
+
+
+def _save_train_ctx(ctx, fmts, sr, wgrad_split_k, x: torch.Tensor, bias):
+    """both autograd functions' fields.  `step` of `sr` is advanced in place by the backward: an attribute, not a saved tensor"""
+    ctx.fmts, ctx.sr, ctx.wgrad_split_k = fmts, sr, wgrad_split_k
+    ctx.x_dtype = x.dtype
+    ctx.bias_dtype = None if bias is None else bias.dtype
+
+
+def _quantize_grad(ctx, quantize):
+    """the two forms of dy, which alone take `grad_rounding`, from `quantize(rounding, seed, step)`: row form (dx) on stream 0, column
+    form (dW) on stream 1.  After a stochastic one the counter moves on, on the stream: the next backward or replay draws new words"""
+    rounding, seed, step = ctx.sr
+    forms = quantize(rounding, seed, step)
+    if rounding == "stochastic" and step is not None:
+        step.add_(1)
+    return forms

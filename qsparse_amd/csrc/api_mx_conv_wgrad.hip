@@ -50,10 +50,8 @@ int wgrad_route(const qs_mx_conv2d_wgrad_args& a, WgradPlan* plan) {
     const int st = split_plan(a.Cout, N, Kp, a.split_k, kWgradSplitMax, &sp);
     if (st != QS_OK) return st;
     if (sp.slices > 1) {
-        if (!a.workspace) return QS_ERR_ARG;
-        if (!aligned16(a.workspace)) return QS_ERR_ALIGN;
-        if (a.workspace_bytes < sp.bytes) return QS_ERR_WORKSPACE;
-        if (tiles * sp.slices > kMaxGrid) return QS_ERR_ARG;
+        const int ws = split_workspace_status(sp, a.workspace, a.workspace_bytes, tiles);
+        if (ws != QS_OK) return ws;
     }
     if (plan) *plan = WgradPlan{N, cdiv(Kp, kMxgK), sp};
     return (a.B % 16 == 0 && aligned16(a.dyt_codes) && aligned16(a.xt_codes)) ? QS_MX_CONV_ROUTE_VEC : QS_MX_CONV_ROUTE_PLAIN;
@@ -64,12 +62,7 @@ int wgrad_route(const qs_mx_conv2d_wgrad_args& a, WgradPlan* plan) {
 extern "C" {
 
 int qs_mx_conv2d_wgrad_plan(int64_t M, int64_t N, int64_t K, int32_t split_k, int32_t* slices, uint64_t* workspace_bytes) {
-    SplitPlan p;
-    const int st = split_plan(M, N, K, split_k, kWgradSplitMax, &p);
-    if (st != QS_OK) return st;
-    if (slices) *slices = p.slices;
-    if (workspace_bytes) *workspace_bytes = p.bytes;
-    return QS_OK;
+    return split_plan_out(M, N, K, split_k, kWgradSplitMax, slices, workspace_bytes);
 }
 
 int qs_mx_conv2d_wgrad_route(const qs_mx_conv2d_wgrad_args* args) {
@@ -102,11 +95,7 @@ int qs_mx_conv2d_wgrad_v(const qs_mx_conv2d_wgrad_args* args) {
         return launch_status();
     });
     if (st != 0 || slices == 1) return st;
-    const int64_t groups_n = cdiv(N, 4), groups = M * groups_n;
-    const int64_t blocks = std::min<int64_t>(cdiv(groups, kBlock), kMaxGrid);       // the kernel strides over the rest
-    hipLaunchKernelGGL(mx_gemm_reduce_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s, ws, (const float*)nullptr, a.dw, a.ydt, M, N, slices,
-                       groups_n, ws_vec, y_vec);
-    return launch_status();
+    return mx_launch_reduce(ws, nullptr, a.dw, a.ydt, M, N, slices, s);
 }
 
 }  // extern "C"

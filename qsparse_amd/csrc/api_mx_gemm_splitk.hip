@@ -24,18 +24,15 @@ int splitk_route(const qs_mx_matmul_splitk_args& a, SplitPlan* p) {
     const int st = split_plan(a.M, a.N, a.K, a.split_k, kSplitMax, p);
     if (st != QS_OK) return st;
     if (p->slices == 1) return route;              // forwarded to qs_mx_matmul_v: no workspace
-    if (!a.workspace) return QS_ERR_ARG;
-    if (!aligned16(a.workspace)) return QS_ERR_ALIGN;
-    if (a.workspace_bytes < p->bytes) return QS_ERR_WORKSPACE;
-    const int64_t tiles = cdiv(a.M, kMxgTile) * cdiv(a.N, kMxgTile);       // <= kMaxGrid (qs_mx_matmul_route)
-    if (tiles * p->slices > kMaxGrid) return QS_ERR_ARG;
-    return route;
+    const int64_t tiles = mx_tiles(a.M) * mx_tiles(a.N);       // <= kMaxGrid (qs_mx_matmul_route)
+    const int ws = split_workspace_status(*p, a.workspace, a.workspace_bytes, tiles);
+    return ws != QS_OK ? ws : route;
 }
 
 // the two launches: the partial products of every slice, then their ordered sum
 int launch_split(const qs_mx_matmul_splitk_args& a, const SplitPlan& p, int route) {
-    const int tiles_n = (int)cdiv(a.N, kMxgTile);
-    const int tiles = (int)cdiv(a.M, kMxgTile) * tiles_n;
+    const int tiles_n = (int)mx_tiles(a.N);
+    const int tiles = (int)mx_tiles(a.M) * tiles_n;
     const int64_t grid = (int64_t)tiles * p.slices;
     const int ws_vec = a.N % 4 == 0;               // every row of every slice then keeps the workspace's 16-byte alignment
     float* ws = (float*)a.workspace;
@@ -47,11 +44,7 @@ int launch_split(const qs_mx_matmul_splitk_args& a, const SplitPlan& p, int rout
         return launch_status();
     });
     if (st != 0) return st;
-    const int64_t groups_n = cdiv(a.N, 4), groups = a.M * groups_n;
-    const int64_t blocks = std::min<int64_t>(cdiv(groups, kBlock), kMaxGrid);       // the kernel strides over the rest
-    hipLaunchKernelGGL(mx_gemm_reduce_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s, ws, a.bias, a.y, a.ydt, a.M, a.N, (int)p.slices,
-                       groups_n, ws_vec, mx_y_vec(a.y, a.ydt, a.N));
-    return launch_status();
+    return mx_launch_reduce(ws, a.bias, a.y, a.ydt, a.M, a.N, p.slices, s);
 }
 
 }  // namespace
@@ -59,12 +52,7 @@ int launch_split(const qs_mx_matmul_splitk_args& a, const SplitPlan& p, int rout
 extern "C" {
 
 int qs_mx_matmul_splitk_plan(int64_t M, int64_t N, int64_t K, int32_t split_k, int32_t* slices, uint64_t* workspace_bytes) {
-    SplitPlan p;
-    const int st = split_plan(M, N, K, split_k, kSplitMax, &p);
-    if (st != QS_OK) return st;
-    if (slices) *slices = p.slices;
-    if (workspace_bytes) *workspace_bytes = p.bytes;
-    return QS_OK;
+    return split_plan_out(M, N, K, split_k, kSplitMax, slices, workspace_bytes);
 }
 
 int qs_mx_matmul_splitk_route(const qs_mx_matmul_splitk_args* args) {

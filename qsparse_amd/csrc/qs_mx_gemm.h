@@ -257,6 +257,8 @@ __device__ __forceinline__ void mx_epilogue(const f32x4 (&acc)[4][4], const floa
 // mx_gemm_kernel and mx_gemm_partial_kernel (qs_mx_gemm_splitk.h) state the fetch, the loop and the epilogue themselves, statement
 // for statement what mx_load16 / mx_scale / mx_tile_loop / mx_epilogue say: built on those, with a row-major operand of their own,
 // they gave the same bits from fewer registers but were 3-17 % slower where K is short or the tiles are few.
+// Outside the loop a call stands only where the assembly stays the written-out text's: mx_zero in mx_gemm_kernel.
+// Its epilogue, and the zeroing and the store of mx_gemm_partial_kernel, stay written out: each call reschedules all 50 instantiations.
 // the four 16-code pieces this thread stages per step: piece q = thread + 256 i is piece (q & 7) of tile row (q >> 3)
 template <bool VEC>
 __device__ __forceinline__ void mxg_fetch(u32x4 (&reg)[4], const uint8_t* __restrict__ codes, int64_t row0, int64_t rows, int64_t K,
@@ -310,10 +312,7 @@ __global__ __launch_bounds__(kMxgThreads) void mx_gemm_kernel(const uint8_t* __r
     const int64_t steps = (K + kMxgK - 1) / kMxgK;
 
     f32x4 acc[4][4];                                                // [i: 16 n][j: 16 m]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    mx_zero(acc);
 
     u32x4 ra[4], rb[4];
     uint32_t sa[4], sb[4], sa_next[4], sb_next[4];

@@ -10,8 +10,10 @@
 //                           consecutive n per thread, stored by the epilogue's mx_store4.
 // Every (m < M, n < N) of every slice is written by exactly one lane of the first launch, so the second reads nothing stale and the
 // workspace needs no clearing.  Nothing past slices * M * N floats of the workspace is touched.
+// The launch of the reduction (mx_launch_reduce) stands next to its kernel, so this header, alone among the kernel headers, includes
+// the host helpers (qs_mx_host.h: cdiv, mx_y_vec; qs_host.h: kMaxGrid, launch_status) and not only qs_mx_gemm.h.
 #pragma once
-#include "qs_mx_gemm.h"
+#include "qs_mx_host.h"
 
 namespace qs {
 
@@ -133,6 +135,16 @@ static __global__ __launch_bounds__(kBlock) void mx_gemm_reduce_kernel(const flo
         }
         mx_store4(y, ydt, e, v, n, N, y_vec);
     }
+}
+
+// host: the second launch of a split product, y [M, N] = round_once(sum of the `slices` planes of ws (+ bias)); ws_vec: every row of
+// every slice keeps the workspace's 16-byte alignment
+static inline int mx_launch_reduce(const float* ws, const float* bias, void* y, int ydt, int64_t M, int64_t N, int slices, hipStream_t stream) {
+    const int64_t groups_n = cdiv(N, 4), groups = M * groups_n;
+    const int64_t blocks = std::min<int64_t>(cdiv(groups, kBlock), kMaxGrid);       // the kernel strides over the rest
+    hipLaunchKernelGGL(mx_gemm_reduce_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, ws, bias, y, ydt, M, N, slices, groups_n,
+                       (int)(N % 4 == 0), mx_y_vec(y, ydt, N));
+    return launch_status();
 }
 
 }  // namespace qs

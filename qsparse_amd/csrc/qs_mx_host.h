@@ -1,6 +1,8 @@
 // Host-side helpers shared by the five translation units of the products on MX codes (api_mx_gemm.hip, api_mx_gemm_splitk.hip,
-// api_mx_conv.hip, api_mx_conv_t.hip, api_mx_conv_wgrad.hip): the dispatch over the 5 x 5 format pairs, the store rule of y, the
-// descriptor of a product forwarded to qs_mx_matmul_v, the slicing of a split product, and the checks the two convolutions share.
+// api_mx_conv.hip, api_mx_conv_t.hip, api_mx_conv_wgrad.hip): the dispatch over the 5 x 5 format pairs, the tile count and the store
+// rule of y, the descriptor of a product forwarded to qs_mx_matmul_v, what the two split products (mx_matmul's split-K, the
+// convolution's weight gradient) share -- the slicing, the body of their `_plan` exports, the checks of their workspace; the launch of
+// their reduction is mx_launch_reduce of qs_mx_gemm_splitk.h, next to its kernel -- and the checks the two convolutions share.
 // Internal linkage, as qs_host.h.
 #pragma once
 #include "qs_host.h"
@@ -56,7 +58,7 @@ constexpr int64_t kSplitStepsPerSlice = 8; // a slice keeps at least this many K
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 inline int64_t auto_split(int64_t M, int64_t N, int64_t K, int64_t cap) {
-    const int64_t tiles = cdiv(M, kMxgTile) * cdiv(N, kMxgTile), steps = cdiv(K, kMxgK);
+    const int64_t tiles = mx_tiles(M) * mx_tiles(N), steps = cdiv(K, kMxgK);
     if (steps < kSplitMinSteps || tiles >= kSplitFullTiles) return 1;
     return std::max<int64_t>(1, std::min({kSplitGroups / tiles, steps / kSplitStepsPerSlice, cap}));
 }
@@ -82,6 +84,25 @@ inline int split_plan(int64_t M, int64_t N, int64_t K, int32_t split_k, int64_t 
         if ((uint64_t)(M * N) > UINT64_MAX / 4 / (uint64_t)p->slices) return QS_ERR_ARG;
         p->bytes = (uint64_t)(M * N) * 4u * (uint64_t)p->slices;
     }
+    return QS_OK;
+}
+
+// the body of qs_mx_matmul_splitk_plan and qs_mx_conv2d_wgrad_plan, which differ in `cap`
+inline int split_plan_out(int64_t M, int64_t N, int64_t K, int32_t split_k, int64_t cap, int32_t* slices, uint64_t* workspace_bytes) {
+    SplitPlan p;
+    const int st = split_plan(M, N, K, split_k, cap, &p);
+    if (st != QS_OK) return st;
+    if (slices) *slices = p.slices;
+    if (workspace_bytes) *workspace_bytes = p.bytes;
+    return QS_OK;
+}
+
+// the workspace of a product that `p` splits (p.slices > 1) over `tiles` output tiles: QS_OK or the error, in this order
+inline int split_workspace_status(const SplitPlan& p, const void* workspace, uint64_t workspace_bytes, int64_t tiles) {
+    if (!workspace) return QS_ERR_ARG;
+    if (!aligned16(workspace)) return QS_ERR_ALIGN;
+    if (workspace_bytes < p.bytes) return QS_ERR_WORKSPACE;
+    if (tiles * p.slices > kMaxGrid) return QS_ERR_ARG;
     return QS_OK;
 }
 

@@ -8,55 +8,27 @@ block_dim=1))`` layer exports the weight's.  On the GPU ``mx_conv2d`` is one HIP
 on the block-scaled MFMA of gfx950 that gathers the windows while it stages them -- no im2col matrix is ever written -- and
 accumulates in float32; on the CPU it evaluates the definition in float64.  ``MXConv2d`` is an inference layer; training through
 the three products of a convolution (forward, input gradient, weight gradient) is ``mx_conv2d_train`` / ``MXTrainConv2d`` of
-``qsparse_amd/mx_conv_train.py``."""
+``qsparse_amd/mx_conv_train.py``.  The operand, ``out_dtype`` and bias checks are ``_mx_common.py``'s, shared with ``mx_matmul``."""
+from functools import partial
 from typing import Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from qsparse_amd import _hip
-from qsparse_amd.mx_gemm import _OUT_DTYPES
-from qsparse_amd.quantize import MX_BLOCK, MX_FORMATS, MXQuantizer, _mx_format, mx_dequantize, quantize_with_mx
+from qsparse_amd import _hip, _mx_common
+from qsparse_amd._mx_common import _check_bias, _check_bias_shape, _check_dtype, _pair
+from qsparse_amd.quantize import MX_FORMATS, MXQuantizer, _mx_format, mx_dequantize, quantize_with_mx
 
 
-def _pair(name: str, v, least: int):
-    """`v` as a pair of ints, each >= `least`"""
-    if isinstance(v, str):
-        raise ValueError(f"{name} must be an int or a pair of ints, got the string {v!r} (padding modes such as 'same' are not supported: "
-                         "give the padding as numbers)")
-    if isinstance(v, bool) or not isinstance(v, (int, tuple, list)):
-        raise TypeError(f"{name} must be an int or a pair of ints, got {type(v).__name__}")
-    p = (v, v) if isinstance(v, int) else tuple(v)
-    if len(p) != 2 or any(isinstance(e, bool) or not isinstance(e, int) for e in p):
-        raise ValueError(f"{name} must be an int or a pair of ints, got {v!r}")
-    if min(p) < least:
-        raise ValueError(f"{name} must be >= {least}, got {v!r}")
-    return p
-
-
-def _check_operand(name: str, what: str, codes: torch.Tensor, scales: torch.Tensor, fmt: str):
-    _mx_format(fmt)
-    for label, t in ((f"{name}_codes", codes), (f"{name}_scales", scales)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{label} must be a tensor, got {type(t).__name__}")
-        if t.dtype != torch.uint8:
-            raise TypeError(f"{label} must be uint8 (the bytes quantize_with_mx(..., return_codes=True) returns), got {t.dtype}")
-    if codes.dim() != 4:
-        raise ValueError(f"{name}_codes needs 4 dimensions {what}, got shape {tuple(codes.shape)}")
-    C = codes.shape[-1]
-    want = tuple(codes.shape[:-1]) + ((C + MX_BLOCK - 1) // MX_BLOCK,)
-    if tuple(scales.shape) != want:
-        raise ValueError(f"{name}_scales has shape {tuple(scales.shape)}, expected {want}: one E8M0 byte per block of {MX_BLOCK} "
-                         f"along the last dimension (the channels) of {name}_codes {tuple(codes.shape)}")
-    if scales.device != codes.device:
-        raise ValueError(f"{name}_codes is on {codes.device} but {name}_scales on {scales.device}")
+# a channels-last operand with blocks along the channels
+_check_operand = partial(_mx_common._check_operand, axis=" (the channels)")
 
 
 def _check_product(fn: str, x_codes, x_scales, x_fmt: str, w_codes, w_scales, w_fmt: str, bias, out_dtype):
     """the operand, C, device, out_dtype and bias checks of the public product `fn` (the name in its messages)"""
-    _check_operand("x", "[B, H, W, C]", x_codes, x_scales, x_fmt)
-    _check_operand("w", "[Cout, KH, KW, C]", w_codes, w_scales, w_fmt)
+    _check_operand("x", x_codes, x_scales, x_fmt, "[B, H, W, C]")
+    _check_operand("w", w_codes, w_scales, w_fmt, "[Cout, KH, KW, C]")
     (B, H, W, C), (Cout, KH, KW, Cw) = x_codes.shape, w_codes.shape
     if Cw != C:
         raise ValueError(f"x_codes {tuple(x_codes.shape)} and w_codes {tuple(w_codes.shape)} disagree on C (their last dimensions)")
@@ -64,15 +36,8 @@ def _check_product(fn: str, x_codes, x_scales, x_fmt: str, w_codes, w_scales, w_
         raise ValueError(f"{fn} needs C, H, W, KH, KW >= 1, got x_codes {tuple(x_codes.shape)}, w_codes {tuple(w_codes.shape)}")
     if w_codes.device != x_codes.device:
         raise ValueError(f"x_codes is on {x_codes.device} but w_codes on {w_codes.device}")
-    if out_dtype not in _OUT_DTYPES:
-        raise TypeError(f"out_dtype must be one of {_OUT_DTYPES}, got {out_dtype}")
-    if bias is not None:
-        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
-            raise TypeError("bias must be a float32 tensor")
-        if tuple(bias.shape) != (Cout,):
-            raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({Cout},)")
-        if bias.device != x_codes.device:
-            raise ValueError(f"x_codes is on {x_codes.device} but bias on {bias.device}")
+    _check_dtype("out_dtype", out_dtype)
+    _check_bias(bias, Cout, "x_codes", x_codes.device)
 
 
 def mx_conv2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_codes: torch.Tensor, w_scales: torch.Tensor, w_fmt: str,
@@ -123,11 +88,9 @@ class _MXConvBase(nn.Module):
                  out_dtype: torch.dtype):
         super().__init__()
         _mx_format(act_fmt)
-        _check_operand("w", "[Cout, KH, KW, C]", weight_codes, weight_scales, weight_fmt)
-        if out_dtype not in _OUT_DTYPES:
-            raise TypeError(f"out_dtype must be one of {_OUT_DTYPES}, got {out_dtype}")
-        if bias is not None and tuple(bias.shape) != (weight_codes.shape[0],):
-            raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({weight_codes.shape[0]},)")
+        _check_operand("w", weight_codes, weight_scales, weight_fmt, "[Cout, KH, KW, C]")
+        _check_dtype("out_dtype", out_dtype)
+        _check_bias_shape(bias, weight_codes.shape[0])
         self.weight_fmt, self.act_fmt, self.out_dtype = weight_fmt, act_fmt, out_dtype
         self.stride, self.padding, self.dilation = _pair("stride", stride, 1), _pair("padding", padding, 0), _pair("dilation", dilation, 1)
         self.out_channels, self.in_channels = weight_codes.shape[0], weight_codes.shape[3]

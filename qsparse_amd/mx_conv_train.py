@@ -10,7 +10,9 @@ all taps -- blocks along the output pixels would map to other pixels of ``x`` fo
 input-gradient (``mx_conv2d_input_grad``) operand, since a block of 32 along the flat ``H W C`` axis is then a block along ``C``.
 On the GPU the product is one HIP kernel (``qs_mx_conv2d_wgrad_v``): an implicit GEMM on the block-scaled MFMA of gfx950, split
 along the contraction into slices that are added in a fixed order; on the CPU the definition is evaluated in float64.  A batch
-below 32 pads its block with zero codes: ``B = 8`` spends 3/4 of the products on zeros."""
+below 32 pads its block with zero codes: ``B = 8`` spends 3/4 of the products on zeros.  What the layer and its autograd function
+share with ``MXTrainLinear`` -- options, counter, ``repr``, the quantization of ``dy`` -- is ``_mx_common.py``'s."""
+from functools import partial
 from typing import Optional
 
 import torch
@@ -18,29 +20,17 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from qsparse_amd import _hip
-from qsparse_amd.mx_conv import MXConv2d, _pair, mx_conv2d
+from qsparse_amd import _hip, _mx_common
+from qsparse_amd._mx_common import (_check_bias_shape, _check_dtype, _check_train_entry, _MXTrainMixin, _pair,
+                                    _quantize_grad, _save_train_ctx, _split_request)
+from qsparse_amd.mx_conv import MXConv2d, mx_conv2d
 from qsparse_amd.mx_conv_transpose import mx_conv2d_input_grad
-from qsparse_amd.mx_gemm import _OUT_DTYPES, _split_request, mx_quantize_2way
-from qsparse_amd.quantize import MX_BLOCK, MX_FORMATS, _mx_check_rounding, _mx_format, mx_dequantize, quantize_with_mx
+from qsparse_amd.mx_gemm import mx_quantize_2way
+from qsparse_amd.quantize import MX_BLOCK, MX_FORMATS, mx_dequantize, quantize_with_mx
 
 
-def _check_batch_operand(name: str, what: str, codes: torch.Tensor, scales: torch.Tensor, fmt: str):
-    _mx_format(fmt)
-    for label, t in ((f"{name}_codes", codes), (f"{name}_scales", scales)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{label} must be a tensor, got {type(t).__name__}")
-        if t.dtype != torch.uint8:
-            raise TypeError(f"{label} must be uint8 (the bytes mx_quantize_2way returns), got {t.dtype}")
-    if codes.dim() != 4:
-        raise ValueError(f"{name}_codes needs 4 dimensions {what}, got shape {tuple(codes.shape)}")
-    B = codes.shape[-1]
-    want = tuple(codes.shape[:-1]) + ((B + MX_BLOCK - 1) // MX_BLOCK,)
-    if tuple(scales.shape) != want:
-        raise ValueError(f"{name}_scales has shape {tuple(scales.shape)}, expected {want}: one E8M0 byte per block of {MX_BLOCK} "
-                         f"along the last dimension (the batch) of {name}_codes {tuple(codes.shape)}")
-    if scales.device != codes.device:
-        raise ValueError(f"{name}_codes is on {codes.device} but {name}_scales on {scales.device}")
+# an operand with blocks along the batch, its last axis
+_check_batch_operand = partial(_mx_common._check_operand, source="mx_quantize_2way", axis=" (the batch)")
 
 
 def mx_conv2d_weight_grad(dyt_codes: torch.Tensor, dyt_scales: torch.Tensor, dy_fmt: str, xt_codes: torch.Tensor, xt_scales: torch.Tensor,
@@ -69,8 +59,8 @@ def mx_conv2d_weight_grad(dyt_codes: torch.Tensor, dyt_scales: torch.Tensor, dy_
     splits.  CPU tensors evaluate the expression above in float64 and round once; ``split_k`` is checked and has no order to cut.
     A batch below 32 pads its block with zero codes and spends the rest of the block's products on them."""
     request = _split_request(split_k)
-    _check_batch_operand("dyt", "[OH, OW, Cout, B]", dyt_codes, dyt_scales, dy_fmt)
-    _check_batch_operand("xt", "[H, W, C, B]", xt_codes, xt_scales, x_fmt)
+    _check_batch_operand("dyt", dyt_codes, dyt_scales, dy_fmt, "[OH, OW, Cout, B]")
+    _check_batch_operand("xt", xt_codes, xt_scales, x_fmt, "[H, W, C, B]")
     (OH, OW, Cout, B), (H, W, C, Bx) = dyt_codes.shape, xt_codes.shape
     if Bx != B:
         raise ValueError(f"dyt_codes {tuple(dyt_codes.shape)} and xt_codes {tuple(xt_codes.shape)} disagree on B (their last dimensions)")
@@ -78,8 +68,7 @@ def mx_conv2d_weight_grad(dyt_codes: torch.Tensor, dyt_scales: torch.Tensor, dy_
         raise ValueError(f"mx_conv2d_weight_grad needs B, H, W >= 1, got dyt_codes {tuple(dyt_codes.shape)}, xt_codes {tuple(xt_codes.shape)}")
     if xt_codes.device != dyt_codes.device:
         raise ValueError(f"dyt_codes is on {dyt_codes.device} but xt_codes on {xt_codes.device}")
-    if out_dtype not in _OUT_DTYPES:
-        raise TypeError(f"out_dtype must be one of {_OUT_DTYPES}, got {out_dtype}")
+    _check_dtype("out_dtype", out_dtype)
     KH, KW = _pair("kernel_size", kernel_size, 1)
     stride, padding, dilation = _pair("stride", stride, 1), _pair("padding", padding, 0), _pair("dilation", dilation, 1)
     want = tuple(_hip.mx_conv_out_size(n, k, s, p, d) for n, k, s, p, d in zip((H, W), (KH, KW), stride, padding, dilation))
@@ -150,12 +139,8 @@ class _MXConv2dFunction(torch.autograd.Function):
         # the weight itself (autograd's version counter guards it), and x as its batch-blocked codes: 1 + 1/32 bytes per element
         ctx.save_for_backward(weight, x_col, x_cs)
         ctx.geometry = (stride, padding, dilation)
-        ctx.fmts = (x_fmt, w_fmt, grad_fmt)
-        # `step` is advanced in place by the backward: an attribute, not a saved tensor (no version check, nothing to differentiate)
-        ctx.sr = (grad_rounding, seed, step)
-        ctx.wgrad_split_k = wgrad_split_k
-        ctx.x_size, ctx.x_dtype = tuple(x.shape[2:]), x.dtype
-        ctx.bias_dtype = None if bias is None else bias.dtype
+        _save_train_ctx(ctx, (x_fmt, w_fmt, grad_fmt), (grad_rounding, seed, step), wgrad_split_k, x, bias)
+        ctx.x_size = tuple(x.shape[2:])
         return y.permute(0, 3, 1, 2)
 
     @staticmethod
@@ -168,12 +153,8 @@ class _MXConv2dFunction(torch.autograd.Function):
         dyl = _channels_last_view(dy)
         dx = dw = db = None
         if need_dx or need_dw:
-            # the two forms of dy alone take `grad_rounding` (blocks along Cout: stream 0, for dx; along B: stream 1, for dW); after
-            # a stochastic one the counter moves on, on the stream: the next backward -- or the next replay of this one -- draws new words
-            rounding, seed, step = ctx.sr
-            g_codes, g_scales, g_col, g_cs = _row_and_col(dyl, grad_fmt, need_dx, need_dw, rounding, seed, step)
-            if rounding == "stochastic" and step is not None:
-                step.add_(1)
+            # blocks along Cout for dx, along B for dW
+            g_codes, g_scales, g_col, g_cs = _quantize_grad(ctx, lambda *sr: _row_and_col(dyl, grad_fmt, need_dx, need_dw, *sr))
         if need_dx:
             wt_codes, wt_scales = _weight_rows(weight.permute(1, 2, 3, 0), w_fmt)
             dx = mx_conv2d_input_grad(g_codes, g_scales, grad_fmt, wt_codes, wt_scales, w_fmt, ctx.x_size, stride, padding, dilation,
@@ -215,32 +196,21 @@ def mx_conv2d_train(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.
 
     ``wgrad_split_k`` (an int ``>= 1`` or ``"auto"``) is ``mx_conv2d_weight_grad``'s ``split_k``; ``y`` and ``dx`` are untouched by it.
     A batch below 32 pads the weight gradient's blocks with zero codes (``B = 8``: 3/4 of its products)."""
-    _split_request(wgrad_split_k, "wgrad_split_k")
-    for fmt in (x_fmt, w_fmt, grad_fmt):
-        _mx_format(fmt)
-    for name, t in (("x", x), ("weight", weight)) + ((("bias", bias),) if bias is not None else ()):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
-        if t.dtype not in _OUT_DTYPES:
-            raise TypeError(f"{name} must be one of {_OUT_DTYPES}, got {t.dtype}")
-        if t.device != x.device:
-            raise ValueError(f"x is on {x.device} but {name} on {t.device}")
-    _mx_check_rounding(grad_rounding, step, x)
+    _check_train_entry(x, weight, bias, (x_fmt, w_fmt, grad_fmt), grad_rounding, step, wgrad_split_k)
     if weight.dim() != 4:
         raise ValueError(f"weight must be [Cout, C, KH, KW], got shape {tuple(weight.shape)}")
     if x.dim() != 4 or x.shape[1] != weight.shape[1]:
         raise ValueError(f"x {tuple(x.shape)} must be [B, C, H, W] with the C of weight {tuple(weight.shape)}")
     if x.shape[0] < 1 or min(weight.shape) < 1:
         raise ValueError(f"mx_conv2d_train needs B, Cout, C, KH, KW >= 1, got x {tuple(x.shape)}, weight {tuple(weight.shape)}")
-    if bias is not None and tuple(bias.shape) != (weight.shape[0],):
-        raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({weight.shape[0]},)")
+    _check_bias_shape(bias, weight.shape[0])
     stride, padding, dilation = _pair("stride", stride, 1), _pair("padding", padding, 0), _pair("dilation", dilation, 1)
     need_col = torch.is_grad_enabled() and weight.requires_grad
     return _MXConv2dFunction.apply(x, weight, bias, stride, padding, dilation, x_fmt, w_fmt, grad_fmt, need_col, grad_rounding, seed, step,
                                    wgrad_split_k)
 
 
-class MXTrainConv2d(nn.Conv2d):
+class MXTrainConv2d(_MXTrainMixin, nn.Conv2d):
     """Drop-in ``nn.Conv2d`` (``groups == 1``, zero padding given as numbers) that trains through MX products: float ``weight`` /
     ``bias`` parameters (``nn.Conv2d``'s own ``state_dict``), ``forward`` is ``mx_conv2d_train`` in the formats ``x_fmt`` / ``w_fmt`` /
     ``grad_fmt``.  Under ``torch.autocast`` the input is cast to the autocast dtype, as ``nn.Conv2d``'s would be, and the output has
@@ -265,15 +235,7 @@ class MXTrainConv2d(nn.Conv2d):
             raise ValueError(f"MXTrainConv2d needs the padding as numbers, the layer has padding={padding!r}")
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, padding_mode, device=device,
                          dtype=dtype)
-        for fmt in (x_fmt, w_fmt, grad_fmt):
-            _mx_format(fmt)
-        _mx_check_rounding(grad_rounding, None, self.weight)
-        _split_request(wgrad_split_k, "wgrad_split_k")
-        self.wgrad_split_k = wgrad_split_k
-        self.x_fmt, self.w_fmt, self.grad_fmt, self.grad_rounding = x_fmt, w_fmt, grad_fmt, grad_rounding
-        if grad_rounding == "stochastic":
-            self.sr_seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if seed is None else int(seed)
-            self.register_buffer("sr_step", torch.zeros(1, dtype=torch.int64, device=self.weight.device), persistent=False)
+        self._init_mx(x_fmt, w_fmt, grad_fmt, grad_rounding, seed, wgrad_split_k)
 
     @classmethod
     def from_conv(cls, layer: nn.Conv2d, x_fmt: str = "mxfp8_e4m3", w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2",
@@ -281,25 +243,12 @@ class MXTrainConv2d(nn.Conv2d):
         """a layer on ``layer``'s own parameters (shared, not copied)"""
         if not isinstance(layer, nn.Conv2d):
             raise TypeError(f"MXTrainConv2d.from_conv needs an nn.Conv2d, got {type(layer).__name__}")
-        new = cls(layer.in_channels, layer.out_channels, layer.kernel_size, layer.stride, layer.padding, layer.dilation, layer.groups,
-                  layer.bias is not None, layer.padding_mode, device="meta", x_fmt=x_fmt, w_fmt=w_fmt, grad_fmt=grad_fmt,
-                  grad_rounding=grad_rounding, seed=seed, wgrad_split_k=wgrad_split_k)
-        new.weight, new.bias = layer.weight, layer.bias
-        if grad_rounding == "stochastic":
-            new.sr_step = torch.zeros(1, dtype=torch.int64, device=layer.weight.device)
-        new.train(layer.training)
-        return new
-
-    def extra_repr(self) -> str:
-        sr = f", grad_rounding={self.grad_rounding!r}" if self.grad_rounding != "nearest" else ""
-        split = f", wgrad_split_k={self.wgrad_split_k!r}" if self.wgrad_split_k != "auto" else ""
-        return f"{super().extra_repr()}, x_fmt={self.x_fmt!r}, w_fmt={self.w_fmt!r}, grad_fmt={self.grad_fmt!r}{sr}{split}"
+        return cls(layer.in_channels, layer.out_channels, layer.kernel_size, layer.stride, layer.padding, layer.dilation, layer.groups,
+                   layer.bias is not None, layer.padding_mode, device="meta", x_fmt=x_fmt, w_fmt=w_fmt, grad_fmt=grad_fmt,
+                   grad_rounding=grad_rounding, seed=seed, wgrad_split_k=wgrad_split_k)._adopt(layer)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        dev = x.device.type
-        if torch.is_autocast_enabled(dev):
-            x = x.to(torch.get_autocast_dtype(dev))
-        seed, step = (self.sr_seed, self.sr_step) if self.grad_rounding == "stochastic" else (0, None)
+        x, seed, step = self._mx_input(x)
         return mx_conv2d_train(x, self.weight, self.bias, self.stride, self.padding, self.dilation, self.x_fmt, self.w_fmt, self.grad_fmt,
                                self.grad_rounding, seed, step, self.wgrad_split_k)
 

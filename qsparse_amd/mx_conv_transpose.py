@@ -77,8 +77,8 @@ def mx_conv2d_input_grad(dy_codes: torch.Tensor, dy_scales: torch.Tensor, dy_fmt
     ceil(Cout / 32)]`` the weight ``[Cout, Cin, KH, KW].permute(1, 2, 3, 0)`` with blocks along ``Cout``, ``input_size = (H, W)`` the
     extent of the convolution's input.  It is ``mx_conv_transpose2d`` with the output padding that ``input_size`` implies -- the rows
     and columns of ``x`` that no window reaches get a zero gradient -- and has no kernel of its own."""
-    _check_operand("dy", "[B, OH, OW, Cout]", dy_codes, dy_scales, dy_fmt)
-    _check_operand("wt", "[Cin, KH, KW, Cout]", wt_codes, wt_scales, w_fmt)
+    _check_operand("dy", dy_codes, dy_scales, dy_fmt, "[B, OH, OW, Cout]")
+    _check_operand("wt", wt_codes, wt_scales, w_fmt, "[Cin, KH, KW, Cout]")
     H, W = _pair("input_size", input_size, 1)
     stride, padding, dilation = _pair("stride", stride, 1), _pair("padding", padding, 0), _pair("dilation", dilation, 1)
     (KH, KW), out_pad = wt_codes.shape[1:3], []

@@ -8,50 +8,25 @@ accumulation), on the CPU by evaluating the definition in float64.  ``MXLinear``
 
 Training through the product: ``mx_linear`` / ``MXTrainLinear`` run all three matrix products of a linear layer's step -- forward,
 input gradient, weight gradient -- through ``mx_matmul``; their operands come from ``mx_quantize_2way``, which reads a tensor once
-and writes its codes with blocks along the rows and, transposed, with blocks along the columns (``qs_mx_quant2_v``)."""
+and writes its codes with blocks along the rows and, transposed, with blocks along the columns (``qs_mx_quant2_v``).  The argument
+checks and the layer's options, counter and ``repr`` are ``_mx_common.py``'s, shared with the convolutions."""
+from functools import partial
 from typing import Optional
 
 import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from qsparse_amd import _hip
-from qsparse_amd.quantize import (MX_BLOCK, MX_FORMATS, MXQuantizer, _mx_aten, _mx_check_rounding, _mx_format, _mx_sr_words,
-                                  mx_dequantize, quantize_with_mx)
-
-_OUT_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
-
-
-def _check_operand(name: str, codes: torch.Tensor, scales: torch.Tensor, fmt: str):
-    _mx_format(fmt)
-    for what, t in ((f"{name}_codes", codes), (f"{name}_scales", scales)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{what} must be a tensor, got {type(t).__name__}")
-        if t.dtype != torch.uint8:
-            raise TypeError(f"{what} must be uint8 (the bytes quantize_with_mx(..., return_codes=True) returns), got {t.dtype}")
-    if codes.dim() < 2 and name == "b" or codes.dim() < 1:
-        raise ValueError(f"{name}_codes needs {'2 dimensions [N, K]' if name == 'b' else 'at least one dimension [..., K]'}, "
-                         f"got shape {tuple(codes.shape)}")
-    K = codes.shape[-1]
-    want = tuple(codes.shape[:-1]) + ((K + MX_BLOCK - 1) // MX_BLOCK,)
-    if tuple(scales.shape) != want:
-        raise ValueError(f"{name}_scales has shape {tuple(scales.shape)}, expected {want}: one E8M0 byte per block of {MX_BLOCK} "
-                         f"along the last dimension of {name}_codes {tuple(codes.shape)}")
-    if scales.device != codes.device:
-        raise ValueError(f"{name}_codes is on {codes.device} but {name}_scales on {scales.device}")
+from qsparse_amd import _hip, _mx_common
+from qsparse_amd._mx_common import (_OUT_DTYPES, _check_bias, _check_bias_shape, _check_dtype, _check_train_entry, _MXTrainMixin,
+                                    _quantize_grad, _save_train_ctx, _split_request)
+from qsparse_amd.quantize import (MX_FORMATS, MXQuantizer, _mx_aten, _mx_check_rounding, _mx_format, _mx_sr_words, mx_dequantize,
+                                  quantize_with_mx)
 
 
-def _split_request(split_k, name: str = "split_k") -> int:
-    """the slice count the C ABI takes for `split_k`: an int >= 1 as it is, "auto" as 0 (the library's rule)"""
-    if isinstance(split_k, str):
-        if split_k != "auto":
-            raise ValueError(f'{name} must be an int >= 1 or "auto", got {split_k!r}')
-        return 0
-    if isinstance(split_k, bool) or not isinstance(split_k, int):
-        raise TypeError(f'{name} must be an int >= 1 or "auto", got {type(split_k).__name__}')
-    if not 1 <= split_k < 2 ** 31:
-        raise ValueError(f'{name} must be an int >= 1 or "auto", got {split_k}')
-    return split_k
+# an operand of `mx_matmul`: a is [..., K], b has at least the two dimensions of [N, K]
+_check_a = partial(_mx_common._check_operand, what="[..., K]", least=1, most=None, needs="at least one dimension")
+_check_b = partial(_mx_common._check_operand, what="[N, K]", least=2, most=None, needs="2 dimensions")
 
 
 def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
@@ -75,8 +50,8 @@ def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes
     (1 whenever ``ceil(K / 128) < 32`` or the output has 256 tiles of 128 x 128 or more).  A request that leaves one slice is the
     unsplit call.  The CPU path checks the argument and evaluates the float64 definition, which has no order to cut."""
     request = _split_request(split_k)
-    _check_operand("a", a_codes, a_scales, a_fmt)
-    _check_operand("b", b_codes, b_scales, b_fmt)
+    _check_a("a", a_codes, a_scales, a_fmt)
+    _check_b("b", b_codes, b_scales, b_fmt)
     if b_codes.dim() != 2:
         raise ValueError(f"b_codes must be [N, K], got shape {tuple(b_codes.shape)}")
     K, N = a_codes.shape[-1], b_codes.shape[0]
@@ -86,15 +61,8 @@ def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes
         raise ValueError("mx_matmul needs K >= 1")
     if b_codes.device != a_codes.device:
         raise ValueError(f"a_codes is on {a_codes.device} but b_codes on {b_codes.device}")
-    if out_dtype not in _OUT_DTYPES:
-        raise TypeError(f"out_dtype must be one of {_OUT_DTYPES}, got {out_dtype}")
-    if bias is not None:
-        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
-            raise TypeError("bias must be a float32 tensor")
-        if tuple(bias.shape) != (N,):
-            raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({N},)")
-        if bias.device != a_codes.device:
-            raise ValueError(f"a_codes is on {a_codes.device} but bias on {bias.device}")
+    _check_dtype("out_dtype", out_dtype)
+    _check_bias(bias, N, "a_codes", a_codes.device)
     lead = tuple(a_codes.shape[:-1])
     a2, sa2 = a_codes.reshape(-1, K), a_scales.reshape(-1, a_scales.shape[-1])
     if a_codes.is_cuda:
@@ -122,11 +90,10 @@ class MXLinear(nn.Module):
                  act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32):
         super().__init__()
         _mx_format(act_fmt)
-        _check_operand("b", weight_codes, weight_scales, weight_fmt)
+        _check_b("b", weight_codes, weight_scales, weight_fmt)
         if weight_codes.dim() != 2:
             raise ValueError(f"weight_codes must be [N, K], got shape {tuple(weight_codes.shape)}")
-        if bias is not None and tuple(bias.shape) != (weight_codes.shape[0],):
-            raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({weight_codes.shape[0]},)")
+        _check_bias_shape(bias, weight_codes.shape[0])
         self.weight_fmt, self.act_fmt, self.out_dtype = weight_fmt, act_fmt, out_dtype
         self.out_features, self.in_features = weight_codes.shape
         self.register_buffer("weight_codes", weight_codes.detach().clone().contiguous())
@@ -195,8 +162,7 @@ def mx_quantize_2way(x: torch.Tensor, row_fmt: Optional[str] = None, col_fmt: Op
         raise TypeError(f"x must be a tensor, got {type(x).__name__}")
     if x.dim() != 2:
         raise ValueError(f"mx_quantize_2way needs a 2-d tensor [R, C], got shape {tuple(x.shape)}")
-    if x.dtype not in _OUT_DTYPES:
-        raise TypeError(f"x must be one of {_OUT_DTYPES}, got {x.dtype}")
+    _check_dtype("x", x.dtype)
     if row_fmt is None and col_fmt is None:
         raise ValueError("mx_quantize_2way needs row_fmt, col_fmt or both")
     for fmt in (row_fmt, col_fmt):
@@ -231,12 +197,8 @@ class _MXLinearFunction(torch.autograd.Function):
         y = mx_matmul(x_row, x_rs, x_fmt, w_row, w_rs, w_fmt, b32, x.dtype)
         # the weight itself (autograd's version counter guards it), and x as its transposed codes: 1 + 1/32 bytes per element
         ctx.save_for_backward(weight, x_col, x_cs)
-        ctx.fmts = (x_fmt, w_fmt, grad_fmt)
-        # `step` is advanced in place by the backward: an attribute, not a saved tensor (no version check, nothing to differentiate)
-        ctx.sr = (grad_rounding, seed, step)
-        ctx.wgrad_split_k = wgrad_split_k
-        ctx.x_shape, ctx.x_dtype = x.shape, x.dtype
-        ctx.bias_dtype = None if bias is None else bias.dtype
+        _save_train_ctx(ctx, (x_fmt, w_fmt, grad_fmt), (grad_rounding, seed, step), wgrad_split_k, x, bias)
+        ctx.x_shape = x.shape
         return y.reshape(x.shape[:-1] + (N,))
 
     @staticmethod
@@ -249,13 +211,8 @@ class _MXLinearFunction(torch.autograd.Function):
         dy2 = dy.reshape(-1, N).contiguous()
         dx = dw = db = None
         if need_dx or need_dw:
-            # the two forms of dy alone take `grad_rounding` (row pair: stream 0, for dx; col pair: stream 1, for dW); after a
-            # stochastic one the counter moves on, on the stream: the next backward -- or the next replay of this one -- draws new words
-            rounding, seed, step = ctx.sr
-            g_row, g_rs, g_col, g_cs = mx_quantize_2way(dy2, grad_fmt if need_dx else None, grad_fmt if need_dw else None,
-                                                        rounding, seed, step)
-            if rounding == "stochastic" and step is not None:
-                step.add_(1)
+            g_row, g_rs, g_col, g_cs = _quantize_grad(ctx, lambda *sr: mx_quantize_2way(dy2, grad_fmt if need_dx else None,
+                                                                                         grad_fmt if need_dw else None, *sr))
         if need_dx:
             _, _, w_col, w_cs = mx_quantize_2way(weight, None, w_fmt)
             dx = mx_matmul(g_row, g_rs, grad_fmt, w_col, w_cs, w_fmt, None, ctx.x_dtype).reshape(ctx.x_shape)
@@ -297,30 +254,19 @@ def mx_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
     ``"auto"`` lets the library split that product when its shape leaves most of the GPU idle: ``dW`` then differs from
     ``wgrad_split_k=1`` in the order of its float32 additions only (deterministically: same bits on every run), and only for shapes
     the rule splits -- none with fewer than 3969 rows ``M``, none whose weight has 256 tiles of 128 x 128 or more."""
-    _split_request(wgrad_split_k, "wgrad_split_k")
-    for name, fmt in (("x_fmt", x_fmt), ("w_fmt", w_fmt), ("grad_fmt", grad_fmt)):
-        _mx_format(fmt)
-    _mx_check_rounding(grad_rounding, step, x)
-    for name, t in (("x", x), ("weight", weight)) + ((("bias", bias),) if bias is not None else ()):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
-        if t.dtype not in _OUT_DTYPES:
-            raise TypeError(f"{name} must be one of {_OUT_DTYPES}, got {t.dtype}")
-        if t.device != x.device:
-            raise ValueError(f"x is on {x.device} but {name} on {t.device}")
+    _check_train_entry(x, weight, bias, (x_fmt, w_fmt, grad_fmt), grad_rounding, step, wgrad_split_k)
     if weight.dim() != 2:
         raise ValueError(f"weight must be [N, K], got shape {tuple(weight.shape)}")
     if x.dim() < 1 or x.shape[-1] != weight.shape[1]:
         raise ValueError(f"x {tuple(x.shape)} and weight {tuple(weight.shape)} disagree on K (their last dimensions)")
     if weight.shape[1] < 1:
         raise ValueError("mx_linear needs K >= 1")
-    if bias is not None and tuple(bias.shape) != (weight.shape[0],):
-        raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({weight.shape[0]},)")
+    _check_bias_shape(bias, weight.shape[0])
     need_col = torch.is_grad_enabled() and weight.requires_grad
     return _MXLinearFunction.apply(x, weight, bias, x_fmt, w_fmt, grad_fmt, need_col, grad_rounding, seed, step, wgrad_split_k)
 
 
-class MXTrainLinear(nn.Linear):
+class MXTrainLinear(_MXTrainMixin, nn.Linear):
     """Drop-in ``nn.Linear`` that trains through MX matrix products: float ``weight`` / ``bias`` parameters (``nn.Linear``'s own
     ``state_dict``), ``forward`` is ``mx_linear`` in the formats ``x_fmt`` / ``w_fmt`` / ``grad_fmt``.  Under ``torch.autocast``
     the input is cast to the autocast dtype, as ``nn.Linear``'s would be, and the output has that dtype.
@@ -337,15 +283,7 @@ class MXTrainLinear(nn.Linear):
                  w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2", grad_rounding: str = "nearest", seed: Optional[int] = None,
                  wgrad_split_k="auto"):
         super().__init__(in_features, out_features, bias=bias, device=device, dtype=dtype)
-        for fmt in (x_fmt, w_fmt, grad_fmt):
-            _mx_format(fmt)
-        _mx_check_rounding(grad_rounding, None, self.weight)
-        _split_request(wgrad_split_k, "wgrad_split_k")
-        self.wgrad_split_k = wgrad_split_k
-        self.x_fmt, self.w_fmt, self.grad_fmt, self.grad_rounding = x_fmt, w_fmt, grad_fmt, grad_rounding
-        if grad_rounding == "stochastic":
-            self.sr_seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if seed is None else int(seed)
-            self.register_buffer("sr_step", torch.zeros(1, dtype=torch.int64, device=self.weight.device), persistent=False)
+        self._init_mx(x_fmt, w_fmt, grad_fmt, grad_rounding, seed, wgrad_split_k)
 
     @classmethod
     def from_linear(cls, layer: nn.Linear, x_fmt: str = "mxfp8_e4m3", w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2",
@@ -353,24 +291,11 @@ class MXTrainLinear(nn.Linear):
         """a layer on ``layer``'s own parameters (shared, not copied)"""
         if not isinstance(layer, nn.Linear):
             raise TypeError(f"MXTrainLinear.from_linear needs an nn.Linear, got {type(layer).__name__}")
-        new = cls(layer.in_features, layer.out_features, bias=layer.bias is not None, device="meta", x_fmt=x_fmt, w_fmt=w_fmt,
-                  grad_fmt=grad_fmt, grad_rounding=grad_rounding, seed=seed, wgrad_split_k=wgrad_split_k)
-        new.weight, new.bias = layer.weight, layer.bias
-        if grad_rounding == "stochastic":
-            new.sr_step = torch.zeros(1, dtype=torch.int64, device=layer.weight.device)
-        new.train(layer.training)
-        return new
-
-    def extra_repr(self) -> str:
-        sr = f", grad_rounding={self.grad_rounding!r}" if self.grad_rounding != "nearest" else ""
-        split = f", wgrad_split_k={self.wgrad_split_k!r}" if self.wgrad_split_k != "auto" else ""
-        return f"{super().extra_repr()}, x_fmt={self.x_fmt!r}, w_fmt={self.w_fmt!r}, grad_fmt={self.grad_fmt!r}{sr}{split}"
+        return cls(layer.in_features, layer.out_features, bias=layer.bias is not None, device="meta", x_fmt=x_fmt, w_fmt=w_fmt,
+                   grad_fmt=grad_fmt, grad_rounding=grad_rounding, seed=seed, wgrad_split_k=wgrad_split_k)._adopt(layer)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        dev = x.device.type
-        if torch.is_autocast_enabled(dev):
-            x = x.to(torch.get_autocast_dtype(dev))
-        seed, step = (self.sr_seed, self.sr_step) if self.grad_rounding == "stochastic" else (0, None)
+        x, seed, step = self._mx_input(x)
         return mx_linear(x, self.weight, self.bias, self.x_fmt, self.w_fmt, self.grad_fmt, self.grad_rounding, seed, step,
                          self.wgrad_split_k)
 

@@ -2,27 +2,18 @@
 are carved out of larger allocations whose margins hold a byte pattern; after the launch the margins must be intact and the
 bodies equal the CPU reference.  Partial last blocks and unaligned bases are where these kernels would write too far."""
 import ctypes
+from functools import partial
 
 import pytest
 import torch
 
 import mx_ref as R
+from mx_guard import guarded, intact
 from qsparse_amd import _hip
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-PAD = 256          # bytes on either side
-PATTERN = 0xA5
-
-
-def _guarded(nbytes, offset=0):
-    """(raw, body): `body` = nbytes bytes starting PAD + offset bytes into a pattern-filled allocation"""
-    raw = torch.full((nbytes + 2 * PAD + offset,), PATTERN, dtype=torch.uint8, device=DEV)
-    return raw, raw[PAD + offset:PAD + offset + nbytes]
-
-
-def _intact(raw, nbytes, offset=0):
-    return bool((raw[:PAD + offset] == PATTERN).all()) and bool((raw[PAD + offset + nbytes:] == PATTERN).all())
+_guarded, _intact = partial(guarded, pad=256), partial(intact, pad=256)          # bytes on either side
 
 
 CASES = [  # shape, block dim, byte offset of the bases (in elements of the tensor's dtype), expected route

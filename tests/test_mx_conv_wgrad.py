@@ -327,6 +327,10 @@ def test_entry_points_validate_without_a_gpu(tmp_path):
     assert route(split_k=5, workspace=0x6008, workspace_bytes=need) == -3
     assert route(split_k=5, workspace=0x6000, workspace_bytes=need - 1) == -4
     assert route(split_k=5, workspace=0x6000, workspace_bytes=need) == _hip.MX_CONV_ROUTE_VEC
+    # their precedence: NULL, then the alignment, then the size, then the grid of tiles x slices
+    assert route(split_k=5, workspace_bytes=need - 1) == -2 and route(split_k=5, workspace=0x6008, workspace_bytes=need - 1) == -3
+    big = dict(split_k=5, Cout=2 ** 21, C=2 ** 20, workspace=0x6000)      # 2^14 x 9 2^13 tiles fit a grid, five times as many do not
+    assert route(**big, workspace_bytes=5 * 2 ** 21 * 9 * 2 ** 20 * 4 - 1) == -4 and route(**big, workspace_bytes=5 * 2 ** 21 * 9 * 2 ** 20 * 4) == -2
     assert route(split_k=0) == -2 and route(split_k=0, workspace=0x6000, workspace_bytes=need) == _hip.MX_CONV_ROUTE_VEC      # auto: <= 5 slices
     assert route(split_k=1, workspace=0x6008) == _hip.MX_CONV_ROUTE_VEC   # not looked at when S' == 1
     # 64-bit overflow of a product of extents; more work-groups than a grid holds

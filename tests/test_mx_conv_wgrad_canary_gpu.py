@@ -11,22 +11,11 @@ import torch
 
 import mx_conv_wgrad_ref as R
 import mx_gemm_ref as G
+from mx_guard import PAD, PATTERN, guarded as _guarded, intact as _intact
 from qsparse_amd import _hip
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-PAD = 512          # bytes on either side
-PATTERN = 0xA5
-
-
-def _guarded(nbytes, offset=0):
-    """(raw, body): `body` = nbytes bytes starting PAD + offset bytes into a pattern-filled allocation"""
-    raw = torch.full((nbytes + 2 * PAD + offset,), PATTERN, dtype=torch.uint8, device=DEV)
-    return raw, raw[PAD + offset:PAD + offset + nbytes]
-
-
-def _intact(raw, nbytes, offset=0):
-    return bool((raw[:PAD + offset] == PATTERN).all()) and bool((raw[PAD + offset + nbytes:] == PATTERN).all())
 
 
 CASES = [  # B, H, W, C, Cout, (KH, KW), stride, padding, dilation, byte offset of the code bases, split_k, expected route

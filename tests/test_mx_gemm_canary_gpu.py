@@ -9,22 +9,11 @@ import pytest
 import torch
 
 import mx_gemm_ref as G
+from mx_guard import guarded as _guarded, intact as _intact
 from qsparse_amd import _hip
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-PAD = 512          # bytes on either side
-PATTERN = 0xA5
-
-
-def _guarded(nbytes, offset=0):
-    """(raw, body): `body` = nbytes bytes starting PAD + offset bytes into a pattern-filled allocation"""
-    raw = torch.full((nbytes + 2 * PAD + offset,), PATTERN, dtype=torch.uint8, device=DEV)
-    return raw, raw[PAD + offset:PAD + offset + nbytes]
-
-
-def _intact(raw, nbytes, offset=0):
-    return bool((raw[:PAD + offset] == PATTERN).all()) and bool((raw[PAD + offset + nbytes:] == PATTERN).all())
 
 
 CASES = [  # M, N, K, byte offset of the code bases, expected route

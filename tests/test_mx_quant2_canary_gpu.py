@@ -8,23 +8,12 @@ import pytest
 import torch
 
 import mx_ref as R
+from mx_guard import guarded as _guarded, intact as _intact
 from qsparse_amd import _hip
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-PAD = 512          # bytes on either side
-PATTERN = 0xA5
 VEC, PLAIN = _hip.MX_Q2_ROUTE_TILE_VEC, _hip.MX_Q2_ROUTE_TILE_PLAIN
-
-
-def _guarded(nbytes, offset=0):
-    """(raw, body): `body` = nbytes bytes starting PAD + offset bytes into a pattern-filled allocation"""
-    raw = torch.full((nbytes + 2 * PAD + offset,), PATTERN, dtype=torch.uint8, device=DEV)
-    return raw, raw[PAD + offset:PAD + offset + nbytes]
-
-
-def _intact(raw, nbytes, offset=0):
-    return bool((raw[:PAD + offset] == PATTERN).all()) and bool((raw[PAD + offset + nbytes:] == PATTERN).all())
 
 
 CASES = [  # R, C, element offset of x's base, byte offset of the output bases, which pairs, expected route

@@ -121,6 +121,11 @@ def test_entry_points_are_declared_bound_and_validate_without_a_gpu(tmp_path):
     assert v(workspace_bytes=3 * 130 * 67 * 4 - 1) == ERR_WORKSPACE
     assert v(workspace=(1 << 20) + 4) == ERR_ALIGN and v(workspace=(1 << 20) + 8) == ERR_ALIGN
     assert v(workspace=None) == ERR_ARG and route(workspace=None) == ERR_ARG        # S' = 3: refused, nothing enqueued
+    # their precedence: NULL, then the alignment, then the size, then the grid of tiles x slices
+    assert route(workspace=None, workspace_bytes=0) == ERR_ARG and route(workspace=(1 << 20) + 8, workspace_bytes=0) == ERR_ALIGN
+    big = dict(M=46340 * 128, N=46340 * 128, split_k=2)                             # 46340^2 tiles fit a grid, twice as many do not
+    assert route(**big, workspace_bytes=2 * (46340 * 128) ** 2 * 4 - 1) == ERR_WORKSPACE
+    assert route(**big, workspace_bytes=2 * (46340 * 128) ** 2 * 4) == ERR_ARG and route(**{**big, "split_k": 1}) == _hip.MX_GEMM_ROUTE_PLAIN
     assert route(workspace=None, workspace_bytes=0, K=100) == _hip.MX_GEMM_ROUTE_PLAIN      # S' = 1: no workspace needed
     assert route(workspace=None, workspace_bytes=0, split_k=1) == _hip.MX_GEMM_ROUTE_PLAIN
     assert route(split_k=8, workspace_bytes=8 * 130 * 67 * 4) == _hip.MX_GEMM_ROUTE_PLAIN and v(split_k=8) == ERR_WORKSPACE

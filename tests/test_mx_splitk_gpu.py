@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import mx_gemm_ref as G
+from mx_guard import guarded as _guarded, intact as _intact
 import qsparse_amd as qs
 from qsparse_amd import _hip
 from qsparse_amd.mx_gemm import mx_linear, mx_matmul, mx_quantize_2way
@@ -29,7 +30,6 @@ CASES = [(128, 128, 256, 2, 0),
          (16, 16, 130, 8, 0),          # S' = 2 < S
          (1, 1, 16, 4, 0),             # S' = 1: the unsplit call
          (64, 64, 256, 2, 1)]          # code bases offset by 1 byte (PLAIN)
-PAD, PATTERN = 512, 0xA5
 
 
 @pytest.fixture(autouse=True)
@@ -175,15 +175,6 @@ def test_workspace_contents_do_not_matter_and_hold_the_partials():
         # every partial the reduction read was written by the first launch: the planes ARE the unsplit products of the slices
         planes = ws.view(torch.float32).view(n, M, N)
         assert all(torch.equal(planes[s].view(torch.int32), ps[s].view(torch.int32)) for s in range(n)), (M, N, K, S)
-
-
-def _guarded(nbytes, offset=0):
-    raw = torch.full((nbytes + 2 * PAD + offset,), PATTERN, dtype=torch.uint8, device=DEV)
-    return raw, raw[PAD + offset:PAD + offset + nbytes]
-
-
-def _intact(raw, nbytes, offset=0):
-    return bool((raw[:PAD + offset] == PATTERN).all()) and bool((raw[PAD + offset + nbytes:] == PATTERN).all())
 
 
 @pytest.mark.parametrize("fa,fb", PAIRS)

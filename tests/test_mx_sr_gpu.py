@@ -9,6 +9,7 @@ import torch
 
 import mx_ref as R
 import mx_sr_ref as S
+from mx_guard import PATTERN, guarded as _guarded, intact as _intact
 from qsparse_amd import _hip
 from qsparse_amd.mx_gemm import MXTrainLinear, mx_linear, mx_matmul, mx_quantize_2way
 from qsparse_amd.quantize import quantize_with_mx
@@ -92,18 +93,6 @@ def test_index_base_across_a_carry_of_the_counter_against_the_reference(fmt):
     assert R.same(rc, c) and R.same(rs, s)
     _, c, s = S.reference(x.t().contiguous(), other, -1, torch.float32, 21, 9, 1, BASE)
     assert R.same(cc, c) and R.same(cs, s)
-
-
-PAD, PATTERN = 512, 0xA5
-
-
-def _guarded(nbytes, offset=0):
-    raw = torch.full((nbytes + 2 * PAD + offset,), PATTERN, dtype=torch.uint8, device=DEV)
-    return raw, raw[PAD + offset:PAD + offset + nbytes]
-
-
-def _intact(raw, nbytes, offset=0):
-    return bool((raw[:PAD + offset] == PATTERN).all()) and bool((raw[PAD + offset + nbytes:] == PATTERN).all())
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

@@ -1203,6 +1203,73 @@ int qs_mx_conv2d_wgrad_route(const qs_mx_conv2d_wgrad_args* args);
  * qs_mx_matmul_splitk_plan. */
 int qs_mx_conv2d_wgrad_plan(int64_t M, int64_t N, int64_t K, int32_t split_k, int32_t* slices, uint64_t* workspace_bytes);
 
+/* ---- MX products that write MX codes (fused quantizing epilogue) ---------------------------------------------------------------
+ * Added without raising QS_ABI_VERSION (28): symbols are only added.
+ *
+ * The matrix product and the convolution above with the NEXT layer's quantizer in their epilogue: instead of y they write the MX
+ * codes and E8M0 scale bytes of y, with blocks of 32 along the last axis of y (N / Cout: the next product's K / C).  Definition
+ * (normative).  With v[m, n] the float32 value qs_mx_matmul_v / qs_mx_conv2d_v produce for the same operands with ydt = QS_F32
+ * (float32 accumulation in their order, bias added in float32, no further rounding; m runs over the rows of y seen as [M, N]):
+ *   u = v                                 act == QS_MX_ACT_NONE
+ *   u = v > 0 ? v : (v != v ? v : +0)     act == QS_MX_ACT_RELU: NaN stays NaN, everything else that is not positive becomes +0
+ *   out_codes [M, N], out_scales [M, ceil(N / 32)] = the codes and scales qs_mx_quant_fwd_v writes for u seen as [M, N, 1] in the
+ *   format out_format with QS_MX_ROUND_NEAREST
+ * bit for bit: the last block of a row is short when N % 32 != 0; a block that holds NaN / Inf gets the byte 0xFF and codes 0, an
+ * all-zero block the byte 0.  No y exists in memory; one launch, no workspace, no atomics.  Stochastic rounding of the output is
+ * not offered.
+ *   - Every check of qs_mx_matmul_v / qs_mx_conv2d_v that does not concern y applies, with the same precedence; with the
+ *     QS_ERR_ARG checks of the operands come: out_codes or out_scales NULL, out_format outside enum qs_mx_format, act outside
+ *     QS_MX_ACT_*.  bias: aligned to 4 bytes (QS_ERR_ALIGN).  out_codes, out_scales: any address (N % 4 == 0 with out_codes 4-byte
+ *     aligned stores four codes at once, anything else single bytes).  After the size checks: out_codes sharing a byte with a_codes
+ *     / b_codes (x_codes / w_codes) is QS_ERR_ARG -- a work-group writes its tile while others still read the operands.
+ *   - M == 0 or N == 0 (B == 0 or Cout == 0): nothing is enqueued, 0 is returned.
+ *   - Nothing outside out_codes [M, N] and out_scales [M, ceil(N / 32)] is written.
+ *   - Routes: those of qs_mx_matmul_route / qs_mx_conv2d_route, by the same conditions on the inputs.  QS_MX_CONV_ROUTE_GEMM forwards
+ *     to qs_mx_matmul_q_v on the same bytes.  There is no split-K form. */
+#define QS_MX_ACT_NONE 0
+#define QS_MX_ACT_RELU 1
+typedef struct qs_mx_matmul_q_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_matmul_q_args) as the caller compiled it */
+    int32_t a_format, b_format;      /* the operands of qs_mx_matmul_args, with their meaning ... */
+    const uint8_t* a_codes;
+    const uint8_t* a_scales;
+    const uint8_t* b_codes;
+    const uint8_t* b_scales;
+    const float* bias;
+    int32_t out_format;              /* ... and: enum qs_mx_format of the output */
+    int32_t act;                     /* QS_MX_ACT_* */
+    uint8_t* out_codes;              /* [M, N], one code per byte */
+    uint8_t* out_scales;             /* [M, ceil(N / 32)] E8M0 bytes */
+    int64_t M, N, K;
+    qs_stream_t stream;
+} qs_mx_matmul_q_args;
+int qs_mx_matmul_q_v(const qs_mx_matmul_q_args* args);
+/* the kernel qs_mx_matmul_q_v launches for these operands, nothing enqueued: QS_MX_GEMM_ROUTE_*, 0 for an empty product, or the
+ * QS_ERR_* the call would return */
+int qs_mx_matmul_q_route(const qs_mx_matmul_q_args* args);
+
+typedef struct qs_mx_conv2d_q_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_conv2d_q_args) as the caller compiled it */
+    int32_t x_format, w_format;      /* the operands of qs_mx_conv2d_args, with their meaning ... */
+    const uint8_t* x_codes;
+    const uint8_t* x_scales;
+    const uint8_t* w_codes;
+    const uint8_t* w_scales;
+    const float* bias;
+    int32_t out_format;              /* ... and: enum qs_mx_format of the output */
+    int32_t act;                     /* QS_MX_ACT_* */
+    uint8_t* out_codes;              /* [B, OH, OW, Cout], one code per byte */
+    uint8_t* out_scales;             /* [B, OH, OW, ceil(Cout / 32)] E8M0 bytes */
+    int64_t B, H, W, C, Cout;
+    int32_t KH, KW;
+    int32_t stride_h, stride_w, pad_h, pad_w, dil_h, dil_w;
+    qs_stream_t stream;
+} qs_mx_conv2d_q_args;
+int qs_mx_conv2d_q_v(const qs_mx_conv2d_q_args* args);
+/* the route qs_mx_conv2d_q_v takes for these operands, nothing enqueued: QS_MX_CONV_ROUTE_*, 0 for an empty problem, or the QS_ERR_*
+ * the call would return */
+int qs_mx_conv2d_q_route(const qs_mx_conv2d_q_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

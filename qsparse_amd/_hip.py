@@ -113,6 +113,10 @@ SIGNATURES = {
     "qs_mx_conv2d_wgrad_v": (c_int, [_P]),
     "qs_mx_conv2d_wgrad_route": (c_int, [_P]),
     "qs_mx_conv2d_wgrad_plan": (c_int, [_L, _L, _L, c_int32, _P, _P]),
+    "qs_mx_matmul_q_v": (c_int, [_P]),
+    "qs_mx_matmul_q_route": (c_int, [_P]),
+    "qs_mx_conv2d_q_v": (c_int, [_P]),
+    "qs_mx_conv2d_q_route": (c_int, [_P]),
 }
 
 
@@ -237,6 +241,22 @@ class MxConv2dWgradArgs(ctypes.Structure):
                 ("OH", c_int64), ("OW", c_int64), ("KH", c_int32), ("KW", c_int32), ("stride_h", c_int32), ("stride_w", c_int32),
                 ("pad_h", c_int32), ("pad_w", c_int32), ("dil_h", c_int32), ("dil_w", c_int32), ("stream", c_void_p),
                 ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64)]
+
+
+def _codes_out_fields(fields):
+    """the fields of a codes-out descriptor from its float sibling's: `y`, `ydt` give way to the output format, act and two pointers"""
+    i = [n for n, _ in fields].index("y")
+    return fields[:i] + [("out_format", c_int32), ("act", c_int32), ("out_codes", c_void_p), ("out_scales", c_void_p)] + fields[i + 2:]
+
+
+class MxMatmulQArgs(ctypes.Structure):
+    """`qs_mx_matmul_q_args` of include/qsparse_hip.h"""
+    _fields_ = _codes_out_fields(MxMatmulArgs._fields_)
+
+
+class MxConv2dQArgs(ctypes.Structure):
+    """`qs_mx_conv2d_q_args` of include/qsparse_hip.h"""
+    _fields_ = _codes_out_fields(MxConv2dArgs._fields_)
 
 
 class MultiRow(ctypes.Structure):
@@ -951,6 +971,54 @@ def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes
     return y
 
 
+MX_ACTS = (None, "relu")      # QS_MX_ACT_*, in order
+mx_gemm_q_last_route = None   # the QS_MX_GEMM_ROUTE_* of the last `mx_matmul_q` launch (None: an empty product), for tests and tools
+
+
+def _mx_codes_out(a, rows_shape, N: int, out_fmt: str, act, device, out):
+    """fill the output fields of a codes-out descriptor `a`; returns (codes uint8 [*rows_shape, N], scales uint8 [*rows_shape,
+    ceil(N / 32)]): new tensors, or `out` -- a pair of contiguous uint8 tensors of those sizes, as the guard-byte tests carve them"""
+    nb = (N + MX_BLOCK - 1) // MX_BLOCK
+    if out is None:
+        codes = torch.empty(tuple(rows_shape) + (N,), dtype=torch.uint8, device=device)
+        scales = torch.empty(tuple(rows_shape) + (nb,), dtype=torch.uint8, device=device)
+    else:
+        codes, scales = out
+        rows = 1
+        for d in rows_shape:
+            rows *= d
+        assert codes.dtype == scales.dtype == torch.uint8 and codes.is_contiguous() and scales.is_contiguous()
+        assert codes.numel() == rows * N and scales.numel() == rows * nb, "out: codes [rows, N] and scales [rows, ceil(N / 32)] bytes"
+    a.out_format, a.act = MX_FORMATS.index(out_fmt), MX_ACTS.index(act)
+    a.out_codes, a.out_scales = _ptr(codes), _ptr(scales)
+    return codes, scales
+
+
+def mx_matmul_q(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
+                bias: Optional[torch.Tensor], out_fmt: str, act=None, out=None):
+    """the MX codes [M, N] and scales [M, ceil(N / 32)] in `out_fmt` of act(A . B^T + bias) (qs_mx_matmul_q_v): operands as
+    `mx_matmul`'s, `act` None or "relu".  ONE launch, no float y."""
+    global mx_gemm_q_last_route
+    lib = load()
+    (M, K), N = a_codes.shape, b_codes.shape[0]
+    a = MxMatmulQArgs()
+    codes, scales = _mx_codes_out(a, (M,), N, out_fmt, act, a_codes.device, out)
+    mx_gemm_q_last_route = None
+    if M and N:
+        a.struct_size = ctypes.sizeof(a)
+        a.a_format, a.b_format = MX_FORMATS.index(a_fmt), MX_FORMATS.index(b_fmt)
+        a.a_codes, a.a_scales, a.b_codes, a.b_scales = _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales)
+        a.bias = _ptr(bias)
+        a.M, a.N, a.K = M, N, K
+        a.stream = _stream(a_codes)
+        route = lib.qs_mx_matmul_q_route(ctypes.byref(a))
+        with _timed(f"mx_matmul_q[{route}]", a_codes, a_scales, b_codes, b_scales, bias, codes, scales):
+            st = lib.qs_mx_matmul_q_v(ctypes.byref(a))
+        _check(st, "qs_mx_matmul_q_v")
+        mx_gemm_q_last_route = route
+    return codes, scales
+
+
 MX_CONV_ROUTE_GEMM, MX_CONV_ROUTE_VEC, MX_CONV_ROUTE_PLAIN = 1, 2, 3
 mx_conv_last_route = None     # the QS_MX_CONV_ROUTE_* of the last `mx_conv2d` launch (None: an empty problem), for tests and tools
 
@@ -993,6 +1061,36 @@ def mx_conv2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_codes
     y, mx_conv_last_route = _mx_conv_launch("mx_conv2d", MxConv2dArgs(), x_codes, x_scales, x_fmt, w_codes, w_scales, w_fmt, bias, size,
                                             stride, padding, dilation, out_dtype)
     return y
+
+
+mx_conv_q_last_route = None   # likewise of the last `mx_conv2d_q` launch
+
+
+def mx_conv2d_q(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_codes: torch.Tensor, w_scales: torch.Tensor, w_fmt: str,
+                bias: Optional[torch.Tensor], stride, padding, dilation, out_fmt: str, act=None, out=None):
+    """the MX codes [B, OH, OW, Cout] and scales [B, OH, OW, ceil(Cout / 32)] in `out_fmt` of act(conv2d(x, w) + bias)
+    (qs_mx_conv2d_q_v): operands as `mx_conv2d`'s, `act` None or "relu".  ONE launch, no float y and no im2col matrix."""
+    global mx_conv_q_last_route
+    lib = load()
+    (B, H, W, C), (Cout, KH, KW, _) = x_codes.shape, w_codes.shape
+    size = [mx_conv_out_size(n, k, s, p, d) for n, k, s, p, d in zip((H, W), (KH, KW), stride, padding, dilation)]
+    a = MxConv2dQArgs()
+    codes, scales = _mx_codes_out(a, (B,) + tuple(size), Cout, out_fmt, act, x_codes.device, out)
+    mx_conv_q_last_route = None
+    if B and Cout:
+        a.struct_size = ctypes.sizeof(a)
+        a.x_format, a.w_format = MX_FORMATS.index(x_fmt), MX_FORMATS.index(w_fmt)
+        a.x_codes, a.x_scales, a.w_codes, a.w_scales = _ptr(x_codes), _ptr(x_scales), _ptr(w_codes), _ptr(w_scales)
+        a.bias = _ptr(bias)
+        a.B, a.H, a.W, a.C, a.Cout, a.KH, a.KW = B, H, W, C, Cout, KH, KW
+        (a.stride_h, a.stride_w), (a.pad_h, a.pad_w), (a.dil_h, a.dil_w) = stride, padding, dilation
+        a.stream = _stream(x_codes)
+        route = lib.qs_mx_conv2d_q_route(ctypes.byref(a))
+        with _timed(f"mx_conv2d_q[{route}]", x_codes, x_scales, w_codes, w_scales, bias, codes, scales):
+            st = lib.qs_mx_conv2d_q_v(ctypes.byref(a))
+        _check(st, "qs_mx_conv2d_q_v")
+        mx_conv_q_last_route = route
+    return codes, scales
 
 
 mx_conv_transpose_last_route = None   # likewise of the last `mx_conv_transpose2d` launch

@@ -10,12 +10,7 @@ namespace {
 int mx_conv_route(const qs_mx_conv2d_args& a, MxConvPlan* plan) {
     const int st = mx_conv_check_args(a, true);
     if (st != QS_OK) return st;
-    const int64_t HP = a.H + 2 * (int64_t)a.pad_h, WP = a.W + 2 * (int64_t)a.pad_w;
-    if (HP > INT32_MAX || WP > INT32_MAX) return QS_ERR_ARG;
-    const int64_t EH = (int64_t)a.dil_h * (a.KH - 1) + 1, EW = (int64_t)a.dil_w * (a.KW - 1) + 1;      // extent of the dilated kernel
-    if (EH > HP || EW > WP) return QS_ERR_ARG;                                                        // OH < 1 or OW < 1
-    const int route = mx_conv_plan(a, (HP - EH) / a.stride_h + 1, (WP - EW) / a.stride_w + 1, plan);
-    return route > 0 && mx_conv_is_gemm(a) ? QS_MX_CONV_ROUTE_GEMM : route;
+    return mx_conv2d_route_of(a, plan);
 }
 
 }  // namespace

@@ -7,15 +7,11 @@ namespace {
 
 // the checks of qs_mx_matmul_v and the kernel it launches for these operands: QS_MX_GEMM_ROUTE_*, 0 for an empty product, QS_ERR_*
 int mx_gemm_route(const qs_mx_matmul_args& a) {
-    if (!a.a_codes || !a.a_scales || !a.b_codes || !a.b_scales || !a.y) return QS_ERR_ARG;
-    if (!mx_format_ok(a.a_format) || !mx_format_ok(a.b_format)) return QS_ERR_ARG;
-    if (a.M < 0 || a.N < 0 || a.K < 0) return QS_ERR_ARG;
+    if (!a.y || mx_gemm_check_operands(a) != QS_OK) return QS_ERR_ARG;
     if (!dt_ok(a.ydt)) return QS_ERR_DTYPE;
     if ((((uintptr_t)a.y) & (dt_size(a.ydt) - 1)) != 0 || (a.bias && (((uintptr_t)a.bias) & 3u) != 0)) return QS_ERR_ALIGN;
     if (a.M == 0 || a.N == 0) return 0;
-    if (a.K == 0 || a.M > INT64_MAX / a.N || a.M > INT64_MAX / a.K || a.N > INT64_MAX / a.K) return QS_ERR_ARG;
-    if (mx_tiles(a.M) * mx_tiles(a.N) > kMaxGrid) return QS_ERR_ARG;
-    return (a.K % 16 == 0 && aligned16(a.a_codes) && aligned16(a.b_codes)) ? QS_MX_GEMM_ROUTE_VEC : QS_MX_GEMM_ROUTE_PLAIN;
+    return mx_gemm_sized_route(a);
 }
 
 }  // namespace

@@ -28,6 +28,7 @@
 // is read or written.
 #pragma once
 #include "qs_common.h"
+#include "qs_mx.h"
 
 namespace qs {
 
@@ -250,6 +251,81 @@ __device__ __forceinline__ void mx_epilogue(const f32x4 (&acc)[4][4], const floa
             for (int r = 0; r < 4; ++r) v[r] = bias ? acc[i][j][r] + bv[r] : acc[i][j][r];
             if (m >= M || n >= N) continue;
             mx_store4(y, ydt, m * N + n, v, n, N, y_vec);
+        }
+    }
+}
+
+// The quantizing epilogue (include/qsparse_hip.h, "MX products that write MX codes"): bias in float32, the optional ReLU, then the MX
+// quantizer of qs_mx.h on the wave's 64 (m, from mw) x 64 (n, from nw) corner with blocks of 32 along n -- codes [M, N] and scale
+// bytes [M, ceil(N / 32)] instead of y.  A block is one row m and the 32 columns nw + 32 b ..: the accumulators acc[2 b][j] and
+// acc[2 b + 1][j] (4 consecutive n each) of the four lanes l, l + 16, l + 32, l + 48 that share m = mw + 16 j + (l & 15).  So its
+// abs-max is the maximum over 8 values in the lane and two __shfl_xor steps (lane bits 4 and 5); every lane then holds the block's
+// scale and rounds its own 8 values.  nw is a multiple of 64: no block straddles two waves.  Columns n >= N of a short last block
+// are taken as +0 whatever the accumulator holds (zero codes and no bias give +0 there, but a row of A that holds an Inf code
+// gives Inf * 0 = NaN), so they leave the maximum alone, as the quantizer's padding does.  Rows m >= M, columns n >= N and blocks
+// that start at or past N are never written.
+// c_vec: N % 4 == 0 and codes 4-byte aligned, so n + 3 < N and one aligned 4-byte store takes a lane's four codes
+__device__ __forceinline__ void mx_epilogue_codes(const f32x4 (&acc)[4][4], const float* __restrict__ bias, int relu, const MxFormat& f,
+                                                  uint8_t* __restrict__ codes, uint8_t* __restrict__ scales, int64_t M, int64_t N,
+                                                  int64_t mw, int64_t nw, int lane, int c_vec) {
+    const int64_t nb = (N + QS_MX_BLOCK - 1) / QS_MX_BLOCK;
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const int64_t n0 = nw + QS_MX_BLOCK * b;                    // the block's first column
+        float bv[2][4] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
+        if (bias) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int64_t n = n0 + 16 * h + 4 * (lane >> 4) + r;
+                    if (n < N) bv[h][r] = bias[n];
+                }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t m = mw + 16 * j + (lane & 15);
+            float u[2][4];
+            uint32_t am = 0;
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float v = bias ? acc[2 * b + h][j][r] + bv[h][r] : acc[2 * b + h][j][r];
+                    if (relu) v = v > 0.0f ? v : (v != v ? v : 0.0f);
+                    if (n0 + 16 * h + 4 * (lane >> 4) + r >= N) v = 0.0f;       // (an Inf code in row m times the zero codes past N: NaN)
+                    u[h][r] = v;
+                    const uint32_t a = mx_abs_bits(v);
+                    am = a > am ? a : am;
+                }
+#pragma unroll
+            for (int off = 16; off < 64; off <<= 1) {               // (every lane of the wave takes part: before any early exit)
+                const uint32_t o = (uint32_t)__shfl_xor((int)am, off, 64);
+                am = o > am ? o : am;
+            }
+            if (m >= M || n0 >= N) continue;
+            const MxScale s = mx_scale(am, f);
+            if ((lane >> 4) == 0) scales[m * nb + (n0 >> 5)] = (uint8_t)s.byte;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int64_t n = n0 + 16 * h + 4 * (lane >> 4);
+                if (n >= N) continue;
+                uint32_t c[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    uint32_t sg;
+                    const float q = mx_round_abs(u[h][r], s, f, sg);
+                    c[r] = mx_code(q, sg, s, f);
+                }
+                uint8_t* p = codes + m * N + n;
+                if (c_vec) {
+                    *(uint32_t*)p = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (n + r < N) p[r] = (uint8_t)c[r];
+                }
+            }
         }
     }
 }

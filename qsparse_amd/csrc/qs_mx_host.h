@@ -1,5 +1,5 @@
-// Host-side helpers shared by the five translation units of the products on MX codes (api_mx_gemm.hip, api_mx_gemm_splitk.hip,
-// api_mx_conv.hip, api_mx_conv_t.hip, api_mx_conv_wgrad.hip): the dispatch over the 5 x 5 format pairs, the tile count and the store
+// Host-side helpers shared by the seven translation units of the products on MX codes (api_mx_gemm.hip, api_mx_gemm_splitk.hip,
+// api_mx_conv.hip, api_mx_conv_t.hip, api_mx_conv_wgrad.hip, api_mx_gemm_q.hip, api_mx_conv_q.hip): the dispatch over the 5 x 5 format pairs, the tile count and the store
 // rule of y, the descriptor of a product forwarded to qs_mx_matmul_v, what the two split products (mx_matmul's split-K, the
 // convolution's weight gradient) share -- the slicing, the body of their `_plan` exports, the checks of their workspace; the launch of
 // their reduction is mx_launch_reduce of qs_mx_gemm_splitk.h, next to its kernel -- and the checks the two convolutions share.
@@ -46,6 +46,40 @@ inline qs_mx_matmul_args mx_matmul_args(int fa, int fb, const uint8_t* a_codes, 
     m.M = M, m.N = N, m.K = K;
     m.stream = stream;
     return m;
+}
+
+// ---- what qs_mx_matmul_v and qs_mx_matmul_q_v (codes out) check alike (Args: either descriptor) -----------------------------------
+// the operands and extents, all QS_ERR_ARG: they come before the checks of the output's dtype and alignment
+template <class Args>
+int mx_gemm_check_operands(const Args& a) {
+    if (!a.a_codes || !a.a_scales || !a.b_codes || !a.b_scales) return QS_ERR_ARG;
+    if (!mx_format_ok(a.a_format) || !mx_format_ok(a.b_format)) return QS_ERR_ARG;
+    if (a.M < 0 || a.N < 0 || a.K < 0) return QS_ERR_ARG;
+    return QS_OK;
+}
+
+// after them, for a product that is not empty: QS_MX_GEMM_ROUTE_VEC or _PLAIN, or QS_ERR_ARG
+template <class Args>
+int mx_gemm_sized_route(const Args& a) {
+    if (a.K == 0 || a.M > INT64_MAX / a.N || a.M > INT64_MAX / a.K || a.N > INT64_MAX / a.K) return QS_ERR_ARG;
+    if (mx_tiles(a.M) * mx_tiles(a.N) > kMaxGrid) return QS_ERR_ARG;
+    return (a.K % 16 == 0 && aligned16(a.a_codes) && aligned16(a.b_codes)) ? QS_MX_GEMM_ROUTE_VEC : QS_MX_GEMM_ROUTE_PLAIN;
+}
+
+// ---- the outputs of the products that write MX codes (qs_mx_matmul_q_v, qs_mx_conv2d_q_v) ---------------------------------------------
+// their own arguments, all QS_ERR_ARG
+template <class Args>
+bool mx_q_args_ok(const Args& a) {
+    return a.out_codes && a.out_scales && mx_format_ok(a.out_format) && (a.act == QS_MX_ACT_NONE || a.act == QS_MX_ACT_RELU);
+}
+
+// four consecutive codes per lane in one store: every row of out_codes [., N] must keep the store's alignment
+inline int mx_c_vec(const void* codes, int64_t N) { return N % 4 == 0 && (((uintptr_t)codes) & 3u) == 0; }
+
+// do the `bytes` (> 0) bytes at `out` and the `in_bytes` (> 0) at `in` share a byte
+inline bool mx_overlap(const void* out, int64_t bytes, const void* in, int64_t in_bytes) {
+    const uintptr_t o = (uintptr_t)out, i = (uintptr_t)in;
+    return o < i + (uint64_t)in_bytes && i < o + (uint64_t)bytes;
 }
 
 // ---- the slicing of a product split along K and the automatic slice count (qs_mx_matmul_splitk_plan, qs_mx_conv2d_wgrad_plan;
@@ -111,19 +145,30 @@ struct MxConvPlan {
     int64_t OH, OW, M;
 };
 
-// before the output size: QS_OK or the error.  `own_ok`: the caller's own conditions on the arguments, which fail before the dtype's
+// the operands and the geometry, all QS_ERR_ARG.  `own_ok`: the caller's own conditions on the arguments, which fail before the dtype's
 template <class Args>
-int mx_conv_check_args(const Args& a, bool own_ok) {
-    if (!a.x_codes || !a.x_scales || !a.w_codes || !a.w_scales || !a.y) return QS_ERR_ARG;
+int mx_conv_check_operands(const Args& a, bool own_ok) {
+    if (!a.x_codes || !a.x_scales || !a.w_codes || !a.w_scales) return QS_ERR_ARG;
     if (!mx_format_ok(a.x_format) || !mx_format_ok(a.w_format)) return QS_ERR_ARG;
     if (a.B < 0 || a.Cout < 0 || a.H < 1 || a.W < 1 || a.C < 1 || a.KH < 1 || a.KW < 1) return QS_ERR_ARG;
     if (a.stride_h < 1 || a.stride_w < 1 || a.dil_h < 1 || a.dil_w < 1 || a.pad_h < 0 || a.pad_w < 0) return QS_ERR_ARG;
-    if (!own_ok) return QS_ERR_ARG;
+    return own_ok ? QS_OK : QS_ERR_ARG;
+}
+
+// the kernels keep coordinates inside one image in 32 bits (addresses: 64); H and W are the caller's to bound
+template <class Args>
+int mx_conv_check_limits(const Args& a) {
+    return a.C > INT32_MAX - QS_MX_BLOCK || a.B > INT32_MAX || a.Cout > INT32_MAX ? QS_ERR_ARG : QS_OK;
+}
+
+// before the output size, for the products that write y: QS_OK or the error
+template <class Args>
+int mx_conv_check_args(const Args& a, bool own_ok) {
+    const int st = mx_conv_check_operands(a, own_ok && a.y);
+    if (st != QS_OK) return st;
     if (!dt_ok(a.ydt)) return QS_ERR_DTYPE;
     if ((((uintptr_t)a.y) & (dt_size(a.ydt) - 1)) != 0 || (a.bias && (((uintptr_t)a.bias) & 3u) != 0)) return QS_ERR_ALIGN;
-    // the kernels keep coordinates inside one image in 32 bits (addresses: 64); H and W are the caller's to bound
-    if (a.C > INT32_MAX - QS_MX_BLOCK || a.B > INT32_MAX || a.Cout > INT32_MAX) return QS_ERR_ARG;
-    return QS_OK;
+    return mx_conv_check_limits(a);
 }
 
 // after it (1 <= OH, OW; H, W <= INT32_MAX): the sizes, the plan and the kernel -- QS_MX_CONV_ROUTE_VEC or _PLAIN, 0 for an empty
@@ -147,6 +192,18 @@ int mx_conv_plan(const Args& a, int64_t OH, int64_t OW, MxConvPlan* plan) {
 template <class Args>
 bool mx_conv_is_gemm(const Args& a) {
     return a.KH == 1 && a.KW == 1 && a.stride_h == 1 && a.stride_w == 1 && a.pad_h == 0 && a.pad_w == 0 && a.C % QS_MX_BLOCK == 0;
+}
+
+// after the argument checks of qs_mx_conv2d_v's convolution (Args: its descriptor or the codes-out one): the output size, then
+// mx_conv_plan -- QS_MX_CONV_ROUTE_*, 0 for an empty problem, QS_ERR_ARG
+template <class Args>
+int mx_conv2d_route_of(const Args& a, MxConvPlan* plan) {
+    const int64_t HP = a.H + 2 * (int64_t)a.pad_h, WP = a.W + 2 * (int64_t)a.pad_w;
+    if (HP > INT32_MAX || WP > INT32_MAX) return QS_ERR_ARG;
+    const int64_t EH = (int64_t)a.dil_h * (a.KH - 1) + 1, EW = (int64_t)a.dil_w * (a.KW - 1) + 1;      // extent of the dilated kernel
+    if (EH > HP || EW > WP) return QS_ERR_ARG;                                                        // OH < 1 or OW < 1
+    const int route = mx_conv_plan(a, (HP - EH) / a.stride_h + 1, (WP - EW) / a.stride_w + 1, plan);
+    return route > 0 && mx_conv_is_gemm(a) ? QS_MX_CONV_ROUTE_GEMM : route;
 }
 
 // QS_MX_CONV_ROUTE_GEMM: the call forwarded to qs_mx_matmul_v on the same bytes

@@ -17,7 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from qsparse_amd import _hip, _mx_common
-from qsparse_amd._mx_common import _check_bias, _check_bias_shape, _check_dtype, _pair
+from qsparse_amd._mx_common import MXActivation, _check_bias, _check_bias_shape, _check_codes_out, _check_dtype, _codes_out_cpu, _pair
 from qsparse_amd.quantize import MX_FORMATS, MXQuantizer, _mx_format, mx_dequantize, quantize_with_mx
 
 
@@ -41,7 +41,8 @@ def _check_product(fn: str, x_codes, x_scales, x_fmt: str, w_codes, w_scales, w_
 
 
 def mx_conv2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_codes: torch.Tensor, w_scales: torch.Tensor, w_fmt: str,
-              bias: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+              bias: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1, out_dtype: torch.dtype = torch.float32,
+              out_fmt: Optional[str] = None, act: Optional[str] = None):
     """``conv2d(x, w) (+ bias)`` on MX codes, channels-last.  ``x_codes`` ``[B, H, W, C]`` and ``w_codes`` ``[Cout, KH, KW, C]`` are
     uint8 codes of the formats ``x_fmt`` / ``w_fmt`` (``MX_FORMATS``; they may differ) with blocks along C, ``x_scales`` ``[B, H, W,
     ceil(C / 32)]`` and ``w_scales`` ``[Cout, KH, KW, ceil(C / 32)]`` their E8M0 bytes, ``bias`` float32 ``[Cout]``; ``stride``,
@@ -56,7 +57,16 @@ def mx_conv2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_codes
     makes every output whose window reads that block NaN.  GPU tensors take the HIP kernel -- float32 accumulation in the order of
     ``mx_matmul`` on the im2col operands, to which the result is bit-identical; there is no fallback: without the library the call
     raises -- CPU tensors evaluate the expression above in float64 and round once.  Input channels are padded to a multiple of 32
-    per tap inside the kernel, so a stem (C = 3) spends most of its products on zeros and is slow."""
+    per tap inside the kernel, so a stem (C = 3) spends most of its products on zeros and is slow.
+
+    ``out_fmt`` (a name of ``MX_FORMATS``) makes the convolution hand out MX codes instead of a float tensor: the return is ``(codes
+    uint8 [B, OH, OW, Cout], scales uint8 [B, OH, OW, ceil(Cout / 32)])``, bit for bit the codes and scales of
+    ``quantize_with_mx(act(y), out_fmt, -1, return_codes=True)`` with ``y`` the float32 result above and blocks along Cout -- the next
+    convolution's C.  ``act`` is ``None`` or ``"relu"`` (NaN stays NaN, everything else that is not positive becomes +0) and needs
+    ``out_fmt``; ``out_dtype`` must stay at its default.  On the GPU it is one kernel (``qs_mx_conv2d_q_v``): the quantizer runs on
+    the accumulators and no float ``y`` is written or read.  CPU tensors round the float64 result once to float32, apply ``act`` and
+    run the CPU quantizer."""
+    _check_codes_out("mx_conv2d", out_fmt, act, out_dtype)
     _check_product("mx_conv2d", x_codes, x_scales, x_fmt, w_codes, w_scales, w_fmt, bias, out_dtype)
     (H, W), (KH, KW) = x_codes.shape[1:3], w_codes.shape[1:3]
     stride, padding, dilation = _pair("stride", stride, 1), _pair("padding", padding, 0), _pair("dilation", dilation, 1)
@@ -65,6 +75,9 @@ def mx_conv2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_codes
     if OH < 1 or OW < 1:
         raise ValueError(f"the kernel {KH}x{KW} (dilation {dilation}) does not fit the padded image {H + 2 * padding[0]}x{W + 2 * padding[1]}: "
                          f"the output would be {OH}x{OW}")
+    if x_codes.is_cuda and out_fmt is not None:
+        return _hip.mx_conv2d_q(x_codes.contiguous(), x_scales.contiguous(), x_fmt, w_codes.contiguous(), w_scales.contiguous(), w_fmt,
+                                None if bias is None else bias.contiguous(), stride, padding, dilation, out_fmt, act)
     if x_codes.is_cuda:
         return _hip.mx_conv2d(x_codes.contiguous(), x_scales.contiguous(), x_fmt, w_codes.contiguous(), w_scales.contiguous(), w_fmt,
                               None if bias is None else bias.contiguous(), stride, padding, dilation, out_dtype)
@@ -72,7 +85,8 @@ def mx_conv2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_codes
     w = mx_dequantize(w_codes, w_scales, w_fmt, -1, torch.float64).permute(0, 3, 1, 2)
     # a 0xFF block is NaN in every window that reads it, also against a zero (NaN * 0 is NaN): the convolution's own propagation
     y = F.conv2d(x, w, None if bias is None else bias.to(torch.float64), stride, padding, dilation)
-    return y.permute(0, 2, 3, 1).to(out_dtype).contiguous()
+    y = y.permute(0, 2, 3, 1).to(out_dtype).contiguous()
+    return y if out_fmt is None else _codes_out_cpu(y, out_fmt, act)
 
 
 class _MXConvBase(nn.Module):
@@ -125,7 +139,8 @@ class _MXConvBase(nn.Module):
     def _product(self, codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def _input_codes(self, x: torch.Tensor):
+        """the checks of a float input ``[B, C, H, W]`` and its channels-last codes and scales in ``act_fmt``"""
         layer = self._layer.__name__
         if torch.is_grad_enabled() and x.requires_grad:
             raise RuntimeError(f"MX{layer} is an inference layer: its input requires grad.  Train with the simulated layer "
@@ -136,6 +151,11 @@ class _MXConvBase(nn.Module):
             _, codes, scales = quantize_with_mx(x.permute(0, 2, 3, 1), self.act_fmt, -1, return_codes=True)
             if not codes.is_contiguous():      # an input that was not channels_last: one layout pass
                 codes, scales = codes.contiguous(), scales.contiguous()
+            return codes, scales
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        codes, scales = self._input_codes(x)
+        with torch.no_grad():
             return self._product(codes, scales).permute(0, 3, 1, 2)
 
 
@@ -149,23 +169,38 @@ class MXConv2d(_MXConvBase):
 
     Memory format: a ``torch.channels_last`` input is quantized where it lies (its ``[B, H, W, C]`` view is contiguous and takes
     the quantizer's innermost-axis route).  An NCHW-contiguous input pays one extra layout pass over the activation before the
-    quantizer; keep the network channels_last to avoid it."""
+    quantizer; keep the network channels_last to avoid it.
+
+    Chaining without a float tensor in between: with ``out_fmt`` (keyword; optionally ``act="relu"``) ``forward`` returns an
+    ``MXActivation`` holding channels-last codes ``[B, OH, OW, Cout]`` -- the codes and scales of ``quantize_with_mx(act(y), out_fmt)``
+    along the channels, written by the convolution's own epilogue -- and ``forward`` also TAKES an ``MXActivation`` with ``[B, H, W,
+    C]`` codes in place of a float tensor: its codes are convolved as they are, in their own format (``act_fmt`` is not consulted: the
+    product takes any pair).  ``nn.Sequential(MXConv2d(..., out_fmt=f, act="relu"), MXConv2d(...))`` computes bit for bit what the
+    two layers compute with a float ReLU between them when the second one's ``act_fmt`` is ``f``."""
 
     _layer, _weight_layout, _perm, _block_dim, _block_dim_note = nn.Conv2d, "[Cout, C, KH, KW]", (0, 2, 3, 1), 1, "dim 1"
 
     def __init__(self, weight_codes: torch.Tensor, weight_scales: torch.Tensor, weight_fmt: str, bias: Optional[torch.Tensor] = None,
-                 stride=1, padding=0, dilation=1, act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32):
+                 stride=1, padding=0, dilation=1, act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32, *,
+                 out_fmt: Optional[str] = None, act: Optional[str] = None):
         super().__init__(weight_codes, weight_scales, weight_fmt, bias, stride, padding, dilation, act_fmt, out_dtype)
+        _check_codes_out("MXConv2d", out_fmt, act, out_dtype)
+        self.out_fmt, self.act = out_fmt, act
+
+    def extra_repr(self) -> str:
+        return (super().extra_repr() + (f", out_fmt={self.out_fmt!r}" if self.out_fmt is not None else "") +
+                (f", act={self.act!r}" if self.act is not None else ""))
 
     @classmethod
     def from_exported(cls, qt, bias: Optional[torch.Tensor] = None, stride=1, padding=0, dilation=1, act_fmt: str = "mxfp8_e4m3",
-                      out_dtype: torch.dtype = torch.float32):
+                      out_dtype: torch.dtype = torch.float32, *, out_fmt: Optional[str] = None, act: Optional[str] = None):
         """from the ``QuantizedTensor(kind="mx")`` ``export_integer`` returns for a conv layer's weight ``[Cout, C, KH, KW]`` with
         blocks along dim 1; codes and scales are permuted to channels-last once, here"""
-        return cls(*cls._channels_last(qt), qt.fmt, bias, stride, padding, dilation, act_fmt, out_dtype)
+        return cls(*cls._channels_last(qt), qt.fmt, bias, stride, padding, dilation, act_fmt, out_dtype, out_fmt=out_fmt, act=act)
 
     @classmethod
-    def from_quantized(cls, layer: nn.Module, act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32):
+    def from_quantized(cls, layer: nn.Module, act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32, *,
+                       out_fmt: Optional[str] = None, act: Optional[str] = None):
         """from a ``quantize(nn.Conv2d(...), bits=w, callback=MXQuantizer(fmt, block_dim=1))`` layer that is past its timeout: the
         weight codes are the export's, stride / padding / dilation the layer's, the bias what its evaluation-mode forward adds"""
         from qsparse_amd.export import export_integer
@@ -189,11 +224,22 @@ class MXConv2d(_MXConvBase):
                 bias = None if b is None else b.detach().to(torch.float32)
         finally:
             layer.train(was)
-        return cls.from_exported(rec.weight, bias, tuple(layer.stride), tuple(layer.padding), tuple(layer.dilation), act_fmt, out_dtype)
+        return cls.from_exported(rec.weight, bias, tuple(layer.stride), tuple(layer.padding), tuple(layer.dilation), act_fmt, out_dtype,
+                                 out_fmt=out_fmt, act=act)
 
-    def _product(self, codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
-        return mx_conv2d(codes, scales, self.act_fmt, self.weight_codes, self.weight_scales, self.weight_fmt, self.bias, self.stride,
-                         self.padding, self.dilation, self.out_dtype)
+    def forward(self, x):
+        if isinstance(x, MXActivation):
+            codes, scales, fmt = x.codes, x.scales, x.fmt
+            if not x.channels_last:
+                raise ValueError("MXConv2d expects an MXActivation with channels_last=True: codes [B, H, W, C] with blocks along the channels")
+            if codes.dim() != 4 or codes.shape[3] != self.in_channels:
+                raise ValueError(f"MXConv2d expects an MXActivation with codes [B, H, W, {self.in_channels}], got shape {tuple(codes.shape)}")
+        else:
+            (codes, scales), fmt = self._input_codes(x), self.act_fmt
+        with torch.no_grad():
+            y = mx_conv2d(codes, scales, fmt, self.weight_codes, self.weight_scales, self.weight_fmt, self.bias, self.stride, self.padding,
+                          self.dilation, self.out_dtype, self.out_fmt, self.act)
+            return y.permute(0, 3, 1, 2) if self.out_fmt is None else MXActivation(*y, self.out_fmt, True)
 
 
-__all__ = ["mx_conv2d", "MXConv2d", "MX_FORMATS"]
+__all__ = ["mx_conv2d", "MXConv2d", "MXActivation", "MX_FORMATS"]

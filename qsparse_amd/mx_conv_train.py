@@ -252,11 +252,12 @@ class MXTrainConv2d(_MXTrainMixin, nn.Conv2d):
         return mx_conv2d_train(x, self.weight, self.bias, self.stride, self.padding, self.dilation, self.x_fmt, self.w_fmt, self.grad_fmt,
                                self.grad_rounding, seed, step, self.wgrad_split_k)
 
-    def to_inference(self, act_fmt: Optional[str] = None, out_dtype: torch.dtype = torch.float32) -> MXConv2d:
+    def to_inference(self, act_fmt: Optional[str] = None, out_dtype: torch.dtype = torch.float32, *, out_fmt: Optional[str] = None,
+                     act: Optional[str] = None) -> MXConv2d:
         """the ``MXConv2d`` on the current weight: its weight bytes are the codes the training forward convolves with"""
         codes, scales = _weight_rows(self.weight.detach().permute(0, 2, 3, 1), self.w_fmt)
         return MXConv2d(codes, scales, self.w_fmt, None if self.bias is None else self.bias.detach(), self.stride, self.padding,
-                        self.dilation, act_fmt or self.x_fmt, out_dtype)
+                        self.dilation, act_fmt or self.x_fmt, out_dtype, out_fmt=out_fmt, act=act)
 
 
 __all__ = ["mx_conv2d_weight_grad", "mx_conv2d_train", "MXTrainConv2d", "MX_FORMATS"]

@@ -18,8 +18,8 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from qsparse_amd import _hip, _mx_common
-from qsparse_amd._mx_common import (_OUT_DTYPES, _check_bias, _check_bias_shape, _check_dtype, _check_train_entry, _MXTrainMixin,
-                                    _quantize_grad, _save_train_ctx, _split_request)
+from qsparse_amd._mx_common import (_OUT_DTYPES, MXActivation, _check_bias, _check_bias_shape, _check_codes_out, _check_dtype,
+                                    _check_train_entry, _codes_out_cpu, _MXTrainMixin, _quantize_grad, _save_train_ctx, _split_request)
 from qsparse_amd.quantize import (MX_FORMATS, MXQuantizer, _mx_aten, _mx_check_rounding, _mx_format, _mx_sr_words, mx_dequantize,
                                   quantize_with_mx)
 
@@ -30,7 +30,8 @@ _check_b = partial(_mx_common._check_operand, what="[N, K]", least=2, most=None,
 
 
 def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
-              bias: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32, *, split_k=1) -> torch.Tensor:
+              bias: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32, *, split_k=1, out_fmt: Optional[str] = None,
+              act: Optional[str] = None):
     """``A . B^T (+ bias)`` on MX codes.  ``a_codes`` ``[..., K]`` and ``b_codes`` ``[N, K]`` (an ``nn.Linear`` weight) are uint8
     codes of the formats ``a_fmt`` / ``b_fmt`` (``MX_FORMATS``; they may differ) with blocks along K, ``a_scales`` ``[..., ceil(K /
     32)]`` and ``b_scales`` ``[N, ceil(K / 32)]`` their E8M0 bytes, ``bias`` float32 ``[N]``.  Returns ``[..., N]`` in ``out_dtype``
@@ -48,8 +49,17 @@ def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes
     the same on every run.  It is for products with a small output and a long K (a weight gradient), which otherwise occupy a
     fraction of the GPU.  ``1`` (the default) is the unsplit kernel, bit for bit; ``"auto"`` lets the library choose from the shape
     (1 whenever ``ceil(K / 128) < 32`` or the output has 256 tiles of 128 x 128 or more).  A request that leaves one slice is the
-    unsplit call.  The CPU path checks the argument and evaluates the float64 definition, which has no order to cut."""
+    unsplit call.  The CPU path checks the argument and evaluates the float64 definition, which has no order to cut.
+
+    ``out_fmt`` (keyword; a name of ``MX_FORMATS``) makes the product hand out MX codes instead of a float tensor: the return is
+    ``(codes uint8 [..., N], scales uint8 [..., ceil(N / 32)])``, bit for bit the codes and scales of
+    ``quantize_with_mx(act(y), out_fmt, -1, return_codes=True)`` with ``y`` the float32 result above and blocks along N -- the next
+    product's K.  ``act`` (keyword) is ``None`` or ``"relu"`` (NaN stays NaN, everything else that is not positive becomes +0) and
+    needs ``out_fmt``.  On the GPU it is one kernel (``qs_mx_matmul_q_v``): the quantizer runs on the accumulators and no float ``y``
+    is written or read.  ``out_dtype`` must stay at its default and ``split_k`` at 1 (the split product's reduction does not
+    quantize).  CPU tensors round the float64 result once to float32, apply ``act`` and run the CPU quantizer."""
     request = _split_request(split_k)
+    _check_codes_out("mx_matmul", out_fmt, act, out_dtype, request)
     _check_a("a", a_codes, a_scales, a_fmt)
     _check_b("b", b_codes, b_scales, b_fmt)
     if b_codes.dim() != 2:
@@ -65,6 +75,10 @@ def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes
     _check_bias(bias, N, "a_codes", a_codes.device)
     lead = tuple(a_codes.shape[:-1])
     a2, sa2 = a_codes.reshape(-1, K), a_scales.reshape(-1, a_scales.shape[-1])
+    if a_codes.is_cuda and out_fmt is not None:
+        codes, scales = _hip.mx_matmul_q(a2.contiguous(), sa2.contiguous(), a_fmt, b_codes.contiguous(), b_scales.contiguous(), b_fmt,
+                                         None if bias is None else bias.contiguous(), out_fmt, act)
+        return codes.reshape(lead + (N,)), scales.reshape(lead + (scales.shape[-1],))
     if a_codes.is_cuda:
         y = _hip.mx_matmul(a2.contiguous(), sa2.contiguous(), a_fmt, b_codes.contiguous(), b_scales.contiguous(), b_fmt,
                            None if bias is None else bias.contiguous(), out_dtype, request)
@@ -76,6 +90,8 @@ def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes
         if bias is not None:
             y = y + bias.to(torch.float64)
         y = y.to(out_dtype)
+        if out_fmt is not None:
+            return _codes_out_cpu(y.reshape(lead + (N,)), out_fmt, act)
     return y.reshape(lead + (N,))
 
 
@@ -84,12 +100,22 @@ class MXLinear(nn.Module):
     ``weight_scales [N, ceil(K / 32)]`` of the format ``weight_fmt`` (buffers, with the optional float32 ``bias``); ``forward``
     quantizes its input to ``act_fmt`` along the last dimension with the MX quantizer (``quantize_with_mx``) and multiplies the two
     sets of codes with ``mx_matmul``.  The output is float32 (or ``out_dtype``) and never requires grad; an input that requires
-    grad while gradients are enabled is refused -- training runs on the simulated layers this one is built from."""
+    grad while gradients are enabled is refused -- training runs on the simulated layers this one is built from.
+
+    Chaining without a float tensor in between: with ``out_fmt`` (keyword; optionally ``act="relu"``) ``forward`` returns an
+    ``MXActivation`` -- the codes and scales of ``quantize_with_mx(act(y), out_fmt, -1)``, written by the product's own epilogue --
+    and ``forward`` also TAKES an ``MXActivation`` in place of a float tensor: its codes are multiplied as they are, in their own
+    format (``act_fmt`` is not consulted: the product takes any pair).  ``nn.Sequential(MXLinear(..., out_fmt=f, act="relu"),
+    MXLinear(...))`` computes bit for bit what the two layers compute with a float ReLU between them when the second one's
+    ``act_fmt`` is ``f``."""
 
     def __init__(self, weight_codes: torch.Tensor, weight_scales: torch.Tensor, weight_fmt: str, bias: Optional[torch.Tensor] = None,
-                 act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32):
+                 act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32, *, out_fmt: Optional[str] = None,
+                 act: Optional[str] = None):
         super().__init__()
         _mx_format(act_fmt)
+        _check_codes_out("MXLinear", out_fmt, act, out_dtype)
+        self.out_fmt, self.act = out_fmt, act
         _check_b("b", weight_codes, weight_scales, weight_fmt)
         if weight_codes.dim() != 2:
             raise ValueError(f"weight_codes must be [N, K], got shape {tuple(weight_codes.shape)}")
@@ -102,10 +128,12 @@ class MXLinear(nn.Module):
 
     def extra_repr(self) -> str:
         return (f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, "
-                f"weight_fmt={self.weight_fmt!r}, act_fmt={self.act_fmt!r}")
+                f"weight_fmt={self.weight_fmt!r}, act_fmt={self.act_fmt!r}" +
+                (f", out_fmt={self.out_fmt!r}" if self.out_fmt is not None else "") + (f", act={self.act!r}" if self.act is not None else ""))
 
     @classmethod
-    def from_exported(cls, qt, bias: Optional[torch.Tensor] = None, act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32):
+    def from_exported(cls, qt, bias: Optional[torch.Tensor] = None, act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32, *,
+                      out_fmt: Optional[str] = None, act: Optional[str] = None):
         """from the ``QuantizedTensor(kind="mx")`` ``export_integer`` returns for a linear layer's weight"""
         if getattr(qt, "kind", None) != "mx":
             raise ValueError(f"MXLinear needs an MX weight (QuantizedTensor.kind == 'mx'), got kind {getattr(qt, 'kind', None)!r}")
@@ -114,10 +142,11 @@ class MXLinear(nn.Module):
         if qt.block_dim % qt.codes.dim() != 1:
             raise ValueError(f"the weight's MX blocks run along dim {qt.block_dim}, not along K (dim 1): blocks along N cannot feed the "
                              "matrix instruction -- quantize the layer with MXQuantizer(fmt, block_dim=1)")
-        return cls(qt.codes, qt.block_scale, qt.fmt, bias, act_fmt, out_dtype)
+        return cls(qt.codes, qt.block_scale, qt.fmt, bias, act_fmt, out_dtype, out_fmt=out_fmt, act=act)
 
     @classmethod
-    def from_quantized(cls, layer: nn.Module, act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32):
+    def from_quantized(cls, layer: nn.Module, act_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32, *,
+                       out_fmt: Optional[str] = None, act: Optional[str] = None):
         """from a ``quantize(nn.Linear(...), bits=w, callback=MXQuantizer(fmt, block_dim=1))`` layer that is past its timeout:
         the weight codes are the export's, the bias what the layer's evaluation-mode forward adds"""
         from qsparse_amd.export import export_integer
@@ -135,15 +164,25 @@ class MXLinear(nn.Module):
                 bias = None if b is None else b.detach().to(torch.float32)
         finally:
             layer.train(was)
-        return cls.from_exported(rec.weight, bias, act_fmt, out_dtype)
+        return cls.from_exported(rec.weight, bias, act_fmt, out_dtype, out_fmt=out_fmt, act=act)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if torch.is_grad_enabled() and x.requires_grad:
+    def forward(self, x):
+        taken = isinstance(x, MXActivation)
+        if not taken and torch.is_grad_enabled() and x.requires_grad:
             raise RuntimeError("MXLinear is an inference layer: its input requires grad.  Train with the simulated layer "
                                "(quantize(nn.Linear(...), callback=MXQuantizer(...))) or call it under torch.no_grad()")
         with torch.no_grad():
-            _, codes, scales = quantize_with_mx(x, self.act_fmt, -1, return_codes=True)
-            return mx_matmul(codes, scales, self.act_fmt, self.weight_codes, self.weight_scales, self.weight_fmt, self.bias, self.out_dtype)
+            if taken:
+                if x.channels_last:
+                    raise ValueError("MXLinear got an MXActivation with channels_last=True: the [B, H, W, C] codes of a convolution, whose "
+                                     "float form is [B, C, H, W] -- flatten the float tensor, or pass MXActivation(codes, scales, fmt)")
+                codes, scales, fmt = x.codes, x.scales, x.fmt
+            else:
+                fmt = self.act_fmt
+                _, codes, scales = quantize_with_mx(x, fmt, -1, return_codes=True)
+            y = mx_matmul(codes, scales, fmt, self.weight_codes, self.weight_scales, self.weight_fmt, self.bias, self.out_dtype,
+                          out_fmt=self.out_fmt, act=self.act)
+            return y if self.out_fmt is None else MXActivation(*y, self.out_fmt)
 
 
 def mx_quantize_2way(x: torch.Tensor, row_fmt: Optional[str] = None, col_fmt: Optional[str] = None, rounding: str = "nearest",
@@ -299,10 +338,12 @@ class MXTrainLinear(_MXTrainMixin, nn.Linear):
         return mx_linear(x, self.weight, self.bias, self.x_fmt, self.w_fmt, self.grad_fmt, self.grad_rounding, seed, step,
                          self.wgrad_split_k)
 
-    def to_inference(self, act_fmt: Optional[str] = None, out_dtype: torch.dtype = torch.float32) -> MXLinear:
+    def to_inference(self, act_fmt: Optional[str] = None, out_dtype: torch.dtype = torch.float32, *, out_fmt: Optional[str] = None,
+                     act: Optional[str] = None) -> MXLinear:
         """the ``MXLinear`` on the current weight: its weight bytes are the row pair the training forward multiplies with"""
         codes, scales, _, _ = mx_quantize_2way(self.weight, self.w_fmt, None)
-        return MXLinear(codes, scales, self.w_fmt, None if self.bias is None else self.bias.detach(), act_fmt or self.x_fmt, out_dtype)
+        return MXLinear(codes, scales, self.w_fmt, None if self.bias is None else self.bias.detach(), act_fmt or self.x_fmt, out_dtype,
+                        out_fmt=out_fmt, act=act)
 
 
-__all__ = ["mx_matmul", "MXLinear", "mx_quantize_2way", "mx_linear", "MXTrainLinear", "MX_FORMATS"]
+__all__ = ["mx_matmul", "MXLinear", "MXActivation", "mx_quantize_2way", "mx_linear", "MXTrainLinear", "MX_FORMATS"]

@@ -1270,6 +1270,71 @@ int qs_mx_conv2d_q_v(const qs_mx_conv2d_q_args* args);
  * the call would return */
 int qs_mx_conv2d_q_route(const qs_mx_conv2d_q_args* args);
 
+/* ---- MX batched matrix product -----------------------------------------------------------------------------------------------
+ * Added without raising QS_ABI_VERSION (28), by the same rule as qs_mx_matmul_v above: symbols are only added.
+ *
+ * G independent products in one launch, neither operand shared between them (attention's Q . K^T and P . V per image and head, a
+ * linear layer per expert):
+ *   y[g, m, n] = round_once_to_ydt( sum_k val_a(a_codes[g, m, k]) * 2^(a_scales[g, m, k / 32] - 127)
+ *                                       * val_b(b_codes[g, n, k]) * 2^(b_scales[g, n, k / 32] - 127)  +  bias[g or -, n] )
+ * Definition (normative): slice g of y equals, bit for bit, what qs_mx_matmul_v writes for slice g of the operands -- the same
+ * tile, the same walk along K in steps of 128, the same order of the 16 MFMAs of a step -- so everything said there about range,
+ * short last blocks and unspecified code bytes holds per slice.  A scale byte 0xFF makes every output that reads it NaN, in that
+ * slice only.
+ *   - All four operands and y are dense: slice g lies g whole slices (M K, M ceil(K / 32), N K, N ceil(K / 32), M N elements) past
+ *     its base.  bias is NULL, [N] shared by the slices (bias_batch_stride == 0) or [G, N] (bias_batch_stride == N, in elements);
+ *     any other stride is QS_ERR_ARG.
+ *   - Checks in the order and with the status codes of qs_mx_matmul_v: a NULL operand, a format outside enum qs_mx_format, a
+ *     negative extent or a bad bias stride is QS_ERR_ARG; then ydt (QS_ERR_DTYPE); then y aligned to its element and bias to 4
+ *     bytes (QS_ERR_ALIGN).  G == 0, M == 0 or N == 0: nothing is enqueued, 0 is returned.  K == 0 of a non-empty product, any of
+ *     G M K, G N K, G M N beyond INT64_MAX, or G ceil(M / 128) ceil(N / 128) beyond 2^31 - 1 work-groups: QS_ERR_ARG.
+ *   - One launch, one work-group per 128 x 128 tile of one slice -- unless a slice has 512 tiles or more and fills the GPU by itself:
+ *     the slices are then launched one by one, as qs_mx_matmul_v launches them (G launches, the same bits).  Nothing outside the five
+ *     operands and y is read or written.
+ *   - Routes: K % 16 == 0 with both code bases 16-byte aligned (every slice base then is) takes QS_MX_GEMM_ROUTE_VEC, anything else
+ *     QS_MX_GEMM_ROUTE_PLAIN, with the same bits.  No workspace, no split-K form. */
+typedef struct qs_mx_bmm_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_bmm_args) as the caller compiled it */
+    int32_t a_format, b_format;      /* enum qs_mx_format, may differ */
+    const uint8_t* a_codes;          /* [G, M, K], one code per byte, dense */
+    const uint8_t* a_scales;         /* [G, M, ceil(K / 32)] E8M0 bytes */
+    const uint8_t* b_codes;          /* [G, N, K] */
+    const uint8_t* b_scales;         /* [G, N, ceil(K / 32)] */
+    const float* bias;               /* nullable, float32 [N] or [G, N] */
+    int64_t bias_batch_stride;       /* elements from one slice's bias to the next: 0 or N */
+    void* y;                         /* [G, M, N] dense */
+    int32_t ydt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    int64_t G, M, N, K;
+    qs_stream_t stream;
+} qs_mx_bmm_args;
+int qs_mx_bmm_v(const qs_mx_bmm_args* args);
+/* the kernel qs_mx_bmm_v launches for these operands, nothing enqueued: QS_MX_GEMM_ROUTE_*, 0 for an empty product, or the
+ * QS_ERR_* the call would return */
+int qs_mx_bmm_route(const qs_mx_bmm_args* args);
+
+/* The batched product with the quantizing epilogue ("MX products that write MX codes" above): out_codes [G, M, N] and out_scales
+ * [G, M, ceil(N / 32)] instead of y, slice g bit for bit what qs_mx_matmul_q_v writes for slice g of the operands.  Checks and their
+ * precedence are those of qs_mx_matmul_q_v with the additions of qs_mx_bmm_v; out_codes sharing a byte with a_codes or b_codes --
+ * byte counts over all G slices -- is QS_ERR_ARG.  Routes as qs_mx_bmm_route. */
+typedef struct qs_mx_bmm_q_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_bmm_q_args) as the caller compiled it */
+    int32_t a_format, b_format;      /* the operands of qs_mx_bmm_args, with their meaning ... */
+    const uint8_t* a_codes;
+    const uint8_t* a_scales;
+    const uint8_t* b_codes;
+    const uint8_t* b_scales;
+    const float* bias;
+    int64_t bias_batch_stride;
+    int32_t out_format;              /* ... and: enum qs_mx_format of the output */
+    int32_t act;                     /* QS_MX_ACT_* */
+    uint8_t* out_codes;              /* [G, M, N], one code per byte */
+    uint8_t* out_scales;             /* [G, M, ceil(N / 32)] E8M0 bytes */
+    int64_t G, M, N, K;
+    qs_stream_t stream;
+} qs_mx_bmm_q_args;
+int qs_mx_bmm_q_v(const qs_mx_bmm_q_args* args);
+int qs_mx_bmm_q_route(const qs_mx_bmm_q_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

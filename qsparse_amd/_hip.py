@@ -117,6 +117,10 @@ SIGNATURES = {
     "qs_mx_matmul_q_route": (c_int, [_P]),
     "qs_mx_conv2d_q_v": (c_int, [_P]),
     "qs_mx_conv2d_q_route": (c_int, [_P]),
+    "qs_mx_bmm_v": (c_int, [_P]),
+    "qs_mx_bmm_route": (c_int, [_P]),
+    "qs_mx_bmm_q_v": (c_int, [_P]),
+    "qs_mx_bmm_q_route": (c_int, [_P]),
 }
 
 
@@ -257,6 +261,18 @@ class MxMatmulQArgs(ctypes.Structure):
 class MxConv2dQArgs(ctypes.Structure):
     """`qs_mx_conv2d_q_args` of include/qsparse_hip.h"""
     _fields_ = _codes_out_fields(MxConv2dArgs._fields_)
+
+
+class MxBmmArgs(ctypes.Structure):
+    """`qs_mx_bmm_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("a_format", c_int32), ("b_format", c_int32), ("a_codes", c_void_p),
+                ("a_scales", c_void_p), ("b_codes", c_void_p), ("b_scales", c_void_p), ("bias", c_void_p), ("bias_batch_stride", c_int64),
+                ("y", c_void_p), ("ydt", c_int32), ("G", c_int64), ("M", c_int64), ("N", c_int64), ("K", c_int64), ("stream", c_void_p)]
+
+
+class MxBmmQArgs(ctypes.Structure):
+    """`qs_mx_bmm_q_args` of include/qsparse_hip.h"""
+    _fields_ = _codes_out_fields(MxBmmArgs._fields_)
 
 
 class MultiRow(ctypes.Structure):
@@ -1016,6 +1032,67 @@ def mx_matmul_q(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_cod
             st = lib.qs_mx_matmul_q_v(ctypes.byref(a))
         _check(st, "qs_mx_matmul_q_v")
         mx_gemm_q_last_route = route
+    return codes, scales
+
+
+mx_bmm_last_route = None      # the QS_MX_GEMM_ROUTE_* of the last `mx_bmm` launch (None: an empty product), for tests and tools
+mx_bmm_q_last_route = None    # likewise of the last `mx_bmm_q` launch
+
+
+def _mx_bmm_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias):
+    """fill the operand fields of a batched descriptor `a` from contiguous [G, M, K] / [G, N, K] codes; returns (G, M, N)"""
+    (G, M, K), N = a_codes.shape, b_codes.shape[1]
+    a.struct_size = ctypes.sizeof(a)
+    a.a_format, a.b_format = MX_FORMATS.index(a_fmt), MX_FORMATS.index(b_fmt)
+    a.a_codes, a.a_scales, a.b_codes, a.b_scales = _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales)
+    a.bias, a.bias_batch_stride = _ptr(bias), N if bias is not None and bias.dim() == 2 else 0
+    a.G, a.M, a.N, a.K = G, M, N, K
+    a.stream = _stream(a_codes)
+    return G, M, N
+
+
+def mx_bmm(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
+           bias: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32, out=None) -> torch.Tensor:
+    """y[G, M, N] = A[g] . B[g]^T on MX codes (qs_mx_bmm_v): `a_codes` [G, M, K], `b_codes` [G, N, K] uint8, scales [G, *, ceil(K /
+    32)] uint8, all contiguous GPU tensors (qsparse_amd/mx_bmm.py checks and flattens); `bias` float32 [N], [G, N] or None.  ONE launch.
+    `out`: a contiguous tensor of G M N elements of `out_dtype` to write instead of a new one, as the guard-byte tests carve it."""
+    global mx_bmm_last_route
+    lib = load()
+    a = MxBmmArgs()
+    G, M, N = _mx_bmm_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias)
+    if out is None:
+        y = torch.empty((G, M, N), dtype=out_dtype, device=a_codes.device)
+    else:
+        assert out.dtype == out_dtype and out.is_contiguous() and out.numel() == G * M * N, "out: G M N elements of out_dtype"
+        y = out.view(G, M, N)
+    mx_bmm_last_route = None
+    if G and M and N:
+        a.y, a.ydt = _ptr(y), _DT[out_dtype]
+        route = lib.qs_mx_bmm_route(ctypes.byref(a))
+        with _timed(f"mx_bmm[{route}]", a_codes, a_scales, b_codes, b_scales, bias, y):
+            st = lib.qs_mx_bmm_v(ctypes.byref(a))
+        _check(st, "qs_mx_bmm_v")
+        mx_bmm_last_route = route
+    return y
+
+
+def mx_bmm_q(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
+             bias: Optional[torch.Tensor], out_fmt: str, act=None, out=None):
+    """the MX codes [G, M, N] and scales [G, M, ceil(N / 32)] in `out_fmt` of act(A[g] . B[g]^T + bias) (qs_mx_bmm_q_v): operands as
+    `mx_bmm`'s, `act` None or "relu".  ONE launch, no float y."""
+    global mx_bmm_q_last_route
+    lib = load()
+    a = MxBmmQArgs()
+    (G, M, _), N = a_codes.shape, b_codes.shape[1]
+    codes, scales = _mx_codes_out(a, (G, M), N, out_fmt, act, a_codes.device, out)
+    mx_bmm_q_last_route = None
+    if G and M and N:
+        _mx_bmm_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias)
+        route = lib.qs_mx_bmm_q_route(ctypes.byref(a))
+        with _timed(f"mx_bmm_q[{route}]", a_codes, a_scales, b_codes, b_scales, bias, codes, scales):
+            st = lib.qs_mx_bmm_q_v(ctypes.byref(a))
+        _check(st, "qs_mx_bmm_q_v")
+        mx_bmm_q_last_route = route
     return codes, scales
 
 

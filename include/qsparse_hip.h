@@ -1030,6 +1030,57 @@ int qs_mx_quant2_v(const qs_mx_quant2_args* args);
 #define QS_MX_Q2_ROUTE_TILE_PLAIN 2
 int qs_mx_quant2_route(const qs_mx_quant2_args* args);
 
+/* ---- MX batched two-way quantizer (codes only) ---------------------------------------------------------------------------------
+ * Added without raising QS_ABI_VERSION (28), by the same rule as qs_mx_matmul_v above: symbols are only added.
+ *
+ * qs_mx_quant2_v for G = G0 G1 slices [R, C] of x in ONE launch, each slice read once WHERE IT LIES.  The element stride of x along
+ * C is 1; slice g = g0 G1 + g1 (0 <= g0 < G0, 0 <= g1 < G1) begins at x + g0 x_stride_g0 + g1 x_stride_g1 and its row r begins
+ * r x_stride_r further on, all three strides in elements -- a dense [G, R, C] tensor is G0 = 1 (or G1 = 1) with x_stride_r = C, the
+ * heads of a [B, T, h, d] projection output seen as [B, h, T, d] are G0 = B, G1 = h with the strides (T h d, d, h d).  The four
+ * outputs are DENSE, each pair nullable as a whole, at least one given:
+ *   row pair  row_codes uint8 [G, R, C], row_scales uint8 [G, R, ceil(C / 32)], format row_format, blocks along C
+ *   col pair  col_codes uint8 [G, C, R], col_scales uint8 [G, C, ceil(R / 32)], format col_format, blocks along R
+ * Slice g of the four outputs is, bit for bit, what qs_mx_quant2_v writes for slice g of x made contiguous: short last blocks, zero
+ * blocks, a NaN / Inf block (scale 0xFF, codes 0) and the sign of a zero included.  A block never spans two slices: the short last
+ * block of slice g along R reads nothing of slice g + 1, and nothing outside the G R C addressed elements of x is read at all.
+ * Nothing but the four outputs is written; no atomics, no workspace.
+ * Stochastic rounding (`rounding`, `seed`, `step`, `index_base` as for qs_mx_quant2_v): the random word of a code is indexed by its
+ * row-major index in the WHOLE dense output plus index_base -- (g R + r) C + c with rng_stream 0 for the row pair, (g C + c) R + r
+ * with rng_stream 1 for the col pair -- so both pairs are exactly the stochastic qs_mx_quant_fwd_v on the [G, R, C] tensor and on
+ * its [G, C, R] transpose.
+ *   - checks in qs_mx_quant2_v's order and with its status codes (the rounding operands first; x needs the alignment of its element,
+ *     QS_ERR_ALIGN; QS_ERR_DTYPE).  QS_ERR_ARG in addition: G0 < 0 or G1 < 0; for a tensor that is not empty x_stride_r < C (rows
+ *     would overlap) or a negative x_stride_g0 / x_stride_g1 (0 is allowed: x is only read), G R C or the offset of the last
+ *     addressed element of x beyond INT64_MAX, more than 2^31 - 1 work-groups (G tiles of 128 x 64 per slice).
+ *   - G0, G1, R or C equal to 0: nothing is enqueued, 0 is returned.
+ *   - QS_MX_Q2_ROUTE_TILE_VEC: qs_mx_quant2_v's conditions (C % 8 == 0 for two-byte x, C % 4 == 0 for float32, x 16-byte aligned and,
+ *     when the col pair is written, R % 16 == 0 and col_codes 16-byte aligned -- which keeps every output slice's base aligned) and
+ *     all three strides multiples of the 16-byte vector (8 two-byte elements, 4 float32).  Anything else takes
+ *     QS_MX_Q2_ROUTE_TILE_PLAIN: the same bits. */
+typedef struct qs_mx_quant2_batched_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_quant2_batched_args) as the caller compiled it */
+    int32_t row_format, col_format;  /* enum qs_mx_format, may differ */
+    const void* x;                   /* slice (g0, g1), row r, column c at x[g0 x_stride_g0 + g1 x_stride_g1 + r x_stride_r + c] */
+    int32_t xdt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    uint8_t* row_codes;              /* nullable with row_scales; [G, R, C] */
+    uint8_t* row_scales;             /* [G, R, ceil(C / 32)] */
+    uint8_t* col_codes;              /* nullable with col_scales; [G, C, R] */
+    uint8_t* col_scales;             /* [G, C, ceil(R / 32)] */
+    int64_t R, C;
+    qs_stream_t stream;
+    int32_t rounding;                /* QS_MX_ROUND_* */
+    int32_t reserved0;
+    uint64_t seed;
+    const int64_t* step;             /* nullable (= 0); device memory, one int64, read by the kernel */
+    uint64_t index_base;             /* a multiple of 4; added to the indices of both pairs */
+    int64_t G0, G1;                  /* G = G0 G1 slices */
+    int64_t x_stride_g0, x_stride_g1, x_stride_r;   /* in elements */
+} qs_mx_quant2_batched_args;
+int qs_mx_quant2_batched_v(const qs_mx_quant2_batched_args* args);
+/* the kernel qs_mx_quant2_batched_v launches for these operands, nothing enqueued: QS_MX_Q2_ROUTE_*, 0 for an empty tensor, or the
+ * QS_ERR_* the call would return */
+int qs_mx_quant2_batched_route(const qs_mx_quant2_batched_args* args);
+
 /* ---- MX convolution (implicit GEMM on the block-scaled MFMA) -------------------------------------------------------------------
  * Added without raising QS_ABI_VERSION (28), by the same rule as qs_mx_matmul_v above: symbols are only added.
  *

@@ -11,6 +11,7 @@ from qsparse_amd.export import LayerExport, QuantizedTensor, export_integer
 from qsparse_amd.fuse import fuse_bn
 from qsparse_amd.graphs import resync_host_state
 from qsparse_amd.mx_bmm import MXMultiheadAttention, mx_attention, mx_bmm
+from qsparse_amd.mx_batched_train import MXTrainMultiheadAttention, mx_attention_train, mx_bmm_train, mx_quantize_2way_batched
 from qsparse_amd.mx_conv import MXConv2d, mx_conv2d
 from qsparse_amd.mx_conv_train import MXTrainConv2d, mx_conv2d_train, mx_conv2d_weight_grad
 from qsparse_amd.mx_conv_transpose import MXConvTranspose2d, mx_conv2d_input_grad, mx_conv_transpose2d

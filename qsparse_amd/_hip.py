@@ -102,6 +102,8 @@ SIGNATURES = {
     "qs_mx_matmul_splitk_plan": (c_int, [_L, _L, _L, c_int32, _P, _P]),
     "qs_mx_quant2_v": (c_int, [_P]),
     "qs_mx_quant2_route": (c_int, [_P]),
+    "qs_mx_quant2_batched_v": (c_int, [_P]),
+    "qs_mx_quant2_batched_route": (c_int, [_P]),
     "qs_mx_quant_sr_v": (c_int, [_P]),
     "qs_mx_quant_sr_route": (c_int, [_P]),
     "qs_mx_quant2_sr_v": (c_int, [_P]),
@@ -221,6 +223,12 @@ class MxQuant2Args(ctypes.Structure):
                 ("R", c_int64), ("C", c_int64), ("stream", c_void_p),
                 ("rounding", c_int32), ("reserved0", c_int32), ("seed", ctypes.c_uint64), ("step", c_void_p),
                 ("index_base", ctypes.c_uint64)]                                                # v28
+
+
+class MxQuant2BatchedArgs(ctypes.Structure):
+    """`qs_mx_quant2_batched_args` of include/qsparse_hip.h"""
+    _fields_ = MxQuant2Args._fields_ + [("G0", c_int64), ("G1", c_int64), ("x_stride_g0", c_int64), ("x_stride_g1", c_int64),
+                                        ("x_stride_r", c_int64)]
 
 
 class MxConv2dArgs(ctypes.Structure):
@@ -1269,6 +1277,50 @@ def mx_quant2(x: torch.Tensor, row_fmt: Optional[str], col_fmt: Optional[str], r
             st = lib.qs_mx_quant2_v(ctypes.byref(a))
         _check(st, "qs_mx_quant2_v")
         mx_quant2_last_route = route
+    return rc, rs, cc, cs
+
+
+mx_quant2_batched_last_route = None   # the same of the last `mx_quant2_batched` launch
+
+
+def mx_quant2_batched(x: torch.Tensor, G0: int, G1: int, R: int, C: int, strides, row_fmt: Optional[str], col_fmt: Optional[str],
+                      rounding: str = "nearest", seed: int = 0, step: Optional[torch.Tensor] = None, index_base: int = 0, out=None):
+    """the batched, strided two-way MX quantizer (qs_mx_quant2_batched_v): `x` is a GPU tensor whose memory holds G0 x G1 slices [R, C]
+    with unit stride along C and the element `strides` (g0, g1, row) from x's first element (qsparse_amd/mx_batched_train.py collapses a
+    tensor's leading dimensions to them).  Returns dense (row_codes [G, R, C], row_scales [G, R, ceil(C / 32)], col_codes [G, C, R],
+    col_scales [G, C, ceil(R / 32)]), uint8, a pair None where its format is None -- from ONE launch that reads every slice once.
+    `out`: four contiguous uint8 tensors (or None for an absent pair) to write instead of new ones, as the guard-byte tests carve them."""
+    global mx_quant2_batched_last_route
+    lib = load()
+    G = G0 * G1
+    nb = lambda n: (n + MX_BLOCK - 1) // MX_BLOCK
+    shapes = ((G, R, C), (G, R, nb(C)), (G, C, R), (G, C, nb(R)))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=torch.uint8, device=x.device) if fmt is not None else None
+                    for shape, fmt in zip(shapes, (row_fmt, row_fmt, col_fmt, col_fmt)))
+    else:
+        for t, shape, fmt in zip(out, shapes, (row_fmt, row_fmt, col_fmt, col_fmt)):
+            assert (t is None) == (fmt is None), "out: a tensor for every pair that is asked for, None for the other"
+            assert t is None or (t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == shape[0] * shape[1] * shape[2]), "out: dense uint8"
+        out = tuple(None if t is None else t.view(shape) for t, shape in zip(out, shapes))
+    rc, rs, cc, cs = out
+    mx_quant2_batched_last_route = None
+    if G and R and C:
+        a = MxQuant2BatchedArgs()
+        a.struct_size = ctypes.sizeof(a)
+        a.row_format = MX_FORMATS.index(row_fmt) if row_fmt is not None else 0
+        a.col_format = MX_FORMATS.index(col_fmt) if col_fmt is not None else 0
+        a.x, a.xdt = _ptr(x), dt(x)
+        a.row_codes, a.row_scales, a.col_codes, a.col_scales = _ptr(rc), _ptr(rs), _ptr(cc), _ptr(cs)
+        a.R, a.C, a.G0, a.G1 = R, C, G0, G1
+        a.x_stride_g0, a.x_stride_g1, a.x_stride_r = strides
+        a.stream = _stream(x)
+        _mx_sr_operands(a, x, rounding, seed, step, index_base)
+        route = lib.qs_mx_quant2_batched_route(ctypes.byref(a))
+        with _timed(f"mx_quant2_batched[{route}]", x, rc, rs, cc, cs):
+            st = lib.qs_mx_quant2_batched_v(ctypes.byref(a))
+        _check(st, "qs_mx_quant2_batched_v")
+        mx_quant2_batched_last_route = route
     return rc, rs, cc, cs
 
 

@@ -1,6 +1,6 @@
-"""What the products on MX codes (``mx_gemm.py``, ``mx_conv.py``, ``mx_conv_transpose.py``, ``mx_conv_train.py``) and their two training
-layers say alike, stated once: the argument checks of an operand, of ``out_dtype``, of a bias and of a training entry, the options /
-stochastic-rounding counter / ``repr`` of ``MXTrainLinear`` and ``MXTrainConv2d`` (``_MXTrainMixin``), and the two steps their autograd
+"""What the products on MX codes (``mx_gemm.py``, ``mx_conv.py``, ``mx_conv_transpose.py``, ``mx_conv_train.py``, ``mx_batched_train.py``) and
+their training layers say alike, stated once: the argument checks of an operand, of ``out_dtype``, of a bias and of a training entry,
+the options / stochastic-rounding counter / ``repr`` of ``MXTrainLinear`` and ``MXTrainConv2d`` (``_MXTrainMixin``), and the two steps their autograd
 functions share.  Private: the public modules import from here and keep their own shape messages."""
 from typing import NamedTuple
 
@@ -126,17 +126,19 @@ def _check_bias(bias, n: int, first: str, device):
             raise ValueError(f"{first} is on {device} but bias on {bias.device}")
 
 
-def _check_train_entry(x, weight, bias, fmts, grad_rounding: str, step, wgrad_split_k):
-    """what `mx_linear` and `mx_conv2d_train` check before the shapes"""
-    _split_request(wgrad_split_k, "wgrad_split_k")
+def _check_train_entry(x, weight, bias, fmts, grad_rounding: str, step, wgrad_split_k, names=("x", "weight")):
+    """what `mx_linear`, `mx_conv2d_train` and `mx_bmm_train` check before the shapes.  `names`: what the two operands are called in
+    the messages; `wgrad_split_k` None: an entry without that option"""
+    if wgrad_split_k is not None:
+        _split_request(wgrad_split_k, "wgrad_split_k")
     for fmt in fmts:
         _mx_format(fmt)
-    for name, t in (("x", x), ("weight", weight)) + ((("bias", bias),) if bias is not None else ()):
+    for name, t in ((names[0], x), (names[1], weight)) + ((("bias", bias),) if bias is not None else ()):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
         _check_dtype(name, t.dtype)
         if t.device != x.device:
-            raise ValueError(f"x is on {x.device} but {name} on {t.device}")
+            raise ValueError(f"{names[0]} is on {x.device} but {name} on {t.device}")
     _mx_check_rounding(grad_rounding, step, x)
 
 
@@ -177,7 +179,8 @@ class _MXTrainMixin:
 
 
 def _save_train_ctx(ctx, fmts, sr, wgrad_split_k, x: torch.Tensor, bias):
-    """both autograd functions' fields.  `step` of `sr` is advanced in place by the backward: an attribute, not a saved tensor"""
+    """the autograd functions' fields (`wgrad_split_k` None where the entry has no such option).  `step` of `sr` is advanced in place
+    by the backward: an attribute, not a saved tensor"""
     ctx.fmts, ctx.sr, ctx.wgrad_split_k = fmts, sr, wgrad_split_k
     ctx.x_dtype = x.dtype
     ctx.bias_dtype = None if bias is None else bias.dtype

@@ -22,7 +22,7 @@ Layer step: forward + backward of one linear, (M, N, K) = the two ViT-B MLP shap
   and the step's launches one by one (HIP events around each): the four two-way calls and the three GEMMs.  On commits with
   split-K (`wgrad_split_k`) the step is the default one ("auto": the weight gradient of the two ViT shapes is split), the step with
   wgrad_split_k=1 is timed next to it, and the weight-gradient entry of the launch list is the split call, both launches.
-  `--no-quantizer` skips the two-way quantizer section.
+  `--no-quantizer` skips the two-way quantizer section, `--no-layer` the layer step.
 Stochastic rounding (commits that have it; `--no-stochastic` skips): the two-way call on a gradient-like bf16 tensor of the three
   quantizer shapes, E5M2 and FP4, both pairs, stochastic with a device step counter, next to the nearest-mode call and to the
   yardstick (t) / (s) above in that format.  THE BAR: the stochastic call no slower than the yardstick.  And the layer step with
@@ -263,6 +263,7 @@ def main():
     ap.add_argument("--commit", default="", help="recorded in the output: the commit the figures were measured on")
     ap.add_argument("--no-stochastic", action="store_true", help="skip the stochastic-rounding cases")
     ap.add_argument("--no-quantizer", action="store_true", help="skip the two-way quantizer cases")
+    ap.add_argument("--no-layer", action="store_true", help="skip the layer step (and the stochastic cases, which time it too)")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -282,9 +283,10 @@ def main():
 
     if not args.no_quantizer:
         bench_quantizer(args, out, save)
-    bench_layer(args, out, save)
+    if not args.no_layer:
+        bench_layer(args, out, save)
     import inspect
-    if out["has_two_way"] and "rounding" in inspect.signature(qs.mx_quantize_2way).parameters and not args.no_stochastic:
+    if not args.no_layer and out["has_two_way"] and "rounding" in inspect.signature(qs.mx_quantize_2way).parameters and not args.no_stochastic:
         out["stochastic_quantizer"], out["stochastic_layer_step"] = [], []
         bench_stochastic(args, out, save)
     print("wrote", args.out)

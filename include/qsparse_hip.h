@@ -896,7 +896,13 @@ int qs_mx_quant_route(const qs_mx_quant_args* args);
  * i.e. A . B^T with B laid out as an nn.Linear weight.  val_*: the value of the element format's code (sign, exponent, mantissa in
  * the low bits of the byte, as qs_mx_quant_fwd_v writes them).  Products are exact, the sum is accumulated in float32 by
  * v_mfma_scale_f32_16x16x128_f8f6f4 in steps of 128 along K (the order inside a step is the instruction's), the bias is added in
- * float32, the result rounded once to ydt.  The two formats may differ.
+ * float32, the result rounded once to ydt.  "Accumulated in float32" is as accurate as the instruction, measured (DESIGN.md 3b,
+ * "Accumulation"): inside a group of eight consecutive k a product keeps its bits down to 2^(E - 13), E the largest sum of two
+ * operand exponents (exponent fields, scale bytes included; zero codes aside) in the group, and is cut toward zero below; the group
+ * sums, the four blocks of a step and the incoming sum are then added with 24 significant bits.  So
+ *   |y - exact| <= sum over the groups of (the terms with a bit below the group's quantum) x quantum
+ *                  + 18 ceil(K / 128) 2^-23 sum_k |a_k b_k| + ulp_ydt(y) + 2^-23 |bias|
+ * at every K (tests/mx_gemm_ref.py, model_bound); the first term is zero when both sides are FP4.  The two formats may differ.
  *   - Any M, N >= 0 (M == 0 or N == 0: nothing is enqueued) and K >= 1.  K % 32 != 0: the last block is short, the missing
  *     elements count as zero.  Nothing outside the five operands and y is read or written.
  *   - A scale byte 0xFF (the quantizer's mark of a block that held NaN / Inf) makes every output whose dot product reads that

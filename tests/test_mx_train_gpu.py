@@ -11,7 +11,8 @@ they survive only down to 2^-13 of the group's larger one (probe sect
 contraction lengths where the bound is applied to float32 outputs at or above that, the ragged one included.  (Measured with (M, N,
 K) = (100, 70, 90), float32: largest |err| / bound 0.86 for y at L = 90 and 1.14 for dx at L = 70, while y, dx and dW were bit-identical
 to `mx_matmul` on the one-way quantizer's bytes -- the product kernel's own accumulation, not the new path; (256, 192, 320) gave 0.12 /
-0.23 / 0.15.)"""
+0.23 / 0.15.)  Below L = 512 the products are held to the bound that follows the instruction's measured accumulation,
+``mx_gemm_ref.model_bound``, in tests/test_mx_short_k_gpu.py -- (100, 70, 90) and (45, 33, 40) of ``mx_linear`` among its cases."""
 import copy
 
 import pytest

@@ -149,7 +149,11 @@ def model_bound(a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, y64, S, bias
     bit, less than half a quantum of the larger, and rounds the sum to nearest even, at most half a quantum of it (`2^24 + 3 -> 2^24
     + 4`, `2^25 + 3 -> 2^25`, `2^24 - 1` exact): 4 a step.  The block sum itself is carried wide (4f: `C = -2^24` plus a block
     of `2^24 + 3` gives 3).  That is 16; F_ACROSS stays at the 18 it was set to beforehand (see there).  Every quantum is 2^-23 of a partial sum's binade, at most 2^-23 S.  `inside`: inside_groups of the same operands,
-    where a caller has it already (it depends on neither the bias nor the output dtype)."""
+    where a caller has it already (it depends on neither the bias nor the output dtype).
+
+    The one rounding to the output dtype costs the bound a whole ulp, which cannot tell a wrong rounding rule from the right one.  That
+    rounding is asserted bit for bit, apart from this bound, by tests/test_mx_epilogue_rounding_gpu.py on the operands of `method_a` /
+    `method_b` below, whose float32 value before the cast is exact (tests/test_mx_epilogue_rounding.py: the same on the CPU paths)."""
     K = a_codes.shape[-1]
     steps = -(-K // STEP)                                                 # (split-K slices are whole steps: the same count)
     inside = inside_groups(a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt) if inside is None else inside
@@ -282,3 +286,248 @@ def bits_equal(a, b):
     """elementwise bit-for-bit equality of two tensors of one floating dtype (all NaNs alike), on their device"""
     assert a.dtype == b.dtype and a.shape == b.shape
     return (a.isnan() & b.isnan()) | ((a == b) & (torch.signbit(a) == torch.signbit(b)))
+
+
+# ---- the output rounding, bit for bit: products whose float32 value before the cast is known exactly and has a full mantissa ------------
+# (tests/test_mx_epilogue_rounding.py and its GPU twin).  Everything below works on bit patterns held as Python ints or int64
+# tensors; a float tensor is built from them only to be handed to the code under test.
+TWO_BYTE = (torch.bfloat16, torch.float16)
+# unbiased exponents of the binades the targets are drawn from: the lowest normal one of the dtype, two next to 1, one far on either
+# side, the top one
+BINADES = {torch.bfloat16: (-126, -60, -1, 0, 60, 127), torch.float16: (-14, -8, -1, 0, 9, 15)}
+
+
+def f32_from_bits(bits):
+    """float32 tensor of the given bit patterns (ints 0 .. 2^32 - 1)"""
+    u = torch.as_tensor(bits, dtype=torch.int64).reshape(-1)
+    return torch.where(u >= 2 ** 31, u - 2 ** 32, u).to(torch.int32).view(torch.float32)
+
+
+def f32_bits(t):
+    """int64 tensor of the bit patterns of a float32 tensor"""
+    assert t.dtype == torch.float32
+    return t.detach().cpu().contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+
+
+def two_byte_from_bits(bits, dtype):
+    """bfloat16 / float16 tensor of the given 16-bit patterns (int64 tensor)"""
+    u = torch.as_tensor(bits, dtype=torch.int64)
+    return torch.where(u >= 2 ** 15, u - 2 ** 16, u).to(torch.int16).view(dtype)
+
+
+def rounding_targets(dtype):
+    """float32 tensor [T] of the values the output cast to `dtype` (bfloat16 or float16) is asserted on, every one a float32 normal
+    (2^-126 <= |t| < 2^128), none repeated.  BINADES[dtype] crossed with four patterns of the kept mantissa bits (all clear: kept lsb
+    even; the lsb alone: odd; an alternating one, even; all set, odd -- its round-up carries into the next binade, from the top binade to
+    Inf), the six discarded parts 0, one float32 ulp, half - ulp, half, half + ulp, all ones, and both signs; then the overflow edge
+    and, for float16, the underflow edge with its ties on either side of the subnormals.  bfloat16's subnormals are float32's and are
+    left to the one-term test."""
+    keep = MANT[dtype] - 1                     # mantissa bits the dtype stores: 7, 10
+    drop = 23 - keep                           # discarded ones: 16, 13
+    half = 1 << (drop - 1)
+    alternating = int("10" * 5, 2) >> (10 - keep) << 1 & ((1 << keep) - 1)         # ...1010100 / ...10101010100: lsb clear
+    out = []
+    for e in BINADES[dtype]:
+        for hi in (0, 1, alternating, (1 << keep) - 1):
+            for d in (0, 1, half - 1, half, half + 1, 2 * half - 1):
+                out.append((e + 127) << 23 | hi << drop | d)
+    if dtype == torch.float16:
+        top = (15 + 127) << 23 | 0x3FF << 13                                   # 65504
+        out += [top, top + half - 1, top + half, (16 + 127) << 23]             # 65504, just below 65520, 65520 (tie -> Inf), 2^16
+        ex = lambda e: (e + 127) << 23
+        out += [ex(-14),                       # the smallest normal
+                ex(-15) | 0x3FF << 13,         # 2^-14 - 2^-25: the tie between the largest subnormal and 2^-14 (-> 2^-14, even)
+                ex(-24),                       # the smallest subnormal
+                ex(-24) | 1 << 22,             # 1.5 2^-24: a tie -> 2^-23
+                ex(-25),                       # a tie -> 0
+                ex(-25) | 1,                   # -> 2^-24
+                ex(-26)]                       # -> 0
+    else:
+        top = 0x7F7F0000                                                       # the largest finite bfloat16
+        out += [top, top + 0x7FFF, top + 0x8000, 0x7F7FFFFF]                   # finite, finite, a tie -> Inf, FLT_MAX
+    seen, bits = set(), []
+    for b in out:
+        if b not in seen:
+            seen.add(b)
+            bits += [b, b | 1 << 31]
+    t = f32_from_bits(bits)
+    assert bool(((t.abs().double() >= 2.0 ** -126) & (t.abs().double() < 2.0 ** 128)).all())
+    return t
+
+
+def round_once_bits(t, dtype):
+    """int64 tensor: the bit patterns of float32 `t` rounded once, to nearest with ties to even, to bfloat16 or float16.  Integer
+    arithmetic on the float32 bit pattern, from the definition: |t| = sig 2^E; the result is the multiple of the quantum 2^q, q =
+    max(floor(log2 |t|), emin) - (P - 1), nearest to it -- then encoded (zero, subnormal, normal, Inf past the largest finite).
+    Every NaN becomes the quiet NaN 0x7FC0 / 0x7E00."""
+    P, emin = MANT[dtype], EMIN[dtype]
+    emax, ebits = (127, 8) if dtype == torch.bfloat16 else (15, 5)
+    u = f32_bits(t)
+    sign, exp, man = u >> 31, (u >> 23) & 0xFF, u & 0x7FFFFF
+    sig = torch.where(exp > 0, man | 1 << 23, man)
+    E = exp.clamp(min=1) - 127 - 23
+    length = torch.zeros_like(sig)
+    for i in range(24):
+        length += ((sig >> i) > 0).to(torch.int64)                            # bit length of sig
+    q = torch.maximum(E + length - 1, torch.full_like(E, emin)) - (P - 1)
+    shift = (q - E).clamp(max=40)              # >= 13 for either dtype; past 25 nothing of sig is left of the half
+    kept, rem, tie = sig >> shift, sig & ((1 << shift) - 1), 1 << (shift - 1)
+    kept = kept + ((rem > tie) | ((rem == tie) & (kept & 1 == 1))).to(torch.int64)
+    carry = kept >= 1 << P                     # rounded up to 2^P: one more binade
+    kept, q = torch.where(carry, kept >> 1, kept), q + carry.to(torch.int64)
+    normal = kept >= 1 << (P - 1)
+    field = torch.where(normal, q + (P - 1) + emax, torch.zeros_like(q))       # the biased exponent; 0: zero or subnormal
+    inf = (1 << ebits) - 1
+    mag = torch.where(field >= inf, torch.full_like(q, inf << (P - 1)), field << (P - 1) | (kept & ((1 << (P - 1)) - 1)))
+    mag = torch.where(exp == 255, torch.where(man > 0, torch.full_like(q, inf << (P - 1) | 1 << (P - 2)), torch.full_like(q, inf << (P - 1))), mag)
+    return torch.where((exp == 255) & (man > 0), mag, sign << 15 | mag)
+
+
+def cast_bits(t, dtype):
+    """the same through torch's own cast: the second definition"""
+    return t.detach().cpu().to(dtype).view(torch.int16).to(torch.int64) & 0xFFFF
+
+
+def expected_rounded(t, dtype):
+    """what an output whose float32 value before the cast is `t` must be, in `dtype`: `t` itself, or round_once_bits' value"""
+    return t.clone() if dtype == torch.float32 else two_byte_from_bits(round_once_bits(t, dtype), dtype).reshape(t.shape)
+
+
+def strict_class(want32):
+    """the outputs that are compared bit for bit: those whose exact value before the cast is a float32 -- finite, which a float32
+    tensor of exact values is by construction.  The share is asserted to be 1.0 wherever it is used"""
+    return want32.isfinite() & (want32.double().float() == want32)
+
+
+def one_codes(fmt):
+    """(the code of +1.0, the code of -1.0) of `fmt`: every format has both"""
+    t = table(fmt)[: 1 << WIDTH[fmt]]
+    return int((t == 1.0).nonzero()[0]), int((t == -1.0).nonzero()[0])
+
+
+def _power(sign, e):
+    """float32 bits of (-1)^sign 2^e, -126 <= e <= 127"""
+    assert -126 <= e <= 127
+    return sign << 31 | (e + 127) << 23
+
+
+def _as_int(terms, floor):
+    return sum((-1 if s else 1) << (e - floor) for s, e in terms)
+
+
+def representable24(x):
+    """the integer x (times any power of two) has at most 24 significant bits"""
+    x = abs(x)
+    return x == 0 or x.bit_length() - ((x & -x).bit_length() - 1) <= 24
+
+
+def subsets_exact(terms):
+    """every subset of the signed powers of two `terms` [(sign, e)] sums to something 24 bits hold: then every float32 addition of
+    them, in any order and any grouping, is exact"""
+    floor = min(e for _, e in terms)
+    return all(representable24(_as_int([terms[i] for i in range(len(terms)) if mask >> i & 1], floor)) for mask in range(1 << len(terms)))
+
+
+def power_terms(bits):
+    """the float32 normal with the bit pattern `bits` as at most four signed powers of two [(sign, e)] of distinct exponents -126 ..
+    127, every subset of which 24 bits hold -- or None where there is no such form (more than four, or it needs 2^128).  Its set
+    bits where they are at most four; else the non-adjacent form (a run of ones 2^a + ... + 2^b as 2^(a + 1) - 2^b: `half - ulp`
+    becomes + half - ulp), which is the shortest signed form."""
+    sign, e = bits >> 31, ((bits >> 23) & 0xFF) - 127
+    sig = (bits & 0x7FFFFF) | 1 << 23
+    binary = [(sign, e - 23 + i) for i in range(24) if sig >> i & 1]
+    naf, x, i = [], sig, 0
+    while x:
+        if x & 1:
+            digit = 2 - (x & 3)                # +1 or -1
+            naf.append((sign if digit > 0 else sign ^ 1, e - 23 + i))
+            x -= digit
+        x >>= 1
+        i += 1
+    for terms in (binary, naf):
+        if len(terms) <= 4 and all(-126 <= te <= 127 for _, te in terms) and subsets_exact(terms):
+            return terms[::-1]                 # leading term first
+    return None
+
+
+def tile_targets(targets, N, shift=0):
+    """[N]: the targets repeated cyclically from index `shift` on, so that every one meets every position of the store"""
+    return targets[(torch.arange(N) + shift) % len(targets)]
+
+
+def _sprinkle(g, rows, K):
+    """zero codes [rows, K] under random scale bytes 0 .. 254, which must not matter"""
+    return torch.zeros(rows, K, dtype=torch.uint8), torch.randint(0, 255, (rows, -(-K // BLOCK)), generator=g).to(torch.uint8)
+
+
+def method_a(g, fa, fb, M, K, k0, t, zero_rows=()):
+    """METHOD A, one term plus a bias: (a_codes [M, K], a_scales, b_codes [N, K], b_scales, bias [N], want [M, N] float32).  Column n
+    of B holds one +-1.0 code at k0 under the scale byte that makes p_n = sign(t_n) 2^floor(log2 |t_n|) -- the byte is t_n's own
+    exponent field -- every row of A 1.0 at k0 under scale byte 127, and bias[n] = t_n - p_n: exact in float32 since the two share a
+    binade, so fl32(p_n + bias[n]) = t_n with no rounding (both asserted in float64 here).  A bias that comes out as zero is -0 in
+    every other such column.  The rows `zero_rows` of A hold zero codes only: their output is fl32(+0 + bias[n]), in which -0 becomes
+    +0.  Blocks of zero codes carry random scale bytes."""
+    N, bits = len(t), f32_bits(t)
+    one_a, (one_b, minus_b) = one_codes(fa)[0], one_codes(fb)
+    ac, asc = _sprinkle(g, M, K)
+    bc, bsc = _sprinkle(g, N, K)
+    ac[:, k0], asc[:, k0 // BLOCK] = one_a, 127
+    for r in zero_rows:
+        ac[r, k0] = 0
+    bc[:, k0] = torch.where(bits >> 31 == 1, minus_b, one_b).to(torch.uint8)
+    bsc[:, k0 // BLOCK] = ((bits >> 23) & 0xFF).to(torch.uint8)
+    assert int(bsc[:, k0 // BLOCK].min()) >= 1 and int(bsc[:, k0 // BLOCK].max()) <= 254
+    p = f32_from_bits(bits & 0xFF800000)
+    bias = t - p
+    assert torch.equal(bias.double(), t.double() - p.double()) and torch.equal(p.double() + bias.double(), t.double())
+    zero = (bias == 0).nonzero().reshape(-1)
+    bias[zero[::2]] = -0.0
+    want = t.repeat(M, 1)
+    for r in zero_rows:
+        want[r] = torch.zeros(N) + bias
+    return ac, asc, bc, bsc, bias, want
+
+
+def method_b_targets(dtype, with_bias=False):
+    """the targets of `dtype` that METHOD B can state, as (t [T] float32, terms: a list of [(sign, e)] per target, bias [T] float32 or
+    None).  Without a bias the terms sum to t.  With one they sum to t with its discarded bits below the half bit cleared, and bias
+    = t minus that sum: the two share t's binade, so the bias is exact and fl32(sum + bias) = t without rounding; the accumulator
+    then holds an exact tie (or an exact value of the dtype) and only the bias decides the rounding."""
+    drop = 23 - (MANT[dtype] - 1)
+    ts, terms, biases = [], [], []
+    for b in f32_bits(rounding_targets(dtype)).tolist():
+        acc = b & ~((1 << (drop - 1)) - 1) if with_bias else b
+        found = power_terms(acc)
+        if found is None:
+            continue
+        ts.append(b)
+        terms.append(found)
+        biases.append(acc)
+    t = f32_from_bits(ts)
+    if not with_bias:
+        return t, terms, None
+    acc = f32_from_bits(biases)
+    bias = t - acc
+    assert torch.equal(bias.double(), t.double() - acc.double()) and torch.equal(acc.double() + bias.double(), t.double())
+    return t, terms, bias
+
+
+def method_b(g, fa, fb, M, K, blocks, terms):
+    """METHOD B, a few signed powers of two and no product bias: (a_codes [M, K], a_scales, b_codes [N, K], b_scales).  `blocks` names
+    four blocks of 32 along K.  Column n of B holds its term i -- in an order shuffled per column -- as a +-1.0 code in block
+    blocks[i] under the scale byte e_i + 127, every row of A 1.0 at the same four places under scale byte 127.  Everything else is
+    the zero code under a random scale byte.  The sum over K is then the sum of the terms, each float32 addition of which is exact
+    (subsets_exact), whatever the instruction's, the K loop's or the split's order."""
+    assert len(blocks) == 4 and len(set(blocks)) == 4 and max(blocks) < -(-K // BLOCK)
+    N = len(terms)
+    one_a, (one_b, minus_b) = one_codes(fa)[0], one_codes(fb)
+    ac, asc = _sprinkle(g, M, K)
+    bc, bsc = _sprinkle(g, N, K)
+    at = [blk * BLOCK + int(torch.randint(0, min(BLOCK, K - blk * BLOCK), (1,), generator=g)) for blk in blocks]
+    for blk, k in zip(blocks, at):
+        ac[:, k], asc[:, blk] = one_a, 127
+    for n, tn in enumerate(terms):
+        order = torch.randperm(4, generator=g).tolist()
+        for i, (s, e) in enumerate(tn):
+            bc[n, at[order[i]]], bsc[n, blocks[order[i]]] = (minus_b if s else one_b), e + 127
+    return ac, asc, bc, bsc

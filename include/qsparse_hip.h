@@ -1392,6 +1392,84 @@ typedef struct qs_mx_bmm_q_args {
 int qs_mx_bmm_q_v(const qs_mx_bmm_q_args* args);
 int qs_mx_bmm_q_route(const qs_mx_bmm_q_args* args);
 
+/* ---- MX grouped matrix product ----------------------------------------------------------------------------------------------
+ * Added without raising QS_ABI_VERSION (28), by the same rule as qs_mx_matmul_v above: symbols are only added.
+ *
+ * The ragged product of a mixture-of-experts layer after routing: the T rows of a are E consecutive groups of DIFFERENT sizes, some
+ * of them empty, and group e is multiplied by its own weight b[e].  The sizes are known only on the device: `offs` [E] int32 in
+ * DEVICE memory holds the cumulative END row of every group (the convention of torch's grouped mm).  The host side does no
+ * allocation, no synchronisation and no read of offs; it is one launch, always.
+ * Definition (normative).  Let c_-1 = 0 and c_e = min(max(offs[e], c_{e-1}), T).  Group e is the rows [c_{e-1}, c_e).
+ *   - Rows of a group: for r in group e, y[r, :] is what qs_mx_matmul_v writes for that row with the weight b[e] and the bias of e,
+ *     bit for bit -- the same walk along K, the same MFMA order, one rounding -- so everything said there about range, short last
+ *     blocks and unspecified code bytes holds per row.
+ *   - Tail rows: rows r >= c_{E-1} belong to no group.  They get +0, and no bias is added; in the codes-out form they get code 0 and
+ *     scale byte 0, what the quantizer writes for an all-zero block.  This is what a capacity-padded token buffer needs.
+ *   - Clamped boundaries: with the running maximum and the clamp the groups partition [0, c_{E-1}) for ANY content of offs.  Every
+ *     row of the output is stored exactly once and no address outside the operands is formed.  A non-monotone or out-of-range offs
+ *     gives the results for the clamped boundaries, never a fault.  The clamp is part of the definition, not an optimisation.
+ *   - bias is NULL, [N] shared by the groups (bias_batch_stride == 0) or [E, N] (bias_batch_stride == N, in elements); any other
+ *     stride is QS_ERR_ARG.
+ *   - Checks in the order and with the status codes of qs_mx_bmm_v: a NULL a_codes / a_scales / y, with E > 0 a NULL b_codes /
+ *     b_scales / offs, a format outside enum qs_mx_format, a negative extent, E beyond QS_MX_GROUPED_MAX_GROUPS or a bad bias stride is
+ *     QS_ERR_ARG; then ydt (QS_ERR_DTYPE); then y aligned to its element, bias and offs to 4 bytes (QS_ERR_ALIGN).  T == 0 or N == 0:
+ *     nothing is enqueued, 0 is returned.  E == 0 is legal: every row is then a tail row.  K == 0 of a non-empty product, any of T K,
+ *     E N K, T N beyond INT64_MAX, or a grid beyond 2^31 - 1 work-groups: QS_ERR_ARG.
+ *   - One work-group per 128 x 128 tile; the M-tiles are group-relative, so no tile holds rows of two groups.  The host cannot know
+ *     their number: the grid is the bound floor((T + 127 (E + 1)) / 128) ceil(N / 128), and a work-group beyond the real total returns
+ *     at once.
+ *   - Routes: K % 16 == 0 with both code bases 16-byte aligned (every group's rows and every weight then are) takes
+ *     QS_MX_GEMM_ROUTE_VEC, anything else QS_MX_GEMM_ROUTE_PLAIN, with the same bits.  No workspace, no split-K form. */
+/* The most groups of one call.  Every work-group finds its group by walking offs from the front, so its start-up cost grows with E,
+ * and the grid carries up to E + 1 work-groups per column of tiles that walk all of offs, find no tile and leave.  A full walk
+ * measured 2.7 us at 64 groups and 41 us at 1024, which is already several times the 128 x 128 x 1024 tile it
+ * precedes: the kernel is meant for the expert counts in use (8 .. 256 a layer), and the cap bounds what a call can waste on the
+ * walk (0.16 ms a work-group at 4096) rather than promise speed there.  More groups than this want another decode, not this one. */
+#define QS_MX_GROUPED_MAX_GROUPS 4096
+typedef struct qs_mx_grouped_matmul_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_grouped_matmul_args) as the caller compiled it */
+    int32_t a_format, b_format;      /* enum qs_mx_format, may differ */
+    const uint8_t* a_codes;          /* [T, K], one code per byte, dense: the rows of all groups, group after group */
+    const uint8_t* a_scales;         /* [T, ceil(K / 32)] E8M0 bytes */
+    const uint8_t* b_codes;          /* [E, N, K]: one weight per group */
+    const uint8_t* b_scales;         /* [E, N, ceil(K / 32)] */
+    const float* bias;               /* nullable, float32 [N] or [E, N] */
+    int64_t bias_batch_stride;       /* elements from one group's bias to the next: 0 or N */
+    const int32_t* offs;             /* [E] in DEVICE memory: the cumulative end row of every group; never read by the host */
+    void* y;                         /* [T, N] dense */
+    int32_t ydt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    int64_t T, E, N, K;
+    qs_stream_t stream;
+} qs_mx_grouped_matmul_args;
+int qs_mx_grouped_matmul_v(const qs_mx_grouped_matmul_args* args);
+/* the kernel qs_mx_grouped_matmul_v launches for these operands, nothing enqueued and offs not read: QS_MX_GEMM_ROUTE_*, 0 for an
+ * empty product, or the QS_ERR_* the call would return */
+int qs_mx_grouped_matmul_route(const qs_mx_grouped_matmul_args* args);
+
+/* The grouped product with the quantizing epilogue ("MX products that write MX codes" above): out_codes [T, N] and out_scales
+ * [T, ceil(N / 32)] instead of y, the rows of group e bit for bit what qs_mx_matmul_q_v writes for them with the weight b[e], the tail
+ * rows code 0 and scale byte 0 whatever `act` is.  Checks and their precedence are those of qs_mx_matmul_q_v with the additions of
+ * qs_mx_grouped_matmul_v; out_codes sharing a byte with a_codes or b_codes is QS_ERR_ARG.  Routes as qs_mx_grouped_matmul_route. */
+typedef struct qs_mx_grouped_matmul_q_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_grouped_matmul_q_args) as the caller compiled it */
+    int32_t a_format, b_format;      /* the operands of qs_mx_grouped_matmul_args, with their meaning ... */
+    const uint8_t* a_codes;
+    const uint8_t* a_scales;
+    const uint8_t* b_codes;
+    const uint8_t* b_scales;
+    const float* bias;
+    int64_t bias_batch_stride;
+    const int32_t* offs;
+    int32_t out_format;              /* ... and: enum qs_mx_format of the output */
+    int32_t act;                     /* QS_MX_ACT_* */
+    uint8_t* out_codes;              /* [T, N], one code per byte */
+    uint8_t* out_scales;             /* [T, ceil(N / 32)] E8M0 bytes */
+    int64_t T, E, N, K;
+    qs_stream_t stream;
+} qs_mx_grouped_matmul_q_args;
+int qs_mx_grouped_matmul_q_v(const qs_mx_grouped_matmul_q_args* args);
+int qs_mx_grouped_matmul_q_route(const qs_mx_grouped_matmul_q_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

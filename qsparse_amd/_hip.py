@@ -123,6 +123,10 @@ SIGNATURES = {
     "qs_mx_bmm_route": (c_int, [_P]),
     "qs_mx_bmm_q_v": (c_int, [_P]),
     "qs_mx_bmm_q_route": (c_int, [_P]),
+    "qs_mx_grouped_matmul_v": (c_int, [_P]),
+    "qs_mx_grouped_matmul_route": (c_int, [_P]),
+    "qs_mx_grouped_matmul_q_v": (c_int, [_P]),
+    "qs_mx_grouped_matmul_q_route": (c_int, [_P]),
 }
 
 
@@ -281,6 +285,19 @@ class MxBmmArgs(ctypes.Structure):
 class MxBmmQArgs(ctypes.Structure):
     """`qs_mx_bmm_q_args` of include/qsparse_hip.h"""
     _fields_ = _codes_out_fields(MxBmmArgs._fields_)
+
+
+class MxGroupedMatmulArgs(ctypes.Structure):
+    """`qs_mx_grouped_matmul_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("a_format", c_int32), ("b_format", c_int32), ("a_codes", c_void_p),
+                ("a_scales", c_void_p), ("b_codes", c_void_p), ("b_scales", c_void_p), ("bias", c_void_p), ("bias_batch_stride", c_int64),
+                ("offs", c_void_p), ("y", c_void_p), ("ydt", c_int32), ("T", c_int64), ("E", c_int64), ("N", c_int64), ("K", c_int64),
+                ("stream", c_void_p)]
+
+
+class MxGroupedMatmulQArgs(ctypes.Structure):
+    """`qs_mx_grouped_matmul_q_args` of include/qsparse_hip.h"""
+    _fields_ = _codes_out_fields(MxGroupedMatmulArgs._fields_)
 
 
 class MultiRow(ctypes.Structure):
@@ -1101,6 +1118,66 @@ def mx_bmm_q(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes:
             st = lib.qs_mx_bmm_q_v(ctypes.byref(a))
         _check(st, "qs_mx_bmm_q_v")
         mx_bmm_q_last_route = route
+    return codes, scales
+
+
+mx_grouped_last_route = None      # the QS_MX_GEMM_ROUTE_* of the last `mx_grouped_matmul` launch (None: an empty product)
+mx_grouped_q_last_route = None    # likewise of the last `mx_grouped_matmul_q` launch
+
+
+def _mx_grouped_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, offs, bias):
+    """fill the operand fields of a grouped descriptor `a` from contiguous [T, K] / [E, N, K] codes and the int32 [E] `offs` on
+    their device, which stays there; returns (T, N)"""
+    (T, K), (E, N, _) = a_codes.shape, b_codes.shape
+    a.struct_size = ctypes.sizeof(a)
+    a.a_format, a.b_format = MX_FORMATS.index(a_fmt), MX_FORMATS.index(b_fmt)
+    a.a_codes, a.a_scales, a.b_codes, a.b_scales = _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales)
+    a.bias, a.bias_batch_stride = _ptr(bias), N if bias is not None and bias.dim() == 2 else 0
+    a.offs = _ptr(offs)
+    a.T, a.E, a.N, a.K = T, E, N, K
+    a.stream = _stream(a_codes)
+    return T, N
+
+
+def mx_grouped_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor,
+                      b_fmt: str, offs: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                      out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """y[T, N], the rows of group e = A[c_{e-1} : c_e] . B[e]^T on MX codes (qs_mx_grouped_matmul_v): `a_codes` [T, K], `b_codes`
+    [E, N, K] uint8, scales [*, ceil(K / 32)] uint8, `offs` int32 [E] (cumulative group ends), all contiguous GPU tensors
+    (qsparse_amd/mx_grouped.py checks); `bias` float32 [N], [E, N] or None.  ONE launch; `offs` is not read on the host."""
+    global mx_grouped_last_route
+    lib = load()
+    a = MxGroupedMatmulArgs()
+    T, N = _mx_grouped_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, offs, bias)
+    y = torch.empty((T, N), dtype=out_dtype, device=a_codes.device)
+    mx_grouped_last_route = None
+    if T and N:
+        a.y, a.ydt = _ptr(y), _DT[out_dtype]
+        route = lib.qs_mx_grouped_matmul_route(ctypes.byref(a))
+        with _timed(f"mx_grouped_matmul[{route}]", a_codes, a_scales, b_codes, b_scales, bias, y):
+            st = lib.qs_mx_grouped_matmul_v(ctypes.byref(a))
+        _check(st, "qs_mx_grouped_matmul_v")
+        mx_grouped_last_route = route
+    return y
+
+
+def mx_grouped_matmul_q(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor,
+                        b_fmt: str, offs: torch.Tensor, bias: Optional[torch.Tensor], out_fmt: str, act=None):
+    """the MX codes [T, N] and scales [T, ceil(N / 32)] in `out_fmt` of the grouped product with its bias and `act`
+    (qs_mx_grouped_matmul_q_v): operands as `mx_grouped_matmul`'s, `act` None or "relu".  ONE launch, no float y."""
+    global mx_grouped_q_last_route
+    lib = load()
+    a = MxGroupedMatmulQArgs()
+    T, N = a_codes.shape[0], b_codes.shape[1]
+    codes, scales = _mx_codes_out(a, (T,), N, out_fmt, act, a_codes.device, None)
+    mx_grouped_q_last_route = None
+    if T and N:
+        _mx_grouped_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, offs, bias)
+        route = lib.qs_mx_grouped_matmul_q_route(ctypes.byref(a))
+        with _timed(f"mx_grouped_matmul_q[{route}]", a_codes, a_scales, b_codes, b_scales, bias, codes, scales):
+            st = lib.qs_mx_grouped_matmul_q_v(ctypes.byref(a))
+        _check(st, "qs_mx_grouped_matmul_q_v")
+        mx_grouped_q_last_route = route
     return codes, scales
 
 

@@ -1141,15 +1141,20 @@ def _mx_grouped_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, 
 
 def mx_grouped_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor,
                       b_fmt: str, offs: torch.Tensor, bias: Optional[torch.Tensor] = None,
-                      out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+                      out_dtype: torch.dtype = torch.float32, out=None) -> torch.Tensor:
     """y[T, N], the rows of group e = A[c_{e-1} : c_e] . B[e]^T on MX codes (qs_mx_grouped_matmul_v): `a_codes` [T, K], `b_codes`
     [E, N, K] uint8, scales [*, ceil(K / 32)] uint8, `offs` int32 [E] (cumulative group ends), all contiguous GPU tensors
-    (qsparse_amd/mx_grouped.py checks); `bias` float32 [N], [E, N] or None.  ONE launch; `offs` is not read on the host."""
+    (qsparse_amd/mx_grouped.py checks); `bias` float32 [N], [E, N] or None.  ONE launch; `offs` is not read on the host.
+    `out`: a contiguous tensor of T N elements of `out_dtype` to write instead of a new one, as the guard-byte tests carve it."""
     global mx_grouped_last_route
     lib = load()
     a = MxGroupedMatmulArgs()
     T, N = _mx_grouped_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, offs, bias)
-    y = torch.empty((T, N), dtype=out_dtype, device=a_codes.device)
+    if out is None:
+        y = torch.empty((T, N), dtype=out_dtype, device=a_codes.device)
+    else:
+        assert out.dtype == out_dtype and out.is_contiguous() and out.numel() == T * N, "out: T N elements of out_dtype"
+        y = out.view(T, N)
     mx_grouped_last_route = None
     if T and N:
         a.y, a.ydt = _ptr(y), _DT[out_dtype]
@@ -1162,14 +1167,15 @@ def mx_grouped_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str,
 
 
 def mx_grouped_matmul_q(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor,
-                        b_fmt: str, offs: torch.Tensor, bias: Optional[torch.Tensor], out_fmt: str, act=None):
+                        b_fmt: str, offs: torch.Tensor, bias: Optional[torch.Tensor], out_fmt: str, act=None, out=None):
     """the MX codes [T, N] and scales [T, ceil(N / 32)] in `out_fmt` of the grouped product with its bias and `act`
-    (qs_mx_grouped_matmul_q_v): operands as `mx_grouped_matmul`'s, `act` None or "relu".  ONE launch, no float y."""
+    (qs_mx_grouped_matmul_q_v): operands as `mx_grouped_matmul`'s, `act` None or "relu".  ONE launch, no float y.  `out`: the pair
+    (codes, scales) of `_mx_codes_out` to write instead of new tensors."""
     global mx_grouped_q_last_route
     lib = load()
     a = MxGroupedMatmulQArgs()
     T, N = a_codes.shape[0], b_codes.shape[1]
-    codes, scales = _mx_codes_out(a, (T,), N, out_fmt, act, a_codes.device, None)
+    codes, scales = _mx_codes_out(a, (T,), N, out_fmt, act, a_codes.device, out)
     mx_grouped_q_last_route = None
     if T and N:
         _mx_grouped_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, offs, bias)

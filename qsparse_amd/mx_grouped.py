@@ -21,6 +21,15 @@ _check_a = partial(_mx_common._check_operand, what="[T, K]", least=2, most=2, ne
 _check_b = partial(_mx_common._check_operand, what="[E, N, K]", least=3, most=3, needs="3 dimensions")
 
 
+def _offs_int32(offs: torch.Tensor, T: int) -> torch.Tensor:
+    """the int32 boundaries the kernel reads, on the device of ``offs`` and without a host read.  An int64 entry is clamped into ``[0,
+    min(T, 2^31 - 1)]`` BEFORE it is narrowed (a plain ``.to(torch.int32)`` wraps: 2^31 would become -2^31).  The boundaries ``c_e`` are a
+    running maximum that starts at 0 and is capped at T, so clamping every entry into ``[0, T]`` first changes none of them."""
+    if offs.dtype == torch.int64:
+        offs = offs.clamp(0, min(T, 2 ** 31 - 1))
+    return offs.to(torch.int32).contiguous()
+
+
 def mx_grouped_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
                       offs: torch.Tensor, bias: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32, *,
                       out_fmt: Optional[str] = None, act: Optional[str] = None):
@@ -36,7 +45,8 @@ def mx_grouped_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str,
     c_{E-1}`` belong to no group and are ``+0`` without a bias -- what a capacity-padded token buffer needs.
 
     GPU tensors take the HIP kernel: one launch for all groups, no synchronisation, and ``offs`` is neither read on the host nor
-    validated (an int64 one is converted to int32 on the device), so the call can be captured in a graph and replayed with other
+    validated (an int64 one is clamped into ``[0, min(T, 2^31 - 1)]`` and then narrowed to int32, on the device: narrowing alone would
+    wrap an entry beyond int32, and the clamp changes no ``c_e``), so the call can be captured in a graph and replayed with other
     boundaries written into the same tensor.  The clamp above is the kernel's: the groups partition ``[0, c_{E-1})`` for ANY content of
     ``offs``, a non-monotone or out-of-range one gives the result of the clamped boundaries and never a fault.  There is no fallback:
     without the library the call raises.  CPU tensors refuse an ``offs`` that is not nondecreasing within ``[0, T]`` with a
@@ -78,7 +88,7 @@ def mx_grouped_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str,
             raise ValueError(f"a_codes is on {a_codes.device} but bias on {bias.device}")
     if a_codes.is_cuda:
         ops = (a_codes.contiguous(), a_scales.contiguous(), a_fmt, b_codes.contiguous(), b_scales.contiguous(), b_fmt,
-               offs.to(torch.int32).contiguous(), None if bias is None else bias.contiguous())
+               _offs_int32(offs, T), None if bias is None else bias.contiguous())
         if out_fmt is not None:
             return _hip.mx_grouped_matmul_q(*ops, out_fmt, act)
         return _hip.mx_grouped_matmul(*ops, out_dtype)

@@ -126,6 +126,81 @@ def test_argument_refusals():
     assert qs.mx_grouped_matmul is mx_grouped_matmul and qs.MXGroupedLinear is MXGroupedLinear and qs.MXMoEFeedForward is MXMoEFeedForward
 
 
+# ---- the boundaries of the definition, the grid's bound on the M-tiles and the wrapper's narrowing of an int64 offs ---------------
+TILE = 128
+INT32_MIN, INT32_MAX, INT64_MIN, INT64_MAX = -2 ** 31, 2 ** 31 - 1, -2 ** 63, 2 ** 63 - 1
+TIGHT = ((1, 129, 1, 257), 1)          # sizes and tail that all leave 1 row modulo 128: the bound on the M-tiles is reached
+
+
+def clamped(offs, T):
+    """the header's boundaries in Python integers: c_-1 = 0, c_e = min(max(offs[e], c_{e-1}), T)"""
+    out, c = [], 0
+    for v in offs:
+        c = min(max(int(v), c), T)
+        out.append(c)
+    return out
+
+
+def m_tiles(offs, T):
+    """the M-tiles the kernel has work for: group-relative ones of every group, then the tail's"""
+    c = clamped(offs, T)
+    return sum(-(-(hi - lo) // TILE) for lo, hi in zip([0] + c, c)) + -(-(T - (c[-1] if c else 0)) // TILE)
+
+
+def mt_max(T, E):
+    """the grid's bound (qs_mx_gmm.h, mx_gmm_mt_max)"""
+    return (T + (TILE - 1) * (E + 1)) // TILE
+
+
+def test_the_grid_bound_holds_for_any_offs_and_the_tight_family_reaches_it():
+    g = torch.Generator().manual_seed(11)
+    cases = []
+    for _ in range(300):                                                  # random sizes with a random tail
+        E = int(torch.randint(0, 20, (1,), generator=g))
+        sizes = torch.randint(0, 300, (E,), generator=g).tolist()
+        cases.append((sum(sizes) + int(torch.randint(0, 200, (1,), generator=g)), ends_of(sizes).tolist() if E else []))
+    for _ in range(300):                                                  # any content, not sorted and out of range
+        E, T = int(torch.randint(1, 20, (1,), generator=g)), int(torch.randint(0, 1000, (1,), generator=g))
+        cases.append((T, torch.randint(-200, 1400, (E,), generator=g).tolist()))
+    for T in (0, 1, 127, 128, 129, 900):
+        for E in (0, 1, 7, 8, 9, 4096):
+            cases += [(T, [0] * E), (T, [T] * E), (T, [T] + [0] * (E - 1) if E else []), (T, [0] * (E - 1) + [T] if E else [])]
+    for E in range(0, 12):                                                # every group and the tail 1 modulo 128
+        for tail in (0, 1, 129):
+            sizes = [1 + TILE * int(v) for v in torch.randint(0, 3, (E,), generator=g)]
+            cases.append((sum(sizes) + tail, ends_of(sizes).tolist() if E else []))
+    cases += [(300, v) for v in ([-7, 100, 99, 1000, 200], [INT32_MAX] * 5, [INT32_MIN, 0, INT32_MIN, 300, INT32_MAX], [301, 0, 0, 0, 0],
+                                 [2 ** 31, 0, 0, 0, 0], [100, 2 ** 32 + 5, 150, 2 ** 40, 300], [INT64_MIN, INT64_MAX, 0], [INT64_MAX, INT64_MIN])]
+    for T, offs in cases:
+        c = clamped(offs, T)
+        assert all(0 <= lo <= hi <= T for lo, hi in zip([0] + c, c + [T])), (T, offs)          # a partition of [0, c_{E-1}) and the tail
+        assert m_tiles(offs, T) <= mt_max(T, len(offs)), (T, offs)
+    for sizes, tail in (TIGHT, (TIGHT[0], 0), ((), 129), ((1,) * 40, 1), ((129,) * 7, 257)):
+        T, offs = sum(sizes) + tail, ends_of(sizes).tolist() if sizes else []
+        assert m_tiles(offs, T) == mt_max(T, len(offs)), (sizes, tail)     # reached: an empty tail wastes nothing either
+    sizes = (0, 1, 127, 0, 0, 129, 128, 257, 0)                           # the GPU tests' main case is far from it
+    assert (m_tiles(ends_of(sizes).tolist(), sum(sizes) + 5), mt_max(sum(sizes) + 5, len(sizes))) == (9, 14)
+
+
+def test_the_int64_offs_is_clamped_before_it_is_narrowed():
+    """what the kernel is handed for an int64 ``offs`` gives the boundaries of the int64 definition; a plain ``.to(torch.int32)`` wraps
+    (2^31 -> -2^31, 2^32 + 5 -> 5, -2^31 - 1 -> 2^31 - 1, 2^40 -> 0)"""
+    from qsparse_amd.mx_grouped import _offs_int32
+    rows = [[2 ** 31, 0, 0, 0, 0], [100, 2 ** 32 + 5, 150, 2 ** 40, 300], [-2 ** 31 - 1, 50, INT64_MIN, INT64_MAX, 0], [2 ** 32 + 5], [2 ** 40],
+            [-2 ** 31 - 1], [2 ** 31], [INT64_MAX], [INT64_MIN], [INT64_MIN, INT64_MAX], [INT64_MAX, INT64_MIN], [-1, 5, 3, 299, 300, 301],
+            [INT32_MAX, INT32_MIN], []]
+    for T in (1, 300, INT32_MAX, 2 ** 31, 2 ** 33):
+        for row in rows:
+            wide = torch.tensor(row, dtype=torch.int64)
+            narrow = _offs_int32(wide, T)
+            assert narrow.dtype == torch.int32 and narrow.shape == wide.shape and narrow.is_contiguous()
+            assert clamped(narrow.tolist(), T) == [min(c, INT32_MAX) for c in clamped(row, T)], (T, row)      # (the kernel's cap)
+    for row in ([-7, 100, 99, 1000, 200], [INT32_MAX] * 5, [INT32_MIN, 0, INT32_MIN, 300, INT32_MAX]):
+        narrow = torch.tensor(row, dtype=torch.int32)
+        assert _offs_int32(narrow, 300).tolist() == row                    # an int32 one is the kernel's to clamp: handed on as it is
+    assert _offs_int32(torch.tensor([3, 0, 9, 0])[::2], 5).tolist() == [3, 5]          # (strided in: contiguous out)
+
+
 def per_group_linear(x, offs, wc, ws, w_fmt, bias, act_fmt, **kw):
     """one MXLinear per group on the group's rows; the pieces, in order"""
     out, lo = [], 0
@@ -225,6 +300,63 @@ def test_moe_feed_forward_is_its_composition_and_its_constructors():
         MXMoEFeedForward(router[:3], moe.up, moe.down, 1)
     with pytest.raises(ValueError, match=r"x must be \[T, D\]"):
         moe(x[:, :32])
+
+
+# ---- routing outcomes at the edges: an expert without a token, top_k == E, one token, an expert whose group spans two tiles ------
+ROUTING_GAP = 0.5
+
+
+def routed(g, logits, D, dead=()):
+    """(router [E, D], x [T, D]) in float32 with ``x @ router.t() == logits`` up to float32 rounding, the rows `dead` of the router all
+    zero (their logits are exactly 0): x is the minimum-norm solution plus noise from the router's null space, so its rows are not of
+    rank E"""
+    T, E = logits.shape
+    live = [e for e in range(E) if e not in dead]
+    router = torch.zeros(E, D, dtype=torch.float64)
+    router[live] = torch.randn(len(live), D, generator=g, dtype=torch.float64)
+    pinv = torch.linalg.pinv(router[live])                                     # [D, live]
+    noise = torch.randn(T, D, generator=g, dtype=torch.float64) / 8       # (small: an MX-quantized x keeps the gap as well)
+    x = logits[:, live].double() @ pinv.t() + noise - noise @ (pinv @ router[live])
+    return router.float(), x.float()
+
+
+def moe_routing_cases():
+    """[(name, logits [T, E], dead router rows, k, {expert: the (token, slot) pairs it must get})].  The logits of a token are distinct
+    integers, so the top-k order has a gap of 1 (``routing_of`` asserts more than ROUTING_GAP of it on the device that routes)"""
+    g = torch.Generator().manual_seed(12)
+    T = 37
+    starved = torch.zeros(T, 4)
+    starved[:, [0, 1, 3]] = torch.stack([torch.tensor([1.0, 2.0, 3.0])[torch.randperm(3, generator=g)] for _ in range(T)])
+    two_tiles = torch.tensor([[2.0, 1.0]] * 190 + [[1.0, 2.0]] * 10)[torch.randperm(200, generator=g)]
+    return [("an expert without a token", starved, (2,), 2, {2: 0}),           # its logit 0 is below the other three, 1 2 3
+            ("top_k == E", starved, (2,), 4, {e: T for e in range(4)}),
+            ("one token", torch.tensor([[3.0, 1.0, 2.0, 0.0]]), (), 2, {0: 1, 1: 0, 2: 1, 3: 0}),
+            ("a group of two tiles", two_tiles, (), 1, {0: 190, 1: 10})]
+
+
+def routing_of(x, router, k, counts):
+    """asserts the gap between consecutive logits down to the first one left out, and the `counts`, as ``x`` routes on its device"""
+    ordered = torch.sort(x @ router.t(), -1, descending=True)[0]
+    gaps = (ordered[:, :-1] - ordered[:, 1:])[:, :k]
+    assert gaps.numel() == 0 or float(gaps.min()) > ROUTING_GAP, float(gaps.min())
+    experts = torch.topk(x @ router.t(), k, -1)[1]
+    assert {e: int((experts == e).sum()) for e in counts} == counts
+
+
+@pytest.mark.parametrize("name,logits,dead,k,counts", moe_routing_cases(), ids=[c[0] for c in moe_routing_cases()])
+def test_moe_routing_edges_are_the_composition(name, logits, dead, k, counts):
+    g = torch.Generator().manual_seed(13)
+    E, D, H = logits.shape[1], 64, 96
+    _, up, down = moe_weights(g, E, D, H)
+    router, x = routed(g, logits, D, dead)
+    assert all(not router[e].any() for e in dead)
+    routing_of(x, router, k, counts)
+    moe = MXMoEFeedForward.from_float(router, *up, *down, k)
+    y = moe(x)
+    assert y.shape == x.shape and not y.isnan().any() and bits(y, moe_composition(x, router, up, down, k))
+    xa = MXActivation(*codes_of(x, "mxfp6_e2m3"), "mxfp6_e2m3")
+    routing_of(xa.dequantize(), router, k, counts)
+    assert bits(moe(xa), moe_composition(xa, router, up, down, k))
 
 
 # ---- the C ABI without a GPU: layout of the descriptors, and the checks that come before anything is enqueued --------------------

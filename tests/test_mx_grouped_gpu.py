@@ -11,7 +11,8 @@ import torch
 import mx_gemm_ref as G
 import qsparse_amd as qs
 from qsparse_amd import MXActivation, MXGroupedLinear, MXMoEFeedForward, _hip, mx_bmm, mx_grouped_matmul, mx_matmul, quantize_with_mx
-from test_mx_grouped import codes_of, moe_composition, moe_weights, per_group_linear
+from qsparse_amd.mx_grouped import _offs_int32
+from test_mx_grouped import clamped, codes_of, moe_composition, moe_routing_cases, moe_weights, per_group_linear, routed, routing_of
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -191,6 +192,75 @@ def test_boundaries_are_clamped_on_the_device():
     assert G.same(want, rounded(reference64(cpu, fa, fb, [5, 5, 10]), [5, 5, 10], bias.cpu(), torch.float32))
 
 
+def into_poison(dev, fa, fb, offs, bias=None, dt=torch.float32, **kw):
+    """the public call's launch with its output in a pattern-filled body instead of a fresh ``torch.empty`` (which is often the block a
+    correct call has just freed): a row that is not stored shows as the pattern.  ``offs`` passes through the wrapper's narrowing"""
+    T, N = dev[0].shape[0], dev[2].shape[1]
+    fill = lambda n: torch.full((n,), 0xA5, dtype=torch.uint8, device=DEV)
+    o32 = _offs_int32(offs, T)
+    if kw:
+        return _hip.mx_grouped_matmul_q(dev[0], dev[1], fa, dev[2], dev[3], fb, o32, bias, kw["out_fmt"], kw.get("act"),
+                                        out=(fill(T * N).view(T, N), fill(T * (-(-N // 32))).view(T, -1)))
+    return _hip.mx_grouped_matmul(dev[0], dev[1], fa, dev[2], dev[3], fb, o32, bias, dt, out=fill(T * N * torch.empty(0, dtype=dt).element_size()).view(dt))
+
+
+I32MIN, I32MAX = -2 ** 31, 2 ** 31 - 1
+# offs, its dtype, the boundaries c_e = min(max(offs[e], c_{e-1}), 300) worked out by hand
+HOSTILE = [([-7, 100, 99, 1000, 200], torch.int32, [0, 100, 100, 300, 300]),
+           ([I32MAX] * 5, torch.int32, [300] * 5),
+           ([I32MIN, 0, I32MIN, 300, I32MAX], torch.int32, [0, 0, 0, 300, 300]),
+           ([301, 0, 0, 0, 0], torch.int32, [300] * 5),
+           ([2 ** 31, 0, 0, 0, 0], torch.int64, [300] * 5),                               # narrowing alone: -2^31, group 0 empty
+           ([100, 2 ** 32 + 5, 150, 2 ** 40, 300], torch.int64, [100, 300, 300, 300, 300]),      # ... 5 and 0
+           ([-2 ** 31 - 1, 50, -2 ** 63, 2 ** 63 - 1, 0], torch.int64, [0, 50, 50, 300, 300])]   # ... 2^31 - 1: group 0 takes every row
+
+
+@pytest.fixture(scope="module")
+def hostile_case():
+    """one set of exact-class operands for every row of HOSTILE: T = 300, E = 5, N = 40, K = 96, and their float64 products with
+    every weight, [E, T, N] -- any partition's reference is a selection from it"""
+    g = torch.Generator().manual_seed(49)
+    fa, fb = "mxfp8_e5m2", "mxfp8_e4m3"
+    cpu = grouped_case(g, (60,) * 5, 0, 40, 96, fa, fb)
+    bias = torch.randint(-64, 64, (5, 40), generator=g).float()
+    full = torch.stack([G.reference(cpu[0], cpu[1], fa, cpu[2][e], cpu[3][e], fb)[1] for e in range(5)])
+    return fa, fb, cpu, tuple(t.to(DEV) for t in cpu), bias, full
+
+
+def selected(full, ends):
+    y = torch.zeros(full.shape[1:], dtype=torch.float64)
+    for e, (lo, hi) in enumerate(zip([0] + ends, ends)):
+        y[lo:hi] = full[e, lo:hi]
+    return y
+
+
+@pytest.mark.parametrize("row,dtype,ends", HOSTILE, ids=[str(i) for i in range(len(HOSTILE))])
+def test_hostile_offs_give_the_clamped_boundaries(hostile_case, row, dtype, ends):
+    """entries above T, negative ones, INT32_MIN / INT32_MAX and int64 ones beyond int32: inside the contract (any content of offs
+    gives the result of the clamped boundaries).  MxgmBlock bounds every boundary to [c, cap] with 0 <= c <= cap = min(T, INT32_MAX)
+    before it forms an address (qs_mx_gmm.h: `ce = max(v, c)`, `ce = min(ce, cap)`), and every load of offs is at an index below E"""
+    fa, fb, cpu, dev, bias, full = hostile_case
+    T = 300
+    assert clamped(row, T) == ends
+    offs, hand = torch.tensor(row, dtype=dtype, device=DEV), torch.tensor(ends, dtype=torch.int32, device=DEV)
+    bdev = bias.to(DEV)
+    want64 = rounded(selected(full, ends), ends, bias, torch.float32)
+    want = into_poison(dev, fa, fb, hand, bdev)
+    assert G.same(want, want64) and positive_zero(want[ends[-1]:])
+    for got in (mx_grouped_matmul(dev[0], dev[1], fa, dev[2], dev[3], fb, offs, bdev), into_poison(dev, fa, fb, offs, bdev)):
+        assert G.same(got, want), ("the clamped boundaries", row)
+        assert G.same(got, want64), ("float64 reference", row)
+    kw = dict(out_fmt="mxfp6_e2m3", act="relu")
+    cwant = into_poison(dev, fa, fb, hand, bdev, **kw)
+    assert all(torch.equal(a, b) for a, b in zip(cwant, codes_of(relu(want), kw["out_fmt"])))       # the quantizer of the float result
+    pieces = per_group(dev, fa, fb, ends, bdev, **kw)
+    for lo, hi, (c, s) in pieces:
+        assert torch.equal(cwant[0][lo:hi], c) and torch.equal(cwant[1][lo:hi], s), (lo, hi, row)
+    assert not cwant[0][ends[-1]:].any() and not cwant[1][ends[-1]:].any()
+    for got in (mx_grouped_matmul(dev[0], dev[1], fa, dev[2], dev[3], fb, offs, bdev, **kw), into_poison(dev, fa, fb, offs, bdev, **kw)):
+        assert torch.equal(got[0], cwant[0]) and torch.equal(got[1], cwant[1]), ("codes out", row)
+
+
 def relu(y):
     return torch.where(y > 0, y, torch.where(y != y, y, torch.zeros_like(y)))
 
@@ -250,6 +320,20 @@ def test_graph_capture_replays_with_other_boundaries():
         graph.replay()
         torch.cuda.synchronize()
         assert G.same(static_y, want), o.tolist()
+    # an int64 offs: the clamp and the narrowing are captured with the launch, and contents beyond int32 replay as their clamped
+    # boundaries ([0, 129, 129, 400], [400] * 4 and [0, 0, 3, 400] by hand)
+    wide = [(-5, 129, -2 ** 40, 2 ** 31), (2 ** 32 + 1, 0, 0, 0), (-2 ** 31 - 1, -2 ** 63, 3, 2 ** 63 - 1)]
+    hand = [torch.tensor(v, dtype=torch.int32, device=DEV) for v in ((0, 129, 129, 400), (400, 400, 400, 400), (0, 0, 3, 400))]
+    static_offs = torch.tensor((100, 200, 300, 400), dtype=torch.int64, device=DEV)
+    graph, static_y = captured(step, static_offs)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert G.same(static_y, step(torch.tensor((100, 200, 300, 400), dtype=torch.int32, device=DEV)))
+    for v, h in zip(wide, hand):
+        static_offs.copy_(torch.tensor(v, dtype=torch.int64))
+        graph.replay()
+        torch.cuda.synchronize()
+        assert G.same(static_y, step(h)), v
 
 
 def test_graph_capture_of_the_moe_block_replays_bit_for_bit():
@@ -306,3 +390,159 @@ def test_moe_feed_forward_is_its_composition():
     assert G.same(moe(x), y)                                        # no atomic combine: the same bits on every run
     xa = MXActivation(*codes_of(x, "mxfp6_e2m3"), "mxfp6_e2m3")
     assert G.same(moe(xa), moe_composition(xa, router.to(DEV), to_dev(up), to_dev(down), k))
+
+
+# ---- the decode's chunks of eight entries of offs -----------------------------------------------------------------------------------
+CHUNK_EDGES = (0, 7, 8, 15, 16)        # the first and the last lane of a chunk, for the first three chunks
+
+
+def chunk_patterns(E):
+    """size patterns [E] whose only non-empty groups sit at the CHUNK_EDGES that E has; one of them holds 130 rows (two tiles), the
+    others 3: each edge alone, all of them with the two-tile group at each in turn, each pair of neighbours across a chunk boundary
+    (the last lane of one chunk, then the first lane of the next), and everything past the first eight groups (a whole chunk of empty
+    groups in front).  For E = 9 and 17 the last chunk holds ONE real entry, index 8 / 16, and seven re-reads of it"""
+    at = sorted({e for e in CHUNK_EDGES if e < E} | {E - 1})       # (E - 1: the entry that the lanes past it re-read; new for E = 7 alone)
+    sets = [(e,) for e in at] + [tuple(at)[i:] + tuple(at)[:i] for i in range(len(at))]
+    sets += [(a, b) for a, b in ((7, 8), (8, 7), (15, 16), (16, 15)) if max(a, b) < E]
+    if E > 8:
+        sets.append(tuple(e for e in at if e >= 8))
+    out = []
+    for big, *small in sets:
+        sizes = [0] * E
+        sizes[big] = 130
+        for e in small:
+            sizes[e] = 3
+        out.append(tuple(sizes))
+    return list(dict.fromkeys(out))
+
+
+@pytest.mark.parametrize("E", [7, 8, 9, 16, 17])
+def test_the_decode_at_the_edges_of_its_chunks(E):
+    """a per-group bias and a per-group scale base in both operands: a group index that is off by one shows in every row"""
+    g = torch.Generator().manual_seed(50 + E)
+    fa, fb, N, K, tail = "mxfp8_e4m3", "mxfp4_e2m1", 16, 32, 2
+    patterns = chunk_patterns(E)
+    assert any(not any(p[:8]) for p in patterns) == (E > 8)         # a whole chunk of empty groups in front
+    if E in (9, 17):
+        assert any(p[E - 1] and p[E - 2] for p in patterns) and any(p[E - 1] and not any(p[:E - 1]) for p in patterns)
+    for sizes in patterns:
+        assert all(e in CHUNK_EDGES + (E - 1,) for e, n in enumerate(sizes) if n) and 130 in sizes
+        cpu = grouped_case(g, sizes, tail, N, K, fa, fb)
+        dev = tuple(t.to(DEV) for t in cpu)
+        bias = torch.randint(-64, 64, (E, N), generator=g).float()
+        ends = ends_of(sizes)
+        y = into_poison(dev, fa, fb, torch.tensor(ends, dtype=torch.int32, device=DEV), bias.to(DEV))
+        assert _hip.mx_grouped_last_route == VEC and y.shape == (ends[-1] + tail, N)
+        for lo, hi, want in per_group(dev, fa, fb, ends, bias.to(DEV)):
+            assert G.same(y[lo:hi], want), ("group identity", lo, hi, sizes)
+        assert G.same(y, rounded(reference64(cpu, fa, fb, ends), ends, bias, torch.float32)), ("float64 reference", sizes)
+        assert positive_zero(y[ends[-1]:]), ("tail", sizes)
+
+
+def test_the_largest_number_of_groups():
+    """E = QS_MX_GROUPED_MAX_GROUPS = 4096, T = 4096 + 3: one row a group, groups 1000 .. 1009 empty, 11 rows in the last one, a tail
+    of 3.  The one-row groups against ONE mx_bmm over [G, 1, K] (the per-row mx_matmul by its own definition), the last group against
+    mx_matmul, everything against float64"""
+    g = torch.Generator().manual_seed(51)
+    E, N, K, fa, fb, tail = 4096, 16, 32, "mxfp8_e4m3", "mxfp4_e2m1", 3
+    sizes = torch.ones(E, dtype=torch.int64)
+    sizes[1000:1010], sizes[E - 1] = 0, 11
+    ends = sizes.cumsum(0)
+    T = int(ends[-1]) + tail
+    assert T == 4096 + 3
+    ra, rb = G.scale_windows(K, fa, fb)
+    G.assert_exact_class(K, fa, fb, ra, rb)
+    owner = torch.cat([torch.repeat_interleave(torch.arange(E), sizes), torch.full((tail,), E)])             # [T]: the group; E: the tail
+    suba, subb = G.exact_subset(fa), G.exact_subset(fb)
+    ac = suba[torch.randint(0, len(suba), (T, K), generator=g)].to(torch.uint8)
+    bc = subb[torch.randint(0, len(subb), (E, N, K), generator=g)].to(torch.uint8)
+    asc = (torch.where(owner < E, 120 + 3 * (owner % 9), 127).view(T, 1) + torch.randint(0, ra, (T, 1), generator=g)).to(torch.uint8)
+    bsc = ((134 - 3 * (torch.arange(E) % 9)).view(E, 1, 1) + torch.randint(0, rb, (E, N, 1), generator=g)).to(torch.uint8)
+    bias = torch.randint(-64, 64, (E, N), generator=g).float()
+    dev = tuple(t.to(DEV) for t in (ac, asc, bc, bsc))
+    bdev = bias.to(DEV)
+    y = into_poison(dev, fa, fb, ends.to(DEV), bdev)
+    assert _hip.mx_grouped_last_route == VEC and y.shape == (T, N)
+    rows = (owner < E - 1).nonzero().reshape(-1).to(DEV)           # the rows of the one-row groups, and their groups
+    of = owner.to(DEV)[rows]
+    one = mx_bmm(dev[0][rows, None], dev[1][rows, None], fa, dev[2][of], dev[3][of], fb, bdev[of]).reshape(-1, N)
+    assert len(rows) == E - 11 and G.same(y[rows], one)
+    lo, hi = int(ends[-2]), int(ends[-1])
+    assert hi - lo == 11 and G.same(y[lo:hi], mx_matmul(dev[0][lo:hi], dev[1][lo:hi], fa, dev[2][E - 1], dev[3][E - 1], fb, bdev[E - 1]))
+    grouped = owner[:hi]
+    want = torch.einsum("tk,tnk->tn", G.values(ac[:hi], asc[:hi], fa), G.values(bc, bsc, fb)[grouped]) + bias[grouped].double()
+    assert G.same(y[:hi], (want + 0.0).float()) and positive_zero(y[hi:])
+
+
+# ---- raw codes: every byte value in both operands, NaN and Inf encodings and the bits above the format's width included -----------
+RAW_SIZES, RAW_TAIL = (3, 0, 130, 1), 2
+RAW_SHAPES = [(33, 100), (40, 96), (129, 32)]          # (N, K), one per pair
+
+
+def raw_operand(g, rows, K):
+    """code bytes uniform over 0 .. 255 and scale bytes uniform over 100 .. 150, of any leading shape `rows`"""
+    return (torch.randint(0, 256, rows + (K,), generator=g).to(torch.uint8),
+            torch.randint(100, 151, rows + (-(-K // 32),), generator=g).to(torch.uint8))
+
+
+@pytest.mark.parametrize("fa,fb", PAIRS)
+def test_group_identity_on_raw_codes_and_ff_scale_bytes(fa, fb):
+    """the bit-for-bit claim is about ARBITRARY codes: what mx_matmul gives for bytes that the quantizer never writes is left open
+    per row, but the grouped product gives the same.  Compared under G.same, which takes all NaNs alike and everything else -- Inf and
+    the sign of zero too -- bit for bit.  A raw code may be a NaN by itself, so the 0xFF scale bytes are asserted as a difference: the
+    NaNs after planting them are the NaNs before plus exactly the planted row and the planted column of group 2, and no other output
+    changes"""
+    p = G.FMTS.index(fa) * 5 + G.FMTS.index(fb)
+    g = torch.Generator().manual_seed(800 + p)
+    N, K = RAW_SHAPES[p % len(RAW_SHAPES)]
+    ends, E = ends_of(RAW_SIZES), len(RAW_SIZES)
+    T, nkb = ends[-1] + RAW_TAIL, -(-K // 32)
+    (ac, asc), (bc, bsc) = raw_operand(g, (T,), K), raw_operand(g, (E, N), K)
+    asc[1, 0], asc[70, nkb - 1], asc[T - 1, 0], bsc[0, 2, 0], bsc[2, 5, nkb - 1], bsc[3, N - 1, 0] = 0, 0, 0, 0, 0, 0
+    asc[2, nkb - 1], bsc[3, 0, 0] = 255, 255                       # 0xFF in group 0's last row and in the weight of the one-row group
+    offs = torch.tensor(ends, dtype=torch.int32, device=DEV)
+    route = VEC if K % 16 == 0 else PLAIN
+    outs = []
+    row, col = 3 + 64, N - 2                                        # a row of group 2 (rows 3 .. 132); a column of its weight
+    for planted in (False, True):
+        if planted:
+            asc[row, 0], bsc[2, col, nkb - 1] = 255, 255
+        dev = tuple(t.to(DEV) for t in (ac, asc, bc, bsc))
+        for dt in (torch.float32,) + ((torch.bfloat16,) if p % 2 else ()):
+            y = into_poison(dev, fa, fb, offs, None, dt)
+            assert _hip.mx_grouped_last_route == route
+            for lo, hi, want in per_group(dev, fa, fb, ends, None, dt):
+                assert G.same(y[lo:hi], want), ("group identity", lo, hi, fa, fb, N, K, dt, planted)
+            assert positive_zero(y[ends[-1]:]), ("tail", fa, fb, dt, planted)
+            if dt == torch.float32:
+                outs.append(y.cpu())
+    before, after = outs
+    added = torch.zeros(T, N, dtype=torch.bool)
+    added[row, :] = True
+    added[ends[1]:ends[2], col] = True
+    assert bool(after[added].isnan().all())
+    assert torch.equal(after.isnan(), before.isnan() | added)
+    assert bool(before[2].isnan().all()) and bool(before[ends[2]:ends[3], 0].isnan().all())      # the 0xFF bytes of the first draw
+    keep = ~added
+    assert G.same(after[keep], before[keep])
+
+
+@pytest.mark.parametrize("name,logits,dead,k,counts", moe_routing_cases(), ids=[c[0] for c in moe_routing_cases()])
+def test_moe_routing_edges_are_the_composition(name, logits, dead, k, counts):
+    """routing outcomes that a random router at T = 37 does not produce: an expert that gets no token (an empty group between
+    others), top_k == E (the same expert gets every token), T = 1, and one expert with 190 rows (a group of two tiles).  Against the
+    per-expert loop of MXLinear pairs, which does not use the grouped kernel; the routing itself is asserted, with its gap"""
+    g = torch.Generator().manual_seed(13)
+    E, D, H = logits.shape[1], 64, 96
+    _, up, down = moe_weights(g, E, D, H)
+    router, x = routed(g, logits, D, dead)
+    router, x = router.to(DEV), x.to(DEV)
+    routing_of(x, router, k, counts)
+    moe = MXMoEFeedForward.from_float(router, *up, *down, k).to(DEV)
+    to_dev = lambda pair: tuple(t.to(DEV) for t in pair)
+    y = moe(x)
+    assert y.is_cuda and y.shape == x.shape and not y.isnan().any()
+    assert G.same(y, moe_composition(x, router, to_dev(up), to_dev(down), k)), name
+    xa = MXActivation(*codes_of(x, "mxfp6_e2m3"), "mxfp6_e2m3")
+    routing_of(xa.dequantize(), router, k, counts)
+    assert G.same(moe(xa), moe_composition(xa, router, to_dev(up), to_dev(down), k)), name

@@ -1470,6 +1470,51 @@ typedef struct qs_mx_grouped_matmul_q_args {
 int qs_mx_grouped_matmul_q_v(const qs_mx_grouped_matmul_q_args* args);
 int qs_mx_grouped_matmul_q_route(const qs_mx_grouped_matmul_q_args* args);
 
+/* ---- MX grouped weight gradient ---------------------------------------------------------------------------------------------
+ * Added without raising QS_ABI_VERSION (28), by the same rule as qs_mx_matmul_v above: symbols are only added.
+ *
+ * The third product of a grouped linear layer's training step: dw[e] [N, K] = dy_e^T x_e, the contraction over the tokens of group e
+ * -- the RAGGED axis.  Both operands carry their blocks of 32 along the token axis: gt_codes [N, T] / gt_scales [N, ceil(T / 32)] and
+ * xt_codes [K, T] / xt_scales [K, ceil(T / 32)] are the col pairs of qs_mx_quant2_v on dy [T, N] and x [T, K].  `offs` [E] int32 in
+ * DEVICE memory is qs_mx_grouped_matmul_v's, with its boundaries for ANY content: c_-1 = 0, c_e = min(max(offs[e], c_{e-1}), T),
+ * group e owns the tokens [lo, hi) = [c_{e-1}, c_e).  The host side does no allocation, no synchronisation and no read of offs; it is
+ * one launch, always.
+ * Definition (normative).  If hi == lo, dw[e] is +0.  Otherwise let s0 = 128 floor(lo / 128), s1 = min(T, 128 ceil(hi / 128)), and
+ *     G_e   = gt_codes[:, s0 : s1] with every column t outside [lo, hi) set to byte 0
+ *     GS_e  = gt_scales[:, s0 / 32 : ceil(s1 / 32)] with every block that does not intersect [lo, hi) set to 127
+ *     X_e, XS_e  likewise from xt
+ *   dw[e] is, bit for bit, what qs_mx_matmul_v writes for A = G_e / GS_e [N, s1 - s0] and B = X_e / XS_e [K, s1 - s0] without a bias.
+ *   - The 128-alignment of s0 is part of the definition: the kernel walks the global steps of 128 tokens, so each MFMA sees exactly
+ *     the 128 codes qs_mx_matmul_v sees.
+ *   - A block that straddles a boundary keeps its shared scale byte for both groups; a 0xFF byte there is NaN in both.
+ *   - A block wholly outside the group contributes nothing, whatever its bytes are: a NaN row of another group does not leak.
+ *   - Tokens t >= c_{E-1} belong to no group and reach nothing.
+ *   - Checks: a NULL dw / offs, with T > 0 a NULL gt_codes / gt_scales / xt_codes / xt_scales, a format outside enum qs_mx_format, a
+ *     negative extent or E beyond QS_MX_GROUPED_MAX_GROUPS is QS_ERR_ARG; then ydt (QS_ERR_DTYPE); then dw aligned to its element and
+ *     offs to 4 bytes (QS_ERR_ALIGN).  E == 0, N == 0 or K == 0: nothing is enqueued, 0 is returned.  T == 0 is legal: every group is
+ *     empty and dw is +0.  Any of N T, K T, E N K beyond INT64_MAX or a grid beyond 2^31 - 1 work-groups: QS_ERR_ARG.
+ *   - One work-group per (group, 128 x 128 tile of [N, K]): the grid is E ceil(N / 128) ceil(K / 128), the group the slowest index.
+ *     No split-K form, no atomics, no workspace: every element of dw is stored exactly once.
+ *   - Routes: T % 16 == 0 with both code bases 16-byte aligned takes QS_MX_GEMM_ROUTE_VEC, anything else QS_MX_GEMM_ROUTE_PLAIN, with
+ *     the same bits. */
+typedef struct qs_mx_grouped_wgrad_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_grouped_wgrad_args) as the caller compiled it */
+    int32_t g_format, x_format;      /* enum qs_mx_format of gt and xt, may differ */
+    const uint8_t* gt_codes;         /* [N, T], one code per byte, dense: dy transposed, blocks along T */
+    const uint8_t* gt_scales;        /* [N, ceil(T / 32)] E8M0 bytes */
+    const uint8_t* xt_codes;         /* [K, T]: x transposed, blocks along T */
+    const uint8_t* xt_scales;        /* [K, ceil(T / 32)] */
+    const int32_t* offs;             /* [E] in DEVICE memory: the cumulative end token of every group; never read by the host */
+    void* dw;                        /* [E, N, K] dense */
+    int32_t ydt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    int64_t T, E, N, K;
+    qs_stream_t stream;
+} qs_mx_grouped_wgrad_args;
+int qs_mx_grouped_wgrad_v(const qs_mx_grouped_wgrad_args* args);
+/* the kernel qs_mx_grouped_wgrad_v launches for these operands, nothing enqueued and offs not read: QS_MX_GEMM_ROUTE_*, 0 for an empty
+ * result, or the QS_ERR_* the call would return */
+int qs_mx_grouped_wgrad_route(const qs_mx_grouped_wgrad_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

@@ -127,6 +127,8 @@ SIGNATURES = {
     "qs_mx_grouped_matmul_route": (c_int, [_P]),
     "qs_mx_grouped_matmul_q_v": (c_int, [_P]),
     "qs_mx_grouped_matmul_q_route": (c_int, [_P]),
+    "qs_mx_grouped_wgrad_v": (c_int, [_P]),
+    "qs_mx_grouped_wgrad_route": (c_int, [_P]),
 }
 
 
@@ -298,6 +300,13 @@ class MxGroupedMatmulArgs(ctypes.Structure):
 class MxGroupedMatmulQArgs(ctypes.Structure):
     """`qs_mx_grouped_matmul_q_args` of include/qsparse_hip.h"""
     _fields_ = _codes_out_fields(MxGroupedMatmulArgs._fields_)
+
+
+class MxGroupedWgradArgs(ctypes.Structure):
+    """`qs_mx_grouped_wgrad_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("g_format", c_int32), ("x_format", c_int32), ("gt_codes", c_void_p),
+                ("gt_scales", c_void_p), ("xt_codes", c_void_p), ("xt_scales", c_void_p), ("offs", c_void_p), ("dw", c_void_p),
+                ("ydt", c_int32), ("T", c_int64), ("E", c_int64), ("N", c_int64), ("K", c_int64), ("stream", c_void_p)]
 
 
 class MultiRow(ctypes.Structure):
@@ -1185,6 +1194,40 @@ def mx_grouped_matmul_q(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: st
         _check(st, "qs_mx_grouped_matmul_q_v")
         mx_grouped_q_last_route = route
     return codes, scales
+
+
+mx_grouped_wgrad_last_route = None    # the QS_MX_GEMM_ROUTE_* of the last `mx_grouped_wgrad` launch (None: an empty result)
+
+
+def mx_grouped_wgrad(gt_codes: torch.Tensor, gt_scales: torch.Tensor, g_fmt: str, xt_codes: torch.Tensor, xt_scales: torch.Tensor,
+                     x_fmt: str, offs: torch.Tensor, out_dtype: torch.dtype = torch.float32, out=None) -> torch.Tensor:
+    """dw[E, N, K], dw[e] = dy_e^T x_e over the tokens [c_{e-1}, c_e) on MX codes (qs_mx_grouped_wgrad_v): `gt_codes` [N, T],
+    `xt_codes` [K, T] uint8 with blocks along T, scales [*, ceil(T / 32)] uint8, `offs` int32 [E] (cumulative group ends), all
+    contiguous GPU tensors (qsparse_amd/mx_grouped_train.py checks).  ONE launch; `offs` is not read on the host.
+    `out`: a contiguous tensor of E N K elements of `out_dtype` to write instead of a new one, as the guard-byte tests carve it."""
+    global mx_grouped_wgrad_last_route
+    lib = load()
+    (N, T), K, E = gt_codes.shape, xt_codes.shape[0], offs.shape[0]
+    if out is None:
+        dw = torch.empty((E, N, K), dtype=out_dtype, device=gt_codes.device)
+    else:
+        assert out.dtype == out_dtype and out.is_contiguous() and out.numel() == E * N * K, "out: E N K elements of out_dtype"
+        dw = out.view(E, N, K)
+    mx_grouped_wgrad_last_route = None
+    if E and N and K:
+        a = MxGroupedWgradArgs()
+        a.struct_size = ctypes.sizeof(a)
+        a.g_format, a.x_format = MX_FORMATS.index(g_fmt), MX_FORMATS.index(x_fmt)
+        a.gt_codes, a.gt_scales, a.xt_codes, a.xt_scales = _ptr(gt_codes), _ptr(gt_scales), _ptr(xt_codes), _ptr(xt_scales)
+        a.offs, a.dw, a.ydt = _ptr(offs), _ptr(dw), _DT[out_dtype]
+        a.T, a.E, a.N, a.K = T, E, N, K
+        a.stream = _stream(gt_codes)
+        route = lib.qs_mx_grouped_wgrad_route(ctypes.byref(a))
+        with _timed(f"mx_grouped_wgrad[{route}]", gt_codes, gt_scales, xt_codes, xt_scales, dw):
+            st = lib.qs_mx_grouped_wgrad_v(ctypes.byref(a))
+        _check(st, "qs_mx_grouped_wgrad_v")
+        mx_grouped_wgrad_last_route = route
+    return dw
 
 
 MX_CONV_ROUTE_GEMM, MX_CONV_ROUTE_VEC, MX_CONV_ROUTE_PLAIN = 1, 2, 3

@@ -1515,6 +1515,87 @@ int qs_mx_grouped_wgrad_v(const qs_mx_grouped_wgrad_args* args);
  * result, or the QS_ERR_* the call would return */
 int qs_mx_grouped_wgrad_route(const qs_mx_grouped_wgrad_args* args);
 
+/* ---- MX gated products (SwiGLU / GeGLU: fused GLU epilogue) -------------------------------------------------------------------
+ * Added without raising QS_ABI_VERSION (28), by the same rule as qs_mx_matmul_v above: symbols are only added.
+ *
+ * The hidden layer of a gated MLP, h = act(x W_gate^T) * (x W_up^T), as ONE product on a combined weight b of N = 2 H rows whose
+ * epilogue multiplies the two halves while they are accumulators and writes H columns: a float tensor, or the MX codes the next
+ * product reads.  H % 32 == 0.  The rows of b (and the entries of bias) are INTERLEAVED in runs of 32: for q = 0 .. H / 32 - 1 the
+ * rows [64 q, 64 q + 32) are the gate rows of the hidden units [32 q, 32 q + 32), the rows [64 q + 32, 64 q + 64) their up rows.  The
+ * interleave is the caller's, done once when the weights are laid down.
+ * Definition (normative).  Let v[m, n] be the float32 value qs_mx_matmul_v produces for the same operands (b as [2 H, K]) with ydt
+ * = QS_F32, bias included.  For the hidden unit c = 32 q + t, t < 32:
+ *   g = v[m, 64 q + t],  u = v[m, 64 q + 32 + t],  z[m, c] = act(g) * u      one float32 multiplication
+ *   act(g) = g > 0 ? g : (g != g ? g : +0)                                    QS_MX_GLU_RELU
+ *          = g / (1.0f + expf(-g))                                            QS_MX_GLU_SILU
+ *          = (g * 0.5f) * (1.0f + erff(g * 0.70710678118654752440f))          QS_MX_GLU_GELU (the erf form; there is no tanh form)
+ * all in float32 without contraction, expf / erff the device library's.  The output is
+ *   out_format == -1:  y [M, H] = z rounded once to ydt, or
+ *   out_format an enum qs_mx_format:  out_codes [M, H], out_scales [M, H / 32] = the codes and scales qs_mx_quant_fwd_v writes for z
+ *   seen as [M, H, 1] in that format with QS_MX_ROUND_NEAREST -- a block that holds NaN / Inf gets the byte 0xFF and codes 0, an
+ *   all-zero block the byte 0.
+ * One launch, no workspace, no atomics, no float v or z in memory.  Stochastic rounding of the output and a split-K form are not
+ * offered.
+ *   - Checks and their precedence are those of qs_mx_matmul_q_v on N = 2 H; with its QS_ERR_ARG checks of the operands come: H
+ *     negative or H % 32 != 0, act outside QS_MX_GLU_*, out_format neither -1 nor an enum qs_mx_format, a NULL y (out_format == -1)
+ *     or a NULL out_codes / out_scales (otherwise).  Then, for a float output, ydt (QS_ERR_DTYPE); then y aligned to its element and
+ *     bias to 4 bytes (QS_ERR_ALIGN).  M == 0 or H == 0: nothing is enqueued, 0 is returned.  After the size checks: an output (y,
+ *     out_codes or out_scales) sharing a byte with a_codes or b_codes is QS_ERR_ARG.
+ *   - Nothing outside y [M, H], or out_codes [M, H] and out_scales [M, H / 32], is written.
+ *   - Routes: QS_MX_GEMM_ROUTE_*, by the conditions of qs_mx_matmul_route on the inputs. */
+#define QS_MX_GLU_RELU 0
+#define QS_MX_GLU_SILU 1
+#define QS_MX_GLU_GELU 2
+typedef struct qs_mx_glu_matmul_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_glu_matmul_args) as the caller compiled it */
+    int32_t a_format, b_format;      /* enum qs_mx_format, may differ */
+    const uint8_t* a_codes;          /* [M, K], one code per byte */
+    const uint8_t* a_scales;         /* [M, ceil(K / 32)] E8M0 bytes */
+    const uint8_t* b_codes;          /* [2 H, K], rows interleaved as above */
+    const uint8_t* b_scales;         /* [2 H, ceil(K / 32)] */
+    const float* bias;               /* nullable, float32 [2 H], interleaved as the rows of b */
+    int32_t out_format;              /* enum qs_mx_format of the output, or -1 for a float y */
+    int32_t act;                     /* QS_MX_GLU_* */
+    void* y;                         /* out_format == -1: [M, H] */
+    int32_t ydt;                     /* out_format == -1: QS_F32, QS_BF16 or QS_F16 */
+    uint8_t* out_codes;              /* otherwise: [M, H], one code per byte */
+    uint8_t* out_scales;             /* otherwise: [M, H / 32] E8M0 bytes */
+    int64_t M, H, K;
+    qs_stream_t stream;
+} qs_mx_glu_matmul_args;
+int qs_mx_glu_matmul_v(const qs_mx_glu_matmul_args* args);
+/* the kernel qs_mx_glu_matmul_v launches for these operands, nothing enqueued: QS_MX_GEMM_ROUTE_*, 0 for an empty product, or the
+ * QS_ERR_* the call would return */
+int qs_mx_glu_matmul_route(const qs_mx_glu_matmul_args* args);
+
+/* The grouped product ("MX grouped matrix product" above: offs, its boundaries c_e for ANY content, the tail rows) with the gated
+ * epilogue: b is [E, 2 H, K], every weight interleaved as above, bias NULL, [2 H] (bias_batch_stride == 0) or [E, 2 H]
+ * (bias_batch_stride == 2 H).  A row of group e is bit for bit what qs_mx_glu_matmul_v writes for it with the weight b[e] and the bias
+ * of e.  The tail rows r >= c_{E-1} get +0, or code 0 and the scale byte 0, whatever act is.  Checks and their precedence are those of
+ * qs_mx_grouped_matmul_q_v on N = 2 H with the additions of qs_mx_glu_matmul_v; offs is never read by the host.  Routes as
+ * qs_mx_grouped_matmul_route. */
+typedef struct qs_mx_grouped_glu_matmul_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_grouped_glu_matmul_args) as the caller compiled it */
+    int32_t a_format, b_format;      /* the operands of qs_mx_grouped_matmul_args, with their meaning, b [E, 2 H, K] ... */
+    const uint8_t* a_codes;
+    const uint8_t* a_scales;
+    const uint8_t* b_codes;
+    const uint8_t* b_scales;
+    const float* bias;
+    int64_t bias_batch_stride;       /* 0 or 2 H */
+    const int32_t* offs;
+    int32_t out_format;              /* ... and the outputs of qs_mx_glu_matmul_args on T rows */
+    int32_t act;
+    void* y;
+    int32_t ydt;
+    uint8_t* out_codes;
+    uint8_t* out_scales;
+    int64_t T, E, H, K;
+    qs_stream_t stream;
+} qs_mx_grouped_glu_matmul_args;
+int qs_mx_grouped_glu_matmul_v(const qs_mx_grouped_glu_matmul_args* args);
+int qs_mx_grouped_glu_matmul_route(const qs_mx_grouped_glu_matmul_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

@@ -127,6 +127,10 @@ SIGNATURES = {
     "qs_mx_grouped_matmul_route": (c_int, [_P]),
     "qs_mx_grouped_matmul_q_v": (c_int, [_P]),
     "qs_mx_grouped_matmul_q_route": (c_int, [_P]),
+    "qs_mx_glu_matmul_v": (c_int, [_P]),
+    "qs_mx_glu_matmul_route": (c_int, [_P]),
+    "qs_mx_grouped_glu_matmul_v": (c_int, [_P]),
+    "qs_mx_grouped_glu_matmul_route": (c_int, [_P]),
     "qs_mx_grouped_wgrad_v": (c_int, [_P]),
     "qs_mx_grouped_wgrad_route": (c_int, [_P]),
 }
@@ -300,6 +304,24 @@ class MxGroupedMatmulArgs(ctypes.Structure):
 class MxGroupedMatmulQArgs(ctypes.Structure):
     """`qs_mx_grouped_matmul_q_args` of include/qsparse_hip.h"""
     _fields_ = _codes_out_fields(MxGroupedMatmulArgs._fields_)
+
+
+def _glu_fields(fields):
+    """the fields of a gated descriptor from its float sibling's: `y`, `ydt` become the output format (-1: float), act, `y`, `ydt` and
+    the two pointers of a codes output; `N` is `H`"""
+    i = [n for n, _ in fields].index("y")
+    out = [("out_format", c_int32), ("act", c_int32), ("y", c_void_p), ("ydt", c_int32), ("out_codes", c_void_p), ("out_scales", c_void_p)]
+    return fields[:i] + out + [("H", t) if n == "N" else (n, t) for n, t in fields[i + 2:]]
+
+
+class MxGluMatmulArgs(ctypes.Structure):
+    """`qs_mx_glu_matmul_args` of include/qsparse_hip.h"""
+    _fields_ = _glu_fields(MxMatmulArgs._fields_)
+
+
+class MxGroupedGluMatmulArgs(ctypes.Structure):
+    """`qs_mx_grouped_glu_matmul_args` of include/qsparse_hip.h"""
+    _fields_ = _glu_fields(MxGroupedMatmulArgs._fields_)
 
 
 class MxGroupedWgradArgs(ctypes.Structure):
@@ -1194,6 +1216,86 @@ def mx_grouped_matmul_q(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: st
         _check(st, "qs_mx_grouped_matmul_q_v")
         mx_grouped_q_last_route = route
     return codes, scales
+
+
+MX_GLU_ACTS = ("relu", "silu", "gelu")      # QS_MX_GLU_*, in order
+mx_glu_last_route = None              # the QS_MX_GEMM_ROUTE_* of the last `mx_glu_matmul` launch (None: an empty product)
+mx_grouped_glu_last_route = None      # likewise of the last `mx_grouped_glu_matmul` launch
+
+
+def _mx_glu_out(a, rows: int, H: int, act: str, out_dtype, out_fmt, device, out):
+    """fill the output fields of a gated descriptor `a`; returns y [rows, H] in `out_dtype` (`out_fmt` None) or the pair (codes uint8
+    [rows, H], scales uint8 [rows, H / 32]): new tensors, or `out` -- a contiguous tensor of rows H elements of `out_dtype`, or the
+    pair of `_mx_codes_out` -- as the guard-byte tests carve them"""
+    if out_fmt is not None:
+        res = _mx_codes_out(a, (rows,), H, out_fmt, None, device, out)
+        a.act = MX_GLU_ACTS.index(act)      # (after it: `_mx_codes_out` writes an `act` of the ungated products' enum)
+        return res
+    a.act = MX_GLU_ACTS.index(act)
+    if out is None:
+        y = torch.empty((rows, H), dtype=out_dtype, device=device)
+    else:
+        assert out.dtype == out_dtype and out.is_contiguous() and out.numel() == rows * H, "out: rows H elements of out_dtype"
+        y = out.view(rows, H)
+    a.out_format, a.y, a.ydt = -1, _ptr(y), _DT[out_dtype]
+    return y
+
+
+def mx_glu_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
+                  bias: Optional[torch.Tensor], act: str, out_dtype: torch.dtype = torch.float32, out_fmt: Optional[str] = None, out=None):
+    """act(gate) * up of A . B^T on MX codes (qs_mx_glu_matmul_v): `a_codes` [M, K], `b_codes` [2 H, K] with its rows in the 32-row
+    interleave, `bias` float32 [2 H] or None, `act` of MX_GLU_ACTS, all contiguous GPU tensors (qsparse_amd/mx_glu.py checks).  Returns
+    y [M, H] in `out_dtype`, or with `out_fmt` the pair (codes [M, H], scales [M, H / 32]).  ONE launch.  `out`: see `_mx_glu_out`."""
+    global mx_glu_last_route
+    lib = load()
+    (M, K), H = a_codes.shape, b_codes.shape[0] // 2
+    a = MxGluMatmulArgs()
+    res = _mx_glu_out(a, M, H, act, out_dtype, out_fmt, a_codes.device, out)
+    mx_glu_last_route = None
+    if M and H:
+        a.struct_size = ctypes.sizeof(a)
+        a.a_format, a.b_format = MX_FORMATS.index(a_fmt), MX_FORMATS.index(b_fmt)
+        a.a_codes, a.a_scales, a.b_codes, a.b_scales = _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales)
+        a.bias = _ptr(bias)
+        a.M, a.H, a.K = M, H, K
+        a.stream = _stream(a_codes)
+        route = lib.qs_mx_glu_matmul_route(ctypes.byref(a))
+        outs = res if isinstance(res, tuple) else (res,)
+        with _timed(f"mx_glu_matmul[{route}]", a_codes, a_scales, b_codes, b_scales, bias, *outs):
+            st = lib.qs_mx_glu_matmul_v(ctypes.byref(a))
+        _check(st, "qs_mx_glu_matmul_v")
+        mx_glu_last_route = route
+    return res
+
+
+def mx_grouped_glu_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor,
+                          b_fmt: str, offs: torch.Tensor, bias: Optional[torch.Tensor], act: str,
+                          out_dtype: torch.dtype = torch.float32, out_fmt: Optional[str] = None, out=None):
+    """the grouped product with the gated epilogue (qs_mx_grouped_glu_matmul_v): operands as `mx_grouped_matmul`'s with `b_codes`
+    [E, 2 H, K], every weight in the 32-row interleave, `bias` float32 [2 H], [E, 2 H] or None.  Returns y [T, H] in `out_dtype`, or
+    with `out_fmt` the pair (codes [T, H], scales [T, H / 32]).  ONE launch; `offs` is not read on the host.  `out`: see `_mx_glu_out`."""
+    global mx_grouped_glu_last_route
+    lib = load()
+    T, H = a_codes.shape[0], b_codes.shape[1] // 2
+    a = MxGroupedGluMatmulArgs()
+    res = _mx_glu_out(a, T, H, act, out_dtype, out_fmt, a_codes.device, out)
+    mx_grouped_glu_last_route = None
+    if T and H:
+        (_, K), (E, N, _) = a_codes.shape, b_codes.shape
+        a.struct_size = ctypes.sizeof(a)
+        a.a_format, a.b_format = MX_FORMATS.index(a_fmt), MX_FORMATS.index(b_fmt)
+        a.a_codes, a.a_scales, a.b_codes, a.b_scales = _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales)
+        a.bias, a.bias_batch_stride = _ptr(bias), N if bias is not None and bias.dim() == 2 else 0
+        a.offs = _ptr(offs)
+        a.T, a.E, a.H, a.K = T, E, H, K
+        a.stream = _stream(a_codes)
+        route = lib.qs_mx_grouped_glu_matmul_route(ctypes.byref(a))
+        outs = res if isinstance(res, tuple) else (res,)
+        with _timed(f"mx_grouped_glu_matmul[{route}]", a_codes, a_scales, b_codes, b_scales, bias, *outs):
+            st = lib.qs_mx_grouped_glu_matmul_v(ctypes.byref(a))
+        _check(st, "qs_mx_grouped_glu_matmul_v")
+        mx_grouped_glu_last_route = route
+    return res
 
 
 mx_grouped_wgrad_last_route = None    # the QS_MX_GEMM_ROUTE_* of the last `mx_grouped_wgrad` launch (None: an empty result)

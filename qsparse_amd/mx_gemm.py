@@ -29,6 +29,24 @@ _check_a = partial(_mx_common._check_operand, what="[..., K]", least=1, most=Non
 _check_b = partial(_mx_common._check_operand, what="[N, K]", least=2, most=None, needs="2 dimensions")
 
 
+def _check_matmul_operands(fn: str, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias, out_dtype):
+    """the operands, the bias and `out_dtype` of `mx_matmul`, and of `mx_glu_matmul` (mx_glu.py), which is `fn` then; returns (K, N)"""
+    _check_a("a", a_codes, a_scales, a_fmt)
+    _check_b("b", b_codes, b_scales, b_fmt)
+    if b_codes.dim() != 2:
+        raise ValueError(f"b_codes must be [N, K], got shape {tuple(b_codes.shape)}")
+    K, N = a_codes.shape[-1], b_codes.shape[0]
+    if b_codes.shape[1] != K:
+        raise ValueError(f"a_codes {tuple(a_codes.shape)} and b_codes {tuple(b_codes.shape)} disagree on K (their last dimensions)")
+    if K < 1:
+        raise ValueError(f"{fn} needs K >= 1")
+    if b_codes.device != a_codes.device:
+        raise ValueError(f"a_codes is on {a_codes.device} but b_codes on {b_codes.device}")
+    _check_dtype("out_dtype", out_dtype)
+    _check_bias(bias, N, "a_codes", a_codes.device)
+    return K, N
+
+
 def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
               bias: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32, *, split_k=1, out_fmt: Optional[str] = None,
               act: Optional[str] = None):
@@ -60,19 +78,7 @@ def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes
     quantize).  CPU tensors round the float64 result once to float32, apply ``act`` and run the CPU quantizer."""
     request = _split_request(split_k)
     _check_codes_out("mx_matmul", out_fmt, act, out_dtype, request)
-    _check_a("a", a_codes, a_scales, a_fmt)
-    _check_b("b", b_codes, b_scales, b_fmt)
-    if b_codes.dim() != 2:
-        raise ValueError(f"b_codes must be [N, K], got shape {tuple(b_codes.shape)}")
-    K, N = a_codes.shape[-1], b_codes.shape[0]
-    if b_codes.shape[1] != K:
-        raise ValueError(f"a_codes {tuple(a_codes.shape)} and b_codes {tuple(b_codes.shape)} disagree on K (their last dimensions)")
-    if K < 1:
-        raise ValueError("mx_matmul needs K >= 1")
-    if b_codes.device != a_codes.device:
-        raise ValueError(f"a_codes is on {a_codes.device} but b_codes on {b_codes.device}")
-    _check_dtype("out_dtype", out_dtype)
-    _check_bias(bias, N, "a_codes", a_codes.device)
+    K, N = _check_matmul_operands("mx_matmul", a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias, out_dtype)
     lead = tuple(a_codes.shape[:-1])
     a2, sa2 = a_codes.reshape(-1, K), a_scales.reshape(-1, a_scales.shape[-1])
     if a_codes.is_cuda and out_fmt is not None:

@@ -30,6 +30,41 @@ def _offs_int32(offs: torch.Tensor, T: int) -> torch.Tensor:
     return offs.to(torch.int32).contiguous()
 
 
+def _check_grouped_operands(fn: str, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, offs, bias, out_dtype):
+    """the operands, `offs`, the bias and `out_dtype` of `mx_grouped_matmul`, and of `mx_grouped_glu_matmul` (mx_glu.py), which is `fn`
+    then; returns (T, K, E, N)"""
+    _check_a("a", a_codes, a_scales, a_fmt)
+    if isinstance(b_codes, torch.Tensor) and b_codes.dim() == 2:
+        raise ValueError(f"b_codes must be [E, N, K], one weight per group, got shape {tuple(b_codes.shape)}: one weight [N, K] shared "
+                         "by every row of a is mx_matmul")
+    _check_b("b", b_codes, b_scales, b_fmt)
+    (T, K), (E, N, _) = a_codes.shape, b_codes.shape
+    if b_codes.shape[-1] != K:
+        raise ValueError(f"a_codes {tuple(a_codes.shape)} and b_codes {tuple(b_codes.shape)} disagree on K (their last dimensions)")
+    if K < 1:
+        raise ValueError(f"{fn} needs K >= 1")
+    if b_codes.device != a_codes.device:
+        raise ValueError(f"a_codes is on {a_codes.device} but b_codes on {b_codes.device}")
+    if not isinstance(offs, torch.Tensor):
+        raise TypeError(f"offs must be a tensor, got {type(offs).__name__}")
+    if offs.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"offs must be an int32 or int64 tensor (the cumulative end row of every group), got {offs.dtype}")
+    if tuple(offs.shape) != (E,):
+        raise ValueError(f"offs has shape {tuple(offs.shape)}, expected ({E},): one cumulative end row per weight of b_codes "
+                         f"{tuple(b_codes.shape)}")
+    if offs.device != a_codes.device:
+        raise ValueError(f"a_codes is on {a_codes.device} but offs on {offs.device}")
+    _check_dtype("out_dtype", out_dtype)
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
+            raise TypeError("bias must be a float32 tensor")
+        if tuple(bias.shape) not in ((N,), (E, N)):
+            raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({N},) or {(E, N)}")
+        if bias.device != a_codes.device:
+            raise ValueError(f"a_codes is on {a_codes.device} but bias on {bias.device}")
+    return T, K, E, N
+
+
 def mx_grouped_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
                       offs: torch.Tensor, bias: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32, *,
                       out_fmt: Optional[str] = None, act: Optional[str] = None):
@@ -57,35 +92,7 @@ def mx_grouped_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str,
     product's epilogue on the GPU (``qs_mx_grouped_matmul_q_v``); the tail rows are code 0 with the scale byte 0.  ``act`` is ``None``
     or ``"relu"`` and needs ``out_fmt``, and ``out_dtype`` stays at its default.  There is no ``split_k``."""
     _check_codes_out("mx_grouped_matmul", out_fmt, act, out_dtype)
-    _check_a("a", a_codes, a_scales, a_fmt)
-    if isinstance(b_codes, torch.Tensor) and b_codes.dim() == 2:
-        raise ValueError(f"b_codes must be [E, N, K], one weight per group, got shape {tuple(b_codes.shape)}: one weight [N, K] shared "
-                         "by every row of a is mx_matmul")
-    _check_b("b", b_codes, b_scales, b_fmt)
-    (T, K), (E, N, _) = a_codes.shape, b_codes.shape
-    if b_codes.shape[-1] != K:
-        raise ValueError(f"a_codes {tuple(a_codes.shape)} and b_codes {tuple(b_codes.shape)} disagree on K (their last dimensions)")
-    if K < 1:
-        raise ValueError("mx_grouped_matmul needs K >= 1")
-    if b_codes.device != a_codes.device:
-        raise ValueError(f"a_codes is on {a_codes.device} but b_codes on {b_codes.device}")
-    if not isinstance(offs, torch.Tensor):
-        raise TypeError(f"offs must be a tensor, got {type(offs).__name__}")
-    if offs.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"offs must be an int32 or int64 tensor (the cumulative end row of every group), got {offs.dtype}")
-    if tuple(offs.shape) != (E,):
-        raise ValueError(f"offs has shape {tuple(offs.shape)}, expected ({E},): one cumulative end row per weight of b_codes "
-                         f"{tuple(b_codes.shape)}")
-    if offs.device != a_codes.device:
-        raise ValueError(f"a_codes is on {a_codes.device} but offs on {offs.device}")
-    _check_dtype("out_dtype", out_dtype)
-    if bias is not None:
-        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32:
-            raise TypeError("bias must be a float32 tensor")
-        if tuple(bias.shape) not in ((N,), (E, N)):
-            raise ValueError(f"bias has shape {tuple(bias.shape)}, expected ({N},) or {(E, N)}")
-        if bias.device != a_codes.device:
-            raise ValueError(f"a_codes is on {a_codes.device} but bias on {bias.device}")
+    T, K, E, N = _check_grouped_operands("mx_grouped_matmul", a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, offs, bias, out_dtype)
     if a_codes.is_cuda:
         ops = (a_codes.contiguous(), a_scales.contiguous(), a_fmt, b_codes.contiguous(), b_scales.contiguous(), b_fmt,
                _offs_int32(offs, T), None if bias is None else bias.contiguous())
@@ -208,10 +215,13 @@ class MXMoEFeedForward(nn.Module):
     dropping, no shared expert, no training.  ``state_dict`` keys: ``router``, ``up.weight_codes``, ``up.weight_scales``, ``up.bias``,
     ``down.weight_codes``, ``down.weight_scales``, ``down.bias`` (a bias only where the layer has one)."""
 
+    _up_type = MXGroupedLinear      # what `up` must be: the gated block (mx_glu.py) derives from this one and names its own
+
     def __init__(self, router: torch.Tensor, up: MXGroupedLinear, down: MXGroupedLinear, top_k: int):
         super().__init__()
-        if not isinstance(up, MXGroupedLinear) or not isinstance(down, MXGroupedLinear):
-            raise TypeError("up and down must be MXGroupedLinear layers")
+        if not isinstance(up, self._up_type) or not isinstance(down, MXGroupedLinear):
+            raise TypeError("up and down must be MXGroupedLinear layers" if self._up_type is MXGroupedLinear else
+                            f"up must be an {self._up_type.__name__} layer and down an MXGroupedLinear layer")
         if not isinstance(router, torch.Tensor) or router.dim() != 2:
             raise ValueError("router must be a tensor [E, D]")
         E, D = router.shape
@@ -246,7 +256,7 @@ class MXMoEFeedForward(nn.Module):
     def forward(self, x):
         taken = isinstance(x, MXActivation)
         if not taken and torch.is_grad_enabled() and x.requires_grad:
-            raise RuntimeError("MXMoEFeedForward is an inference layer: its input requires grad.  Call it under torch.no_grad()")
+            raise RuntimeError(f"{type(self).__name__} is an inference layer: its input requires grad.  Call it under torch.no_grad()")
         with torch.no_grad():
             x32 = x.dequantize() if taken else x.to(torch.float32)
             if x32.dim() != 2 or x32.shape[1] != self.embed_dim:

@@ -1562,11 +1562,23 @@ typedef struct qs_mx_glu_matmul_args {
     uint8_t* out_scales;             /* otherwise: [M, H / 32] E8M0 bytes */
     int64_t M, H, K;
     qs_stream_t stream;
+    void* v;                         /* qs_mx_glu_matmul_pre_v only (below): [M, 2 H], columns interleaved as the rows of b */
+    int32_t vdt;                     /* ... QS_F32, QS_BF16 or QS_F16 */
+    int32_t reserved1;
 } qs_mx_glu_matmul_args;
 int qs_mx_glu_matmul_v(const qs_mx_glu_matmul_args* args);
 /* the kernel qs_mx_glu_matmul_v launches for these operands, nothing enqueued: QS_MX_GEMM_ROUTE_*, 0 for an empty product, or the
  * QS_ERR_* the call would return */
 int qs_mx_glu_matmul_route(const qs_mx_glu_matmul_args* args);
+/* The same product for a TRAINING forward: one more output, the pre-activations v [M, 2 H] in vdt.  v[m, n] is the accumulator plus
+ * bias rounded once to vdt: bit for bit what qs_mx_matmul_v writes for the same operands (b as [2 H, K]) with ydt = vdt.  The first
+ * output -- y, or out_codes / out_scales -- is bit for bit qs_mx_glu_matmul_v's.  The kernels are instantiations of their own, so
+ * qs_mx_glu_matmul_v, which never looks at v / vdt, launches what it launched before these fields existed.
+ * Checks: qs_mx_glu_matmul_v's with v where y is -- a NULL v is QS_ERR_ARG, vdt QS_ERR_DTYPE after ydt, v aligned to its element
+ * QS_ERR_ALIGN; after the size checks, v sharing a byte with a_codes, b_codes or the first output is QS_ERR_ARG.  Nothing outside v
+ * [M, 2 H] and the first output is written. */
+int qs_mx_glu_matmul_pre_v(const qs_mx_glu_matmul_args* args);
+int qs_mx_glu_matmul_pre_route(const qs_mx_glu_matmul_args* args);
 
 /* The grouped product ("MX grouped matrix product" above: offs, its boundaries c_e for ANY content, the tail rows) with the gated
  * epilogue: b is [E, 2 H, K], every weight interleaved as above, bias NULL, [2 H] (bias_batch_stride == 0) or [E, 2 H]
@@ -1592,9 +1604,64 @@ typedef struct qs_mx_grouped_glu_matmul_args {
     uint8_t* out_scales;
     int64_t T, E, H, K;
     qs_stream_t stream;
+    void* v;                         /* qs_mx_grouped_glu_matmul_pre_v only: [T, 2 H] */
+    int32_t vdt;
+    int32_t reserved1;
 } qs_mx_grouped_glu_matmul_args;
 int qs_mx_grouped_glu_matmul_v(const qs_mx_grouped_glu_matmul_args* args);
 int qs_mx_grouped_glu_matmul_route(const qs_mx_grouped_glu_matmul_args* args);
+/* qs_mx_glu_matmul_pre_v for the grouped product: v [T, 2 H] is bit for bit what qs_mx_grouped_matmul_v writes for the same operands
+ * (b as [E, 2 H, K]) with ydt = vdt, the tail rows +0; the first output is qs_mx_grouped_glu_matmul_v's.  Checks as there, v as above. */
+int qs_mx_grouped_glu_matmul_pre_v(const qs_mx_grouped_glu_matmul_args* args);
+int qs_mx_grouped_glu_matmul_pre_route(const qs_mx_grouped_glu_matmul_args* args);
+
+/* ---- MX gated backward quantizer (the GLU derivative in front of the two-way quantizer) ----------------------------------------
+ * Added without raising QS_ABI_VERSION (28), by the same rule as qs_mx_matmul_v above: symbols are only added.
+ *
+ * The gradient of h = act(g) * u with respect to the interleaved pre-activations, as the MX operands of the two backward products,
+ * from ONE read of dh [T, H] and v [T, 2 H] (both CONTIGUOUS; float32, bf16 or fp16, independently).  H % 32 == 0.
+ * Definition (normative).  All arithmetic is float32 without contraction on the widened inputs, expf / erff the device library's.
+ * For the hidden unit c = 32 q + t, t < 32:  g = v[m, 64 q + t],  u = v[m, 64 q + 32 + t],  d = dh[m, c],
+ *   dv[m, 64 q + t]      = (d * u) * act'(g)
+ *   dv[m, 64 q + 32 + t] = d * act(g)                       act as for the gated products above
+ *   act'(g) = g > 0 ? 1 : (g != g ? g : +0)                                          QS_MX_GLU_RELU
+ *           = s * (1.0f + g * (1.0f - s)),  s = 1.0f / (1.0f + expf(-g))             QS_MX_GLU_SILU
+ *           = fmaf(g, expf(-0.5f * g * g) * kBeta, 0.5f * (1.0f + erff(g * kAlpha)))  QS_MX_GLU_GELU, kAlpha = (float)sqrt(1/2), kBeta =
+ *             (float)(2/sqrt(pi) * sqrt(1/2) * 0.5): the factor ATen's GPU gelu_backward multiplies by (the one fma is part of it)
+ * The four outputs are bit for bit what qs_mx_quant2_v writes for the float32 tensor dv [R = T, C = 2 H] with the same row_format,
+ * col_format, rounding, seed, step and index_base (the stochastic words: stream 0 at the index of row_codes, stream 1 at that of
+ * col_codes): row_codes [T, 2 H], row_scales [T, 2 H / 32], col_codes [2 H, T], col_scales [2 H, ceil(T / 32)].  dv is never rounded
+ * to a narrower type and never written; nothing but the outputs is written, no workspace, no atomics.
+ * A pair whose format is -1 is skipped and its pointers are ignored; a pair whose format is given needs both its pointers.
+ *   - Checks, in order: the rounding operands as for qs_mx_quant2_v; QS_ERR_ARG: a null or too short descriptor, dh or v NULL, both
+ *     formats -1, a format neither -1 nor an enum qs_mx_format, a NULL pointer of a given pair, T or H negative, H % 32 != 0, act
+ *     outside QS_MX_GLU_*; QS_ERR_DTYPE: dhdt or vdt none of the three; QS_ERR_ALIGN: dh or v not aligned to its element.
+ *   - T == 0 or H == 0: nothing is enqueued, 0 is returned.
+ *   - QS_MX_Q2_ROUTE_TILE_VEC (aligned 16- / 8-byte loads, 16-byte stores of col_codes): dh and v 16-byte aligned and, when the col
+ *     pair is written, T % 16 == 0 and col_codes 16-byte aligned.  Anything else takes QS_MX_Q2_ROUTE_TILE_PLAIN: any T >= 1. */
+typedef struct qs_mx_glu_bwd_quant2_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_glu_bwd_quant2_args) as the caller compiled it */
+    int32_t row_format, col_format;  /* enum qs_mx_format, may differ; -1: that pair is skipped */
+    int32_t act;                     /* QS_MX_GLU_* */
+    const void* dh;                  /* [T, H] row-major */
+    const void* v;                   /* [T, 2 H] row-major, columns in the 32-run interleave */
+    int32_t dhdt, vdt;               /* QS_F32, QS_BF16 or QS_F16 */
+    uint8_t* row_codes;              /* [T, 2 H] */
+    uint8_t* row_scales;             /* [T, 2 H / 32] */
+    uint8_t* col_codes;              /* [2 H, T] */
+    uint8_t* col_scales;             /* [2 H, ceil(T / 32)] */
+    int64_t T, H;
+    qs_stream_t stream;
+    int32_t rounding;                /* QS_MX_ROUND_* */
+    int32_t reserved0;
+    uint64_t seed;
+    const int64_t* step;             /* nullable (= 0); device memory, one int64, read by the kernel */
+    uint64_t index_base;             /* a multiple of 4; added to the indices of both pairs */
+} qs_mx_glu_bwd_quant2_args;
+int qs_mx_glu_bwd_quant2_v(const qs_mx_glu_bwd_quant2_args* args);
+/* the kernel qs_mx_glu_bwd_quant2_v launches for these operands, nothing enqueued: QS_MX_Q2_ROUTE_*, 0 for an empty tensor, or the
+ * QS_ERR_* the call would return */
+int qs_mx_glu_bwd_quant2_route(const qs_mx_glu_bwd_quant2_args* args);
 
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so

@@ -18,6 +18,8 @@ from qsparse_amd.mx_conv_transpose import MXConvTranspose2d, mx_conv2d_input_gra
 from qsparse_amd.mx_gemm import MXActivation, MXLinear, MXTrainLinear, mx_linear, mx_matmul, mx_quantize_2way
 from qsparse_amd.mx_glu import (MXGatedMoEFeedForward, MXGLULinear, MXGroupedGLULinear, mx_glu_deinterleave, mx_glu_interleave,
                                 mx_glu_matmul, mx_grouped_glu_matmul)
+from qsparse_amd.mx_glu_train import (MXTrainGatedMoEFeedForward, MXTrainGLULinear, MXTrainGroupedGLULinear, mx_glu_backward_quantize,
+                                      mx_glu_linear, mx_grouped_glu_linear)
 from qsparse_amd.mx_grouped import MXGroupedLinear, MXMoEFeedForward, mx_grouped_matmul
 from qsparse_amd.mx_grouped_train import MXTrainGroupedLinear, MXTrainMoEFeedForward, mx_grouped_linear, mx_grouped_weight_grad
 from qsparse_amd.quantize import (AdaptiveQuantizer, DecimalQuantizer, MXQuantizer, ScalerQuantizer, quantize,

@@ -131,6 +131,12 @@ SIGNATURES = {
     "qs_mx_glu_matmul_route": (c_int, [_P]),
     "qs_mx_grouped_glu_matmul_v": (c_int, [_P]),
     "qs_mx_grouped_glu_matmul_route": (c_int, [_P]),
+    "qs_mx_glu_matmul_pre_v": (c_int, [_P]),
+    "qs_mx_glu_matmul_pre_route": (c_int, [_P]),
+    "qs_mx_grouped_glu_matmul_pre_v": (c_int, [_P]),
+    "qs_mx_grouped_glu_matmul_pre_route": (c_int, [_P]),
+    "qs_mx_glu_bwd_quant2_v": (c_int, [_P]),
+    "qs_mx_glu_bwd_quant2_route": (c_int, [_P]),
     "qs_mx_grouped_wgrad_v": (c_int, [_P]),
     "qs_mx_grouped_wgrad_route": (c_int, [_P]),
 }
@@ -311,7 +317,8 @@ def _glu_fields(fields):
     the two pointers of a codes output; `N` is `H`"""
     i = [n for n, _ in fields].index("y")
     out = [("out_format", c_int32), ("act", c_int32), ("y", c_void_p), ("ydt", c_int32), ("out_codes", c_void_p), ("out_scales", c_void_p)]
-    return fields[:i] + out + [("H", t) if n == "N" else (n, t) for n, t in fields[i + 2:]]
+    pre = [("v", c_void_p), ("vdt", c_int32), ("reserved1", c_int32)]       # the pre-activations of the `_pre_v` entry points
+    return fields[:i] + out + [("H", t) if n == "N" else (n, t) for n, t in fields[i + 2:]] + pre
 
 
 class MxGluMatmulArgs(ctypes.Structure):
@@ -322,6 +329,15 @@ class MxGluMatmulArgs(ctypes.Structure):
 class MxGroupedGluMatmulArgs(ctypes.Structure):
     """`qs_mx_grouped_glu_matmul_args` of include/qsparse_hip.h"""
     _fields_ = _glu_fields(MxGroupedMatmulArgs._fields_)
+
+
+class MxGluBwdQuant2Args(ctypes.Structure):
+    """`qs_mx_glu_bwd_quant2_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("row_format", c_int32), ("col_format", c_int32), ("act", c_int32), ("dh", c_void_p),
+                ("v", c_void_p), ("dhdt", c_int32), ("vdt", c_int32), ("row_codes", c_void_p), ("row_scales", c_void_p),
+                ("col_codes", c_void_p), ("col_scales", c_void_p), ("T", c_int64), ("H", c_int64), ("stream", c_void_p),
+                ("rounding", c_int32), ("reserved0", c_int32), ("seed", ctypes.c_uint64), ("step", c_void_p),
+                ("index_base", ctypes.c_uint64)]
 
 
 class MxGroupedWgradArgs(ctypes.Structure):
@@ -1241,16 +1257,34 @@ def _mx_glu_out(a, rows: int, H: int, act: str, out_dtype, out_fmt, device, out)
     return y
 
 
+def _mx_glu_pre(a, rows: int, H: int, preact_dtype, device, v_out):
+    """fill the pre-activation fields of a gated descriptor `a`; returns v [rows, 2 H] in `preact_dtype` -- a new tensor, or `v_out`,
+    a contiguous tensor of rows 2 H elements of that dtype, as the guard-byte tests carve it -- or None without `preact_dtype`"""
+    if preact_dtype is None:
+        return None
+    if v_out is None:
+        v = torch.empty((rows, 2 * H), dtype=preact_dtype, device=device)
+    else:
+        assert v_out.dtype == preact_dtype and v_out.is_contiguous() and v_out.numel() == rows * 2 * H, "v_out: rows 2 H elements"
+        v = v_out.view(rows, 2 * H)
+    a.v, a.vdt = _ptr(v), _DT[preact_dtype]
+    return v
+
+
 def mx_glu_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
-                  bias: Optional[torch.Tensor], act: str, out_dtype: torch.dtype = torch.float32, out_fmt: Optional[str] = None, out=None):
+                  bias: Optional[torch.Tensor], act: str, out_dtype: torch.dtype = torch.float32, out_fmt: Optional[str] = None, out=None,
+                  preact_dtype=None, v_out=None):
     """act(gate) * up of A . B^T on MX codes (qs_mx_glu_matmul_v): `a_codes` [M, K], `b_codes` [2 H, K] with its rows in the 32-row
     interleave, `bias` float32 [2 H] or None, `act` of MX_GLU_ACTS, all contiguous GPU tensors (qsparse_amd/mx_glu.py checks).  Returns
-    y [M, H] in `out_dtype`, or with `out_fmt` the pair (codes [M, H], scales [M, H / 32]).  ONE launch.  `out`: see `_mx_glu_out`."""
+    y [M, H] in `out_dtype`, or with `out_fmt` the pair (codes [M, H], scales [M, H / 32]).  ONE launch.  `out`: see `_mx_glu_out`.
+    With `preact_dtype` (qs_mx_glu_matmul_pre_v) the return is (that, v [M, 2 H] in `preact_dtype`); `v_out`: see `_mx_glu_pre`."""
     global mx_glu_last_route
     lib = load()
     (M, K), H = a_codes.shape, b_codes.shape[0] // 2
     a = MxGluMatmulArgs()
     res = _mx_glu_out(a, M, H, act, out_dtype, out_fmt, a_codes.device, out)
+    v = _mx_glu_pre(a, M, H, preact_dtype, a_codes.device, v_out)
+    name = "qs_mx_glu_matmul" if v is None else "qs_mx_glu_matmul_pre"
     mx_glu_last_route = None
     if M and H:
         a.struct_size = ctypes.sizeof(a)
@@ -1259,26 +1293,29 @@ def mx_glu_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_c
         a.bias = _ptr(bias)
         a.M, a.H, a.K = M, H, K
         a.stream = _stream(a_codes)
-        route = lib.qs_mx_glu_matmul_route(ctypes.byref(a))
+        route = getattr(lib, name + "_route")(ctypes.byref(a))
         outs = res if isinstance(res, tuple) else (res,)
-        with _timed(f"mx_glu_matmul[{route}]", a_codes, a_scales, b_codes, b_scales, bias, *outs):
-            st = lib.qs_mx_glu_matmul_v(ctypes.byref(a))
-        _check(st, "qs_mx_glu_matmul_v")
+        with _timed(f"{name[3:]}[{route}]", a_codes, a_scales, b_codes, b_scales, bias, *outs, v):
+            st = getattr(lib, name + "_v")(ctypes.byref(a))
+        _check(st, name + "_v")
         mx_glu_last_route = route
-    return res
+    return res if v is None else (res, v)
 
 
 def mx_grouped_glu_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor,
                           b_fmt: str, offs: torch.Tensor, bias: Optional[torch.Tensor], act: str,
-                          out_dtype: torch.dtype = torch.float32, out_fmt: Optional[str] = None, out=None):
+                          out_dtype: torch.dtype = torch.float32, out_fmt: Optional[str] = None, out=None, preact_dtype=None, v_out=None):
     """the grouped product with the gated epilogue (qs_mx_grouped_glu_matmul_v): operands as `mx_grouped_matmul`'s with `b_codes`
     [E, 2 H, K], every weight in the 32-row interleave, `bias` float32 [2 H], [E, 2 H] or None.  Returns y [T, H] in `out_dtype`, or
-    with `out_fmt` the pair (codes [T, H], scales [T, H / 32]).  ONE launch; `offs` is not read on the host.  `out`: see `_mx_glu_out`."""
+    with `out_fmt` the pair (codes [T, H], scales [T, H / 32]).  ONE launch; `offs` is not read on the host.  `out`: see `_mx_glu_out`.
+    With `preact_dtype` (qs_mx_grouped_glu_matmul_pre_v) the return is (that, v [T, 2 H]); `v_out`: see `_mx_glu_pre`."""
     global mx_grouped_glu_last_route
     lib = load()
     T, H = a_codes.shape[0], b_codes.shape[1] // 2
     a = MxGroupedGluMatmulArgs()
     res = _mx_glu_out(a, T, H, act, out_dtype, out_fmt, a_codes.device, out)
+    v = _mx_glu_pre(a, T, H, preact_dtype, a_codes.device, v_out)
+    name = "qs_mx_grouped_glu_matmul" if v is None else "qs_mx_grouped_glu_matmul_pre"
     mx_grouped_glu_last_route = None
     if T and H:
         (_, K), (E, N, _) = a_codes.shape, b_codes.shape
@@ -1289,13 +1326,52 @@ def mx_grouped_glu_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: 
         a.offs = _ptr(offs)
         a.T, a.E, a.H, a.K = T, E, H, K
         a.stream = _stream(a_codes)
-        route = lib.qs_mx_grouped_glu_matmul_route(ctypes.byref(a))
+        route = getattr(lib, name + "_route")(ctypes.byref(a))
         outs = res if isinstance(res, tuple) else (res,)
-        with _timed(f"mx_grouped_glu_matmul[{route}]", a_codes, a_scales, b_codes, b_scales, bias, *outs):
-            st = lib.qs_mx_grouped_glu_matmul_v(ctypes.byref(a))
-        _check(st, "qs_mx_grouped_glu_matmul_v")
+        with _timed(f"{name[3:]}[{route}]", a_codes, a_scales, b_codes, b_scales, bias, *outs, v):
+            st = getattr(lib, name + "_v")(ctypes.byref(a))
+        _check(st, name + "_v")
         mx_grouped_glu_last_route = route
-    return res
+    return res if v is None else (res, v)
+
+
+mx_glu_bwd_last_route = None          # the QS_MX_Q2_ROUTE_* of the last `mx_glu_bwd_quant2` launch (None: an empty tensor)
+
+
+def mx_glu_bwd_quant2(dh: torch.Tensor, v: torch.Tensor, act: str, row_fmt: Optional[str], col_fmt: Optional[str],
+                      rounding: str = "nearest", seed: int = 0, step: Optional[torch.Tensor] = None, index_base: int = 0, out=None):
+    """the two-way MX quantizer of dv = d(act(g) * u) / dv (qs_mx_glu_bwd_quant2_v) on contiguous GPU tensors `dh` [T, H] and `v`
+    [T, 2 H] (interleaved): returns (row_codes [T, 2 H], row_scales [T, 2 H / 32], col_codes [2 H, T], col_scales [2 H, ceil(T / 32)]),
+    uint8, a pair None where its format is None -- ONE launch, dv is never written.  `out`: the four tensors (None for a skipped
+    pair) to write instead of new ones, as the guard-byte tests carve them."""
+    global mx_glu_bwd_last_route
+    lib = load()
+    (T, H), C = dh.shape, v.shape[1]
+    nb = lambda n: (n + MX_BLOCK - 1) // MX_BLOCK
+    new = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=dh.device)
+    if out is None:
+        rc, rs = (new(T, C), new(T, nb(C))) if row_fmt is not None else (None, None)
+        cc, cs = (new(C, T), new(C, nb(T))) if col_fmt is not None else (None, None)
+    else:
+        rc, rs, cc, cs = out
+    mx_glu_bwd_last_route = None
+    if T and H:
+        a = MxGluBwdQuant2Args()
+        a.struct_size = ctypes.sizeof(a)
+        a.row_format = MX_FORMATS.index(row_fmt) if row_fmt is not None else -1
+        a.col_format = MX_FORMATS.index(col_fmt) if col_fmt is not None else -1
+        a.act = MX_GLU_ACTS.index(act)
+        a.dh, a.v, a.dhdt, a.vdt = _ptr(dh), _ptr(v), dt(dh), dt(v)
+        a.row_codes, a.row_scales, a.col_codes, a.col_scales = _ptr(rc), _ptr(rs), _ptr(cc), _ptr(cs)
+        a.T, a.H = T, H
+        a.stream = _stream(dh)
+        _mx_sr_operands(a, dh, rounding, seed, step, index_base)
+        route = lib.qs_mx_glu_bwd_quant2_route(ctypes.byref(a))
+        with _timed(f"mx_glu_bwd_quant2[{route}]", dh, v, rc, rs, cc, cs):
+            st = lib.qs_mx_glu_bwd_quant2_v(ctypes.byref(a))
+        _check(st, "qs_mx_glu_bwd_quant2_v")
+        mx_glu_bwd_last_route = route
+    return rc, rs, cc, cs
 
 
 mx_grouped_wgrad_last_route = None    # the QS_MX_GEMM_ROUTE_* of the last `mx_grouped_wgrad` launch (None: an empty result)

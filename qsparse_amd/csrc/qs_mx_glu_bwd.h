@@ -1,0 +1,197 @@
+// The two-way MX quantizer with the GLU derivative in front (include/qsparse_hip.h, "MX gated backward quantizer"): the gradient of
+// h = act(g) * u with respect to the interleaved pre-activations v [T, 2 H],
+//   dv[m, 64 q + t]      = (d * u) * act'(g)        the gate half
+//   dv[m, 64 q + 32 + t] = d * act(g)               the up half          g = v[m, 64 q + t], u = v[m, 64 q + 32 + t], d = dh[m, 32 q + t]
+// is computed in registers from ONE read of dh [T, H] and v [T, 2 H] and leaves as the two MX pairs of qs_mx_quant2.h -- row codes
+// [T, 2 H] / scales [T, 2 H / 32] and, transposed, col codes [2 H, T] / scales [2 H, ceil(T / 32)].  dv itself is float32, is never
+// rounded to a narrower type and never exists in memory.  The per-element arithmetic of the quantizer is qs_mx.h's, act is
+// mx_glu_act of qs_mx_glu.h, and the two phases are those of mx_quant2_kernel stated again on values instead of loads: that kernel
+// and its instantiations are not touched (DESIGN.md 3l measured what merging texts costs there).
+//
+// A work-group of 256 lanes owns mxq2_tile's tile, 128 rows x 64 dv columns = the hidden units [32 q, 32 q + 32) of 128 tokens: the
+// interleave puts the gate and the up column of a hidden unit into the same tile, 32 columns apart.
+//   Phase 1, lanes along H: a lane holds 4 consecutive HIDDEN units of a row -- g, u (two loads of 4 elements of v, 32 columns apart:
+//     16 bytes each for a float32 v, 8 for a two-byte one) and d (one load of 4 elements of dh) -- in 128 * 32 / (256 * 4) = 4 passes
+//     whose loads are all issued before the first use.  8 lanes cover a tile row, a wave 8 rows.  The lane evaluates act(g) and act'(g)
+//     once per hidden unit (they share expf / the sigmoid) and so owns 4 + 4 values of dv: 4 of the row's gate block and 4 of its up
+//     block.  A row block of 32 is 8 adjacent lanes: its maximum is three __shfl_xor steps, two blocks per lane and pass.  Both runs of
+//     4 go to the float32 LDS tile [128][64] as 16-byte stores: the 8 lanes of a row write 32 consecutive dwords, the 32 banks of
+//     a store, so no bank is hit twice.
+//   Phase 2 is mx_quant2_kernel's on a float32 tile: lane (c = tid & 63, b = tid >> 6) walks the 32 rows of a column block.
+// No atomics, no workspace; a null pair skips its phase, a null col pair also the LDS traffic and the barrier.  VEC = false is the same
+// tiling with element loads and byte stores, each predicated on its row: any T >= 1, any element-aligned base (2 H % 64 == 0, so no
+// column is ever outside).  SR = true rounds stochastically with the words qs_mx_quant2_v would draw for dv [T, 2 H]: stream 0 at
+// index m * 2 H + n for the row pair, stream 1 at n * T + m for the col pair.
+#pragma once
+#include "qs_mx_glu.h"
+#include "qs_mx_quant2.h"
+
+namespace qs {
+
+// act'(g) of include/qsparse_hip.h, float32 without contraction (gelu_grad_factor's one fma is part of its definition)
+__device__ __forceinline__ float mx_glu_act_grad(float g, int act) {
+    if (act == QS_MX_GLU_RELU) return g > 0.0f ? 1.0f : (g != g ? g : 0.0f);
+    if (act == QS_MX_GLU_SILU) {
+        const float s = 1.0f / (1.0f + expf(-g));
+        return s * (1.0f + g * (1.0f - s));
+    }
+    return gelu_grad_factor(g);
+}
+
+// four consecutive elements of a row as float32: one aligned load of 16 (float32) or 8 bytes (VEC), or four element loads
+template <int DT, bool VEC>
+__device__ __forceinline__ void mxgb_load4(const void* __restrict__ p, int64_t e, bool in, float (&out)[4]) {
+    using raw_t = typename Mxq2Raw<DT>::type;
+    if constexpr (VEC && DT == QS_F32) {
+        u32x4 a = {0u, 0u, 0u, 0u};
+        if (in) a = ld16<true>((const u32x4*)((const raw_t*)p + e));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) out[j] = __uint_as_float(a[j]);
+    } else if constexpr (VEC) {
+        u32x2 a = {0u, 0u};
+        if (in) a = __builtin_nontemporal_load((const u32x2*)((const raw_t*)p + e));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) out[j] = mxq2_widen<DT>((raw_t)(a[j >> 1] >> ((j & 1) * 16)));
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) out[j] = in ? mxq2_widen<DT>(((const raw_t*)p)[e + j]) : 0.0f;
+    }
+}
+
+constexpr int kMxgbUnits = 4;                                   // hidden units per lane and pass
+constexpr int kMxgbLpr = QS_MX_BLOCK / kMxgbUnits;              // 8 lanes per tile row (and per row block)
+constexpr int kMxgbRpp = kMxq2Threads / kMxgbLpr;               // 32 tile rows per pass
+constexpr int kMxgbPasses = kMxq2Rows / kMxgbRpp;               // 4
+
+// `row_vec`: row_codes is 4-byte aligned, so a lane stores its 4 codes at once (VEC only; otherwise byte stores)
+template <int DDT, int VDT, bool VEC, bool SR>
+__global__ __launch_bounds__(kMxq2Threads) void mx_glu_bwd_quant2_kernel(MxFormat fr, MxFormat fc, const void* __restrict__ dh,
+                                                                         const void* __restrict__ v, int act,
+                                                                         uint8_t* __restrict__ row_codes, uint8_t* __restrict__ row_scales,
+                                                                         uint8_t* __restrict__ col_codes, uint8_t* __restrict__ col_scales,
+                                                                         int64_t T, int64_t H, int tiles_c, int row_vec, MxSr sr) {
+    __shared__ __attribute__((aligned(16))) float tile[kMxq2Rows * kMxq2Cols];
+
+    const int tid = threadIdx.x;
+    const int64_t R = T, C = 2 * H;                             // the extents of dv, named as in qs_mx_quant2.h
+    const int64_t r0 = (int64_t)(blockIdx.x / tiles_c) * kMxq2Rows;
+    const int64_t q = blockIdx.x % tiles_c, c0 = q * kMxq2Cols; // (C % 64 == 0: c0 + 64 <= C)
+    const int64_t nbc = C / QS_MX_BLOCK, nbr = (R + QS_MX_BLOCK - 1) / QS_MX_BLOCK;
+    MxSrKey key = {0u, 0u};
+    if constexpr (SR) key = mx_sr_key(sr);
+
+    // ---- phase 1: load, derivative, stage, row pair --------------------------------------------------------------------------
+    const int lrow = tid / kMxgbLpr, t0 = (tid % kMxgbLpr) * kMxgbUnits;
+    float g[kMxgbPasses][4], u[kMxgbPasses][4], d[kMxgbPasses][4];
+#pragma unroll
+    for (int p = 0; p < kMxgbPasses; ++p) {
+        const int64_t gr = r0 + p * kMxgbRpp + lrow;
+        mxgb_load4<VDT, VEC>(v, gr * C + c0 + t0, gr < R, g[p]);
+        mxgb_load4<VDT, VEC>(v, gr * C + c0 + QS_MX_BLOCK + t0, gr < R, u[p]);
+        mxgb_load4<DDT, VEC>(dh, gr * H + q * QS_MX_BLOCK + t0, gr < R, d[p]);
+    }
+#pragma unroll
+    for (int p = 0; p < kMxgbPasses; ++p) {
+        const int64_t gr = r0 + p * kMxgbRpp + lrow;
+        float dv[2][4];                                         // [0]: the gate block's columns c0 + t0 .., [1]: the up block's, 32 on
+        uint32_t am[2] = {0u, 0u};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            dv[0][j] = (d[p][j] * u[p][j]) * mx_glu_act_grad(g[p][j], act);
+            dv[1][j] = d[p][j] * mx_glu_act(g[p][j], act);
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const uint32_t a = mx_abs_bits(dv[b][j]);
+                am[b] = a > am[b] ? a : am[b];
+            }
+        }
+        if (col_codes) {                                        // (rows past T hold +0: every input was taken as 0)
+            float* trow = tile + (p * kMxgbRpp + lrow) * kMxq2Cols + t0;
+            *(u32x4*)trow = u32x4{__float_as_uint(dv[0][0]), __float_as_uint(dv[0][1]), __float_as_uint(dv[0][2]), __float_as_uint(dv[0][3])};
+            *(u32x4*)(trow + QS_MX_BLOCK) =
+                u32x4{__float_as_uint(dv[1][0]), __float_as_uint(dv[1][1]), __float_as_uint(dv[1][2]), __float_as_uint(dv[1][3])};
+        }
+        if (!row_codes) continue;                               // (kernel-uniform)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+#pragma unroll
+            for (int off = 1; off < kMxgbLpr; off <<= 1) {
+                const uint32_t o = (uint32_t)__shfl_xor((int)am[b], off, 64);
+                am[b] = o > am[b] ? o : am[b];
+            }
+            const MxScale s = mx_scale(am[b], fr);
+            const int64_t gc = c0 + b * QS_MX_BLOCK + t0;       // (a multiple of 4, as C and sr.base: one Philox call for the four)
+            uint32_t c[4], w[4] = {0u, 0u, 0u, 0u};
+            if constexpr (SR) mx_sr_words4(key, 0u, sr.base + (uint64_t)(gr * C + gc), w);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint32_t sg;
+                float r;
+                if constexpr (SR) r = mx_round_abs_sr(dv[b][j], s, fr, w[j], sg);
+                else r = mx_round_abs(dv[b][j], s, fr, sg);
+                c[j] = mx_code(r, sg, s, fr);
+            }
+            if (gr < R) {
+                if ((tid % kMxgbLpr) == 0) row_scales[gr * nbc + (gc >> 5)] = (uint8_t)s.byte;
+                uint8_t* out = row_codes + gr * C + gc;
+                if (VEC && row_vec) {
+                    *(uint32_t*)out = mxq2_pack4(c);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) out[j] = (uint8_t)c[j];
+                }
+            }
+        }
+    }
+    if (!col_codes) return;                                     // (kernel-uniform)
+    __syncthreads();
+
+    // ---- phase 2: col pair, as mx_quant2_kernel<QS_F32> ------------------------------------------------------------------------
+    const int cc = tid & (kMxq2Cols - 1), cb = tid / kMxq2Cols;
+    const int64_t oc = c0 + cc, orow = r0 + cb * QS_MX_BLOCK;
+    float w[QS_MX_BLOCK];
+    uint32_t am = 0;
+#pragma unroll
+    for (int j = 0; j < QS_MX_BLOCK; ++j) {
+        w[j] = tile[(cb * QS_MX_BLOCK + j) * kMxq2Cols + cc];
+        const uint32_t a = mx_abs_bits(w[j]);
+        am = a > am ? a : am;
+    }
+    if (orow >= R) return;
+    const MxScale s = mx_scale(am, fc);
+    col_scales[oc * nbr + (orow >> 5)] = (uint8_t)s.byte;
+    uint32_t c[QS_MX_BLOCK];
+    if constexpr (SR && VEC) {                                  // (R % 16 == 0, orow % 32 == 0: eight calls for the lane's 32 codes)
+#pragma unroll
+        for (int k = 0; k < QS_MX_BLOCK; k += 4) {
+            uint32_t rw[4];
+            mx_sr_words4(key, 1u, sr.base + (uint64_t)(oc * R + orow) + k, rw);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint32_t sg;
+                const float r = mx_round_abs_sr(w[k + j], s, fc, rw[j], sg);
+                c[k + j] = mx_code(r, sg, s, fc);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < QS_MX_BLOCK; ++j) {
+            uint32_t sg;
+            float r;
+            if constexpr (SR) r = mx_round_abs_sr(w[j], s, fc, mx_sr_word(key, 1u, sr.base + (uint64_t)(oc * R + orow + j)), sg);
+            else r = mx_round_abs(w[j], s, fc, sg);
+            c[j] = mx_code(r, sg, s, fc);
+        }
+    }
+    uint8_t* out = col_codes + oc * R + orow;
+    if constexpr (VEC) {                                        // (R % 16 == 0: each half of the block is inside or outside as a whole)
+        *(u32x4*)out = u32x4{mxq2_pack4(c), mxq2_pack4(c + 4), mxq2_pack4(c + 8), mxq2_pack4(c + 12)};
+        if (orow + 16 < R) *(u32x4*)(out + 16) = u32x4{mxq2_pack4(c + 16), mxq2_pack4(c + 20), mxq2_pack4(c + 24), mxq2_pack4(c + 28)};
+    } else {
+#pragma unroll
+        for (int j = 0; j < QS_MX_BLOCK; ++j)
+            if (orow + j < R) out[j] = (uint8_t)c[j];
+    }
+}
+
+}  // namespace qs

@@ -8,8 +8,9 @@ meet in one lane the combined weight's rows are INTERLEAVED in runs of 32 (``mx_
 gate rows of the hidden units ``[32 q, 32 q + 32)``, rows ``[64 q + 32, 64 q + 64)`` their up rows.  The weights are static, so that is
 done once, when a layer is built.  ``H`` must be a multiple of 32: a block of 32 of the output is one wave's corner of the tile.
 
-Not offered: training through the gated product, stochastic rounding of its output, ``split_k``, the tanh GELU, gated
-``mx_bmm`` / convolutions; the ``act`` keyword of ``mx_matmul`` and its kin stays ``None`` or ``"relu"``."""
+Training through the gated products is ``mx_glu_train.py``; its forward asks the products here for the pre-activations with
+``preact_dtype``.  Not offered: stochastic rounding of the output, ``split_k``, the tanh GELU, gated ``mx_bmm`` /
+convolutions; the ``act`` keyword of ``mx_matmul`` and its kin stays ``None`` or ``"relu"``."""
 from typing import Optional
 
 import torch
@@ -84,9 +85,11 @@ def _glu_act(g: torch.Tensor, act: str) -> torch.Tensor:
     return F.silu(g) if act == "silu" else F.gelu(g) if act == "gelu" else _act(g, "relu")
 
 
-def _check_glu(fn: str, act, out_fmt, out_dtype, b_codes):
+def _check_glu(fn: str, act, out_fmt, out_dtype, b_codes, preact_dtype=None):
     if act not in GLU_ACTS:
         raise ValueError(f"unknown act {act!r}: {fn} takes one of {GLU_ACTS}")
+    if preact_dtype is not None:
+        _check_dtype("preact_dtype", preact_dtype)
     if out_fmt is not None:
         _mx_format(out_fmt)
         if out_dtype is not torch.float32:
@@ -112,7 +115,7 @@ def _glu_cpu(y: torch.Tensor, act: str, out_dtype, out_fmt):
 
 def mx_glu_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
                   bias: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32, *, act: str = "silu",
-                  out_fmt: Optional[str] = None):
+                  out_fmt: Optional[str] = None, preact_dtype: Optional[torch.dtype] = None):
     """``act(A . Wg^T + bg) * (A . Wu^T + bu)`` on MX codes in one product.  ``a_codes`` ``[..., K]`` / ``a_scales`` are
     ``mx_matmul``'s; ``b_codes`` ``[2 H, K]`` / ``b_scales`` ``[2 H, ceil(K / 32)]`` are the codes of ``mx_glu_interleave(Wg, Wu)``
     and ``bias`` float32 ``[2 H]`` is ``mx_glu_interleave(bg, bu)``.  ``act`` (keyword) is one of ``("silu", "gelu", "relu")``: SwiGLU,
@@ -124,23 +127,34 @@ def mx_glu_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_c
     stays NaN) -- then one rounding to ``out_dtype``, or ``quantize_with_mx(z, out_fmt, -1, return_codes=True)``.  GPU tensors take
     the HIP kernel (one launch, no float ``v`` or ``z`` in memory; no fallback: without the library the call raises) and equal that
     composition evaluated on the GPU bit for bit.  CPU tensors evaluate the composition with torch ops.  Across devices the results
-    agree bit for bit only for ``act="relu"``: ``expf`` and ``erff`` are each device's own.  There is no ``split_k``."""
-    _check_glu("mx_glu_matmul", act, out_fmt, out_dtype, b_codes)
+    agree bit for bit only for ``act="relu"``: ``expf`` and ``erff`` are each device's own.  There is no ``split_k``.
+
+    ``preact_dtype`` (keyword; float32, bfloat16 or float16) makes the call also keep the pre-activations, as a training forward
+    needs them: the return is ``(out, v)`` with ``out`` what the call returns without the keyword, bit for bit, and ``v [..., 2 H]``
+    bit for bit ``mx_matmul(..., out_dtype=preact_dtype)`` on the same operands -- the accumulator plus bias, rounded once, columns
+    interleaved as the rows of ``b_codes``.  On the GPU it is still one launch (``qs_mx_glu_matmul_pre_v``)."""
+    _check_glu("mx_glu_matmul", act, out_fmt, out_dtype, b_codes, preact_dtype)
     K, N = _check_matmul_operands("mx_glu_matmul", a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias, out_dtype)
     if not a_codes.is_cuda:
-        return _glu_cpu(mx_matmul(a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias, torch.float32), act, out_dtype, out_fmt)
+        out = _glu_cpu(mx_matmul(a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias, torch.float32), act, out_dtype, out_fmt)
+        if preact_dtype is None:
+            return out
+        return out, mx_matmul(a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias, preact_dtype)
     H, lead = N // 2, tuple(a_codes.shape[:-1])
     res = _hip.mx_glu_matmul(a_codes.reshape(-1, K).contiguous(), a_scales.reshape(-1, a_scales.shape[-1]).contiguous(), a_fmt,
                              b_codes.contiguous(), b_scales.contiguous(), b_fmt, None if bias is None else bias.contiguous(), act,
-                             out_dtype, out_fmt)
+                             out_dtype, out_fmt, preact_dtype=preact_dtype)
+    res, v = res if preact_dtype is not None else (res, None)
     if out_fmt is None:
-        return res.reshape(lead + (H,))
-    return res[0].reshape(lead + (H,)), res[1].reshape(lead + (H // MX_BLOCK,))
+        res = res.reshape(lead + (H,))
+    else:
+        res = res[0].reshape(lead + (H,)), res[1].reshape(lead + (H // MX_BLOCK,))
+    return res if v is None else (res, v.reshape(lead + (N,)))
 
 
 def mx_grouped_glu_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor,
                           b_fmt: str, offs: torch.Tensor, bias: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32, *,
-                          act: str = "silu", out_fmt: Optional[str] = None):
+                          act: str = "silu", out_fmt: Optional[str] = None, preact_dtype: Optional[torch.dtype] = None):
     """``mx_glu_matmul`` for ``E`` ragged groups of rows: ``a_codes`` ``[T, K]`` and ``offs`` ``[E]`` are ``mx_grouped_matmul``'s, with
     its boundaries ``c_e`` for ANY content of ``offs``, its clamp and its tail rule; ``b_codes`` ``[E, 2 H, K]`` holds one interleaved
     weight per group (``mx_glu_interleave`` on ``[E, H, K]`` tensors), ``bias`` is float32 ``[2 H]`` (shared) or ``[E, 2 H]``,
@@ -149,8 +163,11 @@ def mx_grouped_glu_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: 
     A row of group ``e`` is bit for bit ``mx_glu_matmul`` of that row with ``b[e]`` and the bias of ``e``; the tail rows ``r >=
     c_{E-1}`` are ``+0``, or code 0 with the scale byte 0.  GPU tensors take the HIP kernel: one launch, no host synchronisation,
     ``offs`` neither read nor validated on the host (graph capture works as for ``mx_grouped_matmul``).  CPU tensors refuse an
-    ``offs`` that is not nondecreasing within ``[0, T]``, as ``mx_grouped_matmul`` does, and evaluate the composition with torch ops."""
-    _check_glu("mx_grouped_glu_matmul", act, out_fmt, out_dtype, b_codes)
+    ``offs`` that is not nondecreasing within ``[0, T]``, as ``mx_grouped_matmul`` does, and evaluate the composition with torch ops.
+
+    ``preact_dtype`` (keyword) as in ``mx_glu_matmul``: the return is ``(out, v)`` with ``v [T, 2 H]`` bit for bit
+    ``mx_grouped_matmul(..., out_dtype=preact_dtype)`` on the same operands, ``+0`` in the tail rows (``qs_mx_grouped_glu_matmul_pre_v``)."""
+    _check_glu("mx_grouped_glu_matmul", act, out_fmt, out_dtype, b_codes, preact_dtype)
     T, K, E, N = _check_grouped_operands("mx_grouped_glu_matmul", a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, offs, bias,
                                          out_dtype)
     if not a_codes.is_cuda:
@@ -159,9 +176,12 @@ def mx_grouped_glu_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: 
         if out_fmt is not None and E:
             tail = int(offs[-1])
             res[0][tail:], res[1][tail:] = 0, 0      # (whatever the quantizer says of a zero block: the definition)
-        return res
+        if preact_dtype is None:
+            return res
+        return res, mx_grouped_matmul(a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, offs, bias, preact_dtype)
     return _hip.mx_grouped_glu_matmul(a_codes.contiguous(), a_scales.contiguous(), a_fmt, b_codes.contiguous(), b_scales.contiguous(),
-                                      b_fmt, _offs_int32(offs, T), None if bias is None else bias.contiguous(), act, out_dtype, out_fmt)
+                                      b_fmt, _offs_int32(offs, T), None if bias is None else bias.contiguous(), act, out_dtype, out_fmt,
+                                      preact_dtype=preact_dtype)
 
 
 def _quantize_interleaved(w_gate: torch.Tensor, w_up: torch.Tensor, w_fmt: str):

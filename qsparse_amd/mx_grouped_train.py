@@ -296,10 +296,14 @@ class MXTrainMoEFeedForward(nn.Module):
     atomic decides a bit and two runs give the same gradients.  Nothing synchronises with the host.  No auxiliary load-balancing loss,
     no capacity, no token dropping, no shared expert."""
 
+    _up_type = MXTrainGroupedLinear     # what `up` must be, and
+    _hidden_act = "relu"                # the float activation applied to its output: the hooks of MXTrainGatedMoEFeedForward (mx_glu_train.py)
+
     def __init__(self, router: torch.Tensor, up: MXTrainGroupedLinear, down: MXTrainGroupedLinear, top_k: int):
         super().__init__()
-        if not isinstance(up, MXTrainGroupedLinear) or not isinstance(down, MXTrainGroupedLinear):
-            raise TypeError("up and down must be MXTrainGroupedLinear layers")
+        if not isinstance(up, self._up_type) or not isinstance(down, MXTrainGroupedLinear):
+            raise TypeError("up and down must be MXTrainGroupedLinear layers" if self._up_type is MXTrainGroupedLinear else
+                            f"up must be a {self._up_type.__name__} layer and down must be MXTrainGroupedLinear")
         if not isinstance(router, torch.Tensor) or router.dim() != 2:
             raise ValueError("router must be a tensor [E, D]")
         E, D = router.shape
@@ -340,7 +344,7 @@ class MXTrainMoEFeedForward(nn.Module):
         offs = (ids.unsqueeze(1) == torch.arange(E, device=ids.device)).sum(0).cumsum(0).to(torch.int32)
         # row j is token order[j] // k: the k copies of every token, then a permutation
         rows = x.unsqueeze(1).expand(-1, k, -1).reshape(-1, self.embed_dim)[order]
-        hidden = _act(self.up(rows, offs), "relu")
+        hidden = _act(self.up(rows, offs), self._hidden_act)
         y = self.down(hidden, offs)
         y = y[torch.argsort(order)].reshape(-1, k, self.embed_dim)
         return (y * gates.unsqueeze(-1)).sum(1)

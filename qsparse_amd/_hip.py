@@ -928,6 +928,39 @@ mx_last_route = None          # the QS_MX_ROUTE_* of the last `mx_quant_fwd` lau
 MX_ROUNDINGS = ("nearest", "stochastic")      # QS_MX_ROUND_*, in order
 
 
+def _mx_run(entry: str, a, operands, extra_bytes: int = 0, route: Optional[str] = None) -> int:
+    """the launch sequence of every MX binding, spelled here only: size the descriptor `a`, ask `qs_<entry>_route` (`qs_<route>_route`
+    where the export is named otherwise) once, run `qs_<entry>_v` once under the event-log key `<entry>[<route>]` with the algorithmic
+    bytes of `operands` (a None counts nothing) plus `extra_bytes`, check its status.  Returns the route: the caller's `*_last_route`,
+    which it has reset before and which so stays None when this raises"""
+    fns = _mx_entries.get(entry)
+    if fns is None:         # (the two exports and the name in a failure's message, looked up once per entry point)
+        lib = load()
+        fns = _mx_entries[entry] = (getattr(lib, f"qs_{route or entry}_route"), getattr(lib, f"qs_{entry}_v"), f"qs_{entry}_v")
+    a.struct_size = ctypes.sizeof(a)
+    ref = ctypes.byref(a)
+    taken = fns[0](ref)
+    with _timed(f"{entry}[{taken}]", *operands, extra_bytes):
+        st = fns[1](ref)
+    _check(st, fns[2])
+    return taken
+
+
+_mx_entries = {}        # entry -> (route export, _v export, its name) of the library `load()` returned
+
+
+def _mx_new_or_out(shape, dtype, device, out, what: str):
+    """a new tensor of `shape`, or the caller's `out` -- a contiguous tensor of that many elements of `dtype`, as the guard-byte tests
+    carve it -- viewed to it; `what`: the assertion's text"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    n = 1
+    for d in shape:
+        n *= d
+    assert out.dtype == dtype and out.is_contiguous() and out.numel() == n, what
+    return out.view(shape)
+
+
 def _mx_sr_operands(a, x: torch.Tensor, rounding: str, seed: int, step: Optional[torch.Tensor], index_base: int):
     """fill the rounding operands of a `qs_mx_quant_args` / `qs_mx_quant2_args`"""
     a.rounding = MX_ROUNDINGS.index(rounding)
@@ -936,6 +969,33 @@ def _mx_sr_operands(a, x: torch.Tensor, rounding: str, seed: int, step: Optional
         assert step.dtype == torch.int64 and step.numel() == 1 and step.device == x.device, "step: one int64 on x's device"
     a.step = _ptr(step)
     a.index_base = int(index_base)
+
+
+def _mx_quant2_outs(lead, R: int, C: int, row_fmt, col_fmt, device, out=None):
+    """the outputs of a two-way quantizer of [*lead, R, C]: uint8 (row_codes [*lead, R, C], row_scales [*lead, R, ceil(C / 32)],
+    col_codes [*lead, C, R], col_scales [*lead, C, ceil(R / 32)]), a pair None where its format is None -- new tensors, or the four of
+    `out` viewed to those shapes"""
+    nb = lambda n: (n + MX_BLOCK - 1) // MX_BLOCK
+    shapes = (lead + (R, C), lead + (R, nb(C)), lead + (C, R), lead + (C, nb(R)))
+    if out is None:         # (written out: the path of every training step)
+        new = lambda shape: torch.empty(shape, dtype=torch.uint8, device=device)
+        return ((new(shapes[0]), new(shapes[1])) if row_fmt is not None else (None, None)) + \
+               ((new(shapes[2]), new(shapes[3])) if col_fmt is not None else (None, None))
+    fmts = (row_fmt, row_fmt, col_fmt, col_fmt)
+    for t, fmt in zip(out, fmts):
+        assert (t is None) == (fmt is None), "out: a tensor for every pair that is asked for, None for the other"
+    return tuple(None if fmt is None else _mx_new_or_out(shape, torch.uint8, device, t, "out: dense uint8")
+                 for t, shape, fmt in zip(out, shapes, fmts))
+
+
+def _mx_quant2_operands(a, x: torch.Tensor, row_fmt, col_fmt, outs, rounding, seed, step, index_base, absent: int = 0):
+    """fill what the two-way quantizer descriptors share, for the input `x`: the two formats (`absent` for a None), the four output
+    pointers, the stream and the rounding operands"""
+    a.row_format = MX_FORMATS.index(row_fmt) if row_fmt is not None else absent
+    a.col_format = MX_FORMATS.index(col_fmt) if col_fmt is not None else absent
+    a.row_codes, a.row_scales, a.col_codes, a.col_scales = _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3])
+    a.stream = _stream(x)
+    _mx_sr_operands(a, x, rounding, seed, step, index_base)
 
 
 def _mx_memory_view(x: torch.Tensor, block_dim: int):
@@ -961,7 +1021,7 @@ def mx_quant_fwd(x: torch.Tensor, fmt: str, block_dim: int, out_dtype: torch.dty
     "nearest" or "stochastic"; the random word of an element is indexed by its row-major position in x's SHAPE, so a stochastic
     call on a tensor that is not contiguous runs on a contiguous copy."""
     global mx_last_route
-    lib = load()
+    load()                        # (no library is an error for an empty tensor too: here and in every binding below)
     block_dim = block_dim % x.dim()
     if rounding == "stochastic" and not x.is_contiguous():
         xc = x.contiguous()
@@ -979,7 +1039,6 @@ def mx_quant_fwd(x: torch.Tensor, fmt: str, block_dim: int, out_dtype: torch.dty
     mx_last_route = None
     if numel:
         a = MxQuantArgs()
-        a.struct_size = ctypes.sizeof(a)
         a.format = MX_FORMATS.index(fmt)
         a.x, a.y, a.codes, a.scales = _ptr(xm), _ptr(y), _ptr(codes), _ptr(scales)
         a.xdt, a.ydt = dt(xm), _DT[out_dtype]
@@ -987,11 +1046,7 @@ def mx_quant_fwd(x: torch.Tensor, fmt: str, block_dim: int, out_dtype: torch.dty
         a.stream = _stream(xm)
         _mx_sr_operands(a, xm, rounding, seed, step, index_base)
         a.rng_stream = int(stream)
-        route = lib.qs_mx_quant_route(ctypes.byref(a))
-        with _timed(f"mx_quant_fwd[{route}]", xm, y, codes, scales):
-            st = lib.qs_mx_quant_fwd_v(ctypes.byref(a))
-        _check(st, "qs_mx_quant_fwd_v")
-        mx_last_route = route
+        mx_last_route = _mx_run("mx_quant_fwd", a, (xm, y, codes, scales), route="mx_quant")
     if scales is not None and xm is not like:         # (memory-order view of a channels_last tensor: back to the logical dim order)
         inv = [0] * xm.dim()
         for i, p in enumerate((0, 2, 3, 1) if xm.dim() == 4 else (0, 2, 3, 4, 1)):
@@ -1024,37 +1079,42 @@ def mx_split_plan(M: int, N: int, K: int, split_k: int):
     return _mx_plan("qs_mx_matmul_splitk_plan", M, N, K, split_k)
 
 
+def _mx_matmul_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias, cols: str = "N"):
+    """fill the operand fields of a dense descriptor `a` from contiguous [M, K] / [N, K] codes; `cols` names its column extent: `N`, or
+    the `H` of a gated descriptor, whose b_codes has 2 H rows.  Returns the operands, as the event log counts them"""
+    a.a_format, a.b_format = MX_FORMATS.index(a_fmt), MX_FORMATS.index(b_fmt)
+    a.a_codes, a.a_scales, a.b_codes, a.b_scales = _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales)
+    a.stream = _stream(a_codes)
+    a.bias = _ptr(bias)
+    a.M, a.K = a_codes.shape
+    if cols == "H":
+        a.H = b_codes.shape[0] // 2
+    else:
+        a.N = b_codes.shape[0]
+    return a_codes, a_scales, b_codes, b_scales, bias
+
+
 def mx_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
               bias: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32, split_k: int = 1) -> torch.Tensor:
     """y[M, N] = A . B^T on MX codes (qs_mx_matmul_v): `a_codes` [M, K], `b_codes` [N, K] uint8, scales [*, ceil(K / 32)] uint8,
     all contiguous GPU tensors (qsparse_amd/mx_gemm.py checks and flattens); `bias` float32 [N] or None.  ONE launch -- or, when
     `split_k` (0: the library's choice) plans S' > 1 slices of K, the two of qs_mx_matmul_splitk_v, with a workspace (`_mx_workspace`)."""
     global mx_gemm_last_route, mx_gemm_last_split
-    lib = load()
+    load()
     (M, K), N = a_codes.shape, b_codes.shape[0]
     y = torch.empty((M, N), dtype=out_dtype, device=a_codes.device)
     mx_gemm_last_route, mx_gemm_last_split = None, 1
     if M and N:
         slices, nbytes = mx_split_plan(M, N, K, split_k)
         a = MxMatmulSplitkArgs() if slices > 1 else MxMatmulArgs()
-        a.struct_size = ctypes.sizeof(a)
-        a.a_format, a.b_format = MX_FORMATS.index(a_fmt), MX_FORMATS.index(b_fmt)
-        a.a_codes, a.a_scales, a.b_codes, a.b_scales = _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales)
-        a.bias, a.y, a.ydt = _ptr(bias), _ptr(y), _DT[out_dtype]
-        a.M, a.N, a.K = M, N, K
-        a.stream = _stream(a_codes)
+        operands = _mx_matmul_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias) + (y,)
+        a.y, a.ydt = _ptr(y), _DT[out_dtype]
         if slices > 1:
             ws = _mx_workspace(nbytes, a_codes.device)
             a.split_k, a.workspace, a.workspace_bytes = slices, _ptr(ws), nbytes
-            route = lib.qs_mx_matmul_splitk_route(ctypes.byref(a))
-            with _timed(f"mx_matmul_splitk[{route}]", a_codes, a_scales, b_codes, b_scales, bias, y, 2 * nbytes):
-                st = lib.qs_mx_matmul_splitk_v(ctypes.byref(a))
-            _check(st, "qs_mx_matmul_splitk_v")
+            route = _mx_run("mx_matmul_splitk", a, operands, 2 * nbytes)
         else:
-            route = lib.qs_mx_matmul_route(ctypes.byref(a))
-            with _timed(f"mx_matmul[{route}]", a_codes, a_scales, b_codes, b_scales, bias, y):
-                st = lib.qs_mx_matmul_v(ctypes.byref(a))
-            _check(st, "qs_mx_matmul_v")
+            route = _mx_run("mx_matmul", a, operands)
         mx_gemm_last_route, mx_gemm_last_split = route, slices
     return y
 
@@ -1063,9 +1123,10 @@ MX_ACTS = (None, "relu")      # QS_MX_ACT_*, in order
 mx_gemm_q_last_route = None   # the QS_MX_GEMM_ROUTE_* of the last `mx_matmul_q` launch (None: an empty product), for tests and tools
 
 
-def _mx_codes_out(a, rows_shape, N: int, out_fmt: str, act, device, out):
-    """fill the output fields of a codes-out descriptor `a`; returns (codes uint8 [*rows_shape, N], scales uint8 [*rows_shape,
-    ceil(N / 32)]): new tensors, or `out` -- a pair of contiguous uint8 tensors of those sizes, as the guard-byte tests carve them"""
+def _mx_codes_out(a, rows_shape, N: int, out_fmt: str, device, out):
+    """fill the output fields of a codes-out descriptor `a` but its `act`, which is of the caller's enum; returns (codes uint8
+    [*rows_shape, N], scales uint8 [*rows_shape, ceil(N / 32)]): new tensors, or `out` -- a pair of contiguous uint8 tensors of those
+    sizes, as the guard-byte tests carve them"""
     nb = (N + MX_BLOCK - 1) // MX_BLOCK
     if out is None:
         codes = torch.empty(tuple(rows_shape) + (N,), dtype=torch.uint8, device=device)
@@ -1077,8 +1138,7 @@ def _mx_codes_out(a, rows_shape, N: int, out_fmt: str, act, device, out):
             rows *= d
         assert codes.dtype == scales.dtype == torch.uint8 and codes.is_contiguous() and scales.is_contiguous()
         assert codes.numel() == rows * N and scales.numel() == rows * nb, "out: codes [rows, N] and scales [rows, ceil(N / 32)] bytes"
-    a.out_format, a.act = MX_FORMATS.index(out_fmt), MX_ACTS.index(act)
-    a.out_codes, a.out_scales = _ptr(codes), _ptr(scales)
+    a.out_format, a.out_codes, a.out_scales = MX_FORMATS.index(out_fmt), _ptr(codes), _ptr(scales)
     return codes, scales
 
 
@@ -1087,23 +1147,15 @@ def mx_matmul_q(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_cod
     """the MX codes [M, N] and scales [M, ceil(N / 32)] in `out_fmt` of act(A . B^T + bias) (qs_mx_matmul_q_v): operands as
     `mx_matmul`'s, `act` None or "relu".  ONE launch, no float y."""
     global mx_gemm_q_last_route
-    lib = load()
-    (M, K), N = a_codes.shape, b_codes.shape[0]
+    load()
+    M, N = a_codes.shape[0], b_codes.shape[0]
     a = MxMatmulQArgs()
-    codes, scales = _mx_codes_out(a, (M,), N, out_fmt, act, a_codes.device, out)
+    codes, scales = _mx_codes_out(a, (M,), N, out_fmt, a_codes.device, out)
+    a.act = MX_ACTS.index(act)
     mx_gemm_q_last_route = None
     if M and N:
-        a.struct_size = ctypes.sizeof(a)
-        a.a_format, a.b_format = MX_FORMATS.index(a_fmt), MX_FORMATS.index(b_fmt)
-        a.a_codes, a.a_scales, a.b_codes, a.b_scales = _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales)
-        a.bias = _ptr(bias)
-        a.M, a.N, a.K = M, N, K
-        a.stream = _stream(a_codes)
-        route = lib.qs_mx_matmul_q_route(ctypes.byref(a))
-        with _timed(f"mx_matmul_q[{route}]", a_codes, a_scales, b_codes, b_scales, bias, codes, scales):
-            st = lib.qs_mx_matmul_q_v(ctypes.byref(a))
-        _check(st, "qs_mx_matmul_q_v")
-        mx_gemm_q_last_route = route
+        operands = _mx_matmul_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias)
+        mx_gemm_q_last_route = _mx_run("mx_matmul_q", a, operands + (codes, scales))
     return codes, scales
 
 
@@ -1112,15 +1164,15 @@ mx_bmm_q_last_route = None    # likewise of the last `mx_bmm_q` launch
 
 
 def _mx_bmm_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias):
-    """fill the operand fields of a batched descriptor `a` from contiguous [G, M, K] / [G, N, K] codes; returns (G, M, N)"""
-    (G, M, K), N = a_codes.shape, b_codes.shape[1]
-    a.struct_size = ctypes.sizeof(a)
+    """fill the operand fields of a batched descriptor `a` from contiguous [G, M, K] / [G, N, K] codes; returns the operands, as the
+    event log counts them"""
     a.a_format, a.b_format = MX_FORMATS.index(a_fmt), MX_FORMATS.index(b_fmt)
     a.a_codes, a.a_scales, a.b_codes, a.b_scales = _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales)
-    a.bias, a.bias_batch_stride = _ptr(bias), N if bias is not None and bias.dim() == 2 else 0
-    a.G, a.M, a.N, a.K = G, M, N, K
     a.stream = _stream(a_codes)
-    return G, M, N
+    a.G, a.M, a.K = a_codes.shape
+    a.N = N = b_codes.shape[1]
+    a.bias, a.bias_batch_stride = _ptr(bias), N if bias is not None and bias.dim() == 2 else 0
+    return a_codes, a_scales, b_codes, b_scales, bias
 
 
 def mx_bmm(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
@@ -1129,22 +1181,15 @@ def mx_bmm(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: t
     32)] uint8, all contiguous GPU tensors (qsparse_amd/mx_bmm.py checks and flattens); `bias` float32 [N], [G, N] or None.  ONE launch.
     `out`: a contiguous tensor of G M N elements of `out_dtype` to write instead of a new one, as the guard-byte tests carve it."""
     global mx_bmm_last_route
-    lib = load()
+    load()
     a = MxBmmArgs()
-    G, M, N = _mx_bmm_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias)
-    if out is None:
-        y = torch.empty((G, M, N), dtype=out_dtype, device=a_codes.device)
-    else:
-        assert out.dtype == out_dtype and out.is_contiguous() and out.numel() == G * M * N, "out: G M N elements of out_dtype"
-        y = out.view(G, M, N)
+    operands = _mx_bmm_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias)
+    (G, M, _), N = a_codes.shape, b_codes.shape[1]
+    y = _mx_new_or_out((G, M, N), out_dtype, a_codes.device, out, "out: G M N elements of out_dtype")
     mx_bmm_last_route = None
     if G and M and N:
         a.y, a.ydt = _ptr(y), _DT[out_dtype]
-        route = lib.qs_mx_bmm_route(ctypes.byref(a))
-        with _timed(f"mx_bmm[{route}]", a_codes, a_scales, b_codes, b_scales, bias, y):
-            st = lib.qs_mx_bmm_v(ctypes.byref(a))
-        _check(st, "qs_mx_bmm_v")
-        mx_bmm_last_route = route
+        mx_bmm_last_route = _mx_run("mx_bmm", a, operands + (y,))
     return y
 
 
@@ -1153,18 +1198,15 @@ def mx_bmm_q(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes:
     """the MX codes [G, M, N] and scales [G, M, ceil(N / 32)] in `out_fmt` of act(A[g] . B[g]^T + bias) (qs_mx_bmm_q_v): operands as
     `mx_bmm`'s, `act` None or "relu".  ONE launch, no float y."""
     global mx_bmm_q_last_route
-    lib = load()
+    load()
     a = MxBmmQArgs()
     (G, M, _), N = a_codes.shape, b_codes.shape[1]
-    codes, scales = _mx_codes_out(a, (G, M), N, out_fmt, act, a_codes.device, out)
+    codes, scales = _mx_codes_out(a, (G, M), N, out_fmt, a_codes.device, out)
+    a.act = MX_ACTS.index(act)
     mx_bmm_q_last_route = None
     if G and M and N:
-        _mx_bmm_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias)
-        route = lib.qs_mx_bmm_q_route(ctypes.byref(a))
-        with _timed(f"mx_bmm_q[{route}]", a_codes, a_scales, b_codes, b_scales, bias, codes, scales):
-            st = lib.qs_mx_bmm_q_v(ctypes.byref(a))
-        _check(st, "qs_mx_bmm_q_v")
-        mx_bmm_q_last_route = route
+        operands = _mx_bmm_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias)
+        mx_bmm_q_last_route = _mx_run("mx_bmm_q", a, operands + (codes, scales))
     return codes, scales
 
 
@@ -1172,18 +1214,22 @@ mx_grouped_last_route = None      # the QS_MX_GEMM_ROUTE_* of the last `mx_group
 mx_grouped_q_last_route = None    # likewise of the last `mx_grouped_matmul_q` launch
 
 
-def _mx_grouped_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, offs, bias):
+def _mx_grouped_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, offs, bias, cols: str = "N"):
     """fill the operand fields of a grouped descriptor `a` from contiguous [T, K] / [E, N, K] codes and the int32 [E] `offs` on
-    their device, which stays there; returns (T, N)"""
-    (T, K), (E, N, _) = a_codes.shape, b_codes.shape
-    a.struct_size = ctypes.sizeof(a)
+    their device, which stays there; `cols` as in `_mx_matmul_operands` (the bias stride of a gated one is still the 2 H rows of a
+    weight).  Returns the operands, as the event log counts them"""
     a.a_format, a.b_format = MX_FORMATS.index(a_fmt), MX_FORMATS.index(b_fmt)
     a.a_codes, a.a_scales, a.b_codes, a.b_scales = _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales)
+    a.stream = _stream(a_codes)
+    a.T, a.K = a_codes.shape
+    a.E, N = b_codes.shape[:2]
+    if cols == "H":
+        a.H = N // 2
+    else:
+        a.N = N
     a.bias, a.bias_batch_stride = _ptr(bias), N if bias is not None and bias.dim() == 2 else 0
     a.offs = _ptr(offs)
-    a.T, a.E, a.N, a.K = T, E, N, K
-    a.stream = _stream(a_codes)
-    return T, N
+    return a_codes, a_scales, b_codes, b_scales, bias
 
 
 def mx_grouped_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor,
@@ -1194,22 +1240,15 @@ def mx_grouped_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str,
     (qsparse_amd/mx_grouped.py checks); `bias` float32 [N], [E, N] or None.  ONE launch; `offs` is not read on the host.
     `out`: a contiguous tensor of T N elements of `out_dtype` to write instead of a new one, as the guard-byte tests carve it."""
     global mx_grouped_last_route
-    lib = load()
+    load()
     a = MxGroupedMatmulArgs()
-    T, N = _mx_grouped_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, offs, bias)
-    if out is None:
-        y = torch.empty((T, N), dtype=out_dtype, device=a_codes.device)
-    else:
-        assert out.dtype == out_dtype and out.is_contiguous() and out.numel() == T * N, "out: T N elements of out_dtype"
-        y = out.view(T, N)
+    operands = _mx_grouped_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, offs, bias)
+    T, N = a_codes.shape[0], b_codes.shape[1]
+    y = _mx_new_or_out((T, N), out_dtype, a_codes.device, out, "out: T N elements of out_dtype")
     mx_grouped_last_route = None
     if T and N:
         a.y, a.ydt = _ptr(y), _DT[out_dtype]
-        route = lib.qs_mx_grouped_matmul_route(ctypes.byref(a))
-        with _timed(f"mx_grouped_matmul[{route}]", a_codes, a_scales, b_codes, b_scales, bias, y):
-            st = lib.qs_mx_grouped_matmul_v(ctypes.byref(a))
-        _check(st, "qs_mx_grouped_matmul_v")
-        mx_grouped_last_route = route
+        mx_grouped_last_route = _mx_run("mx_grouped_matmul", a, operands + (y,))
     return y
 
 
@@ -1219,18 +1258,15 @@ def mx_grouped_matmul_q(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: st
     (qs_mx_grouped_matmul_q_v): operands as `mx_grouped_matmul`'s, `act` None or "relu".  ONE launch, no float y.  `out`: the pair
     (codes, scales) of `_mx_codes_out` to write instead of new tensors."""
     global mx_grouped_q_last_route
-    lib = load()
+    load()
     a = MxGroupedMatmulQArgs()
     T, N = a_codes.shape[0], b_codes.shape[1]
-    codes, scales = _mx_codes_out(a, (T,), N, out_fmt, act, a_codes.device, out)
+    codes, scales = _mx_codes_out(a, (T,), N, out_fmt, a_codes.device, out)
+    a.act = MX_ACTS.index(act)
     mx_grouped_q_last_route = None
     if T and N:
-        _mx_grouped_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, offs, bias)
-        route = lib.qs_mx_grouped_matmul_q_route(ctypes.byref(a))
-        with _timed(f"mx_grouped_matmul_q[{route}]", a_codes, a_scales, b_codes, b_scales, bias, codes, scales):
-            st = lib.qs_mx_grouped_matmul_q_v(ctypes.byref(a))
-        _check(st, "qs_mx_grouped_matmul_q_v")
-        mx_grouped_q_last_route = route
+        operands = _mx_grouped_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, offs, bias)
+        mx_grouped_q_last_route = _mx_run("mx_grouped_matmul_q", a, operands + (codes, scales))
     return codes, scales
 
 
@@ -1243,16 +1279,10 @@ def _mx_glu_out(a, rows: int, H: int, act: str, out_dtype, out_fmt, device, out)
     """fill the output fields of a gated descriptor `a`; returns y [rows, H] in `out_dtype` (`out_fmt` None) or the pair (codes uint8
     [rows, H], scales uint8 [rows, H / 32]): new tensors, or `out` -- a contiguous tensor of rows H elements of `out_dtype`, or the
     pair of `_mx_codes_out` -- as the guard-byte tests carve them"""
-    if out_fmt is not None:
-        res = _mx_codes_out(a, (rows,), H, out_fmt, None, device, out)
-        a.act = MX_GLU_ACTS.index(act)      # (after it: `_mx_codes_out` writes an `act` of the ungated products' enum)
-        return res
     a.act = MX_GLU_ACTS.index(act)
-    if out is None:
-        y = torch.empty((rows, H), dtype=out_dtype, device=device)
-    else:
-        assert out.dtype == out_dtype and out.is_contiguous() and out.numel() == rows * H, "out: rows H elements of out_dtype"
-        y = out.view(rows, H)
+    if out_fmt is not None:
+        return _mx_codes_out(a, (rows,), H, out_fmt, device, out)
+    y = _mx_new_or_out((rows, H), out_dtype, device, out, "out: rows H elements of out_dtype")
     a.out_format, a.y, a.ydt = -1, _ptr(y), _DT[out_dtype]
     return y
 
@@ -1262,13 +1292,15 @@ def _mx_glu_pre(a, rows: int, H: int, preact_dtype, device, v_out):
     a contiguous tensor of rows 2 H elements of that dtype, as the guard-byte tests carve it -- or None without `preact_dtype`"""
     if preact_dtype is None:
         return None
-    if v_out is None:
-        v = torch.empty((rows, 2 * H), dtype=preact_dtype, device=device)
-    else:
-        assert v_out.dtype == preact_dtype and v_out.is_contiguous() and v_out.numel() == rows * 2 * H, "v_out: rows 2 H elements"
-        v = v_out.view(rows, 2 * H)
+    v = _mx_new_or_out((rows, 2 * H), preact_dtype, device, v_out, "v_out: rows 2 H elements")
     a.v, a.vdt = _ptr(v), _DT[preact_dtype]
     return v
+
+
+def _mx_glu_run(entry: str, a, operands, res, v) -> int:
+    """`_mx_run` of the gated entry point `entry`, of `<entry>_pre` when the pre-activations `v` are kept, on the filled descriptor"""
+    outs = res if isinstance(res, tuple) else (res,)
+    return _mx_run(entry if v is None else entry + "_pre", a, operands + outs + (v,))
 
 
 def mx_glu_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: torch.Tensor, b_scales: torch.Tensor, b_fmt: str,
@@ -1279,26 +1311,15 @@ def mx_glu_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_c
     y [M, H] in `out_dtype`, or with `out_fmt` the pair (codes [M, H], scales [M, H / 32]).  ONE launch.  `out`: see `_mx_glu_out`.
     With `preact_dtype` (qs_mx_glu_matmul_pre_v) the return is (that, v [M, 2 H] in `preact_dtype`); `v_out`: see `_mx_glu_pre`."""
     global mx_glu_last_route
-    lib = load()
-    (M, K), H = a_codes.shape, b_codes.shape[0] // 2
+    load()
+    M, H = a_codes.shape[0], b_codes.shape[0] // 2
     a = MxGluMatmulArgs()
     res = _mx_glu_out(a, M, H, act, out_dtype, out_fmt, a_codes.device, out)
     v = _mx_glu_pre(a, M, H, preact_dtype, a_codes.device, v_out)
-    name = "qs_mx_glu_matmul" if v is None else "qs_mx_glu_matmul_pre"
     mx_glu_last_route = None
     if M and H:
-        a.struct_size = ctypes.sizeof(a)
-        a.a_format, a.b_format = MX_FORMATS.index(a_fmt), MX_FORMATS.index(b_fmt)
-        a.a_codes, a.a_scales, a.b_codes, a.b_scales = _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales)
-        a.bias = _ptr(bias)
-        a.M, a.H, a.K = M, H, K
-        a.stream = _stream(a_codes)
-        route = getattr(lib, name + "_route")(ctypes.byref(a))
-        outs = res if isinstance(res, tuple) else (res,)
-        with _timed(f"{name[3:]}[{route}]", a_codes, a_scales, b_codes, b_scales, bias, *outs, v):
-            st = getattr(lib, name + "_v")(ctypes.byref(a))
-        _check(st, name + "_v")
-        mx_glu_last_route = route
+        operands = _mx_matmul_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, bias, "H")
+        mx_glu_last_route = _mx_glu_run("mx_glu_matmul", a, operands, res, v)
     return res if v is None else (res, v)
 
 
@@ -1310,28 +1331,15 @@ def mx_grouped_glu_matmul(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: 
     with `out_fmt` the pair (codes [T, H], scales [T, H / 32]).  ONE launch; `offs` is not read on the host.  `out`: see `_mx_glu_out`.
     With `preact_dtype` (qs_mx_grouped_glu_matmul_pre_v) the return is (that, v [T, 2 H]); `v_out`: see `_mx_glu_pre`."""
     global mx_grouped_glu_last_route
-    lib = load()
+    load()
     T, H = a_codes.shape[0], b_codes.shape[1] // 2
     a = MxGroupedGluMatmulArgs()
     res = _mx_glu_out(a, T, H, act, out_dtype, out_fmt, a_codes.device, out)
     v = _mx_glu_pre(a, T, H, preact_dtype, a_codes.device, v_out)
-    name = "qs_mx_grouped_glu_matmul" if v is None else "qs_mx_grouped_glu_matmul_pre"
     mx_grouped_glu_last_route = None
     if T and H:
-        (_, K), (E, N, _) = a_codes.shape, b_codes.shape
-        a.struct_size = ctypes.sizeof(a)
-        a.a_format, a.b_format = MX_FORMATS.index(a_fmt), MX_FORMATS.index(b_fmt)
-        a.a_codes, a.a_scales, a.b_codes, a.b_scales = _ptr(a_codes), _ptr(a_scales), _ptr(b_codes), _ptr(b_scales)
-        a.bias, a.bias_batch_stride = _ptr(bias), N if bias is not None and bias.dim() == 2 else 0
-        a.offs = _ptr(offs)
-        a.T, a.E, a.H, a.K = T, E, H, K
-        a.stream = _stream(a_codes)
-        route = getattr(lib, name + "_route")(ctypes.byref(a))
-        outs = res if isinstance(res, tuple) else (res,)
-        with _timed(f"{name[3:]}[{route}]", a_codes, a_scales, b_codes, b_scales, bias, *outs, v):
-            st = getattr(lib, name + "_v")(ctypes.byref(a))
-        _check(st, name + "_v")
-        mx_grouped_glu_last_route = route
+        operands = _mx_grouped_operands(a, a_codes, a_scales, a_fmt, b_codes, b_scales, b_fmt, offs, bias, "H")
+        mx_grouped_glu_last_route = _mx_glu_run("mx_grouped_glu_matmul", a, operands, res, v)
     return res if v is None else (res, v)
 
 
@@ -1345,33 +1353,18 @@ def mx_glu_bwd_quant2(dh: torch.Tensor, v: torch.Tensor, act: str, row_fmt: Opti
     uint8, a pair None where its format is None -- ONE launch, dv is never written.  `out`: the four tensors (None for a skipped
     pair) to write instead of new ones, as the guard-byte tests carve them."""
     global mx_glu_bwd_last_route
-    lib = load()
+    load()
     (T, H), C = dh.shape, v.shape[1]
-    nb = lambda n: (n + MX_BLOCK - 1) // MX_BLOCK
-    new = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=dh.device)
-    if out is None:
-        rc, rs = (new(T, C), new(T, nb(C))) if row_fmt is not None else (None, None)
-        cc, cs = (new(C, T), new(C, nb(T))) if col_fmt is not None else (None, None)
-    else:
-        rc, rs, cc, cs = out
+    outs = tuple(out) if out is not None else _mx_quant2_outs((), T, C, row_fmt, col_fmt, dh.device)
     mx_glu_bwd_last_route = None
     if T and H:
         a = MxGluBwdQuant2Args()
-        a.struct_size = ctypes.sizeof(a)
-        a.row_format = MX_FORMATS.index(row_fmt) if row_fmt is not None else -1
-        a.col_format = MX_FORMATS.index(col_fmt) if col_fmt is not None else -1
+        _mx_quant2_operands(a, dh, row_fmt, col_fmt, outs, rounding, seed, step, index_base, absent=-1)
         a.act = MX_GLU_ACTS.index(act)
         a.dh, a.v, a.dhdt, a.vdt = _ptr(dh), _ptr(v), dt(dh), dt(v)
-        a.row_codes, a.row_scales, a.col_codes, a.col_scales = _ptr(rc), _ptr(rs), _ptr(cc), _ptr(cs)
         a.T, a.H = T, H
-        a.stream = _stream(dh)
-        _mx_sr_operands(a, dh, rounding, seed, step, index_base)
-        route = lib.qs_mx_glu_bwd_quant2_route(ctypes.byref(a))
-        with _timed(f"mx_glu_bwd_quant2[{route}]", dh, v, rc, rs, cc, cs):
-            st = lib.qs_mx_glu_bwd_quant2_v(ctypes.byref(a))
-        _check(st, "qs_mx_glu_bwd_quant2_v")
-        mx_glu_bwd_last_route = route
-    return rc, rs, cc, cs
+        mx_glu_bwd_last_route = _mx_run("mx_glu_bwd_quant2", a, (dh, v) + outs)
+    return outs
 
 
 mx_grouped_wgrad_last_route = None    # the QS_MX_GEMM_ROUTE_* of the last `mx_grouped_wgrad` launch (None: an empty result)
@@ -1384,27 +1377,18 @@ def mx_grouped_wgrad(gt_codes: torch.Tensor, gt_scales: torch.Tensor, g_fmt: str
     contiguous GPU tensors (qsparse_amd/mx_grouped_train.py checks).  ONE launch; `offs` is not read on the host.
     `out`: a contiguous tensor of E N K elements of `out_dtype` to write instead of a new one, as the guard-byte tests carve it."""
     global mx_grouped_wgrad_last_route
-    lib = load()
+    load()
     (N, T), K, E = gt_codes.shape, xt_codes.shape[0], offs.shape[0]
-    if out is None:
-        dw = torch.empty((E, N, K), dtype=out_dtype, device=gt_codes.device)
-    else:
-        assert out.dtype == out_dtype and out.is_contiguous() and out.numel() == E * N * K, "out: E N K elements of out_dtype"
-        dw = out.view(E, N, K)
+    dw = _mx_new_or_out((E, N, K), out_dtype, gt_codes.device, out, "out: E N K elements of out_dtype")
     mx_grouped_wgrad_last_route = None
     if E and N and K:
-        a = MxGroupedWgradArgs()
-        a.struct_size = ctypes.sizeof(a)
+        a = MxGroupedWgradArgs()        # (the format of `g` belongs to the codes of `gt`)
         a.g_format, a.x_format = MX_FORMATS.index(g_fmt), MX_FORMATS.index(x_fmt)
         a.gt_codes, a.gt_scales, a.xt_codes, a.xt_scales = _ptr(gt_codes), _ptr(gt_scales), _ptr(xt_codes), _ptr(xt_scales)
         a.offs, a.dw, a.ydt = _ptr(offs), _ptr(dw), _DT[out_dtype]
         a.T, a.E, a.N, a.K = T, E, N, K
         a.stream = _stream(gt_codes)
-        route = lib.qs_mx_grouped_wgrad_route(ctypes.byref(a))
-        with _timed(f"mx_grouped_wgrad[{route}]", gt_codes, gt_scales, xt_codes, xt_scales, dw):
-            st = lib.qs_mx_grouped_wgrad_v(ctypes.byref(a))
-        _check(st, "qs_mx_grouped_wgrad_v")
-        mx_grouped_wgrad_last_route = route
+        mx_grouped_wgrad_last_route = _mx_run("mx_grouped_wgrad", a, (gt_codes, gt_scales, xt_codes, xt_scales, dw))
     return dw
 
 
@@ -1417,26 +1401,29 @@ def mx_conv_out_size(n: int, k: int, stride: int, pad: int, dil: int) -> int:
     return (n + 2 * pad - dil * (k - 1) - 1) // stride + 1
 
 
+def _mx_conv_operands(a, x_codes, x_scales, x_fmt, w_codes, w_scales, w_fmt, bias, stride, padding, dilation):
+    """fill the operand and geometry fields of a convolution descriptor `a` from contiguous [B, H, W, C] / [Cout, KH, KW, C] codes;
+    returns the operands, as the event log counts them"""
+    a.x_format, a.w_format = MX_FORMATS.index(x_fmt), MX_FORMATS.index(w_fmt)
+    a.x_codes, a.x_scales, a.w_codes, a.w_scales = _ptr(x_codes), _ptr(x_scales), _ptr(w_codes), _ptr(w_scales)
+    a.bias, a.stream = _ptr(bias), _stream(x_codes)
+    a.B, a.H, a.W, a.C = x_codes.shape
+    a.Cout, a.KH, a.KW = w_codes.shape[:3]
+    (a.stride_h, a.stride_w), (a.pad_h, a.pad_w), (a.dil_h, a.dil_w) = stride, padding, dilation
+    return x_codes, x_scales, w_codes, w_scales, bias
+
+
 def _mx_conv_launch(name: str, a, x_codes, x_scales, x_fmt, w_codes, w_scales, w_fmt, bias, size, stride, padding, dilation, out_dtype):
     """fill the descriptor `a` (`MxConv2dArgs` or, with its output padding already set, `MxConvTranspose2dArgs`) and run
     `qs_<name>_v` into a new y [B, *size, Cout]; returns y and the route taken (None: an empty problem, nothing enqueued)"""
-    lib = load()
-    (B, H, W, C), (Cout, KH, KW, _) = x_codes.shape, w_codes.shape
+    load()
+    B, Cout = x_codes.shape[0], w_codes.shape[0]
     y = torch.empty((B,) + tuple(size) + (Cout,), dtype=out_dtype, device=x_codes.device)
     if not (B and Cout):
         return y, None
-    a.struct_size = ctypes.sizeof(a)
-    a.x_format, a.w_format = MX_FORMATS.index(x_fmt), MX_FORMATS.index(w_fmt)
-    a.x_codes, a.x_scales, a.w_codes, a.w_scales = _ptr(x_codes), _ptr(x_scales), _ptr(w_codes), _ptr(w_scales)
-    a.bias, a.y, a.ydt = _ptr(bias), _ptr(y), _DT[out_dtype]
-    a.B, a.H, a.W, a.C, a.Cout, a.KH, a.KW = B, H, W, C, Cout, KH, KW
-    (a.stride_h, a.stride_w), (a.pad_h, a.pad_w), (a.dil_h, a.dil_w) = stride, padding, dilation
-    a.stream = _stream(x_codes)
-    route = getattr(lib, f"qs_{name}_route")(ctypes.byref(a))
-    with _timed(f"{name}[{route}]", x_codes, x_scales, w_codes, w_scales, bias, y):
-        st = getattr(lib, f"qs_{name}_v")(ctypes.byref(a))
-    _check(st, f"qs_{name}_v")
-    return y, route
+    operands = _mx_conv_operands(a, x_codes, x_scales, x_fmt, w_codes, w_scales, w_fmt, bias, stride, padding, dilation)
+    a.y, a.ydt = _ptr(y), _DT[out_dtype]
+    return y, _mx_run(name, a, operands + (y,))
 
 
 def mx_conv2d(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_codes: torch.Tensor, w_scales: torch.Tensor, w_fmt: str,
@@ -1460,25 +1447,16 @@ def mx_conv2d_q(x_codes: torch.Tensor, x_scales: torch.Tensor, x_fmt: str, w_cod
     """the MX codes [B, OH, OW, Cout] and scales [B, OH, OW, ceil(Cout / 32)] in `out_fmt` of act(conv2d(x, w) + bias)
     (qs_mx_conv2d_q_v): operands as `mx_conv2d`'s, `act` None or "relu".  ONE launch, no float y and no im2col matrix."""
     global mx_conv_q_last_route
-    lib = load()
-    (B, H, W, C), (Cout, KH, KW, _) = x_codes.shape, w_codes.shape
-    size = [mx_conv_out_size(n, k, s, p, d) for n, k, s, p, d in zip((H, W), (KH, KW), stride, padding, dilation)]
+    load()
+    B, Cout = x_codes.shape[0], w_codes.shape[0]
+    size = [mx_conv_out_size(n, k, s, p, d) for n, k, s, p, d in zip(x_codes.shape[1:3], w_codes.shape[1:3], stride, padding, dilation)]
     a = MxConv2dQArgs()
-    codes, scales = _mx_codes_out(a, (B,) + tuple(size), Cout, out_fmt, act, x_codes.device, out)
+    codes, scales = _mx_codes_out(a, (B,) + tuple(size), Cout, out_fmt, x_codes.device, out)
+    a.act = MX_ACTS.index(act)
     mx_conv_q_last_route = None
     if B and Cout:
-        a.struct_size = ctypes.sizeof(a)
-        a.x_format, a.w_format = MX_FORMATS.index(x_fmt), MX_FORMATS.index(w_fmt)
-        a.x_codes, a.x_scales, a.w_codes, a.w_scales = _ptr(x_codes), _ptr(x_scales), _ptr(w_codes), _ptr(w_scales)
-        a.bias = _ptr(bias)
-        a.B, a.H, a.W, a.C, a.Cout, a.KH, a.KW = B, H, W, C, Cout, KH, KW
-        (a.stride_h, a.stride_w), (a.pad_h, a.pad_w), (a.dil_h, a.dil_w) = stride, padding, dilation
-        a.stream = _stream(x_codes)
-        route = lib.qs_mx_conv2d_q_route(ctypes.byref(a))
-        with _timed(f"mx_conv2d_q[{route}]", x_codes, x_scales, w_codes, w_scales, bias, codes, scales):
-            st = lib.qs_mx_conv2d_q_v(ctypes.byref(a))
-        _check(st, "qs_mx_conv2d_q_v")
-        mx_conv_q_last_route = route
+        operands = _mx_conv_operands(a, x_codes, x_scales, x_fmt, w_codes, w_scales, w_fmt, bias, stride, padding, dilation)
+        mx_conv_q_last_route = _mx_run("mx_conv2d_q", a, operands + (codes, scales))
     return codes, scales
 
 
@@ -1524,15 +1502,14 @@ def mx_conv2d_wgrad(dyt_codes: torch.Tensor, dyt_scales: torch.Tensor, dy_fmt: s
     `stride`, `padding`, `dilation` pairs of ints; `split_k` slices of the contraction (0: the library's choice).  ONE launch -- two
     when S' > 1, with a workspace (`_mx_workspace`)."""
     global mx_conv_wgrad_last_route, mx_conv_wgrad_last_split
-    lib = load()
+    load()
     (OH, OW, Cout, B), (H, W, C, _), (KH, KW) = dyt_codes.shape, xt_codes.shape, kernel_size
     dw = torch.empty((Cout, KH, KW, C), dtype=out_dtype, device=xt_codes.device)
     mx_conv_wgrad_last_route, mx_conv_wgrad_last_split = None, 1
     if Cout and C:
         Bp = (B + MX_BLOCK - 1) // MX_BLOCK * MX_BLOCK
         slices, nbytes = mx_conv_wgrad_plan(Cout, KH * KW * C, OH * OW * Bp, split_k)
-        a = MxConv2dWgradArgs()
-        a.struct_size = ctypes.sizeof(a)
+        a = MxConv2dWgradArgs()         # (the format of `dy` belongs to the codes of `dyt`)
         a.dy_format, a.x_format = MX_FORMATS.index(dy_fmt), MX_FORMATS.index(x_fmt)
         a.dyt_codes, a.dyt_scales, a.xt_codes, a.xt_scales = _ptr(dyt_codes), _ptr(dyt_scales), _ptr(xt_codes), _ptr(xt_scales)
         a.dw, a.ydt, a.split_k = _ptr(dw), _DT[out_dtype], slices
@@ -1541,10 +1518,7 @@ def mx_conv2d_wgrad(dyt_codes: torch.Tensor, dyt_scales: torch.Tensor, dy_fmt: s
         a.stream = _stream(xt_codes)
         ws = _mx_workspace(nbytes, xt_codes.device) if slices > 1 else None
         a.workspace, a.workspace_bytes = _ptr(ws), nbytes
-        route = lib.qs_mx_conv2d_wgrad_route(ctypes.byref(a))
-        with _timed(f"mx_conv2d_wgrad[{route}]", dyt_codes, dyt_scales, xt_codes, xt_scales, dw, 2 * nbytes):
-            st = lib.qs_mx_conv2d_wgrad_v(ctypes.byref(a))
-        _check(st, "qs_mx_conv2d_wgrad_v")
+        route = _mx_run("mx_conv2d_wgrad", a, (dyt_codes, dyt_scales, xt_codes, xt_scales, dw), 2 * nbytes)
         mx_conv_wgrad_last_route, mx_conv_wgrad_last_split = route, slices
     return dw
 
@@ -1559,29 +1533,17 @@ def mx_quant2(x: torch.Tensor, row_fmt: Optional[str], col_fmt: Optional[str], r
     row_scales [R, ceil(C / 32)], col_codes [C, R], col_scales [C, ceil(R / 32)]), uint8, a pair None where its format is None --
     from ONE launch that reads x once.  `rounding` is "nearest" or "stochastic"."""
     global mx_quant2_last_route
-    lib = load()
+    load()
     R, C = x.shape
-    nb = lambda n: (n + MX_BLOCK - 1) // MX_BLOCK
-    new = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=x.device)
-    rc, rs = (new(R, C), new(R, nb(C))) if row_fmt is not None else (None, None)
-    cc, cs = (new(C, R), new(C, nb(R))) if col_fmt is not None else (None, None)
+    outs = _mx_quant2_outs((), R, C, row_fmt, col_fmt, x.device)
     mx_quant2_last_route = None
     if R and C:
         a = MxQuant2Args()
-        a.struct_size = ctypes.sizeof(a)
-        a.row_format = MX_FORMATS.index(row_fmt) if row_fmt is not None else 0
-        a.col_format = MX_FORMATS.index(col_fmt) if col_fmt is not None else 0
+        _mx_quant2_operands(a, x, row_fmt, col_fmt, outs, rounding, seed, step, index_base)
         a.x, a.xdt = _ptr(x), dt(x)
-        a.row_codes, a.row_scales, a.col_codes, a.col_scales = _ptr(rc), _ptr(rs), _ptr(cc), _ptr(cs)
         a.R, a.C = R, C
-        a.stream = _stream(x)
-        _mx_sr_operands(a, x, rounding, seed, step, index_base)
-        route = lib.qs_mx_quant2_route(ctypes.byref(a))
-        with _timed(f"mx_quant2[{route}]", x, rc, rs, cc, cs):
-            st = lib.qs_mx_quant2_v(ctypes.byref(a))
-        _check(st, "qs_mx_quant2_v")
-        mx_quant2_last_route = route
-    return rc, rs, cc, cs
+        mx_quant2_last_route = _mx_run("mx_quant2", a, (x,) + outs)
+    return outs
 
 
 mx_quant2_batched_last_route = None   # the same of the last `mx_quant2_batched` launch
@@ -1595,37 +1557,18 @@ def mx_quant2_batched(x: torch.Tensor, G0: int, G1: int, R: int, C: int, strides
     col_scales [G, C, ceil(R / 32)]), uint8, a pair None where its format is None -- from ONE launch that reads every slice once.
     `out`: four contiguous uint8 tensors (or None for an absent pair) to write instead of new ones, as the guard-byte tests carve them."""
     global mx_quant2_batched_last_route
-    lib = load()
+    load()
     G = G0 * G1
-    nb = lambda n: (n + MX_BLOCK - 1) // MX_BLOCK
-    shapes = ((G, R, C), (G, R, nb(C)), (G, C, R), (G, C, nb(R)))
-    if out is None:
-        out = tuple(torch.empty(shape, dtype=torch.uint8, device=x.device) if fmt is not None else None
-                    for shape, fmt in zip(shapes, (row_fmt, row_fmt, col_fmt, col_fmt)))
-    else:
-        for t, shape, fmt in zip(out, shapes, (row_fmt, row_fmt, col_fmt, col_fmt)):
-            assert (t is None) == (fmt is None), "out: a tensor for every pair that is asked for, None for the other"
-            assert t is None or (t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == shape[0] * shape[1] * shape[2]), "out: dense uint8"
-        out = tuple(None if t is None else t.view(shape) for t, shape in zip(out, shapes))
-    rc, rs, cc, cs = out
+    outs = _mx_quant2_outs((G,), R, C, row_fmt, col_fmt, x.device, out)
     mx_quant2_batched_last_route = None
     if G and R and C:
         a = MxQuant2BatchedArgs()
-        a.struct_size = ctypes.sizeof(a)
-        a.row_format = MX_FORMATS.index(row_fmt) if row_fmt is not None else 0
-        a.col_format = MX_FORMATS.index(col_fmt) if col_fmt is not None else 0
+        _mx_quant2_operands(a, x, row_fmt, col_fmt, outs, rounding, seed, step, index_base)
         a.x, a.xdt = _ptr(x), dt(x)
-        a.row_codes, a.row_scales, a.col_codes, a.col_scales = _ptr(rc), _ptr(rs), _ptr(cc), _ptr(cs)
         a.R, a.C, a.G0, a.G1 = R, C, G0, G1
         a.x_stride_g0, a.x_stride_g1, a.x_stride_r = strides
-        a.stream = _stream(x)
-        _mx_sr_operands(a, x, rounding, seed, step, index_base)
-        route = lib.qs_mx_quant2_batched_route(ctypes.byref(a))
-        with _timed(f"mx_quant2_batched[{route}]", x, rc, rs, cc, cs):
-            st = lib.qs_mx_quant2_batched_v(ctypes.byref(a))
-        _check(st, "qs_mx_quant2_batched_v")
-        mx_quant2_batched_last_route = route
-    return rc, rs, cc, cs
+        mx_quant2_batched_last_route = _mx_run("mx_quant2_batched", a, (x,) + outs)
+    return outs
 
 
 def quant_line_fwd(x: torch.Tensor, lines: torch.Tensor, bits: int, channel_index: int, float_zero_point: bool,

@@ -1,7 +1,9 @@
-"""What the products on MX codes (``mx_gemm.py``, ``mx_conv.py``, ``mx_conv_transpose.py``, ``mx_conv_train.py``, ``mx_batched_train.py``) and
-their training layers say alike, stated once: the argument checks of an operand, of ``out_dtype``, of a bias and of a training entry,
-the options / stochastic-rounding counter / ``repr`` of ``MXTrainLinear`` and ``MXTrainConv2d`` (``_MXTrainMixin``), and the two steps their autograd
-functions share.  Private: the public modules import from here and keep their own shape messages."""
+"""What the products on MX codes and their training layers say alike, stated once.  The inference modules (``mx_gemm.py``,
+``mx_conv.py``, ``mx_conv_transpose.py``, ``mx_bmm.py``, ``mx_grouped.py``, ``mx_glu.py``) take the argument checks of an operand, of
+``out_dtype``, of a bias and of the codes-out keywords, and ``MXActivation``; the training modules (``mx_gemm.py``, ``mx_conv_train.py``,
+``mx_batched_train.py``, ``mx_grouped_train.py``, ``mx_glu_train.py``) the check of a training entry, the scaffold of their layers
+(``_MXTrainMixin``: options, stochastic-rounding seed and counter, autocast) and the two steps their autograd functions share.
+Private: the public modules import from here and keep their own shape messages."""
 from typing import NamedTuple
 
 import torch
@@ -143,18 +145,34 @@ def _check_train_entry(x, weight, bias, fmts, grad_rounding: str, step, wgrad_sp
 
 
 class _MXTrainMixin:
-    """what ``MXTrainLinear`` and ``MXTrainConv2d`` share, mixed in before the torch layer they derive from"""
+    """the scaffold of every layer that trains through MX products -- ``MXTrainLinear``, ``MXTrainConv2d``, ``MXTrainGroupedLinear``,
+    ``MXTrainGLULinear``, ``MXTrainGroupedGLULinear``, ``MXTrainMultiheadAttention`` -- mixed in before the torch class they derive
+    from.  ``_adopt`` and ``extra_repr`` are those of the first two, which own ``wgrad_split_k`` and derive from a torch layer"""
 
-    def _init_mx(self, x_fmt: str, w_fmt: str, grad_fmt: str, grad_rounding: str, seed, wgrad_split_k):
-        for fmt in (x_fmt, w_fmt, grad_fmt):
+    def _check_mx(self, fmts: dict, dtypes: dict):
+        """the formats, then the dtype options as the entries check them: ``out_dtype`` may be None (the input's)"""
+        for fmt in fmts.values():
             _mx_format(fmt)
-        _mx_check_rounding(grad_rounding, None, self.weight)
-        _split_request(wgrad_split_k, "wgrad_split_k")
-        self.wgrad_split_k = wgrad_split_k
-        self.x_fmt, self.w_fmt, self.grad_fmt, self.grad_rounding = x_fmt, w_fmt, grad_fmt, grad_rounding
+        for name, dtype in dtypes.items():
+            if dtype is not None or name != "out_dtype":
+                _check_dtype(name, dtype)
+
+    def _init_mx(self, fmts: dict, grad_rounding: str, seed, weight=None, **dtypes):
+        """check and keep the options every such layer has.  `fmts` and `dtypes` map attribute names to formats and dtype options;
+        `weight`: the tensor whose device counts the backwards (default: ``self.weight``).  Under "stochastic" the layer gets
+        ``sr_seed`` -- `seed`, or ONE draw from torch's default CPU generator -- and the non-persistent buffer ``sr_step``"""
+        weight = self.weight if weight is None else weight
+        self._check_mx(fmts, dtypes)
+        _mx_check_rounding(grad_rounding, None, weight)
+        for name, value in (*fmts.items(), *dtypes.items(), ("grad_rounding", grad_rounding)):
+            setattr(self, name, value)
         if grad_rounding == "stochastic":
             self.sr_seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if seed is None else int(seed)
-            self.register_buffer("sr_step", torch.zeros(1, dtype=torch.int64, device=self.weight.device), persistent=False)
+            self.register_buffer("sr_step", torch.zeros(1, dtype=torch.int64, device=weight.device), persistent=False)
+
+    def _init_split(self, wgrad_split_k):
+        _split_request(wgrad_split_k, "wgrad_split_k")
+        self.wgrad_split_k = wgrad_split_k
 
     def _adopt(self, layer):
         """take `layer`'s parameters (shared, not copied), count on its device and follow its mode; returns self"""
@@ -169,13 +187,16 @@ class _MXTrainMixin:
         split = f", wgrad_split_k={self.wgrad_split_k!r}" if self.wgrad_split_k != "auto" else ""
         return f"{super().extra_repr()}, x_fmt={self.x_fmt!r}, w_fmt={self.w_fmt!r}, grad_fmt={self.grad_fmt!r}{sr}{split}"
 
+    def _mx_sr(self):
+        """(seed, step) for the functional form"""
+        return (self.sr_seed, self.sr_step) if self.grad_rounding == "stochastic" else (0, None)
+
     def _mx_input(self, x: torch.Tensor):
         """(x in the autocast dtype, seed, step) for the functional form"""
         dev = x.device.type
         if torch.is_autocast_enabled(dev):
             x = x.to(torch.get_autocast_dtype(dev))
-        seed, step = (self.sr_seed, self.sr_step) if self.grad_rounding == "stochastic" else (0, None)
-        return x, seed, step
+        return (x,) + self._mx_sr()
 
 
 def _save_train_ctx(ctx, fmts, sr, wgrad_split_k, x: torch.Tensor, bias):

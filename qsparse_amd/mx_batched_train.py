@@ -16,7 +16,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from qsparse_amd import _hip
-from qsparse_amd._mx_common import _check_dtype, _check_train_entry, _quantize_grad, _save_train_ctx
+from qsparse_amd._mx_common import _check_dtype, _check_train_entry, _MXTrainMixin, _quantize_grad, _save_train_ctx
 from qsparse_amd.mx_bmm import MXMultiheadAttention, _attention_mask, mx_bmm
 from qsparse_amd.mx_gemm import MXTrainLinear
 from qsparse_amd.quantize import MX_BLOCK, _mx_aten, _mx_check_rounding, _mx_format, _mx_sr_words
@@ -233,7 +233,7 @@ def mx_attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_m
     return mx_bmm_train(torch.softmax(s, -1), v, b_layout="kn", a_fmt=p_fmt, b_fmt=v_fmt, out_dtype=q.dtype, seed=seed, **sr)
 
 
-class MXTrainMultiheadAttention(nn.Module):
+class MXTrainMultiheadAttention(_MXTrainMixin, nn.Module):
     """A self-attention ``nn.MultiheadAttention`` that trains on MX codes throughout: two ``MXTrainLinear`` s -- the packed ``in_proj``
     ``[3 E, E]`` and ``out_proj`` ``[E, E]`` -- around ``mx_attention_train`` over ``[B, h, T, d]``.  ``forward(x, attn_mask=None,
     is_causal=False)`` takes ``x`` ``[T, B, E]`` (``[B, T, E]`` with ``batch_first``) and returns ``(output, None)``.  ``q``, ``k`` and
@@ -256,15 +256,9 @@ class MXTrainMultiheadAttention(nn.Module):
                              f"[{out_proj.out_features}, {out_proj.in_features}]")
         if isinstance(num_heads, bool) or not isinstance(num_heads, int) or num_heads < 1 or E % num_heads:
             raise ValueError(f"num_heads must be an int >= 1 that divides embed_dim {E}, got {num_heads!r}")
-        for fmt in (qk_fmt, p_fmt, v_fmt, grad_fmt):
-            _mx_format(fmt)
-        _mx_check_rounding(grad_rounding, None, in_proj.weight)
+        self._init_mx(dict(qk_fmt=qk_fmt, p_fmt=p_fmt, v_fmt=v_fmt, grad_fmt=grad_fmt), grad_rounding, seed, in_proj.weight)
         self.in_proj, self.out_proj = in_proj, out_proj
         self.embed_dim, self.num_heads, self.batch_first = E, num_heads, bool(batch_first)
-        self.qk_fmt, self.p_fmt, self.v_fmt, self.grad_fmt, self.grad_rounding = qk_fmt, p_fmt, v_fmt, grad_fmt, grad_rounding
-        if grad_rounding == "stochastic":
-            self.sr_seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if seed is None else int(seed)
-            self.register_buffer("sr_step", torch.zeros(1, dtype=torch.int64, device=in_proj.weight.device), persistent=False)
 
     def extra_repr(self) -> str:
         sr = f", grad_rounding={self.grad_rounding!r}" if self.grad_rounding != "nearest" else ""
@@ -308,7 +302,7 @@ class MXTrainMultiheadAttention(nn.Module):
         xb = x if self.batch_first else x.transpose(0, 1)
         B, T = xb.shape[:2]
         q, k, v = (t.view(B, T, h, E // h).transpose(1, 2) for t in self.in_proj(xb).chunk(3, -1))      # views: nothing is copied
-        seed, step = (self.sr_seed, self.sr_step) if self.grad_rounding == "stochastic" else (0, None)
+        seed, step = self._mx_sr()
         o = mx_attention_train(q, k, v, attn_mask, is_causal, qk_fmt=self.qk_fmt, p_fmt=self.p_fmt, v_fmt=self.v_fmt,
                                grad_fmt=self.grad_fmt, grad_rounding=self.grad_rounding, seed=seed, step=step)
         y = self.out_proj(o.transpose(1, 2).reshape(B, T, E))

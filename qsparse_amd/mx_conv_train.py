@@ -235,7 +235,8 @@ class MXTrainConv2d(_MXTrainMixin, nn.Conv2d):
             raise ValueError(f"MXTrainConv2d needs the padding as numbers, the layer has padding={padding!r}")
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, bias, padding_mode, device=device,
                          dtype=dtype)
-        self._init_mx(x_fmt, w_fmt, grad_fmt, grad_rounding, seed, wgrad_split_k)
+        self._init_mx(dict(x_fmt=x_fmt, w_fmt=w_fmt, grad_fmt=grad_fmt), grad_rounding, seed)
+        self._init_split(wgrad_split_k)
 
     @classmethod
     def from_conv(cls, layer: nn.Conv2d, x_fmt: str = "mxfp8_e4m3", w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2",

@@ -328,7 +328,8 @@ class MXTrainLinear(_MXTrainMixin, nn.Linear):
                  w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2", grad_rounding: str = "nearest", seed: Optional[int] = None,
                  wgrad_split_k="auto"):
         super().__init__(in_features, out_features, bias=bias, device=device, dtype=dtype)
-        self._init_mx(x_fmt, w_fmt, grad_fmt, grad_rounding, seed, wgrad_split_k)
+        self._init_mx(dict(x_fmt=x_fmt, w_fmt=w_fmt, grad_fmt=grad_fmt), grad_rounding, seed)
+        self._init_split(wgrad_split_k)
 
     @classmethod
     def from_linear(cls, layer: nn.Linear, x_fmt: str = "mxfp8_e4m3", w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2",

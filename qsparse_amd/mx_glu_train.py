@@ -16,15 +16,13 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from qsparse_amd import _hip
-from qsparse_amd._mx_common import (_act, _check_bias_shape, _check_dtype, _check_train_entry, _quantize_grad, _save_train_ctx,
-                                    _split_request)
+from qsparse_amd._mx_common import (_act, _check_bias_shape, _check_dtype, _check_train_entry, _MXTrainMixin, _quantize_grad,
+                                    _save_train_ctx)
 from qsparse_amd.mx_batched_train import mx_quantize_2way_batched
 from qsparse_amd.mx_gemm import mx_matmul, mx_quantize_2way
 from qsparse_amd.mx_glu import (GLU_ACTS, MXGatedMoEFeedForward, MXGLULinear, MXGroupedGLULinear, _check_hidden, mx_glu_deinterleave,
                                 mx_glu_interleave, mx_glu_matmul, mx_grouped_glu_matmul)
-from qsparse_amd.mx_grouped import mx_grouped_matmul
-from qsparse_amd.mx_grouped_train import (MXTrainGroupedLinear, MXTrainMoEFeedForward, _check_offs, _group_membership,
-                                          mx_grouped_weight_grad)
+from qsparse_amd.mx_grouped_train import MXTrainGroupedLinear, MXTrainMoEFeedForward, _check_offs, _grouped_backward
 from qsparse_amd.quantize import MX_BLOCK, _mx_check_rounding, _mx_format
 
 _GELU_ALPHA = math.sqrt(0.5)
@@ -89,12 +87,6 @@ def mx_glu_backward_quantize(dh: torch.Tensor, v: torch.Tensor, *, act: str, row
     return mx_quantize_2way(_glu_dv(dh, v, act), row_fmt, col_fmt, rounding, seed, step)
 
 
-def _glu_bias_grad(dh, v, act, bias_dtype, member=None):
-    """dbias: the float32 row sum of dv (per group through the 0/1 matrix `member` [E, T]) by torch ops -- a pass of its own"""
-    dv = _glu_dv(dh, v, act)
-    return (dv.sum(0, dtype=torch.float32) if member is None else member @ dv).to(bias_dtype)
-
-
 class _MXGLULinearFunction(torch.autograd.Function):
     """the table of `mx_glu_linear` on MX codes; every quantizer straight-through.  `need_dx` / `need_dw`: that gradient can be asked
     for -- decided by mx_glu_linear, where the grad mode is still the caller's"""
@@ -130,8 +122,8 @@ class _MXGLULinearFunction(torch.autograd.Function):
             dx = mx_matmul(g_row, g_rs, grad_fmt, w_col, w_cs, w_fmt, None, ctx.x_dtype).reshape(ctx.x_shape)
         if need_dw:
             dw = mx_matmul(g_col, g_cs, grad_fmt, x_col, x_cs, x_fmt, None, ctx.w_dtype, split_k=ctx.wgrad_split_k)
-        if need_db:
-            db = _glu_bias_grad(dh2, v, ctx.act, ctx.bias_dtype)
+        if need_db:         # the float32 row sum of dv by torch ops: a pass of its own
+            db = _glu_dv(dh2, v, ctx.act).sum(0, dtype=torch.float32).to(ctx.bias_dtype)
         return (dx, dw, db) + (None,) * 12
 
 
@@ -203,23 +195,12 @@ class _MXGroupedGLULinearFunction(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dh):
-        v, x_col, x_cs, w_col, w_cs, offs = ctx.saved_tensors
-        x_fmt, w_fmt, grad_fmt = ctx.fmts
-        need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
-        need_dx, need_dw = need_dx and w_col is not None, need_dw and x_col is not None
+        v, *pairs_offs = ctx.saved_tensors
         dh = dh.contiguous()
-        dx = dw = db = None
-        if need_dx or need_dw:
-            g_row, g_rs, g_col, g_cs = _quantize_grad(ctx, lambda *sr: mx_glu_backward_quantize(
-                dh, v, act=ctx.act, row_fmt=grad_fmt if need_dx else None, col_fmt=grad_fmt if need_dw else None, rounding=sr[0],
-                seed=sr[1], step=sr[2]))
-        if need_dx:         # (the tail rows reach nothing: +0)
-            dx = mx_grouped_matmul(g_row, g_rs, grad_fmt, w_col, w_cs, w_fmt, offs, None, ctx.x_dtype)
-        if need_dw:
-            dw = mx_grouped_weight_grad(g_col, g_cs, grad_fmt, x_col, x_cs, x_fmt, offs, ctx.w_dtype)
-        if need_db:         # a 0/1 matrix times dv in float32: no atomics, no host read of offs
-            db = _glu_bias_grad(dh, v, ctx.act, ctx.bias_dtype, _group_membership(offs, dh.shape[0]))
-        return (dx, dw, db) + (None,) * 12
+        quantize = lambda row_fmt, col_fmt, rounding, seed, step: mx_glu_backward_quantize(
+            dh, v, act=ctx.act, row_fmt=row_fmt, col_fmt=col_fmt, rounding=rounding, seed=seed, step=step)
+        # mx_grouped_linear's backward on the operands of dv; dbias sums dv, evaluated again in float32 by torch ops
+        return _grouped_backward(ctx, dh, *pairs_offs, quantize, lambda: _glu_dv(dh, v, ctx.act)) + (None,) * 12
 
 
 def mx_grouped_glu_linear(x: torch.Tensor, weight: torch.Tensor, offs: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
@@ -254,28 +235,22 @@ def mx_grouped_glu_linear(x: torch.Tensor, weight: torch.Tensor, offs: torch.Ten
                                              grad and x.requires_grad, grad and weight.requires_grad, grad_rounding, seed, step)
 
 
-class _TrainGLUMixin:
-    """what ``MXTrainGLULinear`` and ``MXTrainGroupedGLULinear`` share: ONE interleaved parameter per kind, the options, ``repr``"""
+class _TrainGLUMixin(_MXTrainMixin):
+    """what ``MXTrainGLULinear`` and ``MXTrainGroupedGLULinear`` add to the scaffold: ONE interleaved parameter per kind, ``act``,
+    ``preact_dtype``, ``repr``"""
 
     def _init_glu(self, weight, bias, act, x_fmt, w_fmt, grad_fmt, out_dtype, preact_dtype, grad_rounding, seed):
         if act not in GLU_ACTS:
             raise ValueError(f"unknown act {act!r}: {type(self).__name__} takes one of {GLU_ACTS}")
-        for fmt in (x_fmt, w_fmt, grad_fmt):
-            _mx_format(fmt)
-        if out_dtype is not None:
-            _check_dtype("out_dtype", out_dtype)
-        _check_dtype("preact_dtype", preact_dtype)
+        fmts, dtypes = dict(x_fmt=x_fmt, w_fmt=w_fmt, grad_fmt=grad_fmt), dict(out_dtype=out_dtype, preact_dtype=preact_dtype)
+        self._check_mx(fmts, dtypes)        # (before the weight is looked at, as ever; `_init_mx` makes them again)
         _check_interleaved_rows(type(self).__name__, weight.shape[-2])
         as_param = lambda t: t if isinstance(t, nn.Parameter) else nn.Parameter(t.detach())
         self.weight = as_param(weight)
         self.bias = None if bias is None else as_param(bias)
-        _mx_check_rounding(grad_rounding, None, self.weight)
-        self.act, self.x_fmt, self.w_fmt, self.grad_fmt = act, x_fmt, w_fmt, grad_fmt
-        self.out_dtype, self.preact_dtype, self.grad_rounding = out_dtype, preact_dtype, grad_rounding
+        self._init_mx(fmts, grad_rounding, seed, **dtypes)
+        self.act = act
         self.out_features, self.in_features = weight.shape[-2] // 2, weight.shape[-1]
-        if grad_rounding == "stochastic":
-            self.sr_seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if seed is None else int(seed)
-            self.register_buffer("sr_step", torch.zeros(1, dtype=torch.int64, device=self.weight.device), persistent=False)
 
     @classmethod
     def from_float(cls, w_gate: torch.Tensor, w_up: torch.Tensor, b_gate: Optional[torch.Tensor] = None,
@@ -301,11 +276,9 @@ class _TrainGLUMixin:
         return (f"{groups}in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, "
                 f"act={self.act!r}, x_fmt={self.x_fmt!r}, w_fmt={self.w_fmt!r}, grad_fmt={self.grad_fmt!r}{sr}")
 
-    def _mx_input(self, x: torch.Tensor):
-        dev = x.device.type
-        if torch.is_autocast_enabled(dev):
-            x = x.to(torch.get_autocast_dtype(dev))
-        seed, step = (self.sr_seed, self.sr_step) if self.grad_rounding == "stochastic" else (0, None)
+    def _mx_glu_input(self, x: torch.Tensor):
+        """(x in the autocast dtype, the keywords of the functional form)"""
+        x, seed, step = self._mx_input(x)
         return x, dict(act=self.act, x_fmt=self.x_fmt, w_fmt=self.w_fmt, grad_fmt=self.grad_fmt, out_dtype=self.out_dtype,
                        preact_dtype=self.preact_dtype, grad_rounding=self.grad_rounding, seed=seed, step=step)
 
@@ -325,12 +298,11 @@ class MXTrainGLULinear(_TrainGLUMixin, nn.Module):
             raise ValueError("MXTrainGLULinear needs an interleaved weight tensor [2 H, K]")
         _check_interleaved_rows("MXTrainGLULinear", weight.shape[0])
         _check_bias_shape(bias, weight.shape[0])
-        _split_request(wgrad_split_k, "wgrad_split_k")
-        self.wgrad_split_k = wgrad_split_k
+        self._init_split(wgrad_split_k)
         self._init_glu(weight, bias, act, x_fmt, w_fmt, grad_fmt, out_dtype, preact_dtype, grad_rounding, seed)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        x, opts = self._mx_input(x)
+        x, opts = self._mx_glu_input(x)
         return mx_glu_linear(x, self.weight, self.bias, wgrad_split_k=self.wgrad_split_k, **opts)
 
     def to_inference(self, act_fmt: Optional[str] = None, out_dtype: torch.dtype = torch.float32, *,
@@ -358,7 +330,7 @@ class MXTrainGroupedGLULinear(_TrainGLUMixin, nn.Module):
         self._init_glu(weight, bias, act, x_fmt, w_fmt, grad_fmt, out_dtype, preact_dtype, grad_rounding, seed)
 
     def forward(self, x: torch.Tensor, offs: torch.Tensor) -> torch.Tensor:
-        x, opts = self._mx_input(x)
+        x, opts = self._mx_glu_input(x)
         return mx_grouped_glu_linear(x, self.weight, offs, self.bias, **opts)
 
     def to_inference(self, act_fmt: Optional[str] = None, out_dtype: torch.dtype = torch.float32, *,

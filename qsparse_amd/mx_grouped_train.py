@@ -16,11 +16,11 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from qsparse_amd import _hip, _mx_common
-from qsparse_amd._mx_common import _act, _check_dtype, _check_train_entry, _quantize_grad, _save_train_ctx
+from qsparse_amd._mx_common import _act, _check_dtype, _check_train_entry, _MXTrainMixin, _quantize_grad, _save_train_ctx
 from qsparse_amd.mx_batched_train import mx_quantize_2way_batched
 from qsparse_amd.mx_gemm import mx_quantize_2way
 from qsparse_amd.mx_grouped import MXGroupedLinear, MXMoEFeedForward, _offs_int32, mx_grouped_matmul
-from qsparse_amd.quantize import MX_BLOCK, _mx_check_rounding, _mx_format, mx_dequantize
+from qsparse_amd.quantize import MX_BLOCK, mx_dequantize
 
 _STEP = 128        # tokens per step of the kernel's walk: the alignment of a group's slice in the definition
 
@@ -118,6 +118,26 @@ def _group_membership(offs: torch.Tensor, T: int) -> torch.Tensor:
     return ((t >= lo.unsqueeze(1)) & (t < c.unsqueeze(1))).to(torch.float32)
 
 
+def _grouped_backward(ctx, dy: torch.Tensor, x_col, x_cs, w_col, w_cs, offs, quantize, bias_rows):
+    """(dx, dw, dbias) of a grouped table from the contiguous incoming gradient `dy` [T, *] and the pairs its forward saved.
+    `quantize(row_fmt, col_fmt, rounding, seed, step)`: the four gradient operands [T, N] / [N, T] (a format None: that pair is not
+    asked for); `bias_rows()`: the float32 [T, N] whose sum over the rows of a group is its dbias"""
+    x_fmt, w_fmt, grad_fmt = ctx.fmts
+    need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
+    need_dx, need_dw = need_dx and w_col is not None, need_dw and x_col is not None
+    dx = dw = db = None
+    if need_dx or need_dw:
+        g_row, g_rs, g_col, g_cs = _quantize_grad(ctx, lambda *sr: quantize(grad_fmt if need_dx else None,
+                                                                             grad_fmt if need_dw else None, *sr))
+    if need_dx:         # (the tail rows reach nothing: +0)
+        dx = mx_grouped_matmul(g_row, g_rs, grad_fmt, w_col, w_cs, w_fmt, offs, None, ctx.x_dtype)
+    if need_dw:
+        dw = mx_grouped_weight_grad(g_col, g_cs, grad_fmt, x_col, x_cs, x_fmt, offs, ctx.w_dtype)
+    if need_db:         # a 0/1 matrix times the rows in float32: no atomics, no host read of offs
+        db = (_group_membership(offs, dy.shape[0]) @ bias_rows()).to(ctx.bias_dtype)
+    return dx, dw, db
+
+
 class _MXGroupedLinearFunction(torch.autograd.Function):
     """the table of `mx_grouped_linear` on MX codes; every quantizer straight-through.  `need_dx` / `need_dw`: that gradient can be
     asked for -- decided by mx_grouped_linear, where the grad mode is still the caller's (as mx_linear's `need_col`)"""
@@ -138,22 +158,9 @@ class _MXGroupedLinearFunction(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        x_col, x_cs, w_col, w_cs, offs = ctx.saved_tensors
-        x_fmt, w_fmt, grad_fmt = ctx.fmts
-        need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
-        need_dx, need_dw = need_dx and w_col is not None, need_dw and x_col is not None
         dy = dy.contiguous()
-        dx = dw = db = None
-        if need_dx or need_dw:
-            g_row, g_rs, g_col, g_cs = _quantize_grad(ctx, lambda *sr: mx_quantize_2way(dy, grad_fmt if need_dx else None,
-                                                                                         grad_fmt if need_dw else None, *sr))
-        if need_dx:         # (the tail rows of dy reach nothing: +0)
-            dx = mx_grouped_matmul(g_row, g_rs, grad_fmt, w_col, w_cs, w_fmt, offs, None, ctx.x_dtype)
-        if need_dw:
-            dw = mx_grouped_weight_grad(g_col, g_cs, grad_fmt, x_col, x_cs, x_fmt, offs, ctx.w_dtype)
-        if need_db:         # a 0/1 matrix times dy in float32: no atomics, no host read of offs
-            db = (_group_membership(offs, dy.shape[0]) @ dy.to(torch.float32)).to(ctx.bias_dtype)
-        return dx, dw, db, None, None, None, None, None, None, None, None, None, None
+        return _grouped_backward(ctx, dy, *ctx.saved_tensors, lambda *fmts_sr: mx_quantize_2way(dy, *fmts_sr),
+                                 lambda: dy.to(torch.float32)) + (None,) * 10
 
 
 def mx_grouped_linear(x: torch.Tensor, weight: torch.Tensor, offs: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
@@ -199,7 +206,7 @@ def mx_grouped_linear(x: torch.Tensor, weight: torch.Tensor, offs: torch.Tensor,
                                           grad and weight.requires_grad, grad_rounding, seed, step)
 
 
-class MXTrainGroupedLinear(nn.Module):
+class MXTrainGroupedLinear(_MXTrainMixin, nn.Module):
     """``E`` linear layers that train through grouped MX matrix products: float parameters ``weight [E, N, K]`` and ``bias [E, N]``,
     ``forward(x, offs)`` is ``mx_grouped_linear`` in the formats ``x_fmt`` / ``w_fmt`` / ``grad_fmt``; the output is ``out_dtype``, by
     default the input's.  Under ``torch.autocast`` the input is cast to the autocast dtype, as ``MXTrainLinear``'s.
@@ -223,18 +230,7 @@ class MXTrainGroupedLinear(nn.Module):
                 self.weight.uniform_(-bound, bound)
                 if bias:
                     self.bias.uniform_(-bound, bound)
-        self._init_mx(x_fmt, w_fmt, grad_fmt, out_dtype, grad_rounding, seed)
-
-    def _init_mx(self, x_fmt, w_fmt, grad_fmt, out_dtype, grad_rounding, seed):
-        for fmt in (x_fmt, w_fmt, grad_fmt):
-            _mx_format(fmt)
-        if out_dtype is not None:
-            _check_dtype("out_dtype", out_dtype)
-        _mx_check_rounding(grad_rounding, None, self.weight)
-        self.x_fmt, self.w_fmt, self.grad_fmt, self.out_dtype, self.grad_rounding = x_fmt, w_fmt, grad_fmt, out_dtype, grad_rounding
-        if grad_rounding == "stochastic":
-            self.sr_seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if seed is None else int(seed)
-            self.register_buffer("sr_step", torch.zeros(1, dtype=torch.int64, device=self.weight.device), persistent=False)
+        self._init_mx(dict(x_fmt=x_fmt, w_fmt=w_fmt, grad_fmt=grad_fmt), grad_rounding, seed, out_dtype=out_dtype)
 
     def extra_repr(self) -> str:
         sr = f", grad_rounding={self.grad_rounding!r}" if self.grad_rounding != "nearest" else ""
@@ -264,10 +260,7 @@ class MXTrainGroupedLinear(nn.Module):
         return layer
 
     def forward(self, x: torch.Tensor, offs: torch.Tensor) -> torch.Tensor:
-        dev = x.device.type
-        if torch.is_autocast_enabled(dev):
-            x = x.to(torch.get_autocast_dtype(dev))
-        seed, step = (self.sr_seed, self.sr_step) if self.grad_rounding == "stochastic" else (0, None)
+        x, seed, step = self._mx_input(x)
         return mx_grouped_linear(x, self.weight, offs, self.bias, x_fmt=self.x_fmt, w_fmt=self.w_fmt, grad_fmt=self.grad_fmt,
                                  out_dtype=self.out_dtype, grad_rounding=self.grad_rounding, seed=seed, step=step)
 

@@ -1663,6 +1663,71 @@ int qs_mx_glu_bwd_quant2_v(const qs_mx_glu_bwd_quant2_args* args);
  * QS_ERR_* the call would return */
 int qs_mx_glu_bwd_quant2_route(const qs_mx_glu_bwd_quant2_args* args);
 
+/* ---- MX normalising quantizer (RMSNorm / LayerNorm in front of the one-way / two-way quantizer) -----------------------------------
+ * Added without raising QS_ABI_VERSION (28), by the same rule as qs_mx_matmul_v above: symbols are only added.
+ *
+ * The MX operands of y = norm(x) * weight (+ bias) from x [R, C] (CONTIGUOUS, C innermost; float32, bf16 or fp16) without the float
+ * y in memory: the normalisation runs over C, `weight` [C] and `bias` [C] are float32 (NULL: ones / none).
+ * Definition (normative).  All arithmetic is float32 without contraction on the widened inputs; `/` and sqrt are the correctly
+ * rounded IEEE operations; Cf = (float)C.
+ *   sum(t) over a row, t_0 .. t_(C-1) -- a FIXED order that depends on C alone (not on R, the dtype, the route, the launch or mode):
+ *     t_i = +0 for C <= i < 512 ceil(C / 512)
+ *     quad sums        q_m = (t_4m + t_(4m+1)) + (t_(4m+2) + t_(4m+3))
+ *     128 strided partial sums   P_j = (((+0 + q_j) + q_(j+128)) + q_(j+256)) + ...      j < 128, ascending
+ *     pairwise tree    for s = 64, 32, 16, 8, 4, 2, 1:  P_j = P_j + P_(j+s), j < s;   sum = P_0
+ *     (with tensors: pad to [K, 128, 4]; q = (t[..,0] + t[..,1]) + (t[..,2] + t[..,3]); P = 0; P = P + q[k] for k = 0 .. K-1; then
+ *      seven element-wise additions of the upper half of P to the lower)
+ *   QS_MX_NORM_RMS     ms   = sum(x_i * x_i) / Cf
+ *                      rstd = 1.0f / sqrt(ms + eps)
+ *                      y_i  = (x_i * rstd) * w_i (+ b_i)
+ *   QS_MX_NORM_LAYER   mean = sum(x_i) / Cf
+ *                      d_i  = x_i - mean
+ *                      ms   = sum(d_i * d_i) / Cf                (the two-pass variance; the padding terms are +0, not mean^2)
+ *                      rstd = 1.0f / sqrt(ms + eps)
+ *                      y_i  = (d_i * rstd) * w_i (+ b_i)
+ *   rstd is a quiet NaN where ms is not finite: a row that holds a NaN or an Inf (or whose squares overflow) is NaN in EVERY element
+ *   of y, so every block that row touches has the scale byte 0xFF and zero codes, in both pairs.  A multiplication by an absent
+ *   weight and an addition of an absent bias are not performed.  An all-zero row gives y = b (eps > 0).
+ * Outputs: row_codes [R, C] / row_scales [R, ceil(C / 32)] are bit for bit the codes and scales qs_mx_quant_fwd_v writes for y with
+ * blocks along C in row_format, col_codes [C, R] / col_scales [C, ceil(R / 32)] the col pair qs_mx_quant2_v writes for y in col_format
+ * (col_format -1: skipped, its pointers ignored); both round to nearest-even -- stochastic rounding is not offered.  rstd [R]
+ * float32 is always written (it is also the only workspace: the statistics launch writes it, the quantizing launch reads it), mean [R]
+ * float32 in layer mode (ignored in rms mode).  Nothing else is written; no atomics; two launches on `stream`, nothing read by the host.
+ *   - Checks, in order: QS_ERR_ARG: a null or too short descriptor, an unknown mode, x, row_codes, row_scales or rstd NULL, mean NULL
+ *     in layer mode, row_format no enum qs_mx_format, col_format neither -1 nor one, a NULL pointer of a given col pair, eps negative
+ *     or not finite, R or C negative; QS_ERR_DTYPE: xdt none of the three; QS_ERR_ALIGN: x not aligned to its element, or weight, bias,
+ *     rstd or mean not to 4 bytes.
+ *   - R == 0 or C == 0: nothing is enqueued, 0 is returned.
+ *   - QS_MX_NORM_ROUTE_VEC (16-byte loads of x in the statistics, 16- / 8-byte loads in the quantizing launch, 4-byte stores of
+ *     row_codes where it is 4-byte aligned, 16-byte stores of col_codes where R % 16 == 0 and it is 16-byte aligned): C % 32 == 0
+ *     and x, weight, bias 16-byte aligned.  Anything else takes QS_MX_NORM_ROUTE_PLAIN, element accesses: any R, C >= 1, same bits. */
+#define QS_MX_NORM_RMS 0
+#define QS_MX_NORM_LAYER 1
+typedef struct qs_mx_norm_quant_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_norm_quant_args) as the caller compiled it */
+    int32_t mode;                    /* QS_MX_NORM_* */
+    int32_t row_format, col_format;  /* enum qs_mx_format, may differ; col_format -1: the col pair is skipped */
+    int32_t xdt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    float eps;
+    const void* x;                   /* [R, C] row-major */
+    const float* weight;             /* [C], nullable (ones) */
+    const float* bias;               /* [C], nullable (none) */
+    uint8_t* row_codes;              /* [R, C] */
+    uint8_t* row_scales;             /* [R, ceil(C / 32)] */
+    uint8_t* col_codes;              /* [C, R] */
+    uint8_t* col_scales;             /* [C, ceil(R / 32)] */
+    float* rstd;                     /* [R] */
+    float* mean;                     /* [R], layer mode */
+    int64_t R, C;
+    qs_stream_t stream;
+} qs_mx_norm_quant_args;
+int qs_mx_norm_quant_v(const qs_mx_norm_quant_args* args);
+/* the kernels qs_mx_norm_quant_v launches for these operands, nothing enqueued: QS_MX_NORM_ROUTE_*, 0 for an empty tensor, or the
+ * QS_ERR_* the call would return */
+#define QS_MX_NORM_ROUTE_VEC 1
+#define QS_MX_NORM_ROUTE_PLAIN 2
+int qs_mx_norm_quant_route(const qs_mx_norm_quant_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

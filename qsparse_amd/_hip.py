@@ -139,6 +139,8 @@ SIGNATURES = {
     "qs_mx_glu_bwd_quant2_route": (c_int, [_P]),
     "qs_mx_grouped_wgrad_v": (c_int, [_P]),
     "qs_mx_grouped_wgrad_route": (c_int, [_P]),
+    "qs_mx_norm_quant_v": (c_int, [_P]),
+    "qs_mx_norm_quant_route": (c_int, [_P]),
 }
 
 
@@ -338,6 +340,14 @@ class MxGluBwdQuant2Args(ctypes.Structure):
                 ("col_codes", c_void_p), ("col_scales", c_void_p), ("T", c_int64), ("H", c_int64), ("stream", c_void_p),
                 ("rounding", c_int32), ("reserved0", c_int32), ("seed", ctypes.c_uint64), ("step", c_void_p),
                 ("index_base", ctypes.c_uint64)]
+
+
+class MxNormQuantArgs(ctypes.Structure):
+    """`qs_mx_norm_quant_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("mode", c_int32), ("row_format", c_int32), ("col_format", c_int32), ("xdt", c_int32),
+                ("eps", c_float), ("x", c_void_p), ("weight", c_void_p), ("bias", c_void_p), ("row_codes", c_void_p),
+                ("row_scales", c_void_p), ("col_codes", c_void_p), ("col_scales", c_void_p), ("rstd", c_void_p), ("mean", c_void_p),
+                ("R", c_int64), ("C", c_int64), ("stream", c_void_p)]
 
 
 class MxGroupedWgradArgs(ctypes.Structure):
@@ -1569,6 +1579,38 @@ def mx_quant2_batched(x: torch.Tensor, G0: int, G1: int, R: int, C: int, strides
         a.x_stride_g0, a.x_stride_g1, a.x_stride_r = strides
         mx_quant2_batched_last_route = _mx_run("mx_quant2_batched", a, (x,) + outs)
     return outs
+
+
+MX_NORMS = ("rms", "layer")             # QS_MX_NORM_*, in order
+MX_NORM_ROUTE_VEC, MX_NORM_ROUTE_PLAIN = 1, 2
+mx_norm_last_route = None     # the QS_MX_NORM_ROUTE_* of the last `mx_norm_quant` launch (None: an empty tensor), for tests and tools
+
+
+def mx_norm_quant(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], norm: str, eps: float, row_fmt: str,
+                  col_fmt: Optional[str]):
+    """RMSNorm / LayerNorm in front of the MX quantizer (qs_mx_norm_quant_v) on a contiguous GPU tensor `x` [R, C] and float32
+    `weight` / `bias` [C] (or None): returns (row_codes [R, C], row_scales [R, ceil(C / 32)], col_codes [C, R] | None, col_scales
+    [C, ceil(R / 32)] | None, rstd [R], mean [R] | None) -- mean in layer mode -- from two launches."""
+    global mx_norm_last_route
+    load()
+    R, C = x.shape
+    outs = _mx_quant2_outs((), R, C, row_fmt, col_fmt, x.device)
+    rstd = torch.empty(R, dtype=torch.float32, device=x.device)
+    mean = torch.empty(R, dtype=torch.float32, device=x.device) if norm == "layer" else None
+    mx_norm_last_route = None
+    if R and C:
+        a = MxNormQuantArgs()
+        a.mode = MX_NORMS.index(norm)
+        a.row_format = MX_FORMATS.index(row_fmt)
+        a.col_format = MX_FORMATS.index(col_fmt) if col_fmt is not None else -1
+        a.xdt, a.eps = dt(x), float(eps)
+        a.x, a.weight, a.bias = _ptr(x), _ptr(weight), _ptr(bias)
+        a.row_codes, a.row_scales, a.col_codes, a.col_scales = _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3])
+        a.rstd, a.mean = _ptr(rstd), _ptr(mean)
+        a.R, a.C = R, C
+        a.stream = _stream(x)
+        mx_norm_last_route = _mx_run("mx_norm_quant", a, (x, weight, bias) + outs + (rstd, mean))
+    return outs + (rstd, mean)
 
 
 def quant_line_fwd(x: torch.Tensor, lines: torch.Tensor, bits: int, channel_index: int, float_zero_point: bool,

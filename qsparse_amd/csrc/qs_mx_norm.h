@@ -1,0 +1,232 @@
+// RMSNorm / LayerNorm in front of the MX quantizer (include/qsparse_hip.h, "MX normalising quantizer"): x [R, C] leaves as the row
+// pair and, optionally, the transposed col pair of y = norm(x) * w (+ b); the float y never exists in memory.  Two launches:
+//
+//   mx_norm_stats_kernel   one WAVE per row (four rows per work-group, no LDS, no barrier): rstd [R] and, in layer mode, mean [R].
+//     A lane takes 8 consecutive elements per pass of 512 (one 16-byte load for two-byte inputs, two for float32, on the VEC route),
+//     forms the two quad sums (t0 + t1) + (t2 + t3) and adds them to its two partial sums; the lanes' 128 partial sums are folded by
+//     six __shfl_down steps (offsets 32 .. 1) and one last addition -- exactly the order the header defines, which so is a function of
+//     C alone.  Layer mode walks the row twice (mean, then the centred squares): the second walk is served from the cache.
+//   mx_norm_apply_kernel   the tile of qs_mx_quant2.h (128 rows x 64 columns, 256 lanes) with the normalisation as its widen step.
+//     Phase 1, lanes along C: a lane holds 4 consecutive elements of a row (16 bytes of float32, 8 of a two-byte input) in 8 passes
+//     of 16 rows whose loads -- x, the row's rstd / mean -- are all issued before the first use; w and b of the lane's 4 columns are
+//     loaded once.  A row block of 32 is 8 adjacent lanes: three __shfl_xor steps.  y goes to the float32 LDS tile [128][64] as one
+//     16-byte store per lane and pass (the 16 lanes of a row write 64 consecutive dwords: no bank is hit twice per 32-bank phase).
+//   Phase 2 is mx_quant2_kernel's on a float32 tile: lane (c = tid & 63, b = tid >> 6) walks the 32 rows of a column block, the
+//     transposition happens in registers.  Elements outside [R, C] are +0 in the tile, as the quantizer's short last blocks.
+// The per-element arithmetic of the quantizer is qs_mx.h's; nothing of it is restated here.  No atomics, no workspace beyond rstd /
+// mean; a null col pair skips the LDS traffic, the barrier and phase 2 (kernel-uniform).  VEC = false is the same text with element
+// accesses, each predicated on its own index: any R, C >= 1, any element-aligned base.  Rounding is to nearest only.
+#pragma once
+#include "qs_mx_quant2.h"
+
+namespace qs {
+
+constexpr int kMxnStatRows = kMxq2Threads / 64;                 // rows per work-group of the stats kernel: one per wave
+constexpr int kMxnPass = 64 * 8;                                // elements of a row a wave takes per pass
+
+// the 8 elements [c, c + 8) of the row at `base` as float32 and whether each exists; what does not exist is +0
+template <int XDT, bool VEC>
+__device__ __forceinline__ void mxn_load8(const void* __restrict__ x, int64_t base, int64_t c, int64_t C, float (&v)[8], bool (&in)[8]) {
+    if constexpr (VEC) {                                        // (C % 8 == 0: the 8 are inside or outside together)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            v[j] = 0.0f;
+            in[j] = c < C;
+        }
+        if (c < C) unpack8<XDT>(load8_raw<XDT, false>(x, (base + c) >> 3), v);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            in[j] = c + j < C;
+            v[j] = in[j] ? load1<XDT>(x, base + c + j) : 0.0f;
+        }
+    }
+}
+
+// sum over the row of t_i = x_i (TERM 0), x_i * x_i (1) or (x_i - mu) * (x_i - mu) (2) in the header's order; every lane returns it
+template <int XDT, bool VEC, int TERM>
+__device__ __forceinline__ float mxn_row_sum(const void* __restrict__ x, int64_t base, int64_t C, int lane, float mu) {
+    float pa = 0.0f, pb = 0.0f;                                 // the partial sums 2 lane and 2 lane + 1
+    for (int64_t c0 = 0; c0 < C; c0 += kMxnPass) {              // (wave-uniform trip count)
+        float v[8];
+        bool in[8];
+        mxn_load8<XDT, VEC>(x, base, c0 + lane * 8, C, v, in);
+        float t[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if constexpr (TERM == 0) t[j] = v[j];
+            if constexpr (TERM == 1) t[j] = v[j] * v[j];
+            if constexpr (TERM == 2) {
+                const float d = v[j] - mu;
+                t[j] = in[j] ? d * d : 0.0f;
+            }
+        }
+        pa = pa + ((t[0] + t[1]) + (t[2] + t[3]));
+        pb = pb + ((t[4] + t[5]) + (t[6] + t[7]));
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {                   // partial j += partial j + 2 off, j < 2 off (the lanes above hold
+        pa = pa + __shfl_down(pa, off, 64);                     //  sums nobody reads)
+        pb = pb + __shfl_down(pb, off, 64);
+    }
+    return __shfl(pa + pb, 0, 64);
+}
+
+template <int XDT, bool VEC>
+__global__ __launch_bounds__(kMxq2Threads) void mx_norm_stats_kernel(const void* __restrict__ x, float* __restrict__ rstd,
+                                                                     float* __restrict__ mean, int64_t R, int64_t C, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * kMxnStatRows + (threadIdx.x >> 6);
+    if (r >= R) return;                                         // (wave-uniform; the kernel has no barrier)
+    const float cf = (float)C;
+    float mu = 0.0f, ms;
+    if (mean) {                                                 // (kernel-uniform: layer mode)
+        mu = mxn_row_sum<XDT, VEC, 0>(x, r * C, C, lane, 0.0f) / cf;
+        ms = mxn_row_sum<XDT, VEC, 2>(x, r * C, C, lane, mu) / cf;
+    } else {
+        ms = mxn_row_sum<XDT, VEC, 1>(x, r * C, C, lane, 0.0f) / cf;
+    }
+    float rs = 1.0f / sqrtf(ms + eps);                          // (both correctly rounded: the build's default for HIP)
+    if (mx_abs_bits(ms) >= 0x7f800000u) rs = __uint_as_float(0x7fc00000u);      // a row that is not finite is NaN as a whole
+    if (lane == 0) {
+        rstd[r] = rs;
+        if (mean) mean[r] = mu;
+    }
+}
+
+constexpr int kMxnV = 4;                                        // elements per lane and pass of the apply kernel
+constexpr int kMxnLpr = kMxq2Cols / kMxnV;                      // 16 lanes per tile row
+constexpr int kMxnLpb = QS_MX_BLOCK / kMxnV;                    // 8 lanes per row block
+constexpr int kMxnRpp = kMxq2Threads / kMxnLpr;                 // 16 tile rows per pass
+constexpr int kMxnPasses = kMxq2Rows / kMxnRpp;                 // 8
+
+// `row_vec`: row_codes is 4-byte aligned, so a lane stores its 4 codes at once; `col_vec`: R % 16 == 0 and col_codes 16-byte aligned,
+// so a lane stores its column block as two 16-byte runs (both VEC only; otherwise byte stores)
+template <int XDT, bool VEC>
+__global__ __launch_bounds__(kMxq2Threads) void mx_norm_apply_kernel(MxFormat fr, MxFormat fc, const void* __restrict__ x,
+                                                                     const float* __restrict__ wt, const float* __restrict__ bs,
+                                                                     const float* __restrict__ rstd, const float* __restrict__ mean,
+                                                                     uint8_t* __restrict__ row_codes, uint8_t* __restrict__ row_scales,
+                                                                     uint8_t* __restrict__ col_codes, uint8_t* __restrict__ col_scales,
+                                                                     int64_t R, int64_t C, int tiles_c, int row_vec, int col_vec) {
+    using raw_t = typename Mxq2Raw<XDT>::type;
+    __shared__ __attribute__((aligned(16))) float tile[kMxq2Rows * kMxq2Cols];
+
+    const int tid = threadIdx.x;
+    const int64_t r0 = (int64_t)(blockIdx.x / tiles_c) * kMxq2Rows;
+    const int64_t c0 = (int64_t)(blockIdx.x % tiles_c) * kMxq2Cols;
+    const int64_t nbc = (C + QS_MX_BLOCK - 1) / QS_MX_BLOCK, nbr = (R + QS_MX_BLOCK - 1) / QS_MX_BLOCK;
+
+    // ---- phase 1: load, normalise, stage, row pair ---------------------------------------------------------------------------
+    const int lrow = tid / kMxnLpr, lcol = (tid % kMxnLpr) * kMxnV;
+    const int64_t gc = c0 + lcol;
+    raw_t raw[kMxnPasses][kMxnV];
+    float rs[kMxnPasses], mu[kMxnPasses];
+#pragma unroll
+    for (int p = 0; p < kMxnPasses; ++p) {
+        const int64_t gr = r0 + p * kMxnRpp + lrow;
+        if constexpr (VEC) {                                    // (C % 4 == 0: the lane's 4 elements are inside or outside together)
+            if constexpr (XDT == QS_F32) {
+                u32x4 a = {0u, 0u, 0u, 0u};
+                if (gr < R && gc < C) a = ld16<true>((const u32x4*)((const raw_t*)x + gr * C + gc));
+#pragma unroll
+                for (int j = 0; j < kMxnV; ++j) raw[p][j] = a[j];
+            } else {
+                u32x2 a = {0u, 0u};
+                if (gr < R && gc < C) a = __builtin_nontemporal_load((const u32x2*)((const raw_t*)x + gr * C + gc));
+#pragma unroll
+                for (int j = 0; j < kMxnV; ++j) raw[p][j] = (raw_t)(a[j >> 1] >> ((j & 1) * 16));
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < kMxnV; ++j) raw[p][j] = (gr < R && gc + j < C) ? ((const raw_t*)x)[gr * C + gc + j] : (raw_t)0;
+        }
+        rs[p] = gr < R ? rstd[gr] : 0.0f;
+        mu[p] = (mean && gr < R) ? mean[gr] : 0.0f;
+    }
+    float w[kMxnV], b[kMxnV];
+#pragma unroll
+    for (int j = 0; j < kMxnV; ++j) {
+        w[j] = (wt && gc + j < C) ? wt[gc + j] : 1.0f;
+        b[j] = (bs && gc + j < C) ? bs[gc + j] : 0.0f;
+    }
+#pragma unroll
+    for (int p = 0; p < kMxnPasses; ++p) {
+        const int64_t gr = r0 + p * kMxnRpp + lrow;
+        float y[kMxnV];
+        uint32_t am = 0;
+#pragma unroll
+        for (int j = 0; j < kMxnV; ++j) {
+            float v = mxq2_widen<XDT>(raw[p][j]);
+            if (mean) v = v - mu[p];                            // (kernel-uniform, as the two below)
+            v = v * rs[p];
+            if (wt) v = v * w[j];
+            if (bs) v = v + b[j];
+            y[j] = (gr < R && gc + j < C) ? v : 0.0f;
+            const uint32_t a = mx_abs_bits(y[j]);
+            am = a > am ? a : am;
+        }
+        if (col_codes)
+            *(u32x4*)(tile + (p * kMxnRpp + lrow) * kMxq2Cols + lcol) =
+                u32x4{__float_as_uint(y[0]), __float_as_uint(y[1]), __float_as_uint(y[2]), __float_as_uint(y[3])};
+#pragma unroll
+        for (int off = 1; off < kMxnLpb; off <<= 1) {
+            const uint32_t o = (uint32_t)__shfl_xor((int)am, off, 64);
+            am = o > am ? o : am;
+        }
+        const MxScale s = mx_scale(am, fr);
+        uint32_t c[kMxnV];
+#pragma unroll
+        for (int j = 0; j < kMxnV; ++j) {
+            uint32_t sg;
+            const float r = mx_round_abs(y[j], s, fr, sg);
+            c[j] = mx_code(r, sg, s, fr);
+        }
+        if (gr < R && gc < C) {
+            if ((tid % kMxnLpb) == 0) row_scales[gr * nbc + (gc >> 5)] = (uint8_t)s.byte;
+            uint8_t* out = row_codes + gr * C + gc;
+            if (VEC && row_vec) {
+                *(uint32_t*)out = mxq2_pack4(c);
+            } else {
+#pragma unroll
+                for (int j = 0; j < kMxnV; ++j)
+                    if (VEC || gc + j < C) out[j] = (uint8_t)c[j];
+            }
+        }
+    }
+    if (!col_codes) return;                                     // (kernel-uniform)
+    __syncthreads();
+
+    // ---- phase 2: col pair, as mx_quant2_kernel<QS_F32> ------------------------------------------------------------------------
+    const int cc = tid & (kMxq2Cols - 1), cb = tid / kMxq2Cols;
+    const int64_t oc = c0 + cc, orow = r0 + cb * QS_MX_BLOCK;
+    float t[QS_MX_BLOCK];
+    uint32_t am = 0;
+#pragma unroll
+    for (int j = 0; j < QS_MX_BLOCK; ++j) {
+        t[j] = tile[(cb * QS_MX_BLOCK + j) * kMxq2Cols + cc];
+        const uint32_t a = mx_abs_bits(t[j]);
+        am = a > am ? a : am;
+    }
+    if (oc >= C || orow >= R) return;
+    const MxScale s = mx_scale(am, fc);
+    col_scales[oc * nbr + (orow >> 5)] = (uint8_t)s.byte;
+    uint32_t c[QS_MX_BLOCK];
+#pragma unroll
+    for (int j = 0; j < QS_MX_BLOCK; ++j) {
+        uint32_t sg;
+        const float r = mx_round_abs(t[j], s, fc, sg);
+        c[j] = mx_code(r, sg, s, fc);
+    }
+    uint8_t* out = col_codes + oc * R + orow;
+    if (VEC && col_vec) {                                       // (R % 16 == 0: each half of the block is inside or outside as a whole)
+        *(u32x4*)out = u32x4{mxq2_pack4(c), mxq2_pack4(c + 4), mxq2_pack4(c + 8), mxq2_pack4(c + 12)};
+        if (orow + 16 < R) *(u32x4*)(out + 16) = u32x4{mxq2_pack4(c + 16), mxq2_pack4(c + 20), mxq2_pack4(c + 24), mxq2_pack4(c + 28)};
+    } else {
+#pragma unroll
+        for (int j = 0; j < QS_MX_BLOCK; ++j)
+            if (orow + j < R) out[j] = (uint8_t)c[j];
+    }
+}
+
+}  // namespace qs

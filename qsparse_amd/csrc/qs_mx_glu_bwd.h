@@ -5,8 +5,8 @@
 // is computed in registers from ONE read of dh [T, H] and v [T, 2 H] and leaves as the two MX pairs of qs_mx_quant2.h -- row codes
 // [T, 2 H] / scales [T, 2 H / 32] and, transposed, col codes [2 H, T] / scales [2 H, ceil(T / 32)].  dv itself is float32, is never
 // rounded to a narrower type and never exists in memory.  The per-element arithmetic of the quantizer is qs_mx.h's, act is
-// mx_glu_act of qs_mx_glu.h, and the two phases are those of mx_quant2_kernel stated again on values instead of loads: that kernel
-// and its instantiations are not touched (DESIGN.md 3l measured what merging texts costs there).
+// mx_glu_act of qs_mx_glu.h.  This file states the loads and the derivative; what follows once a value is a float under a scale --
+// the row block's maximum, the encode step, the code stores, the whole of phase 2 -- is qs_mx_quant2.h's shared functions.
 //
 // A work-group of 256 lanes owns mxq2_tile's tile, 128 rows x 64 dv columns = the hidden units [32 q, 32 q + 32) of 128 tokens: the
 // interleave puts the gate and the up column of a hidden unit into the same tile, 32 columns apart.
@@ -17,7 +17,7 @@
 //     block.  A row block of 32 is 8 adjacent lanes: its maximum is three __shfl_xor steps, two blocks per lane and pass.  Both runs of
 //     4 go to the float32 LDS tile [128][64] as 16-byte stores: the 8 lanes of a row write 32 consecutive dwords, the 32 banks of
 //     a store, so no bank is hit twice.
-//   Phase 2 is mx_quant2_kernel's on a float32 tile: lane (c = tid & 63, b = tid >> 6) walks the 32 rows of a column block.
+//   Phase 2 is mxq2_col_phase on a float32 tile (C % 64 == 0, so its column test never binds): lane (c = tid & 63, b = tid >> 6) walks the 32 rows of a column block.
 // No atomics, no workspace; a null pair skips its phase, a null col pair also the LDS traffic and the barrier.  VEC = false is the same
 // tiling with element loads and byte stores, each predicated on its row: any T >= 1, any element-aligned base (2 H % 64 == 0, so no
 // column is ever outside).  SR = true rounds stochastically with the words qs_mx_quant2_v would draw for dv [T, 2 H]: stream 0 at
@@ -114,84 +114,19 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_glu_bwd_quant2_kernel(MxForma
         if (!row_codes) continue;                               // (kernel-uniform)
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-#pragma unroll
-            for (int off = 1; off < kMxgbLpr; off <<= 1) {
-                const uint32_t o = (uint32_t)__shfl_xor((int)am[b], off, 64);
-                am[b] = o > am[b] ? o : am[b];
-            }
-            const MxScale s = mx_scale(am[b], fr);
+            const MxScale s = mx_scale(mxq2_block_max<kMxgbLpr>(am[b]), fr);
             const int64_t gc = c0 + b * QS_MX_BLOCK + t0;       // (a multiple of 4, as C and sr.base: one Philox call for the four)
-            uint32_t c[4], w[4] = {0u, 0u, 0u, 0u};
-            if constexpr (SR) mx_sr_words4(key, 0u, sr.base + (uint64_t)(gr * C + gc), w);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                uint32_t sg;
-                float r;
-                if constexpr (SR) r = mx_round_abs_sr(dv[b][j], s, fr, w[j], sg);
-                else r = mx_round_abs(dv[b][j], s, fr, sg);
-                c[j] = mx_code(r, sg, s, fr);
-            }
+            uint32_t c[4];
+            mx_encode_run<4, SR, true>(dv[b], s, fr, key, 0u, sr.base + (uint64_t)(gr * C + gc), c);
             if (gr < R) {
                 if ((tid % kMxgbLpr) == 0) row_scales[gr * nbc + (gc >> 5)] = (uint8_t)s.byte;
-                uint8_t* out = row_codes + gr * C + gc;
-                if (VEC && row_vec) {
-                    *(uint32_t*)out = mxq2_pack4(c);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) out[j] = (uint8_t)c[j];
-                }
+                mxq2_store_row<4, true>(row_codes + gr * C + gc, c, VEC && row_vec, gc, C);
             }
         }
     }
     if (!col_codes) return;                                     // (kernel-uniform)
     __syncthreads();
-
-    // ---- phase 2: col pair, as mx_quant2_kernel<QS_F32> ------------------------------------------------------------------------
-    const int cc = tid & (kMxq2Cols - 1), cb = tid / kMxq2Cols;
-    const int64_t oc = c0 + cc, orow = r0 + cb * QS_MX_BLOCK;
-    float w[QS_MX_BLOCK];
-    uint32_t am = 0;
-#pragma unroll
-    for (int j = 0; j < QS_MX_BLOCK; ++j) {
-        w[j] = tile[(cb * QS_MX_BLOCK + j) * kMxq2Cols + cc];
-        const uint32_t a = mx_abs_bits(w[j]);
-        am = a > am ? a : am;
-    }
-    if (orow >= R) return;
-    const MxScale s = mx_scale(am, fc);
-    col_scales[oc * nbr + (orow >> 5)] = (uint8_t)s.byte;
-    uint32_t c[QS_MX_BLOCK];
-    if constexpr (SR && VEC) {                                  // (R % 16 == 0, orow % 32 == 0: eight calls for the lane's 32 codes)
-#pragma unroll
-        for (int k = 0; k < QS_MX_BLOCK; k += 4) {
-            uint32_t rw[4];
-            mx_sr_words4(key, 1u, sr.base + (uint64_t)(oc * R + orow) + k, rw);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                uint32_t sg;
-                const float r = mx_round_abs_sr(w[k + j], s, fc, rw[j], sg);
-                c[k + j] = mx_code(r, sg, s, fc);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < QS_MX_BLOCK; ++j) {
-            uint32_t sg;
-            float r;
-            if constexpr (SR) r = mx_round_abs_sr(w[j], s, fc, mx_sr_word(key, 1u, sr.base + (uint64_t)(oc * R + orow + j)), sg);
-            else r = mx_round_abs(w[j], s, fc, sg);
-            c[j] = mx_code(r, sg, s, fc);
-        }
-    }
-    uint8_t* out = col_codes + oc * R + orow;
-    if constexpr (VEC) {                                        // (R % 16 == 0: each half of the block is inside or outside as a whole)
-        *(u32x4*)out = u32x4{mxq2_pack4(c), mxq2_pack4(c + 4), mxq2_pack4(c + 8), mxq2_pack4(c + 12)};
-        if (orow + 16 < R) *(u32x4*)(out + 16) = u32x4{mxq2_pack4(c + 16), mxq2_pack4(c + 20), mxq2_pack4(c + 24), mxq2_pack4(c + 28)};
-    } else {
-#pragma unroll
-        for (int j = 0; j < QS_MX_BLOCK; ++j)
-            if (orow + j < R) out[j] = (uint8_t)c[j];
-    }
+    mxq2_col_phase<QS_F32, VEC, SR>(tile, fc, col_codes, col_scales, R, C, r0, c0, nbr, true, key, sr.base);
 }
 
 }  // namespace qs

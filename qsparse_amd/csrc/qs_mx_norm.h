@@ -11,7 +11,7 @@
 //     of 16 rows whose loads -- x, the row's rstd / mean -- are all issued before the first use; w and b of the lane's 4 columns are
 //     loaded once.  A row block of 32 is 8 adjacent lanes: three __shfl_xor steps.  y goes to the float32 LDS tile [128][64] as one
 //     16-byte store per lane and pass (the 16 lanes of a row write 64 consecutive dwords: no bank is hit twice per 32-bank phase).
-//   Phase 2 is mx_quant2_kernel's on a float32 tile: lane (c = tid & 63, b = tid >> 6) walks the 32 rows of a column block, the
+//   Phase 2 is qs_mx_quant2.h's mxq2_col_phase on a float32 tile, with `col_vec` as its run-time store rule: lane (c = tid & 63, b = tid >> 6) walks the 32 rows of a column block, the
 //     transposition happens in registers.  Elements outside [R, C] are +0 in the tile, as the quantizer's short last blocks.
 // The per-element arithmetic of the quantizer is qs_mx.h's; nothing of it is restated here.  No atomics, no workspace beyond rstd /
 // mean; a null col pair skips the LDS traffic, the barrier and phase 2 (kernel-uniform).  VEC = false is the same text with element
@@ -169,64 +169,17 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_norm_apply_kernel(MxFormat fr
         if (col_codes)
             *(u32x4*)(tile + (p * kMxnRpp + lrow) * kMxq2Cols + lcol) =
                 u32x4{__float_as_uint(y[0]), __float_as_uint(y[1]), __float_as_uint(y[2]), __float_as_uint(y[3])};
-#pragma unroll
-        for (int off = 1; off < kMxnLpb; off <<= 1) {
-            const uint32_t o = (uint32_t)__shfl_xor((int)am, off, 64);
-            am = o > am ? o : am;
-        }
-        const MxScale s = mx_scale(am, fr);
+        const MxScale s = mx_scale(mxq2_block_max<kMxnLpb>(am), fr);
         uint32_t c[kMxnV];
-#pragma unroll
-        for (int j = 0; j < kMxnV; ++j) {
-            uint32_t sg;
-            const float r = mx_round_abs(y[j], s, fr, sg);
-            c[j] = mx_code(r, sg, s, fr);
-        }
+        mx_encode_run<kMxnV, false, false>(y, s, fr, MxSrKey{0u, 0u}, 0u, 0ull, c);
         if (gr < R && gc < C) {
             if ((tid % kMxnLpb) == 0) row_scales[gr * nbc + (gc >> 5)] = (uint8_t)s.byte;
-            uint8_t* out = row_codes + gr * C + gc;
-            if (VEC && row_vec) {
-                *(uint32_t*)out = mxq2_pack4(c);
-            } else {
-#pragma unroll
-                for (int j = 0; j < kMxnV; ++j)
-                    if (VEC || gc + j < C) out[j] = (uint8_t)c[j];
-            }
+            mxq2_store_row<kMxnV, VEC>(row_codes + gr * C + gc, c, VEC && row_vec, gc, C);
         }
     }
     if (!col_codes) return;                                     // (kernel-uniform)
     __syncthreads();
-
-    // ---- phase 2: col pair, as mx_quant2_kernel<QS_F32> ------------------------------------------------------------------------
-    const int cc = tid & (kMxq2Cols - 1), cb = tid / kMxq2Cols;
-    const int64_t oc = c0 + cc, orow = r0 + cb * QS_MX_BLOCK;
-    float t[QS_MX_BLOCK];
-    uint32_t am = 0;
-#pragma unroll
-    for (int j = 0; j < QS_MX_BLOCK; ++j) {
-        t[j] = tile[(cb * QS_MX_BLOCK + j) * kMxq2Cols + cc];
-        const uint32_t a = mx_abs_bits(t[j]);
-        am = a > am ? a : am;
-    }
-    if (oc >= C || orow >= R) return;
-    const MxScale s = mx_scale(am, fc);
-    col_scales[oc * nbr + (orow >> 5)] = (uint8_t)s.byte;
-    uint32_t c[QS_MX_BLOCK];
-#pragma unroll
-    for (int j = 0; j < QS_MX_BLOCK; ++j) {
-        uint32_t sg;
-        const float r = mx_round_abs(t[j], s, fc, sg);
-        c[j] = mx_code(r, sg, s, fc);
-    }
-    uint8_t* out = col_codes + oc * R + orow;
-    if (VEC && col_vec) {                                       // (R % 16 == 0: each half of the block is inside or outside as a whole)
-        *(u32x4*)out = u32x4{mxq2_pack4(c), mxq2_pack4(c + 4), mxq2_pack4(c + 8), mxq2_pack4(c + 12)};
-        if (orow + 16 < R) *(u32x4*)(out + 16) = u32x4{mxq2_pack4(c + 16), mxq2_pack4(c + 20), mxq2_pack4(c + 24), mxq2_pack4(c + 28)};
-    } else {
-#pragma unroll
-        for (int j = 0; j < QS_MX_BLOCK; ++j)
-            if (orow + j < R) out[j] = (uint8_t)c[j];
-    }
+    mxq2_col_phase<QS_F32, VEC, false>(tile, fc, col_codes, col_scales, R, C, r0, c0, nbr, col_vec, MxSrKey{0u, 0u}, 0ull);
 }
 
 }  // namespace qs

@@ -22,6 +22,8 @@
 // at stream 1 and index oc * R + orow of col_codes.  On the VEC route both indices are multiples of 4 at a lane's first code, so a
 // Philox call serves four codes: V / 4 calls per lane and pass in phase 1, eight per lane in phase 2.  PLAIN spends a call per code.
 #pragma once
+#include <type_traits>
+
 #include "qs_mx.h"
 
 namespace qs {
@@ -46,10 +48,103 @@ __device__ __forceinline__ float mxq2_widen(typename Mxq2Raw<XDT>::type raw) {
 
 __device__ __forceinline__ uint32_t mxq2_pack4(const uint32_t* c) { return c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24); }
 
+// ---- what every kernel on this tile shares (this file, qs_mx_glu_bwd.h, qs_mx_norm.h): all that happens once a value is a float ----
+// the maximum of `am` over the LPB adjacent lanes of a row block
+template <int LPB>
+__device__ __forceinline__ uint32_t mxq2_block_max(uint32_t am) {
+#pragma unroll
+    for (int off = 1; off < LPB; off <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)am, off, 64);
+        am = o > am ? o : am;
+    }
+    return am;
+}
+
+// N values under one scale to N codes.  SR draws the words of `stream` at index .. index + N - 1 (sr.base included): QUAD -- index
+// and N are multiples of 4 -- with one Philox call per four codes, otherwise with one per code.  SR = false draws nothing.
+template <int N, bool SR, bool QUAD>
+__device__ __forceinline__ void mx_encode_run(const float (&v)[N], MxScale s, MxFormat f, MxSrKey key,
+                                              uint32_t stream, uint64_t index, uint32_t (&c)[N]) {
+    if constexpr (SR && QUAD) {
+#pragma unroll
+        for (int q = 0; q < N; q += 4) {
+            uint32_t w[4];
+            mx_sr_words4(key, stream, index + q, w);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint32_t sg;
+                const float r = mx_round_abs_sr(v[q + j], s, f, w[j], sg);
+                c[q + j] = mx_code(r, sg, s, f);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            uint32_t sg;
+            float r;
+            if constexpr (SR) r = mx_round_abs_sr(v[j], s, f, mx_sr_word(key, stream, index + j), sg);
+            else r = mx_round_abs(v[j], s, f, sg);
+            c[j] = mx_code(r, sg, s, f);
+        }
+    }
+}
+
+// phase 1's code store at out = row_codes + gr * C + gc: one store of V = 4 or 8 bytes when `vec` (out is aligned to V), else byte
+// stores.  FULL: the lane's V columns are inside together (the VEC route; the GLU tile); otherwise each is predicated on gc + j < C.
+template <int V, bool FULL>
+__device__ __forceinline__ void mxq2_store_row(uint8_t* out, const uint32_t (&c)[V], bool vec, int64_t gc, int64_t C) {
+    if (vec) {
+        if constexpr (V == 8) *(u32x2*)out = u32x2{mxq2_pack4(c), mxq2_pack4(c + 4)};
+        else *(uint32_t*)out = mxq2_pack4(c);
+    } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j)
+            if (FULL || gc + j < C) out[j] = (uint8_t)c[j];
+    }
+}
+
+// Phase 2, after the barrier: lane (cc = tid & 63, cb = tid >> 6) walks the column block tile[32 cb .. 32 cb + 31][cc] and writes its
+// 32 codes and its scale byte into the transposed col pair.  The tile holds raw elements of type XDT, or floats (widened by nothing).
+// `col_vec`: R % 16 == 0 and col_codes is 16-byte aligned, so each half of the block is inside or outside as a whole and leaves as one
+// 16-byte store; a constant `true` where the VEC route guarantees it.  SR && VEC: orow % 32 == 0 and R % 4 == 0, so eight Philox
+// calls serve the lane's 32 codes.  `base` is sr.base.
+template <int XDT, bool VEC, bool SR, typename T>
+__device__ __forceinline__ void mxq2_col_phase(const T* tile, MxFormat fc, uint8_t* __restrict__ col_codes,
+                                               uint8_t* __restrict__ col_scales, int64_t R, int64_t C, int64_t r0, int64_t c0, int64_t nbr,
+                                               bool col_vec, MxSrKey key, uint64_t base) {
+    const int tid = threadIdx.x;
+    const int cc = tid & (kMxq2Cols - 1), cb = tid / kMxq2Cols;
+    const int64_t oc = c0 + cc, orow = r0 + cb * QS_MX_BLOCK;
+    float w[QS_MX_BLOCK];
+    uint32_t am = 0;
+#pragma unroll
+    for (int j = 0; j < QS_MX_BLOCK; ++j) {
+        if constexpr (std::is_same<T, float>::value) w[j] = tile[(cb * QS_MX_BLOCK + j) * kMxq2Cols + cc];
+        else w[j] = mxq2_widen<XDT>(tile[(cb * QS_MX_BLOCK + j) * kMxq2Cols + cc]);
+        const uint32_t a = mx_abs_bits(w[j]);
+        am = a > am ? a : am;
+    }
+    if (oc >= C || orow >= R) return;
+    const MxScale s = mx_scale(am, fc);
+    col_scales[oc * nbr + (orow >> 5)] = (uint8_t)s.byte;
+    uint32_t c[QS_MX_BLOCK];
+    mx_encode_run<QS_MX_BLOCK, SR, VEC>(w, s, fc, key, 1u, base + (uint64_t)(oc * R + orow), c);
+    uint8_t* out = col_codes + oc * R + orow;
+    if (VEC && col_vec) {
+        *(u32x4*)out = u32x4{mxq2_pack4(c), mxq2_pack4(c + 4), mxq2_pack4(c + 8), mxq2_pack4(c + 12)};
+        if (orow + 16 < R) *(u32x4*)(out + 16) = u32x4{mxq2_pack4(c + 16), mxq2_pack4(c + 20), mxq2_pack4(c + 24), mxq2_pack4(c + 28)};
+    } else {
+#pragma unroll
+        for (int j = 0; j < QS_MX_BLOCK; ++j)
+            if (orow + j < R) out[j] = (uint8_t)c[j];
+    }
+}
+
 // The tile's two phases as a function of the bases and the row pitch of x: the tile at (r0, c0) of x [R, C] whose row r begins at
-// x + r * pitch.  mx_quant2_batched_kernel calls it with ONE SLICE's x, outputs, R and C and the slice's row stride; it also serves
-// pitch = C on a whole tensor, which mx_quant2_kernel does not use (see there).  `row_vec`: row_codes is aligned to the V bytes a lane stores at once (VEC only;
-// otherwise byte stores).  `sr.base` is the index of the pairs' first code: index_base, plus g R C for slice g.
+// x + r * pitch.  mx_quant2_batched_kernel calls it with ONE SLICE's x, outputs, R and C and the slice's row stride, mx_quant2_kernel
+// with the whole tensor and pitch = C.  Only the loads are the tile's own; everything behind them is the shared functions above.
+// `row_vec`: row_codes is aligned to the V bytes a lane stores at once (VEC only; otherwise byte stores).  `sr.base` is the index of
+// the pairs' first code: index_base, plus g R C for slice g.
 template <int XDT, bool VEC, bool SR>
 __device__ __forceinline__ void mxq2_tile(MxFormat fr, MxFormat fc, const void* __restrict__ x, int64_t pitch,
                                           uint8_t* __restrict__ row_codes, uint8_t* __restrict__ row_scales,
@@ -104,252 +199,34 @@ __device__ __forceinline__ void mxq2_tile(MxFormat fr, MxFormat fc, const void* 
                 const uint32_t a = mx_abs_bits(v[j]);
                 am = a > am ? a : am;
             }
-#pragma unroll
-            for (int off = 1; off < LPB; off <<= 1) {
-                const uint32_t o = (uint32_t)__shfl_xor((int)am, off, 64);
-                am = o > am ? o : am;
-            }
-            const MxScale s = mx_scale(am, fr);
-            uint32_t c[V];
-            if constexpr (SR && VEC) {                    // (C % V == 0, gc % V == 0: the lane's first index is a multiple of 4)
-#pragma unroll
-                for (int q = 0; q < V; q += 4) {
-                    uint32_t w[4];
-                    mx_sr_words4(key, 0u, sr.base + (uint64_t)(gr * C + gc) + q, w);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        uint32_t sg;
-                        const float r = mx_round_abs_sr(v[q + j], s, fr, w[j], sg);
-                        c[q + j] = mx_code(r, sg, s, fr);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < V; ++j) {
-                    uint32_t sg;
-                    float r;
-                    if constexpr (SR) r = mx_round_abs_sr(v[j], s, fr, mx_sr_word(key, 0u, sr.base + (uint64_t)(gr * C + gc + j)), sg);
-                    else r = mx_round_abs(v[j], s, fr, sg);
-                    c[j] = mx_code(r, sg, s, fr);
-                }
-            }
+            const MxScale s = mx_scale(mxq2_block_max<LPB>(am), fr);
+            uint32_t c[V];                                // (VEC: C % V == 0, gc % V == 0: the lane's first index is a multiple of 4)
+            mx_encode_run<V, SR, VEC>(v, s, fr, key, 0u, sr.base + (uint64_t)(gr * C + gc), c);
             if (gr < R && gc < C) {
                 if ((tid % LPB) == 0) row_scales[gr * nbc + (gc >> 5)] = (uint8_t)s.byte;
-                uint8_t* out = row_codes + gr * C + gc;
-                if (VEC && row_vec) {
-                    if constexpr (V == 8) *(u32x2*)out = u32x2{mxq2_pack4(c), mxq2_pack4(c + 4)};
-                    else *(uint32_t*)out = mxq2_pack4(c);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < V; ++j)
-                        if (VEC || gc + j < C) out[j] = (uint8_t)c[j];
-                }
+                mxq2_store_row<V, VEC>(row_codes + gr * C + gc, c, VEC && row_vec, gc, C);
             }
         }
     }
     if (!col_codes) return;                               // (kernel-uniform)
     __syncthreads();
-
-    // ---- phase 2: col pair ---------------------------------------------------------------------------------------------------
-    const int cc = tid & (kMxq2Cols - 1), cb = tid / kMxq2Cols;
-    const int64_t oc = c0 + cc, orow = r0 + cb * QS_MX_BLOCK;
-    float w[QS_MX_BLOCK];
-    uint32_t am = 0;
-#pragma unroll
-    for (int j = 0; j < QS_MX_BLOCK; ++j) {
-        w[j] = mxq2_widen<XDT>(tile[(cb * QS_MX_BLOCK + j) * kMxq2Cols + cc]);
-        const uint32_t a = mx_abs_bits(w[j]);
-        am = a > am ? a : am;
-    }
-    if (oc >= C || orow >= R) return;
-    const MxScale s = mx_scale(am, fc);
-    col_scales[oc * nbr + (orow >> 5)] = (uint8_t)s.byte;
-    uint32_t c[QS_MX_BLOCK];
-    if constexpr (SR && VEC) {                            // (R % 16 == 0, orow % 32 == 0: eight calls for the lane's 32 codes)
-#pragma unroll
-        for (int q = 0; q < QS_MX_BLOCK; q += 4) {
-            uint32_t rw[4];
-            mx_sr_words4(key, 1u, sr.base + (uint64_t)(oc * R + orow) + q, rw);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                uint32_t sg;
-                const float r = mx_round_abs_sr(w[q + j], s, fc, rw[j], sg);
-                c[q + j] = mx_code(r, sg, s, fc);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < QS_MX_BLOCK; ++j) {
-            uint32_t sg;
-            float r;
-            if constexpr (SR) r = mx_round_abs_sr(w[j], s, fc, mx_sr_word(key, 1u, sr.base + (uint64_t)(oc * R + orow + j)), sg);
-            else r = mx_round_abs(w[j], s, fc, sg);
-            c[j] = mx_code(r, sg, s, fc);
-        }
-    }
-    uint8_t* out = col_codes + oc * R + orow;
-    if constexpr (VEC) {                                  // (R % 16 == 0: each half of the block is inside or outside as a whole)
-        *(u32x4*)out = u32x4{mxq2_pack4(c), mxq2_pack4(c + 4), mxq2_pack4(c + 8), mxq2_pack4(c + 12)};
-        if (orow + 16 < R) *(u32x4*)(out + 16) = u32x4{mxq2_pack4(c + 16), mxq2_pack4(c + 20), mxq2_pack4(c + 24), mxq2_pack4(c + 28)};
-    } else {
-#pragma unroll
-        for (int j = 0; j < QS_MX_BLOCK; ++j)
-            if (orow + j < R) out[j] = (uint8_t)c[j];
-    }
+    mxq2_col_phase<XDT, VEC, SR>(tile, fc, col_codes, col_scales, R, C, r0, c0, nbr, true, key, sr.base);
 }
 
-// mx_quant2_kernel keeps its own statement of the two phases: calling mxq2_tile with pitch = C measured 1.5 - 2.8 % slower than this
-// text on three of the six cases of tools/bench_mx_train.py, beyond the run-to-run spread of the text's own repetitions (DESIGN.md 3l;
-// a different register assignment, the same counts).  mxq2_tile below is the batched kernel's; a change to either is a change to both.
+// The 2-d kernel is the tile at pitch = C: there is ONE text of the two phases.  The phase-2 text and the encode step are shared with
+// mx_glu_bwd_quant2_kernel and mx_norm_apply_kernel as mxq2_col_phase and mx_encode_run; those kernels keep their phase-1 loads.
+// Measured (profiles/mx_quant2_share.json): no instantiation is the former text's instruction for instruction -- the
+// scheduler orders the same work differently -- so each was timed against the parent in alternating fresh processes; every case of
+// the four benchmarks stayed inside the parent's own band or 1 %.  DESIGN 3l's 1.5 - 2.8 % miss of this merge did not reproduce
+// (-1.0 .. +0.4 % here, the 2-d kernel's twelve instantiations 0 - 56 instructions shorter than their former text).
 // `row_vec`: row_codes is aligned to the V bytes a lane stores at once (VEC only; otherwise byte stores)
 template <int XDT, bool VEC, bool SR>
 __global__ __launch_bounds__(kMxq2Threads) void mx_quant2_kernel(MxFormat fr, MxFormat fc, const void* __restrict__ x,
                                                                  uint8_t* __restrict__ row_codes, uint8_t* __restrict__ row_scales,
                                                                  uint8_t* __restrict__ col_codes, uint8_t* __restrict__ col_scales,
                                                                  int64_t R, int64_t C, int tiles_c, int row_vec, MxSr sr) {
-    using raw_t = typename Mxq2Raw<XDT>::type;
-    constexpr int V = XDT == QS_F32 ? 4 : 8;              // elements per lane and pass: 16 bytes
-    constexpr int LPB = QS_MX_BLOCK / V;                  // lanes per row block
-    constexpr int LPR = kMxq2Cols / V;                    // lanes per tile row
-    constexpr int RPP = kMxq2Threads / LPR;               // tile rows per pass
-    constexpr int PASSES = kMxq2Rows / RPP;
-    __shared__ __attribute__((aligned(16))) raw_t tile[kMxq2Rows * kMxq2Cols];
-
-    const int tid = threadIdx.x;
-    const int64_t r0 = (int64_t)(blockIdx.x / tiles_c) * kMxq2Rows;
-    const int64_t c0 = (int64_t)(blockIdx.x % tiles_c) * kMxq2Cols;
-    const int64_t nbc = (C + QS_MX_BLOCK - 1) / QS_MX_BLOCK, nbr = (R + QS_MX_BLOCK - 1) / QS_MX_BLOCK;
-    MxSrKey key = {0u, 0u};
-    if constexpr (SR) key = mx_sr_key(sr);
-
-    // ---- phase 1: load, stage, row pair --------------------------------------------------------------------------------------
-    const int lrow = tid / LPR, lcol = (tid % LPR) * V;
-    const int64_t gc = c0 + lcol;
-    raw_t raw[PASSES][V];
-#pragma unroll
-    for (int p = 0; p < PASSES; ++p) {
-        const int64_t gr = r0 + p * RPP + lrow;
-        if constexpr (VEC) {                              // (C % V == 0: the lane's V elements are inside or outside together)
-            u32x4 a = {0u, 0u, 0u, 0u};
-            if (gr < R && gc < C) a = ld16<true>((const u32x4*)((const raw_t*)x + gr * C + gc));
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                if constexpr (XDT == QS_F32) raw[p][j] = a[j];
-                else raw[p][j] = (raw_t)(a[j >> 1] >> ((j & 1) * 16));
-            }
-            if (col_codes) *(u32x4*)(tile + (p * RPP + lrow) * kMxq2Cols + lcol) = a;
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                raw[p][j] = (gr < R && gc + j < C) ? ((const raw_t*)x)[gr * C + gc + j] : (raw_t)0;
-                if (col_codes) tile[(p * RPP + lrow) * kMxq2Cols + lcol + j] = raw[p][j];
-            }
-        }
-    }
-    if (row_codes) {
-#pragma unroll
-        for (int p = 0; p < PASSES; ++p) {
-            const int64_t gr = r0 + p * RPP + lrow;
-            float v[V];
-            uint32_t am = 0;
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                v[j] = mxq2_widen<XDT>(raw[p][j]);
-                const uint32_t a = mx_abs_bits(v[j]);
-                am = a > am ? a : am;
-            }
-#pragma unroll
-            for (int off = 1; off < LPB; off <<= 1) {
-                const uint32_t o = (uint32_t)__shfl_xor((int)am, off, 64);
-                am = o > am ? o : am;
-            }
-            const MxScale s = mx_scale(am, fr);
-            uint32_t c[V];
-            if constexpr (SR && VEC) {                    // (C % V == 0, gc % V == 0: the lane's first index is a multiple of 4)
-#pragma unroll
-                for (int q = 0; q < V; q += 4) {
-                    uint32_t w[4];
-                    mx_sr_words4(key, 0u, sr.base + (uint64_t)(gr * C + gc) + q, w);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        uint32_t sg;
-                        const float r = mx_round_abs_sr(v[q + j], s, fr, w[j], sg);
-                        c[q + j] = mx_code(r, sg, s, fr);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < V; ++j) {
-                    uint32_t sg;
-                    float r;
-                    if constexpr (SR) r = mx_round_abs_sr(v[j], s, fr, mx_sr_word(key, 0u, sr.base + (uint64_t)(gr * C + gc + j)), sg);
-                    else r = mx_round_abs(v[j], s, fr, sg);
-                    c[j] = mx_code(r, sg, s, fr);
-                }
-            }
-            if (gr < R && gc < C) {
-                if ((tid % LPB) == 0) row_scales[gr * nbc + (gc >> 5)] = (uint8_t)s.byte;
-                uint8_t* out = row_codes + gr * C + gc;
-                if (VEC && row_vec) {
-                    if constexpr (V == 8) *(u32x2*)out = u32x2{mxq2_pack4(c), mxq2_pack4(c + 4)};
-                    else *(uint32_t*)out = mxq2_pack4(c);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < V; ++j)
-                        if (VEC || gc + j < C) out[j] = (uint8_t)c[j];
-                }
-            }
-        }
-    }
-    if (!col_codes) return;                               // (kernel-uniform)
-    __syncthreads();
-
-    // ---- phase 2: col pair ---------------------------------------------------------------------------------------------------
-    const int cc = tid & (kMxq2Cols - 1), cb = tid / kMxq2Cols;
-    const int64_t oc = c0 + cc, orow = r0 + cb * QS_MX_BLOCK;
-    float w[QS_MX_BLOCK];
-    uint32_t am = 0;
-#pragma unroll
-    for (int j = 0; j < QS_MX_BLOCK; ++j) {
-        w[j] = mxq2_widen<XDT>(tile[(cb * QS_MX_BLOCK + j) * kMxq2Cols + cc]);
-        const uint32_t a = mx_abs_bits(w[j]);
-        am = a > am ? a : am;
-    }
-    if (oc >= C || orow >= R) return;
-    const MxScale s = mx_scale(am, fc);
-    col_scales[oc * nbr + (orow >> 5)] = (uint8_t)s.byte;
-    uint32_t c[QS_MX_BLOCK];
-    if constexpr (SR && VEC) {                            // (R % 16 == 0, orow % 32 == 0: eight calls for the lane's 32 codes)
-#pragma unroll
-        for (int q = 0; q < QS_MX_BLOCK; q += 4) {
-            uint32_t rw[4];
-            mx_sr_words4(key, 1u, sr.base + (uint64_t)(oc * R + orow) + q, rw);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                uint32_t sg;
-                const float r = mx_round_abs_sr(w[q + j], s, fc, rw[j], sg);
-                c[q + j] = mx_code(r, sg, s, fc);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < QS_MX_BLOCK; ++j) {
-            uint32_t sg;
-            float r;
-            if constexpr (SR) r = mx_round_abs_sr(w[j], s, fc, mx_sr_word(key, 1u, sr.base + (uint64_t)(oc * R + orow + j)), sg);
-            else r = mx_round_abs(w[j], s, fc, sg);
-            c[j] = mx_code(r, sg, s, fc);
-        }
-    }
-    uint8_t* out = col_codes + oc * R + orow;
-    if constexpr (VEC) {                                  // (R % 16 == 0: each half of the block is inside or outside as a whole)
-        *(u32x4*)out = u32x4{mxq2_pack4(c), mxq2_pack4(c + 4), mxq2_pack4(c + 8), mxq2_pack4(c + 12)};
-        if (orow + 16 < R) *(u32x4*)(out + 16) = u32x4{mxq2_pack4(c + 16), mxq2_pack4(c + 20), mxq2_pack4(c + 24), mxq2_pack4(c + 28)};
-    } else {
-#pragma unroll
-        for (int j = 0; j < QS_MX_BLOCK; ++j)
-            if (orow + j < R) out[j] = (uint8_t)c[j];
-    }
+    mxq2_tile<XDT, VEC, SR>(fr, fc, x, C, row_codes, row_scales, col_codes, col_scales, R, C, (int64_t)(blockIdx.x / tiles_c) * kMxq2Rows,
+                            (int64_t)(blockIdx.x % tiles_c) * kMxq2Cols, row_vec, sr);
 }
 
 // The batched, strided form (include/qsparse_hip.h, "MX batched two-way quantizer"): G = G0 G1 slices [R, C] of x, slice g = g0 G1 +

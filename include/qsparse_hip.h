@@ -1728,6 +1728,80 @@ int qs_mx_norm_quant_v(const qs_mx_norm_quant_args* args);
 #define QS_MX_NORM_ROUTE_PLAIN 2
 int qs_mx_norm_quant_route(const qs_mx_norm_quant_args* args);
 
+/* ---- MX norm backward (the backward of the normalisation of the MX normalising quantizer) ------------------------------------------
+ * Added without raising QS_ABI_VERSION (28), by the same rule as qs_mx_matmul_v above: symbols are only added.
+ *
+ * From dxhat [R, C], the gradient with respect to the norm's output y = xhat * weight (+ bias) (float32, bf16 or fp16), x [R, C] in
+ * its own dtype, the statistics rstd [R] and (layer mode) mean [R] the forward wrote, and weight [C] (float32; NULL: ones):
+ * dx [R, C] in x's dtype, dweight [C] and dbias [C] float32.  All three tensors are CONTIGUOUS, C innermost; each output is nullable
+ * and is then neither computed nor written.
+ * Definition (normative).  All arithmetic is float32 without contraction on the widened inputs; `/` is the correctly rounded IEEE
+ * operation; Cf = (float)C.
+ *   xhat_i = (x_i - mean) * rstd     QS_MX_NORM_LAYER           xhat_i = x_i * rstd     QS_MX_NORM_RMS      (as the forward forms it)
+ *   g_i    = dxhat_i * w_i           (an absent weight: g_i = dxhat_i, no multiplication)
+ *   c1     = rowsum(g_i * xhat_i) / Cf
+ *   c2     = rowsum(g_i) / Cf        layer mode only
+ *   dx_i   = rstd * (g_i - xhat_i * c1)                  rms
+ *   dx_i   = rstd * ((g_i - xhat_i * c1) - c2)           layer           rounded once, to nearest-even, to x's dtype
+ *   dweight_c = colsum_r(dxhat[r, c] * xhat[r, c])
+ *   dbias_c   = colsum_r(dxhat[r, c])
+ *   rowsum is the sum over a row of the MX normalising quantizer above -- a function of C alone; the terms behind the row are +0.
+ *   colsum(t) over a column, t_0 .. t_(R-1) -- a FIXED order that depends on R alone (not on C, a dtype, the route, the launch, the
+ *   mode or on which outputs are asked for):
+ *     t_r = +0 for R <= r < 128 T, T = ceil(R / 128) row tiles
+ *     in row tile k, on u_i = t_(128 k + i):
+ *       16 strided partial sums   S_l = (((+0 + u_l) + u_(l+16)) + u_(l+32)) + ... + u_(l+112)      l < 16, ascending
+ *       pairwise tree             for s = 8, 4, 2, 1:  S_l = S_l + S_(l+s), l < s;   v_k = S_0
+ *     over the tiles:
+ *       128 strided partial sums  P_j = ((+0 + v_j) + v_(j+128)) + ...                              j < 128, ascending; +0 for j >= T
+ *       pairwise tree             for s = 64, 32, 16, 8, 4, 2, 1:  P_j = P_j + P_(j+s), j < s;   colsum = P_0
+ *     (with tensors: pad to [T, 8, 16, C]; S = 0; S = S + u[:, m] for m = 0 .. 7; four element-wise additions of the upper half of S
+ *      to the lower give v [T, C]; pad v to [K, 128, C]; P = 0; P = P + v[k] for k = 0 .. K-1; seven more halvings)
+ *   There are no special cases: NaN and Inf propagate as the arithmetic propagates them -- a row whose rstd is NaN (a row of x the
+ *   forward found not finite) has NaN in every element of dx and makes every element of dweight NaN.  No atomics: the same bits on
+ *   every run.
+ * Workspace: caller-provided, `workspace_bytes` at least what qs_mx_norm_bwd_plan tells for the same R, C, mode and needs, 16-byte
+ * aligned.  It holds c1 [R] and c2 [R] (layer mode) when dx is asked for, and the row tiles' column sums, two arrays [T, C], when
+ * dweight or dbias is -- float32, each part at the next multiple of 16 bytes.  Its contents on return are unspecified.
+ * Up to three launches on `stream`, nothing read by the host: the row statistics (only with dx), the apply launch over 128 x 64
+ * tiles (dx and the tiles' column sums), the fold of those sums (only with dweight or dbias).
+ *   - Checks, in order: QS_ERR_ARG: a null or too short descriptor, an unknown mode, dxhat, x or rstd NULL, mean NULL in layer mode,
+ *     dx, dweight and dbias all NULL, R or C negative; QS_ERR_DTYPE: xdt or gdt none of the three; QS_ERR_ALIGN: x or dx not aligned to
+ *     x's element, dxhat not to its own, weight, rstd, mean, dweight or dbias not to 4 bytes, workspace not to 16; QS_ERR_ARG: R * C
+ *     beyond 64 bits or more tiles than a launch takes (2^31 - 1); QS_ERR_WORKSPACE: workspace NULL or shorter than the plan.
+ *   - R == 0 or C == 0: nothing is enqueued and nothing written, 0 is returned -- the dweight / dbias of a tensor with R == 0 and
+ *     C > 0 are sums of no terms, +0, and are the CALLER's to fill (the Python binding does).
+ *   - QS_MX_NORM_BWD_ROUTE_VEC (16-byte accesses of float32 tensors, 16- / 8-byte ones of two-byte tensors): C % 32 == 0 and dxhat,
+ *     x, weight, dx 16-byte aligned.  Anything else takes QS_MX_NORM_BWD_ROUTE_PLAIN, element accesses: any R, C >= 1, same bits. */
+typedef struct qs_mx_norm_bwd_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_norm_bwd_args) as the caller compiled it */
+    int32_t mode;                    /* QS_MX_NORM_* */
+    int32_t xdt;                     /* dtype of x and dx: QS_F32, QS_BF16 or QS_F16 */
+    int32_t gdt;                     /* dtype of dxhat, likewise */
+    const void* dxhat;               /* [R, C] row-major */
+    const void* x;                   /* [R, C] row-major */
+    const float* weight;             /* [C], nullable (ones) */
+    const float* rstd;               /* [R] */
+    const float* mean;               /* [R], layer mode */
+    void* dx;                        /* [R, C], nullable */
+    float* dweight;                  /* [C], nullable */
+    float* dbias;                    /* [C], nullable */
+    void* workspace;
+    uint64_t workspace_bytes;
+    int64_t R, C;
+    qs_stream_t stream;
+} qs_mx_norm_bwd_args;
+int qs_mx_norm_bwd_v(const qs_mx_norm_bwd_args* args);
+/* the kernels qs_mx_norm_bwd_v launches for these operands, nothing enqueued: QS_MX_NORM_BWD_ROUTE_*, 0 for an empty tensor, or the
+ * QS_ERR_* the call would return */
+#define QS_MX_NORM_BWD_ROUTE_VEC 1
+#define QS_MX_NORM_BWD_ROUTE_PLAIN 2
+int qs_mx_norm_bwd_route(const qs_mx_norm_bwd_args* args);
+/* the workspace qs_mx_norm_bwd_v needs for [R, C] in `mode` when dx is asked for (need_dx != 0) and when dweight or dbias is
+ * (need_cols != 0): up16(4 R) (twice in layer mode) with need_dx, plus 2 up16(4 ceil(R / 128) C) with need_cols, up16 rounding up to a
+ * multiple of 16; 0 for an empty tensor.  QS_ERR_ARG: workspace_bytes NULL, an unknown mode, a negative extent, extents the call refuses. */
+int qs_mx_norm_bwd_plan(int64_t R, int64_t C, int32_t mode, int32_t need_dx, int32_t need_cols, uint64_t* workspace_bytes);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

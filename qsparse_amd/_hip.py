@@ -141,6 +141,9 @@ SIGNATURES = {
     "qs_mx_grouped_wgrad_route": (c_int, [_P]),
     "qs_mx_norm_quant_v": (c_int, [_P]),
     "qs_mx_norm_quant_route": (c_int, [_P]),
+    "qs_mx_norm_bwd_v": (c_int, [_P]),
+    "qs_mx_norm_bwd_route": (c_int, [_P]),
+    "qs_mx_norm_bwd_plan": (c_int, [_L, _L, c_int32, c_int32, c_int32, _P]),
 }
 
 
@@ -348,6 +351,14 @@ class MxNormQuantArgs(ctypes.Structure):
                 ("eps", c_float), ("x", c_void_p), ("weight", c_void_p), ("bias", c_void_p), ("row_codes", c_void_p),
                 ("row_scales", c_void_p), ("col_codes", c_void_p), ("col_scales", c_void_p), ("rstd", c_void_p), ("mean", c_void_p),
                 ("R", c_int64), ("C", c_int64), ("stream", c_void_p)]
+
+
+class MxNormBwdArgs(ctypes.Structure):
+    """`qs_mx_norm_bwd_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("mode", c_int32), ("xdt", c_int32), ("gdt", c_int32), ("dxhat", c_void_p),
+                ("x", c_void_p), ("weight", c_void_p), ("rstd", c_void_p), ("mean", c_void_p), ("dx", c_void_p), ("dweight", c_void_p),
+                ("dbias", c_void_p), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64), ("R", c_int64), ("C", c_int64),
+                ("stream", c_void_p)]
 
 
 class MxGroupedWgradArgs(ctypes.Structure):
@@ -1611,6 +1622,47 @@ def mx_norm_quant(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optiona
         a.stream = _stream(x)
         mx_norm_last_route = _mx_run("mx_norm_quant", a, (x, weight, bias) + outs + (rstd, mean))
     return outs + (rstd, mean)
+
+
+MX_NORM_BWD_ROUTE_VEC, MX_NORM_BWD_ROUTE_PLAIN = 1, 2
+mx_norm_bwd_last_route = None     # the QS_MX_NORM_BWD_ROUTE_* of the last `mx_norm_bwd` launch (None: an empty tensor)
+
+
+def mx_norm_bwd_plan(R: int, C: int, norm: str, need_dx: bool, need_cols: bool) -> int:
+    """the workspace bytes `qs_mx_norm_bwd_v` needs (`qs_mx_norm_bwd_plan`)"""
+    nbytes = ctypes.c_uint64(0)
+    _check(load().qs_mx_norm_bwd_plan(R, C, MX_NORMS.index(norm), int(need_dx), int(need_cols), ctypes.byref(nbytes)),
+           "qs_mx_norm_bwd_plan")
+    return nbytes.value
+
+
+def mx_norm_bwd(dxhat: torch.Tensor, x: torch.Tensor, rstd: torch.Tensor, mean: Optional[torch.Tensor],
+                weight: Optional[torch.Tensor], norm: str, need_dx: bool = True, need_dweight: bool = True, need_dbias: bool = True):
+    """the backward of the normalisation (qs_mx_norm_bwd_v) on contiguous GPU tensors `dxhat`, `x` [R, C], float32 `rstd` / `mean` [R]
+    (mean: layer mode) and float32 `weight` [C] (or None): returns (dx [R, C] in x's dtype, dweight [C], dbias [C] float32), None
+    where not needed -- from up to three launches and a workspace (`_mx_workspace`).  The column sums of a tensor without rows are
+    +0 and filled here: the library enqueues nothing for an empty tensor."""
+    global mx_norm_bwd_last_route
+    load()
+    R, C = x.shape
+    empty = R == 0 or C == 0
+    dx = torch.empty_like(x) if need_dx else None
+    new = torch.zeros if empty else torch.empty
+    dw = new(C, dtype=torch.float32, device=x.device) if need_dweight else None
+    db = new(C, dtype=torch.float32, device=x.device) if need_dbias else None
+    mx_norm_bwd_last_route = None
+    if not empty and (need_dx or need_dweight or need_dbias):
+        nbytes = mx_norm_bwd_plan(R, C, norm, need_dx, need_dweight or need_dbias)
+        ws = _mx_workspace(nbytes, x.device)
+        a = MxNormBwdArgs()
+        a.mode, a.xdt, a.gdt = MX_NORMS.index(norm), dt(x), dt(dxhat)
+        a.dxhat, a.x, a.weight, a.rstd, a.mean = _ptr(dxhat), _ptr(x), _ptr(weight), _ptr(rstd), _ptr(mean)
+        a.dx, a.dweight, a.dbias = _ptr(dx), _ptr(dw), _ptr(db)
+        a.workspace, a.workspace_bytes = _ptr(ws), nbytes
+        a.R, a.C = R, C
+        a.stream = _stream(x)
+        mx_norm_bwd_last_route = _mx_run("mx_norm_bwd", a, (dxhat, x, dx))
+    return dx, dw, db
 
 
 def quant_line_fwd(x: torch.Tensor, lines: torch.Tensor, bits: int, channel_index: int, float_zero_point: bool,

@@ -43,6 +43,22 @@ __device__ __forceinline__ void mxn_load8(const void* __restrict__ x, int64_t ba
     }
 }
 
+// the header's row sum in two steps, shared with qs_mx_norm_bwd.h so that its order is written once: a pass adds a lane's two quad
+// sums to its partial sums `pa` (2 lane) and `pb` (2 lane + 1); the fold is the pairwise tree over the wave's 128, every lane returns it
+__device__ __forceinline__ void mxn_add_quads(const float (&t)[8], float& pa, float& pb) {
+    pa = pa + ((t[0] + t[1]) + (t[2] + t[3]));
+    pb = pb + ((t[4] + t[5]) + (t[6] + t[7]));
+}
+
+__device__ __forceinline__ float mxn_fold(float pa, float pb) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {                   // partial j += partial j + 2 off, j < 2 off (the lanes above hold
+        pa = pa + __shfl_down(pa, off, 64);                     //  sums nobody reads)
+        pb = pb + __shfl_down(pb, off, 64);
+    }
+    return __shfl(pa + pb, 0, 64);
+}
+
 // sum over the row of t_i = x_i (TERM 0), x_i * x_i (1) or (x_i - mu) * (x_i - mu) (2) in the header's order; every lane returns it
 template <int XDT, bool VEC, int TERM>
 __device__ __forceinline__ float mxn_row_sum(const void* __restrict__ x, int64_t base, int64_t C, int lane, float mu) {
@@ -61,15 +77,9 @@ __device__ __forceinline__ float mxn_row_sum(const void* __restrict__ x, int64_t
                 t[j] = in[j] ? d * d : 0.0f;
             }
         }
-        pa = pa + ((t[0] + t[1]) + (t[2] + t[3]));
-        pb = pb + ((t[4] + t[5]) + (t[6] + t[7]));
+        mxn_add_quads(t, pa, pb);
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {                   // partial j += partial j + 2 off, j < 2 off (the lanes above hold
-        pa = pa + __shfl_down(pa, off, 64);                     //  sums nobody reads)
-        pb = pb + __shfl_down(pb, off, 64);
-    }
-    return __shfl(pa + pb, 0, 64);
+    return mxn_fold(pa, pb);
 }
 
 template <int XDT, bool VEC>

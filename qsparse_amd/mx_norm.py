@@ -251,12 +251,126 @@ def _norm_backward(dxhat: torch.Tensor, xhat: torch.Tensor, rstd: torch.Tensor, 
     return dx, dw, db
 
 
+_COL_TILE, _COL_PARTS = 128, 16     # a column is summed in row tiles of 128: 16 strided partial sums, then 128 over the tiles
+
+
+def _halve(P: torch.Tensor) -> torch.Tensor:
+    """the pairwise tree over the first axis: the upper half added to the lower until one slice is left"""
+    s = P.shape[0] // 2
+    while s >= 1:
+        P = P[:s] + P[s:2 * s]
+        s //= 2
+    return P[0]
+
+
+def _col_sum(t: torch.Tensor) -> torch.Tensor:
+    """sum over the first axis of float32 ``t [R, C]`` in the definition's order (include/qsparse_hip.h, "MX norm backward"): zero
+    padding to a multiple of 128 rows; per row tile 16 strided partial sums in ascending order and a pairwise tree; over the tiles
+    128 strided partial sums and a pairwise tree -- element-wise additions on slices only, a function of ``R`` alone"""
+    R, C = t.shape
+    T = -(-R // _COL_TILE)
+    u = F.pad(t, (0, 0, 0, T * _COL_TILE - R)).view(T, _COL_TILE // _COL_PARTS, _COL_PARTS, C)
+    S = torch.zeros(T, _COL_PARTS, C, dtype=torch.float32, device=t.device)
+    for m in range(_COL_TILE // _COL_PARTS):
+        S = S + u[:, m]
+    v = _halve(S.transpose(0, 1))                                       # [T, C]: the tile sums
+    K = -(-T // _PARTIALS)
+    v = F.pad(v, (0, 0, 0, K * _PARTIALS - T)).view(K, _PARTIALS, C)
+    P = torch.zeros(_PARTIALS, C, dtype=torch.float32, device=t.device)
+    for k in range(K):
+        P = P + v[k]
+    return _halve(P)
+
+
+def _mx_norm_backward_f32(dxhat2: torch.Tensor, x2: torch.Tensor, rstd: torch.Tensor, mean: Optional[torch.Tensor],
+                          weight: Optional[torch.Tensor], need_dx: bool = True, need_dw: bool = True, need_db: bool = True):
+    """the definition of the norm's backward in torch float32 ops on ``[R, C]`` tensors (``mean`` None: rms mode): returns (dx float32,
+    BEFORE its one rounding to x's dtype, dweight, dbias), None where not needed -- the CPU path of ``mx_norm_backward``"""
+    d32 = dxhat2.to(torch.float32)
+    xhat = _norm_xhat(x2, rstd, mean)
+    dx = dw = db = None
+    if need_dx:
+        cf = torch.tensor(float(x2.shape[1]), dtype=torch.float32, device=x2.device)
+        g = d32 if weight is None else d32 * weight
+        inner = g - xhat * (_row_sum(g * xhat) / cf)[:, None]
+        if mean is not None:
+            inner = inner - (_row_sum(g) / cf)[:, None]
+        dx = rstd[:, None] * inner
+    if need_dw:
+        dw = _col_sum(d32 * xhat)
+    if need_db:
+        db = _col_sum(d32)
+    return dx, dw, db
+
+
+def mx_norm_backward(dxhat: torch.Tensor, x: torch.Tensor, rstd: torch.Tensor, mean: Optional[torch.Tensor] = None,
+                     weight: Optional[torch.Tensor] = None, *, norm: str = "rms", need_dx: bool = True, need_dweight: bool = True,
+                     need_dbias: bool = True):
+    """The backward of the normalisation ``y = norm(x) * weight (+ bias)`` that ``mx_norm_quantize`` computes, over the last dimension
+    of ``x [..., C]``: ``dxhat [..., C]`` (float32 / bfloat16 / float16) is the gradient with respect to ``y``, ``rstd`` / ``mean``
+    (float32, shaped ``x.shape[:-1]``; ``mean`` in layer mode only) are ``mx_norm_quantize(..., return_stats=True)``'s, ``weight`` is
+    ``[C]`` or None (ones).  Returns ``(dx, dweight, dbias)`` -- ``dx`` shaped and typed as ``x``, the other two float32 ``[C]`` -- with
+    None where ``need_dx`` / ``need_dweight`` / ``need_dbias`` is False; an output that is asked for does not depend on the others.
+    All arithmetic is float32, ``xhat`` as the forward forms it:
+
+        xhat = (x - mean) * rstd   (x * rstd in rms mode),   g = dxhat * weight
+        c1 = sum_C(g * xhat) / C,   c2 = sum_C(g) / C
+        rms     dx = rstd * (g - xhat * c1)
+        layer   dx = rstd * ((g - xhat * c1) - c2)                      rounded once to x's dtype
+        dweight = sum_R(dxhat * xhat),   dbias = sum_R(dxhat)
+
+    with every sum in one fixed order: the row sums in ``mx_norm_quantize``'s (a function of ``C`` alone), the column sums in row tiles
+    of 128 -- 16 strided partial sums and a pairwise tree per tile, 128 strided partial sums and a pairwise tree over the tiles (a
+    function of ``R`` alone).  So the bits are the same on the CPU and on the GPU, on every run (no atomics), for every dtype and
+    whatever is asked for; they are NOT those of torch's own reductions.  NaN and Inf propagate: a row whose ``rstd`` is NaN has a NaN
+    ``dx`` and makes ``dweight`` NaN.  GPU tensors take the HIP kernels of ``qs_mx_norm_bwd_v`` (no fallback), CPU tensors the torch
+    expression of the definition.  Nothing here is differentiable."""
+    weight, _ = _check_norm_args(x, weight, None, norm, 0.0)
+    if not isinstance(dxhat, torch.Tensor):
+        raise TypeError(f"dxhat must be a tensor, got {type(dxhat).__name__}")
+    _check_dtype("dxhat", dxhat.dtype)
+    if dxhat.shape != x.shape:
+        raise ValueError(f"dxhat has shape {tuple(dxhat.shape)}, expected x's {tuple(x.shape)}")
+    if norm == "layer" and mean is None:
+        raise ValueError("norm='layer' needs mean: the second statistic of mx_norm_quantize(..., return_stats=True)")
+    stats = (("rstd", rstd),) + ((("mean", mean),) if norm == "layer" else ())
+    for name, t in stats:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+        if t.shape != x.shape[:-1]:
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(x.shape[:-1])}: one value per row of x {tuple(x.shape)}")
+    for name, t in (("dxhat", dxhat),) + stats:
+        if t.device != x.device:
+            raise ValueError(f"x is on {x.device} but {name} on {t.device}")
+    C = x.shape[-1]
+    x2, d2 = x.detach().reshape(-1, C), dxhat.detach().reshape(-1, C)
+    rstd1 = rstd.detach().reshape(-1)
+    mean1 = mean.detach().reshape(-1) if norm == "layer" else None
+    if x.is_cuda:
+        dx, dw, db = _hip.mx_norm_bwd(d2.contiguous(), x2.contiguous(), rstd1.contiguous(), None if mean1 is None else mean1.contiguous(),
+                                      weight, norm, need_dx, need_dweight, need_dbias)
+    else:
+        dx, dw, db = _mx_norm_backward_f32(d2, x2, rstd1, mean1, weight, need_dx, need_dweight, need_dbias)
+        dx = None if dx is None else dx.to(x.dtype)
+    return None if dx is None else dx.reshape(x.shape), dw, db
+
+
+MX_NORM_BACKWARDS = ("torch", "fused")
+
+
+def _check_norm_backward(norm_backward):
+    if norm_backward not in MX_NORM_BACKWARDS:
+        raise ValueError(f"unknown norm_backward {norm_backward!r}: one of {MX_NORM_BACKWARDS}")
+
+
 class _MXNormLinearFunction(torch.autograd.Function):
     """y = Q(norm(x)) Q(W)^T + b; the linear part's three products as ``_MXLinearFunction``'s, the norm's backward in float32"""
 
     @staticmethod
     def forward(ctx, x, norm_weight, norm_bias, weight, bias, norm, eps, x_fmt, w_fmt, grad_fmt, need_col, grad_rounding="nearest",
-                seed=0, step=None, wgrad_split_k=1):
+                seed=0, step=None, wgrad_split_k=1, norm_backward="torch"):
         N, K = weight.shape
         x2 = x.reshape(-1, K)
         res = mx_norm_quantize(x2, norm_weight, norm_bias, norm=norm, eps=eps, fmt=x_fmt, col_fmt=x_fmt if need_col else None,
@@ -269,7 +383,7 @@ class _MXNormLinearFunction(torch.autograd.Function):
         y = mx_matmul(x_row, x_rs, x_fmt, w_row, w_rs, w_fmt, b32, x.dtype)
         ctx.save_for_backward(x, norm_weight, weight, rstd, mean, x_col, x_cs)
         _save_train_ctx(ctx, (x_fmt, w_fmt, grad_fmt), (grad_rounding, seed, step), wgrad_split_k, x, bias)
-        ctx.norm = norm
+        ctx.norm, ctx.norm_backward = norm, norm_backward
         ctx.norm_dtypes = tuple(None if t is None else t.dtype for t in (norm_weight, norm_bias))
         return y.reshape(x.shape[:-1] + (N,))
 
@@ -289,8 +403,12 @@ class _MXNormLinearFunction(torch.autograd.Function):
         if need_dxhat:
             _, _, w_col, w_cs = mx_quantize_2way(weight, None, w_fmt)
             dxhat = mx_matmul(g_row, g_rs, grad_fmt, w_col, w_cs, w_fmt, None, torch.float32)
-            xhat = _norm_xhat(x.reshape(-1, K), rstd, mean)
-            dx, dnw, dnb = _norm_backward(dxhat, xhat, rstd, norm_weight, ctx.norm, need_dx, need_dnw, need_dnb)
+            if ctx.norm_backward == "fused":
+                dx, dnw, dnb = mx_norm_backward(dxhat, x.reshape(-1, K), rstd, mean, norm_weight, norm=ctx.norm, need_dx=need_dx,
+                                                need_dweight=need_dnw, need_dbias=need_dnb)
+            else:
+                xhat = _norm_xhat(x.reshape(-1, K), rstd, mean)
+                dx, dnw, dnb = _norm_backward(dxhat, xhat, rstd, norm_weight, ctx.norm, need_dx, need_dnw, need_dnb)
             dx = None if dx is None else dx.to(ctx.x_dtype).reshape(x.shape)
             dnw = None if dnw is None else dnw.to(ctx.norm_dtypes[0])
             dnb = None if dnb is None else dnb.to(ctx.norm_dtypes[1])
@@ -298,13 +416,13 @@ class _MXNormLinearFunction(torch.autograd.Function):
             dw = mx_matmul(g_col, g_cs, grad_fmt, x_col, x_cs, x_fmt, None, weight.dtype, split_k=ctx.wgrad_split_k)
         if need_db:
             db = dy2.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
-        return (dx, dnw, dnb, dw, db) + (None,) * 10
+        return (dx, dnw, dnb, dw, db) + (None,) * 11
 
 
 def mx_norm_linear(x: torch.Tensor, norm_weight: Optional[torch.Tensor], norm_bias: Optional[torch.Tensor], weight: torch.Tensor,
                    bias: Optional[torch.Tensor] = None, *, norm: str = "rms", eps: float = 1e-6, x_fmt: str = "mxfp8_e4m3",
                    w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2", grad_rounding: str = "nearest", seed: int = 0,
-                   step: Optional[torch.Tensor] = None, wgrad_split_k="auto") -> torch.Tensor:
+                   step: Optional[torch.Tensor] = None, wgrad_split_k="auto", norm_backward: str = "torch") -> torch.Tensor:
     """``mx_linear(norm(x) * norm_weight (+ norm_bias), weight, bias)`` without the float tensor between the two, differentiable in
     all five tensors.  ``x`` is ``[..., K]``, ``norm_weight`` / ``norm_bias`` ``[K]`` or None, ``weight`` ``[N, K]``, ``bias`` ``[N]``;
     the result is ``[..., N]`` in ``x.dtype``.  The forward is ONE ``mx_norm_quantize`` call -- the row pair for the product, the
@@ -320,9 +438,12 @@ def mx_norm_linear(x: torch.Tensor, norm_weight: Optional[torch.Tensor], norm_bi
         layer   dx = rstd * ((g - xhat * mean_C(g * xhat)) - mean_C(g))
         d norm_weight = sum_R(dxhat * xhat),   d norm_bias = sum_R(dxhat)
 
-    The normalisation's backward is torch float32 ops on ``[R, K]`` tensors -- it is NOT fused -- each result cast once to its
-    tensor's dtype.  Gradients nobody asks for are not computed; without grad the col pair is not produced.  ``grad_rounding``,
-    ``seed``, ``step`` and ``wgrad_split_k`` are ``mx_linear``'s and touch the two forms of ``dy`` and the ``dW`` product alone."""
+    With ``norm_backward="torch"`` (the default) the normalisation's backward is torch float32 ops on ``[R, K]`` tensors -- not fused;
+    its sums are torch's own ``mean(-1)`` / ``sum(0)``.  ``norm_backward="fused"`` hands it to ``mx_norm_backward``: the same formulas
+    in up to three HIP launches on the GPU, with the sums in that function's fixed order -- other last bits than torch's, the same on
+    the CPU and the GPU.  The forward, ``dW`` and ``db`` do not depend on it.  Either way each result is cast once to its tensor's
+    dtype.  Gradients nobody asks for are not computed; without grad the col pair is not produced.  ``grad_rounding``, ``seed``,
+    ``step`` and ``wgrad_split_k`` are ``mx_linear``'s and touch the two forms of ``dy`` and the ``dW`` product alone."""
     _check_train_entry(x, weight, bias, (x_fmt, w_fmt, grad_fmt), grad_rounding, step, wgrad_split_k)
     if weight.dim() != 2:
         raise ValueError(f"weight must be [N, K], got shape {tuple(weight.shape)}")
@@ -330,25 +451,29 @@ def mx_norm_linear(x: torch.Tensor, norm_weight: Optional[torch.Tensor], norm_bi
         raise ValueError(f"x {tuple(x.shape)} and weight {tuple(weight.shape)} disagree on K (their last dimensions)")
     _check_norm_args(x, norm_weight, norm_bias, norm, eps)
     _check_bias_shape(bias, weight.shape[0])
+    _check_norm_backward(norm_backward)
     need_col = torch.is_grad_enabled() and weight.requires_grad
     return _MXNormLinearFunction.apply(x, norm_weight, norm_bias, weight, bias, norm, float(eps), x_fmt, w_fmt, grad_fmt, need_col,
-                                       grad_rounding, seed, step, wgrad_split_k)
+                                       grad_rounding, seed, step, wgrad_split_k, norm_backward)
 
 
 class MXTrainNormLinear(_MXTrainMixin, nn.Module):
     """A normalisation and the linear layer behind it as one training layer: ``forward`` is ``mx_norm_linear``.  The parameters are
     ``norm_weight`` / ``norm_bias`` (``[in_features]``; None where the norm has none) and ``weight`` / ``bias`` as ``nn.Linear``'s.
     ``norm`` is ``"rms"`` or ``"layer"``; ``eps=None`` is the machine epsilon of the input's dtype (``nn.RMSNorm``'s rule).  The
+    ``norm_backward`` is ``mx_norm_linear``'s: ``"torch"`` (the default) or ``"fused"``, the HIP kernels of ``mx_norm_backward``.  The
     options, the stochastic-rounding seed and counter and the autocast behaviour are ``MXTrainLinear``'s."""
 
     def __init__(self, in_features: int, out_features: int, bias: bool = True, norm: str = "rms", eps: Optional[float] = 1e-6,
                  elementwise_affine: bool = True, norm_bias: bool = True, device=None, dtype=None, x_fmt: str = "mxfp8_e4m3",
                  w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2", grad_rounding: str = "nearest", seed: Optional[int] = None,
-                 wgrad_split_k="auto"):
+                 wgrad_split_k="auto", norm_backward: str = "torch"):
         super().__init__()
         if norm not in MX_NORMS:
             raise ValueError(f"unknown norm {norm!r}: one of {MX_NORMS}")
+        _check_norm_backward(norm_backward)
         self.in_features, self.out_features, self.norm, self.eps = in_features, out_features, norm, eps
+        self.norm_backward = norm_backward
         lin = nn.Linear(in_features, out_features, bias=bias, device=device, dtype=dtype)
         self.weight, self.bias = lin.weight, lin.bias
         kw = dict(device=device, dtype=dtype)
@@ -360,7 +485,8 @@ class MXTrainNormLinear(_MXTrainMixin, nn.Module):
 
     @classmethod
     def from_float(cls, norm_module: nn.Module, linear: nn.Linear, x_fmt: str = "mxfp8_e4m3", w_fmt: str = "mxfp8_e4m3",
-                   grad_fmt: str = "mxfp8_e5m2", grad_rounding: str = "nearest", seed: Optional[int] = None, wgrad_split_k="auto"):
+                   grad_fmt: str = "mxfp8_e5m2", grad_rounding: str = "nearest", seed: Optional[int] = None, wgrad_split_k="auto",
+                   norm_backward: str = "torch"):
         """a layer on the two modules' own parameters (shared, not copied): ``linear(norm_module(x))``"""
         norm = _norm_kind(norm_module)
         if not isinstance(linear, nn.Linear):
@@ -369,21 +495,22 @@ class MXTrainNormLinear(_MXTrainMixin, nn.Module):
             raise ValueError(f"normalized_shape {tuple(norm_module.normalized_shape)} does not match in_features {linear.in_features}")
         self = cls(linear.in_features, linear.out_features, bias=linear.bias is not None, norm=norm, eps=norm_module.eps,
                    elementwise_affine=False, device="meta", x_fmt=x_fmt, w_fmt=w_fmt, grad_fmt=grad_fmt, grad_rounding=grad_rounding,
-                   seed=seed, wgrad_split_k=wgrad_split_k)._adopt(linear)
+                   seed=seed, wgrad_split_k=wgrad_split_k, norm_backward=norm_backward)._adopt(linear)
         self.norm_weight, self.norm_bias = norm_module.weight, getattr(norm_module, "bias", None)
         return self
 
     def extra_repr(self) -> str:
         sr = f", grad_rounding={self.grad_rounding!r}" if self.grad_rounding != "nearest" else ""
         split = f", wgrad_split_k={self.wgrad_split_k!r}" if self.wgrad_split_k != "auto" else ""
+        nb = f", norm_backward={self.norm_backward!r}" if self.norm_backward != "torch" else ""
         return (f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, norm={self.norm!r}, "
-                f"eps={self.eps}, x_fmt={self.x_fmt!r}, w_fmt={self.w_fmt!r}, grad_fmt={self.grad_fmt!r}{sr}{split}")
+                f"eps={self.eps}, x_fmt={self.x_fmt!r}, w_fmt={self.w_fmt!r}, grad_fmt={self.grad_fmt!r}{sr}{split}{nb}")
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         x, seed, step = self._mx_input(x)
         return mx_norm_linear(x, self.norm_weight, self.norm_bias, self.weight, self.bias, norm=self.norm, eps=_eps_of(self.eps, x),
                               x_fmt=self.x_fmt, w_fmt=self.w_fmt, grad_fmt=self.grad_fmt, grad_rounding=self.grad_rounding, seed=seed,
-                              step=step, wgrad_split_k=self.wgrad_split_k)
+                              step=step, wgrad_split_k=self.wgrad_split_k, norm_backward=self.norm_backward)
 
     def to_inference(self, out_dtype: torch.dtype = torch.float32) -> nn.Sequential:
         """``nn.Sequential(MXRMSNorm | MXLayerNorm, MXLinear)`` on the current parameters: the norm (sharing this layer's) hands the
@@ -400,4 +527,5 @@ class MXTrainNormLinear(_MXTrainMixin, nn.Module):
                                             out_dtype))
 
 
-__all__ = ["mx_norm_quantize", "MXRMSNorm", "MXLayerNorm", "mx_norm_linear", "MXTrainNormLinear", "MX_NORMS"]
+__all__ = ["mx_norm_quantize", "mx_norm_backward", "MXRMSNorm", "MXLayerNorm", "mx_norm_linear", "MXTrainNormLinear", "MX_NORMS",
+           "MX_NORM_BACKWARDS"]

@@ -7,11 +7,12 @@ PAD = 512          # bytes on either side
 PATTERN = 0xA5
 
 
-def guarded(nbytes, offset=0, pad=PAD):
-    """(raw, body): `body` = nbytes bytes starting pad + offset bytes into a pattern-filled allocation"""
-    raw = torch.full((nbytes + 2 * pad + offset,), PATTERN, dtype=torch.uint8, device=DEV)
+def guarded(nbytes, offset=0, pad=PAD, pattern=PATTERN):
+    """(raw, body): `body` = nbytes bytes starting pad + offset bytes into an allocation filled with `pattern` (0xFF around an input:
+    a NaN in float32, bfloat16 and float16, so an over-read poisons what is computed from it)"""
+    raw = torch.full((nbytes + 2 * pad + offset,), pattern, dtype=torch.uint8, device=DEV)
     return raw, raw[pad + offset:pad + offset + nbytes]
 
 
-def intact(raw, nbytes, offset=0, pad=PAD):
-    return bool((raw[:pad + offset] == PATTERN).all()) and bool((raw[pad + offset + nbytes:] == PATTERN).all())
+def intact(raw, nbytes, offset=0, pad=PAD, pattern=PATTERN):
+    return bool((raw[:pad + offset] == pattern).all()) and bool((raw[pad + offset + nbytes:] == pattern).all())

@@ -1743,6 +1743,8 @@ int qs_mx_norm_quant_route(const qs_mx_norm_quant_args* args);
  *   c2     = rowsum(g_i) / Cf        layer mode only
  *   dx_i   = rstd * (g_i - xhat_i * c1)                  rms
  *   dx_i   = rstd * ((g_i - xhat_i * c1) - c2)           layer           rounded once, to nearest-even, to x's dtype
+ *   with `dresidual` [R, C] in x's dtype (qs_mx_norm_bwd_res_v below only): dx_i = (the float32 value above) + f32(dresidual_i), one
+ *   more float32 addition in front of that single rounding; without it nothing changes
  *   dweight_c = colsum_r(dxhat[r, c] * xhat[r, c])
  *   dbias_c   = colsum_r(dxhat[r, c])
  *   rowsum is the sum over a row of the MX normalising quantizer above -- a function of C alone; the terms behind the row are +0.
@@ -1801,6 +1803,94 @@ int qs_mx_norm_bwd_route(const qs_mx_norm_bwd_args* args);
  * (need_cols != 0): up16(4 R) (twice in layer mode) with need_dx, plus 2 up16(4 ceil(R / 128) C) with need_cols, up16 rounding up to a
  * multiple of 16; 0 for an empty tensor.  QS_ERR_ARG: workspace_bytes NULL, an unknown mode, a negative extent, extents the call refuses. */
 int qs_mx_norm_bwd_plan(int64_t R, int64_t C, int32_t mode, int32_t need_dx, int32_t need_cols, uint64_t* workspace_bytes);
+
+/* MX norm backward with the residual stream's gradient.  Added without raising QS_ABI_VERSION (28): symbols are only added;
+ * qs_mx_norm_bwd_args and qs_mx_norm_bwd_v above are unchanged.
+ *
+ * The definition above with one more operand, `dresidual` [R, C] (CONTIGUOUS, the dtype of x and dx; nullable), the gradient that
+ * reaches the norm's input by the residual stream:
+ *   dx_i   = rstd * (g_i - xhat_i * c1)          + f32(dresidual_i)       rms
+ *   dx_i   = rstd * ((g_i - xhat_i * c1) - c2)   + f32(dresidual_i)       layer
+ * ONE more float32 addition, in front of the single rounding to x's dtype (not dx rounded and then added).  c1, c2, dweight and
+ * dbias do not see it.  With dresidual NULL every output is qs_mx_norm_bwd_v's, bit for bit.  The workspace, its plan
+ * (qs_mx_norm_bwd_plan) and the launches are qs_mx_norm_bwd_v's; dresidual is read by the apply launch, with the tile's other loads.
+ *   - Checks: qs_mx_norm_bwd_v's, in its order, and with them: QS_ERR_ARG (after "dx, dweight and dbias all NULL"): dresidual given
+ *     and dx NULL; QS_ERR_ALIGN: dresidual not aligned to x's element.
+ *   - QS_MX_NORM_BWD_ROUTE_VEC: as above and dresidual 16-byte aligned. */
+typedef struct qs_mx_norm_bwd_res_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_norm_bwd_res_args) as the caller compiled it */
+    int32_t mode;                    /* QS_MX_NORM_* */
+    int32_t xdt;                     /* dtype of x, dx and dresidual: QS_F32, QS_BF16 or QS_F16 */
+    int32_t gdt;                     /* dtype of dxhat, likewise */
+    const void* dxhat;               /* [R, C] row-major */
+    const void* x;                   /* [R, C] row-major */
+    const float* weight;             /* [C], nullable (ones) */
+    const float* rstd;               /* [R] */
+    const float* mean;               /* [R], layer mode */
+    void* dx;                        /* [R, C], nullable */
+    float* dweight;                  /* [C], nullable */
+    float* dbias;                    /* [C], nullable */
+    void* workspace;
+    uint64_t workspace_bytes;
+    int64_t R, C;
+    qs_stream_t stream;
+    const void* dresidual;           /* [R, C] row-major, nullable; needs dx */
+} qs_mx_norm_bwd_res_args;
+int qs_mx_norm_bwd_res_v(const qs_mx_norm_bwd_res_args* args);
+/* the kernels qs_mx_norm_bwd_res_v launches for these operands, nothing enqueued: QS_MX_NORM_BWD_ROUTE_*, 0 for an empty tensor, or
+ * the QS_ERR_* the call would return */
+int qs_mx_norm_bwd_res_route(const qs_mx_norm_bwd_res_args* args);
+
+/* ---- MX add-norm quantizer (the residual add of a pre-norm block in front of the MX normalising quantizer) ----------------------------
+ * Added without raising QS_ABI_VERSION (28), by the same rule as qs_mx_matmul_v above: symbols are only added.
+ *
+ * From x [R, C] (the output of the previous branch) and residual [R, C] (the stream), both CONTIGUOUS, C innermost, each float32,
+ * bf16 or fp16 and not necessarily alike: the new stream h [R, C] in RESIDUAL's dtype, and the MX operands of norm(h) * weight (+ bias).
+ * Definition (normative).
+ *   h_i = round_hdt(f32(x_i) + f32(r_i))      ONE float32 addition, without contraction, rounded once to nearest-even to h's dtype
+ *                                             (float32: no rounding).  A NaN or an Inf of the sum is kept in h.
+ *   Everything else is the MX normalising quantizer above applied to that ROUNDED h: the sums run over the widened h_i, not over the
+ *   unrounded float32 sums.  So row_codes, row_scales, col_codes, col_scales, rstd and mean are, bit for bit, what
+ *   qs_mx_norm_quant_v writes for x = h, xdt = rdt -- the NaN-row rule included: a row whose h holds a NaN or an Inf is NaN as a whole.
+ * h must not overlap x or residual (an in-place update of the stream is not offered); the outputs must not overlap the inputs.
+ * Two launches on `stream`, nothing read by the host: a statistics launch that loads x and residual, stores h and forms the row sums
+ * from the rounded values (layer mode's second walk forms h again from x and residual; it does not read h back), then the quantizing
+ * launch of qs_mx_norm_quant_v on h.  No atomics, no workspace beyond rstd / mean.
+ *   - Checks, in order: QS_ERR_ARG: a null or too short descriptor, an unknown mode, x, residual, h, row_codes, row_scales or rstd
+ *     NULL, mean NULL in layer mode, row_format no enum qs_mx_format, col_format neither -1 nor one, a NULL pointer of a given col
+ *     pair, eps negative or not finite, R or C negative; QS_ERR_DTYPE: xdt or rdt none of the three; QS_ERR_ALIGN: x not aligned to
+ *     its element, residual or h not to rdt's, or weight, bias, rstd or mean not to 4 bytes; QS_ERR_ARG: R * C beyond 64 bits or more
+ *     tiles than a launch takes.
+ *   - R == 0 or C == 0: nothing is enqueued, 0 is returned.
+ *   - QS_MX_NORM_ROUTE_VEC (16-byte loads of x and residual and 16-byte stores of h in the statistics launch; the quantizing launch
+ *     as above): C % 32 == 0 and x, residual, h, weight, bias 16-byte aligned.  Anything else takes QS_MX_NORM_ROUTE_PLAIN, element
+ *     accesses: any R, C >= 1, same bits. */
+typedef struct qs_mx_add_norm_quant_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_add_norm_quant_args) as the caller compiled it */
+    int32_t mode;                    /* QS_MX_NORM_* */
+    int32_t row_format, col_format;  /* enum qs_mx_format, may differ; col_format -1: the col pair is skipped */
+    int32_t xdt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    float eps;
+    const void* x;                   /* [R, C] row-major */
+    const float* weight;             /* [C], nullable (ones) */
+    const float* bias;               /* [C], nullable (none) */
+    uint8_t* row_codes;              /* [R, C] */
+    uint8_t* row_scales;             /* [R, ceil(C / 32)] */
+    uint8_t* col_codes;              /* [C, R] */
+    uint8_t* col_scales;             /* [C, ceil(R / 32)] */
+    float* rstd;                     /* [R] */
+    float* mean;                     /* [R], layer mode */
+    int64_t R, C;
+    qs_stream_t stream;
+    const void* residual;            /* [R, C] row-major */
+    void* h;                         /* [R, C] row-major, residual's dtype: written */
+    int32_t rdt;                     /* dtype of residual and h: QS_F32, QS_BF16 or QS_F16 */
+    int32_t reserved0;               /* 0 */
+} qs_mx_add_norm_quant_args;
+int qs_mx_add_norm_quant_v(const qs_mx_add_norm_quant_args* args);
+/* the kernels qs_mx_add_norm_quant_v launches for these operands, nothing enqueued: QS_MX_NORM_ROUTE_*, 0 for an empty tensor, or the
+ * QS_ERR_* the call would return */
+int qs_mx_add_norm_quant_route(const qs_mx_add_norm_quant_args* args);
 
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so

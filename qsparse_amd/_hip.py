@@ -144,6 +144,10 @@ SIGNATURES = {
     "qs_mx_norm_bwd_v": (c_int, [_P]),
     "qs_mx_norm_bwd_route": (c_int, [_P]),
     "qs_mx_norm_bwd_plan": (c_int, [_L, _L, c_int32, c_int32, c_int32, _P]),
+    "qs_mx_norm_bwd_res_v": (c_int, [_P]),
+    "qs_mx_norm_bwd_res_route": (c_int, [_P]),
+    "qs_mx_add_norm_quant_v": (c_int, [_P]),
+    "qs_mx_add_norm_quant_route": (c_int, [_P]),
 }
 
 
@@ -359,6 +363,16 @@ class MxNormBwdArgs(ctypes.Structure):
                 ("x", c_void_p), ("weight", c_void_p), ("rstd", c_void_p), ("mean", c_void_p), ("dx", c_void_p), ("dweight", c_void_p),
                 ("dbias", c_void_p), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64), ("R", c_int64), ("C", c_int64),
                 ("stream", c_void_p)]
+
+
+class MxNormBwdResArgs(ctypes.Structure):
+    """`qs_mx_norm_bwd_res_args` of include/qsparse_hip.h"""
+    _fields_ = MxNormBwdArgs._fields_ + [("dresidual", c_void_p)]
+
+
+class MxAddNormQuantArgs(ctypes.Structure):
+    """`qs_mx_add_norm_quant_args` of include/qsparse_hip.h"""
+    _fields_ = MxNormQuantArgs._fields_ + [("residual", c_void_p), ("h", c_void_p), ("rdt", c_int32), ("reserved0", c_int32)]
 
 
 class MxGroupedWgradArgs(ctypes.Structure):
@@ -1597,20 +1611,16 @@ MX_NORM_ROUTE_VEC, MX_NORM_ROUTE_PLAIN = 1, 2
 mx_norm_last_route = None     # the QS_MX_NORM_ROUTE_* of the last `mx_norm_quant` launch (None: an empty tensor), for tests and tools
 
 
-def mx_norm_quant(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], norm: str, eps: float, row_fmt: str,
-                  col_fmt: Optional[str]):
-    """RMSNorm / LayerNorm in front of the MX quantizer (qs_mx_norm_quant_v) on a contiguous GPU tensor `x` [R, C] and float32
-    `weight` / `bias` [C] (or None): returns (row_codes [R, C], row_scales [R, ceil(C / 32)], col_codes [C, R] | None, col_scales
-    [C, ceil(R / 32)] | None, rstd [R], mean [R] | None) -- mean in layer mode -- from two launches."""
-    global mx_norm_last_route
-    load()
+def _mx_norm_quant_run(entry: str, a, x: torch.Tensor, weight, bias, norm: str, eps: float, row_fmt: str, col_fmt, extra=()):
+    """what `mx_norm_quant` and `mx_add_norm_quant` share: the outputs of the quantizing launch for `x` [R, C], the descriptor's common
+    fields and -- for a tensor that is not empty -- the run of `entry` (`extra`: the operands `a` holds beyond these).  Returns
+    ((row_codes, row_scales, col_codes | None, col_scales | None, rstd, mean | None), route | None)"""
     R, C = x.shape
     outs = _mx_quant2_outs((), R, C, row_fmt, col_fmt, x.device)
     rstd = torch.empty(R, dtype=torch.float32, device=x.device)
     mean = torch.empty(R, dtype=torch.float32, device=x.device) if norm == "layer" else None
-    mx_norm_last_route = None
+    route = None
     if R and C:
-        a = MxNormQuantArgs()
         a.mode = MX_NORMS.index(norm)
         a.row_format = MX_FORMATS.index(row_fmt)
         a.col_format = MX_FORMATS.index(col_fmt) if col_fmt is not None else -1
@@ -1620,8 +1630,38 @@ def mx_norm_quant(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optiona
         a.rstd, a.mean = _ptr(rstd), _ptr(mean)
         a.R, a.C = R, C
         a.stream = _stream(x)
-        mx_norm_last_route = _mx_run("mx_norm_quant", a, (x, weight, bias) + outs + (rstd, mean))
-    return outs + (rstd, mean)
+        route = _mx_run(entry, a, (x, weight, bias) + extra + outs + (rstd, mean))
+    return outs + (rstd, mean), route
+
+
+def mx_norm_quant(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], norm: str, eps: float, row_fmt: str,
+                  col_fmt: Optional[str]):
+    """RMSNorm / LayerNorm in front of the MX quantizer (qs_mx_norm_quant_v) on a contiguous GPU tensor `x` [R, C] and float32
+    `weight` / `bias` [C] (or None): returns (row_codes [R, C], row_scales [R, ceil(C / 32)], col_codes [C, R] | None, col_scales
+    [C, ceil(R / 32)] | None, rstd [R], mean [R] | None) -- mean in layer mode -- from two launches."""
+    global mx_norm_last_route
+    load()
+    mx_norm_last_route = None
+    res, mx_norm_last_route = _mx_norm_quant_run("mx_norm_quant", MxNormQuantArgs(), x, weight, bias, norm, eps, row_fmt, col_fmt)
+    return res
+
+
+mx_add_norm_last_route = None     # the QS_MX_NORM_ROUTE_* of the last `mx_add_norm_quant` launch (None: an empty tensor)
+
+
+def mx_add_norm_quant(x: torch.Tensor, residual: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], norm: str,
+                      eps: float, row_fmt: str, col_fmt: Optional[str]):
+    """the residual add in front of the MX normalising quantizer (qs_mx_add_norm_quant_v) on contiguous GPU tensors `x`, `residual`
+    [R, C] (their dtypes may differ): returns (h [R, C] in residual's dtype,) + what `mx_norm_quant` returns for h -- from two
+    launches, the first of which writes h."""
+    global mx_add_norm_last_route
+    load()
+    h = torch.empty_like(residual)
+    a = MxAddNormQuantArgs()
+    a.residual, a.h, a.rdt = _ptr(residual), _ptr(h), dt(residual)
+    mx_add_norm_last_route = None
+    res, mx_add_norm_last_route = _mx_norm_quant_run("mx_add_norm_quant", a, x, weight, bias, norm, eps, row_fmt, col_fmt, (residual, h))
+    return (h,) + res
 
 
 MX_NORM_BWD_ROUTE_VEC, MX_NORM_BWD_ROUTE_PLAIN = 1, 2
@@ -1637,8 +1677,10 @@ def mx_norm_bwd_plan(R: int, C: int, norm: str, need_dx: bool, need_cols: bool) 
 
 
 def mx_norm_bwd(dxhat: torch.Tensor, x: torch.Tensor, rstd: torch.Tensor, mean: Optional[torch.Tensor],
-                weight: Optional[torch.Tensor], norm: str, need_dx: bool = True, need_dweight: bool = True, need_dbias: bool = True):
-    """the backward of the normalisation (qs_mx_norm_bwd_v) on contiguous GPU tensors `dxhat`, `x` [R, C], float32 `rstd` / `mean` [R]
+                weight: Optional[torch.Tensor], norm: str, need_dx: bool = True, need_dweight: bool = True, need_dbias: bool = True,
+                dresidual: Optional[torch.Tensor] = None):
+    """the backward of the normalisation (qs_mx_norm_bwd_v; with `dresidual`, a contiguous tensor as `x` that is added to dx in front
+    of its one rounding, qs_mx_norm_bwd_res_v) on contiguous GPU tensors `dxhat`, `x` [R, C], float32 `rstd` / `mean` [R]
     (mean: layer mode) and float32 `weight` [C] (or None): returns (dx [R, C] in x's dtype, dweight [C], dbias [C] float32), None
     where not needed -- from up to three launches and a workspace (`_mx_workspace`).  The column sums of a tensor without rows are
     +0 and filled here: the library enqueues nothing for an empty tensor."""
@@ -1654,14 +1696,16 @@ def mx_norm_bwd(dxhat: torch.Tensor, x: torch.Tensor, rstd: torch.Tensor, mean: 
     if not empty and (need_dx or need_dweight or need_dbias):
         nbytes = mx_norm_bwd_plan(R, C, norm, need_dx, need_dweight or need_dbias)
         ws = _mx_workspace(nbytes, x.device)
-        a = MxNormBwdArgs()
+        a = MxNormBwdArgs() if dresidual is None else MxNormBwdResArgs()
+        if dresidual is not None:
+            a.dresidual = _ptr(dresidual)
         a.mode, a.xdt, a.gdt = MX_NORMS.index(norm), dt(x), dt(dxhat)
         a.dxhat, a.x, a.weight, a.rstd, a.mean = _ptr(dxhat), _ptr(x), _ptr(weight), _ptr(rstd), _ptr(mean)
         a.dx, a.dweight, a.dbias = _ptr(dx), _ptr(dw), _ptr(db)
         a.workspace, a.workspace_bytes = _ptr(ws), nbytes
         a.R, a.C = R, C
         a.stream = _stream(x)
-        mx_norm_bwd_last_route = _mx_run("mx_norm_bwd", a, (dxhat, x, dx))
+        mx_norm_bwd_last_route = _mx_run("mx_norm_bwd" if dresidual is None else "mx_norm_bwd_res", a, (dxhat, x, dx, dresidual))
     return dx, dw, db
 
 

@@ -1,7 +1,10 @@
 // libqsparse_hip.so -- C ABI (include/qsparse_hip.h), the backward of the normalisation in front of the MX quantizer
 // (qs_mx_norm_bwd.h): the row statistics c1 / c2 of dxhat [R, C] and x in one launch, dx and the row tiles' column sums in a second,
-// dweight / dbias from those partial sums in a third -- each launch only when an output that needs it is asked for.
+// dweight / dbias from those partial sums in a third -- each launch only when an output that needs it is asked for.  With the
+// residual stream's gradient (qs_mx_norm_bwd_res_v) the second launch adds it to dx in front of dx's one rounding.
 // Host side: argument checks, workspace layout, route, launch configuration.  No allocation, no synchronisation.
+#include <stddef.h>
+
 #include "qs_host.h"
 #include "qs_mx_norm_bwd.h"
 
@@ -43,27 +46,40 @@ int norm_bwd_plan(int64_t R, int64_t C, bool layer, bool need_dx, bool need_cols
     return 0;
 }
 
-// the checks of qs_mx_norm_bwd_v and the kernels it launches for these operands: QS_MX_NORM_BWD_ROUTE_*, 0 for an empty tensor, QS_ERR_*
-int norm_bwd_route(const qs_mx_norm_bwd_args& a, NormBwdPlan* plan) {
+// qs_mx_norm_bwd_args as the descriptor with the residual stream's gradient, which it has not: the two agree field for field up to
+// `stream` (static_assert below), and both entry points run the one set of checks and launches on the longer one
+qs_mx_norm_bwd_res_args with_no_residual(const qs_mx_norm_bwd_args& b) {
+    static_assert(offsetof(qs_mx_norm_bwd_res_args, dresidual) == sizeof(qs_mx_norm_bwd_args), "the shared fields are a prefix");
+    qs_mx_norm_bwd_res_args a{};
+    memcpy(&a, &b, sizeof(b));
+    a.struct_size = sizeof(a);
+    return a;
+}
+
+// the checks of qs_mx_norm_bwd_v / qs_mx_norm_bwd_res_v and the kernels it launches for these operands: QS_MX_NORM_BWD_ROUTE_*, 0 for an empty tensor, QS_ERR_*
+int norm_bwd_route(const qs_mx_norm_bwd_res_args& a, NormBwdPlan* plan) {
     const bool layer = a.mode == QS_MX_NORM_LAYER;
     if (a.mode != QS_MX_NORM_RMS && !layer) return QS_ERR_ARG;
     if (!a.dxhat || !a.x || !a.rstd || (layer && !a.mean)) return QS_ERR_ARG;
     if (!a.dx && !a.dweight && !a.dbias) return QS_ERR_ARG;
+    if (a.dresidual && !a.dx) return QS_ERR_ARG;
     if (a.R < 0 || a.C < 0) return QS_ERR_ARG;
     if (!dt_ok(a.xdt) || !dt_ok(a.gdt)) return QS_ERR_DTYPE;
     const uintptr_t xm = dt_size(a.xdt) - 1, gm = dt_size(a.gdt) - 1;
-    if ((((uintptr_t)a.x) & xm) != 0 || (((uintptr_t)a.dx) & xm) != 0 || (((uintptr_t)a.dxhat) & gm) != 0 || !aligned4(a.weight) ||
+    if ((((uintptr_t)a.x) & xm) != 0 || (((uintptr_t)a.dx) & xm) != 0 || (((uintptr_t)a.dresidual) & xm) != 0 ||
+        (((uintptr_t)a.dxhat) & gm) != 0 || !aligned4(a.weight) ||
         !aligned4(a.rstd) || (layer && !aligned4(a.mean)) || !aligned4(a.dweight) || !aligned4(a.dbias) || !aligned16(a.workspace))
         return QS_ERR_ALIGN;
     const int st = norm_bwd_plan(a.R, a.C, layer, a.dx != nullptr, a.dweight || a.dbias, plan);
     if (st != 0 || a.R == 0 || a.C == 0) return st;
     if (!a.workspace || a.workspace_bytes < plan->bytes) return QS_ERR_WORKSPACE;
-    const bool vec = a.C % QS_MX_BLOCK == 0 && aligned16(a.dxhat) && aligned16(a.x) && aligned16(a.weight) && aligned16(a.dx);
+    const bool vec = a.C % QS_MX_BLOCK == 0 && aligned16(a.dxhat) && aligned16(a.x) && aligned16(a.weight) && aligned16(a.dx) &&
+                     aligned16(a.dresidual);
     return vec ? QS_MX_NORM_BWD_ROUTE_VEC : QS_MX_NORM_BWD_ROUTE_PLAIN;
 }
 
 template <int XD, int GD, bool VEC>
-void norm_bwd_enqueue(const qs_mx_norm_bwd_args& a, const NormBwdPlan& plan) {
+void norm_bwd_enqueue(const qs_mx_norm_bwd_res_args& a, const NormBwdPlan& plan) {
     const bool layer = a.mode == QS_MX_NORM_LAYER, cols = a.dweight || a.dbias;
     char* ws = (char*)a.workspace;
     const float* mean = layer ? a.mean : nullptr;
@@ -77,14 +93,19 @@ void norm_bwd_enqueue(const qs_mx_norm_bwd_args& a, const NormBwdPlan& plan) {
     if (a.dx)
         hipLaunchKernelGGL((mx_norm_bwd_stats_kernel<XD, GD, VEC>), dim3((unsigned)((a.R + kMxnStatRows - 1) / kMxnStatRows)),
                            dim3(kMxq2Threads), 0, s, a.dxhat, a.x, a.weight, a.rstd, mean, c1, c2, a.R, a.C);
-    hipLaunchKernelGGL((mx_norm_bwd_apply_kernel<XD, GD, VEC>), dim3((unsigned)(tiles_r * tiles_c)), dim3(kMxq2Threads), 0, s, a.dxhat,
-                       a.x, a.weight, a.rstd, mean, (const float*)c1, (const float*)c2, a.dx, pw, pb, a.R, a.C, tiles_c);
+    const dim3 grid((unsigned)(tiles_r * tiles_c));
+    if (a.dresidual)
+        hipLaunchKernelGGL((mx_norm_bwd_apply_kernel<XD, GD, VEC, true>), grid, dim3(kMxq2Threads), 0, s, a.dxhat, a.x, a.weight, a.rstd,
+                           mean, (const float*)c1, (const float*)c2, a.dx, pw, pb, a.R, a.C, tiles_c, a.dresidual);
+    else
+        hipLaunchKernelGGL((mx_norm_bwd_apply_kernel<XD, GD, VEC>), grid, dim3(kMxq2Threads), 0, s, a.dxhat, a.x, a.weight, a.rstd, mean,
+                           (const float*)c1, (const float*)c2, a.dx, pw, pb, a.R, a.C, tiles_c);
     if (cols)
         hipLaunchKernelGGL(mx_norm_bwd_fold_kernel, dim3((unsigned)((a.C + kMxnbFoldCols - 1) / kMxnbFoldCols), 2), dim3(kMxq2Threads),
                            0, s, (const float*)pw, (const float*)pb, a.dweight, a.dbias, tiles_r, a.C);
 }
 
-int norm_bwd_launch(const qs_mx_norm_bwd_args& a, const NormBwdPlan& plan, int route) {
+int norm_bwd_launch(const qs_mx_norm_bwd_res_args& a, const NormBwdPlan& plan, int route) {
     return with_dtype(a.xdt, [&](auto X) {
         return with_dtype(a.gdt, [&](auto G) {
             constexpr int XD = decltype(X)::value, GD = decltype(G)::value;
@@ -111,11 +132,28 @@ int qs_mx_norm_bwd_route(const qs_mx_norm_bwd_args* args) {
     qs_mx_norm_bwd_args a;
     NormBwdPlan plan;
     if (!take_args(args, &a)) return QS_ERR_ARG;
-    return norm_bwd_route(a, &plan);
+    return norm_bwd_route(with_no_residual(a), &plan);
 }
 
 int qs_mx_norm_bwd_v(const qs_mx_norm_bwd_args* args) {
     qs_mx_norm_bwd_args a;
+    NormBwdPlan plan;
+    if (!take_args(args, &a)) return QS_ERR_ARG;
+    const qs_mx_norm_bwd_res_args r = with_no_residual(a);
+    const int route = norm_bwd_route(r, &plan);
+    if (route <= 0) return route;
+    return norm_bwd_launch(r, plan, route);
+}
+
+int qs_mx_norm_bwd_res_route(const qs_mx_norm_bwd_res_args* args) {
+    qs_mx_norm_bwd_res_args a;
+    NormBwdPlan plan;
+    if (!take_args(args, &a)) return QS_ERR_ARG;
+    return norm_bwd_route(a, &plan);
+}
+
+int qs_mx_norm_bwd_res_v(const qs_mx_norm_bwd_res_args* args) {
+    qs_mx_norm_bwd_res_args a;
     NormBwdPlan plan;
     if (!take_args(args, &a)) return QS_ERR_ARG;
     const int route = norm_bwd_route(a, &plan);

@@ -16,6 +16,11 @@
 // The per-element arithmetic of the quantizer is qs_mx.h's; nothing of it is restated here.  No atomics, no workspace beyond rstd /
 // mean; a null col pair skips the LDS traffic, the barrier and phase 2 (kernel-uniform).  VEC = false is the same text with element
 // accesses, each predicated on its own index: any R, C >= 1, any element-aligned base.  Rounding is to nearest only.
+//
+//   mx_add_norm_stats_kernel   the add-norm quantizer's first launch ("MX add-norm quantizer"): mx_norm_stats_kernel whose load step
+//     takes a lane's 8 elements of x and of residual, adds them in float32, rounds once to residual's dtype, stores that h (one
+//     16-byte store for a two-byte h, two for float32, on the VEC route) and hands out the WIDENED ROUNDED values -- the sums, their
+//     order and the tail are the same text.  The second launch is mx_norm_apply_kernel on h, unchanged.
 #pragma once
 #include "qs_mx_quant2.h"
 
@@ -59,14 +64,16 @@ __device__ __forceinline__ float mxn_fold(float pa, float pb) {
     return __shfl(pa + pb, 0, 64);
 }
 
-// sum over the row of t_i = x_i (TERM 0), x_i * x_i (1) or (x_i - mu) * (x_i - mu) (2) in the header's order; every lane returns it
-template <int XDT, bool VEC, int TERM>
-__device__ __forceinline__ float mxn_row_sum(const void* __restrict__ x, int64_t base, int64_t C, int lane, float mu) {
+// sum over the row of t_i = v_i (TERM 0), v_i * v_i (1) or (v_i - mu) * (v_i - mu) (2) in the header's order, every lane returns it;
+// `load(c, v, in)` hands out the 8 elements [c, c + 8) of the row as float32 and whether each exists -- the only step in which the
+// statistics kernels below differ
+template <int TERM, class Load>
+__device__ __forceinline__ float mxn_row_sum(int64_t C, int lane, float mu, Load load) {
     float pa = 0.0f, pb = 0.0f;                                 // the partial sums 2 lane and 2 lane + 1
     for (int64_t c0 = 0; c0 < C; c0 += kMxnPass) {              // (wave-uniform trip count)
         float v[8];
         bool in[8];
-        mxn_load8<XDT, VEC>(x, base, c0 + lane * 8, C, v, in);
+        load(c0 + lane * 8, v, in);
         float t[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -82,19 +89,18 @@ __device__ __forceinline__ float mxn_row_sum(const void* __restrict__ x, int64_t
     return mxn_fold(pa, pb);
 }
 
-template <int XDT, bool VEC>
-__global__ __launch_bounds__(kMxq2Threads) void mx_norm_stats_kernel(const void* __restrict__ x, float* __restrict__ rstd,
-                                                                     float* __restrict__ mean, int64_t R, int64_t C, float eps) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * kMxnStatRows + (threadIdx.x >> 6);
-    if (r >= R) return;                                         // (wave-uniform; the kernel has no barrier)
+// rstd [r] and, with `mean` (kernel-uniform: layer mode), mean [r] of the row `first` hands out; layer mode walks the row twice
+// (mean, then the centred squares), the second time through `again`
+template <class First, class Again>
+__device__ __forceinline__ void mxn_row_stats(float* __restrict__ rstd, float* __restrict__ mean, int64_t r, int64_t C, int lane,
+                                              float eps, First first, Again again) {
     const float cf = (float)C;
     float mu = 0.0f, ms;
-    if (mean) {                                                 // (kernel-uniform: layer mode)
-        mu = mxn_row_sum<XDT, VEC, 0>(x, r * C, C, lane, 0.0f) / cf;
-        ms = mxn_row_sum<XDT, VEC, 2>(x, r * C, C, lane, mu) / cf;
+    if (mean) {
+        mu = mxn_row_sum<0>(C, lane, 0.0f, first) / cf;
+        ms = mxn_row_sum<2>(C, lane, mu, again) / cf;
     } else {
-        ms = mxn_row_sum<XDT, VEC, 1>(x, r * C, C, lane, 0.0f) / cf;
+        ms = mxn_row_sum<1>(C, lane, 0.0f, first) / cf;
     }
     float rs = 1.0f / sqrtf(ms + eps);                          // (both correctly rounded: the build's default for HIP)
     if (mx_abs_bits(ms) >= 0x7f800000u) rs = __uint_as_float(0x7fc00000u);      // a row that is not finite is NaN as a whole
@@ -102,6 +108,86 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_norm_stats_kernel(const void*
         rstd[r] = rs;
         if (mean) mean[r] = mu;
     }
+}
+
+template <int XDT, bool VEC>
+__global__ __launch_bounds__(kMxq2Threads) void mx_norm_stats_kernel(const void* __restrict__ x, float* __restrict__ rstd,
+                                                                     float* __restrict__ mean, int64_t R, int64_t C, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * kMxnStatRows + (threadIdx.x >> 6);
+    if (r >= R) return;                                         // (wave-uniform; the kernel has no barrier)
+    auto load = [&](int64_t c, float (&v)[8], bool (&in)[8]) { mxn_load8<XDT, VEC>(x, r * C, c, C, v, in); };
+    mxn_row_stats(rstd, mean, r, C, lane, eps, load, load);
+}
+
+// ---- the add-norm quantizer's statistics launch (include/qsparse_hip.h, "MX add-norm quantizer") ----------------------------------
+// 8 float32 values as the raw registers of a group of DT, each rounded once to nearest-even
+template <int DT>
+__device__ __forceinline__ Raw8<DT> mxn_pack8(const float (&v)[8]) {
+    Raw8<DT> r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if constexpr (DT == QS_F32) {
+            r.a[j] = __float_as_uint(v[j]);
+            r.b[j] = __float_as_uint(v[4 + j]);
+        } else if constexpr (DT == QS_BF16) {
+            r.a[j] = f32_to_bf16_bits(v[2 * j]) | (f32_to_bf16_bits(v[2 * j + 1]) << 16);
+        } else {
+            r.a[j] = f32_to_f16_bits(v[2 * j]) | (f32_to_f16_bits(v[2 * j + 1]) << 16);
+        }
+    }
+    return r;
+}
+
+// the 8 elements [c, c + 8) of the row at `base` of h = round(x + residual), rounded to RDT and widened again, as mxn_load8 hands out
+// x's; STORE: they are also written to `h` (plain stores: the quantizing launch reads them next).  What does not exist is +0.
+template <int XDT, int RDT, bool VEC, bool STORE>
+__device__ __forceinline__ void mxn_add_load8(const void* __restrict__ x, const void* __restrict__ res, void* __restrict__ h,
+                                              int64_t base, int64_t c, int64_t C, float (&v)[8], bool (&in)[8]) {
+    float a[8], b[8];
+    bool unused[8];
+    mxn_load8<XDT, VEC>(x, base, c, C, a, in);
+    mxn_load8<RDT, VEC>(res, base, c, C, b, unused);
+    if constexpr (VEC) {                                        // (C % 8 == 0: the 8 are inside or outside together)
+        float s[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s[j] = a[j] + b[j];
+        const Raw8<RDT> raw = mxn_pack8<RDT>(s);
+        unpack8<RDT>(raw, v);
+        if constexpr (STORE) {
+            if (c < C) {
+                const int64_t g = (base + c) >> 3;
+                if constexpr (RDT == QS_F32) {
+                    st16<false>((u32x4*)h + 2 * g, raw.a);
+                    st16<false>((u32x4*)h + 2 * g + 1, raw.b);
+                } else {
+                    st16<false>((u32x4*)h + g, raw.a);
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            v[j] = round_through<RDT>(a[j] + b[j]);
+            if constexpr (STORE) {
+                if (in[j]) store1<RDT>(h, base + c + j, v[j]);  // (v is a value of RDT: the store's conversion is exact)
+            }
+        }
+    }
+}
+
+// mx_norm_stats_kernel on h = round(x + residual), which it writes: the first walk over the row stores h, layer mode's second forms
+// it again from x and residual (served from the cache) and does not read `h` back
+template <int XDT, int RDT, bool VEC>
+__global__ __launch_bounds__(kMxq2Threads) void mx_add_norm_stats_kernel(const void* __restrict__ x, const void* __restrict__ res,
+                                                                         void* __restrict__ h, float* __restrict__ rstd,
+                                                                         float* __restrict__ mean, int64_t R, int64_t C, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * kMxnStatRows + (threadIdx.x >> 6);
+    if (r >= R) return;                                         // (wave-uniform; the kernel has no barrier)
+    auto first = [&](int64_t c, float (&v)[8], bool (&in)[8]) { mxn_add_load8<XDT, RDT, VEC, true>(x, res, h, r * C, c, C, v, in); };
+    auto again = [&](int64_t c, float (&v)[8], bool (&in)[8]) { mxn_add_load8<XDT, RDT, VEC, false>(x, res, h, r * C, c, C, v, in); };
+    mxn_row_stats(rstd, mean, r, C, lane, eps, first, again);
 }
 
 constexpr int kMxnV = 4;                                        // elements per lane and pass of the apply kernel

@@ -7,7 +7,8 @@
 //     mxn_add_quads / mxn_fold of qs_mx_norm.h, so their order is the forward's by construction.  One walk over the row.
 //   mx_norm_bwd_apply_kernel   the 128 x 64 tile of mx_norm_apply_kernel with its lane layout: a lane holds 4 consecutive elements of
 //     a row in 8 passes of 16 rows; the loads of a tile -- dxhat, x, and per row rstd, mean, c1, c2 -- are all issued before the first
-//     use.  It writes dx (rounded once to x's dtype) and keeps, per lane and column, the sums of dxhat xhat and of dxhat over its 8
+//     use.  It writes dx (rounded once to x's dtype; with RES, dresidual's tile is one more of those loads and is added to the float32
+//     value in front of that rounding) and keeps, per lane and column, the sums of dxhat xhat and of dxhat over its 8
 //     rows l, l + 16, .. l + 112 in ascending order: the header's 16 strided partial sums of a row tile.  Those meet in LDS
 //     ([2][16][64] float32, one 16-byte store per lane and array: the 16 lanes of a row write 64 consecutive dwords), where the
 //     first two waves fold them by the pairwise tree (lane c reads column c of 16 rows: consecutive banks) and store the tile's
@@ -87,14 +88,16 @@ __device__ __forceinline__ void mxnb_load4(const void* __restrict__ p, int64_t o
 
 constexpr int kMxnbParts = kMxnRpp;                             // 16 strided partial sums per column of a row tile
 
-// `dx`, `pw`, `pb` are each nullable (kernel-uniform): dx with c1 (and c2 in layer mode), pw / pb the partials of dweight / dbias
-template <int XDT, int GDT, bool VEC>
+// `dx`, `pw`, `pb` are each nullable (kernel-uniform): dx with c1 (and c2 in layer mode), pw / pb the partials of dweight / dbias.
+// RES: `dres` [R, C] of x's dtype, the residual stream's gradient, is loaded with the tile's other loads and added to the float32 dx
+// in front of its one rounding (it comes with dx); a template flag, so that the instantiations without it keep their registers
+template <int XDT, int GDT, bool VEC, bool RES = false>
 __global__ __launch_bounds__(kMxq2Threads) void mx_norm_bwd_apply_kernel(const void* __restrict__ dxhat, const void* __restrict__ x,
                                                                          const float* __restrict__ wt, const float* __restrict__ rstd,
                                                                          const float* __restrict__ mean, const float* __restrict__ c1,
                                                                          const float* __restrict__ c2, void* __restrict__ dx,
                                                                          float* __restrict__ pw, float* __restrict__ pb, int64_t R,
-                                                                         int64_t C, int tiles_c) {
+                                                                         int64_t C, int tiles_c, const void* __restrict__ dres = nullptr) {
     using xraw_t = typename Mxq2Raw<XDT>::type;
     using graw_t = typename Mxq2Raw<GDT>::type;
     __shared__ __attribute__((aligned(16))) float red[2 * kMxnbParts * kMxq2Cols];
@@ -108,6 +111,7 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_norm_bwd_apply_kernel(const v
 
     xraw_t xr[kMxnPasses][kMxnV];
     graw_t gr_[kMxnPasses][kMxnV];
+    xraw_t rr[RES ? kMxnPasses : 1][kMxnV];
     float rs[kMxnPasses], mu[kMxnPasses], k1[kMxnPasses], k2[kMxnPasses];
 #pragma unroll
     for (int p = 0; p < kMxnPasses; ++p) {
@@ -115,6 +119,7 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_norm_bwd_apply_kernel(const v
         const bool row_in = gr < R;
         mxnb_load4<XDT, VEC>(x, gr * C + gc, row_in, gc, C, xr[p]);
         mxnb_load4<GDT, VEC>(dxhat, gr * C + gc, row_in, gc, C, gr_[p]);
+        if constexpr (RES) mxnb_load4<XDT, VEC>(dres, gr * C + gc, row_in, gc, C, rr[p]);
         rs[p] = row_in ? rstd[gr] : 0.0f;
         mu[p] = (mean && row_in) ? mean[gr] : 0.0f;
         k1[p] = (dx && row_in) ? c1[gr] : 0.0f;
@@ -143,6 +148,7 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_norm_bwd_apply_kernel(const v
             float t = g - xh * k1[p];
             if (mean) t = t - k2[p];
             d[j] = rs[p] * t;
+            if constexpr (RES) d[j] = d[j] + mxq2_widen<XDT>(rr[p][j]);
             if (pw) aw[j] = aw[j] + (in ? gv * xh : 0.0f);      // (rows and columns outside the tensor are +0)
             if (pb) ab[j] = ab[j] + (in ? gv : 0.0f);
         }

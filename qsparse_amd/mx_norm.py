@@ -103,6 +103,16 @@ def _check_norm_args(x, weight, bias, norm, eps):
     return out
 
 
+def _norm_results(lead, rc, rs, cc, cs, rstd, mean, col_fmt, return_stats):
+    """the flat tuple ``mx_norm_quantize`` returns, from the results on ``[R, C]``: the row pair and the statistics shaped by ``lead``"""
+    out = (rc.reshape(lead + (rc.shape[-1],)), rs.reshape(lead + (rs.shape[-1],)))
+    if col_fmt is not None:
+        out += (cc, cs)
+    if return_stats:
+        out += (rstd.reshape(lead), None if mean is None else mean.reshape(lead))
+    return out
+
+
 def mx_norm_quantize(x: torch.Tensor, weight: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, *, norm: str = "rms",
                      eps: float = 1e-6, fmt: str = "mxfp8_e4m3", col_fmt: Optional[str] = None, return_stats: bool = False):
     """MX codes of ``y = norm(x) * weight (+ bias)`` over the last dimension of ``x [..., C]`` (float32 / bfloat16 / float16), the float
@@ -138,12 +148,47 @@ def mx_norm_quantize(x: torch.Tensor, weight: Optional[torch.Tensor] = None, bia
         y, rstd, mean = _mx_norm_y(x2, weight, bias, norm, float(eps))
         _, rc, rs = quantize_with_mx(y, fmt, -1, return_codes=True)
         cc, cs = mx_quantize_2way(y, None, col_fmt)[2:] if col_fmt is not None else (None, None)
-    out = (rc.reshape(lead + (C,)), rs.reshape(lead + (rs.shape[-1],)))
+    return _norm_results(lead, rc, rs, cc, cs, rstd, mean, col_fmt, return_stats)
+
+
+def _check_residual(x, residual):
+    """the second operand of the add-norm forms: a tensor of x's shape and device, of any of the three dtypes"""
+    if not isinstance(residual, torch.Tensor):
+        raise TypeError(f"residual must be a tensor, got {type(residual).__name__}")
+    _check_dtype("residual", residual.dtype)
+    if residual.shape != x.shape:
+        raise ValueError(f"residual has shape {tuple(residual.shape)}, expected x's {tuple(x.shape)}")
+    if residual.device != x.device:
+        raise ValueError(f"x is on {x.device} but residual on {residual.device}")
+
+
+def mx_add_norm_quantize(x: torch.Tensor, residual: torch.Tensor, weight: Optional[torch.Tensor] = None,
+                         bias: Optional[torch.Tensor] = None, *, norm: str = "rms", eps: float = 1e-6, fmt: str = "mxfp8_e4m3",
+                         col_fmt: Optional[str] = None, return_stats: bool = False):
+    """The residual add of a pre-norm block and ``mx_norm_quantize`` behind it: ``x [..., C]`` is the output of the previous branch,
+    ``residual`` (same shape and device; float32 / bfloat16 / float16, not necessarily ``x``'s dtype) the stream.  Returns
+
+        (h,) + mx_norm_quantize(h, weight, bias, norm=norm, eps=eps, fmt=fmt, col_fmt=col_fmt, return_stats=return_stats)
+
+    with ``h = (x.float() + residual.float()).to(residual.dtype)``, the new stream: ONE float32 addition, rounded once to the stream's
+    dtype.  The normalisation sees that rounded ``h``, so every output is bit for bit the composition's.  On the GPU it is the two
+    launches of ``qs_mx_add_norm_quant_v`` (no fallback): the statistics launch reads ``x`` and ``residual``, writes ``h`` and sums the
+    rounded values; the quantizing launch is ``mx_norm_quantize``'s on ``h`` -- the ``torch.add`` pass and one read of ``h`` less.  A
+    NaN or an Inf in either operand is kept in ``h`` and makes the row NaN as a whole.  ``h`` is a new tensor (the stream is not
+    updated in place).  Nothing here is differentiable (``mx_add_norm_linear`` is)."""
+    weight, bias = _check_norm_args(x, weight, bias, norm, eps)
+    _check_residual(x, residual)
+    _mx_format(fmt)
     if col_fmt is not None:
-        out += (cc, cs)
-    if return_stats:
-        out += (rstd.reshape(lead), None if mean is None else mean.reshape(lead))
-    return out
+        _mx_format(col_fmt)
+    if not x.is_cuda:
+        h = (x.detach().to(torch.float32) + residual.detach().to(torch.float32)).to(residual.dtype)
+        return (h,) + mx_norm_quantize(h, weight, bias, norm=norm, eps=eps, fmt=fmt, col_fmt=col_fmt, return_stats=return_stats)
+    C = x.shape[-1]
+    lead = tuple(x.shape[:-1])
+    h, rc, rs, cc, cs, rstd, mean = _hip.mx_add_norm_quant(x.detach().reshape(-1, C).contiguous(), residual.detach().reshape(-1, C).contiguous(),
+                                                           weight, bias, norm, eps, fmt, col_fmt)
+    return (h.reshape(x.shape),) + _norm_results(lead, rc, rs, cc, cs, rstd, mean, col_fmt, return_stats)
 
 
 def _eps_of(eps, x: torch.Tensor) -> float:
@@ -198,16 +243,23 @@ class _MXNorm(nn.Module):
     def extra_repr(self) -> str:
         return f"{self.normalized_shape}, eps={self.eps}, elementwise_affine={self.elementwise_affine}, out_fmt={self.out_fmt!r}"
 
-    def forward(self, x: torch.Tensor) -> MXActivation:
-        if isinstance(x, torch.Tensor) and torch.is_grad_enabled() and x.requires_grad:
-            raise RuntimeError(f"{type(self).__name__} is an inference layer: its input requires grad.  Train with MXTrainNormLinear or "
-                               "call it under torch.no_grad()")
+    def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None):
+        """the ``MXActivation`` of ``norm(x)``; with ``residual`` (the stream of a pre-norm block) ``(MXActivation of norm(h), h)``,
+        ``h = x + residual`` in ``residual``'s dtype -- ``mx_add_norm_quantize``; ``eps=None`` then follows ``h``'s dtype"""
+        for t in (x, residual):
+            if isinstance(t, torch.Tensor) and torch.is_grad_enabled() and t.requires_grad:
+                raise RuntimeError(f"{type(self).__name__} is an inference layer: its input requires grad.  Train with MXTrainNormLinear "
+                                   "or call it under torch.no_grad()")
         if isinstance(x, torch.Tensor) and x.dim() >= 1 and x.shape[-1] != self.normalized_shape[0]:
             raise ValueError(f"x {tuple(x.shape)} does not end in normalized_shape {self.normalized_shape}")
+        stream = x if residual is None else residual
+        kw = dict(norm=self.norm, eps=_eps_of(self.eps, stream) if isinstance(stream, torch.Tensor) else 0.0, fmt=self.out_fmt)
         with torch.no_grad():
-            codes, scales = mx_norm_quantize(x, self.weight, getattr(self, "bias", None), norm=self.norm,
-                                             eps=_eps_of(self.eps, x) if isinstance(x, torch.Tensor) else 0.0, fmt=self.out_fmt)
-        return MXActivation(codes, scales, self.out_fmt)
+            if residual is None:
+                codes, scales = mx_norm_quantize(x, self.weight, getattr(self, "bias", None), **kw)
+                return MXActivation(codes, scales, self.out_fmt)
+            h, codes, scales = mx_add_norm_quantize(x, residual, self.weight, getattr(self, "bias", None), **kw)
+        return MXActivation(codes, scales, self.out_fmt), h
 
 
 class MXRMSNorm(_MXNorm):
@@ -305,7 +357,7 @@ def _mx_norm_backward_f32(dxhat2: torch.Tensor, x2: torch.Tensor, rstd: torch.Te
 
 def mx_norm_backward(dxhat: torch.Tensor, x: torch.Tensor, rstd: torch.Tensor, mean: Optional[torch.Tensor] = None,
                      weight: Optional[torch.Tensor] = None, *, norm: str = "rms", need_dx: bool = True, need_dweight: bool = True,
-                     need_dbias: bool = True):
+                     need_dbias: bool = True, dresidual: Optional[torch.Tensor] = None):
     """The backward of the normalisation ``y = norm(x) * weight (+ bias)`` that ``mx_norm_quantize`` computes, over the last dimension
     of ``x [..., C]``: ``dxhat [..., C]`` (float32 / bfloat16 / float16) is the gradient with respect to ``y``, ``rstd`` / ``mean``
     (float32, shaped ``x.shape[:-1]``; ``mean`` in layer mode only) are ``mx_norm_quantize(..., return_stats=True)``'s, ``weight`` is
@@ -324,7 +376,12 @@ def mx_norm_backward(dxhat: torch.Tensor, x: torch.Tensor, rstd: torch.Tensor, m
     function of ``R`` alone).  So the bits are the same on the CPU and on the GPU, on every run (no atomics), for every dtype and
     whatever is asked for; they are NOT those of torch's own reductions.  NaN and Inf propagate: a row whose ``rstd`` is NaN has a NaN
     ``dx`` and makes ``dweight`` NaN.  GPU tensors take the HIP kernels of ``qs_mx_norm_bwd_v`` (no fallback), CPU tensors the torch
-    expression of the definition.  Nothing here is differentiable."""
+    expression of the definition.  Nothing here is differentiable.
+
+    ``dresidual`` (shape, dtype and device of ``x``; needs ``need_dx``) is the gradient that reaches the norm's input by the residual
+    stream of a pre-norm block: ``dx = (the float32 value above) + dresidual.float()``, one more float32 addition IN FRONT of the one
+    rounding to ``x``'s dtype -- not ``dx`` rounded and then added.  On the GPU it is loaded and added by the kernel that writes ``dx``
+    (``qs_mx_norm_bwd_res_v``), in place of a ``torch.add`` pass over ``[..., C]``.  ``dweight`` and ``dbias`` do not see it."""
     weight, _ = _check_norm_args(x, weight, None, norm, 0.0)
     if not isinstance(dxhat, torch.Tensor):
         raise TypeError(f"dxhat must be a tensor, got {type(dxhat).__name__}")
@@ -341,6 +398,16 @@ def mx_norm_backward(dxhat: torch.Tensor, x: torch.Tensor, rstd: torch.Tensor, m
             raise TypeError(f"{name} must be float32, got {t.dtype}")
         if t.shape != x.shape[:-1]:
             raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(x.shape[:-1])}: one value per row of x {tuple(x.shape)}")
+    if dresidual is not None:
+        if not isinstance(dresidual, torch.Tensor):
+            raise TypeError(f"dresidual must be a tensor, got {type(dresidual).__name__}")
+        if dresidual.dtype != x.dtype:
+            raise TypeError(f"dresidual must have x's dtype {x.dtype}, got {dresidual.dtype}")
+        if dresidual.shape != x.shape:
+            raise ValueError(f"dresidual has shape {tuple(dresidual.shape)}, expected x's {tuple(x.shape)}")
+        if not need_dx:
+            raise ValueError("dresidual is added to dx: it needs need_dx=True")
+        stats += (("dresidual", dresidual),)
     for name, t in (("dxhat", dxhat),) + stats:
         if t.device != x.device:
             raise ValueError(f"x is on {x.device} but {name} on {t.device}")
@@ -348,11 +415,14 @@ def mx_norm_backward(dxhat: torch.Tensor, x: torch.Tensor, rstd: torch.Tensor, m
     x2, d2 = x.detach().reshape(-1, C), dxhat.detach().reshape(-1, C)
     rstd1 = rstd.detach().reshape(-1)
     mean1 = mean.detach().reshape(-1) if norm == "layer" else None
+    r2 = None if dresidual is None else dresidual.detach().reshape(-1, C)
     if x.is_cuda:
         dx, dw, db = _hip.mx_norm_bwd(d2.contiguous(), x2.contiguous(), rstd1.contiguous(), None if mean1 is None else mean1.contiguous(),
-                                      weight, norm, need_dx, need_dweight, need_dbias)
+                                      weight, norm, need_dx, need_dweight, need_dbias, None if r2 is None else r2.contiguous())
     else:
         dx, dw, db = _mx_norm_backward_f32(d2, x2, rstd1, mean1, weight, need_dx, need_dweight, need_dbias)
+        if r2 is not None:
+            dx = dx + r2.to(torch.float32)
         dx = None if dx is None else dx.to(x.dtype)
     return None if dx is None else dx.reshape(x.shape), dw, db
 
@@ -365,6 +435,60 @@ def _check_norm_backward(norm_backward):
         raise ValueError(f"unknown norm_backward {norm_backward!r}: one of {MX_NORM_BACKWARDS}")
 
 
+def _norm_linear_forward(ctx, h, res, norm_weight, norm_bias, weight, bias, norm, x_fmt, w_fmt, grad_fmt, need_col, grad_rounding, seed,
+                         step, wgrad_split_k, norm_backward):
+    """what the forwards of ``mx_norm_linear`` and ``mx_add_norm_linear`` share behind the normalising quantizer: ``res`` is its result
+    (``return_stats=True``) for the norm's input ``h [R, K]``.  The product, and what the backward keeps; returns ``y [R, N]`` in
+    ``h.dtype``"""
+    x_row, x_rs = res[:2]
+    x_col, x_cs = res[2:4] if need_col else (None, None)
+    rstd, mean = res[-2:]
+    w_row, w_rs, _, _ = mx_quantize_2way(weight, w_fmt, None)
+    b32 = None if bias is None else bias.detach().to(torch.float32)
+    y = mx_matmul(x_row, x_rs, x_fmt, w_row, w_rs, w_fmt, b32, h.dtype)
+    ctx.save_for_backward(h, norm_weight, weight, rstd, mean, x_col, x_cs)
+    _save_train_ctx(ctx, (x_fmt, w_fmt, grad_fmt), (grad_rounding, seed, step), wgrad_split_k, h, bias)
+    ctx.norm, ctx.norm_backward = norm, norm_backward
+    ctx.norm_dtypes = tuple(None if t is None else t.dtype for t in (norm_weight, norm_bias))
+    return y
+
+
+def _norm_linear_backward(ctx, dy, needs, dh_in=None):
+    """the backward the two functions share.  ``needs``: (the norm's input, norm_weight, norm_bias, weight, bias); ``dh_in`` (None, or
+    shaped and typed as the norm's input ``h [R, K]``) is what reaches ``h`` from its other users and is added to the norm's float32
+    input gradient in front of its one rounding.  Returns (dh [R, K] in h's dtype, d norm_weight, d norm_bias, dW, db)"""
+    h, norm_weight, weight, rstd, mean, x_col, x_cs = ctx.saved_tensors
+    x_fmt, w_fmt, grad_fmt = ctx.fmts
+    need_dx, need_dnw, need_dnb, need_dw, need_db = needs
+    need_dxhat = need_dx or need_dnw or need_dnb
+    N, K = weight.shape
+    dy2 = dy.reshape(-1, N).contiguous()
+    h2 = h.reshape(-1, K)
+    dx = dnw = dnb = dw = db = None
+    if need_dxhat or need_dw:
+        g_row, g_rs, g_col, g_cs = _quantize_grad(ctx, lambda *sr: mx_quantize_2way(dy2, grad_fmt if need_dxhat else None,
+                                                                                     grad_fmt if need_dw else None, *sr))
+    if need_dxhat:
+        _, _, w_col, w_cs = mx_quantize_2way(weight, None, w_fmt)
+        dxhat = mx_matmul(g_row, g_rs, grad_fmt, w_col, w_cs, w_fmt, None, torch.float32)
+        dres = dh_in if need_dx else None
+        if ctx.norm_backward == "fused":
+            dx, dnw, dnb = mx_norm_backward(dxhat, h2, rstd, mean, norm_weight, norm=ctx.norm, need_dx=need_dx, need_dweight=need_dnw,
+                                            need_dbias=need_dnb, dresidual=dres)
+        else:
+            dx, dnw, dnb = _norm_backward(dxhat, _norm_xhat(h2, rstd, mean), rstd, norm_weight, ctx.norm, need_dx, need_dnw, need_dnb)
+            if dres is not None:
+                dx = dx + dres.to(torch.float32)
+        dx = None if dx is None else dx.to(ctx.x_dtype)
+        dnw = None if dnw is None else dnw.to(ctx.norm_dtypes[0])
+        dnb = None if dnb is None else dnb.to(ctx.norm_dtypes[1])
+    if need_dw:
+        dw = mx_matmul(g_col, g_cs, grad_fmt, x_col, x_cs, x_fmt, None, weight.dtype, split_k=ctx.wgrad_split_k)
+    if need_db:
+        db = dy2.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
+    return dx, dnw, dnb, dw, db
+
+
 class _MXNormLinearFunction(torch.autograd.Function):
     """y = Q(norm(x)) Q(W)^T + b; the linear part's three products as ``_MXLinearFunction``'s, the norm's backward in float32"""
 
@@ -375,48 +499,61 @@ class _MXNormLinearFunction(torch.autograd.Function):
         x2 = x.reshape(-1, K)
         res = mx_norm_quantize(x2, norm_weight, norm_bias, norm=norm, eps=eps, fmt=x_fmt, col_fmt=x_fmt if need_col else None,
                                return_stats=True)
-        x_row, x_rs = res[:2]
-        x_col, x_cs = res[2:4] if need_col else (None, None)
-        rstd, mean = res[-2:]
-        w_row, w_rs, _, _ = mx_quantize_2way(weight, w_fmt, None)
-        b32 = None if bias is None else bias.detach().to(torch.float32)
-        y = mx_matmul(x_row, x_rs, x_fmt, w_row, w_rs, w_fmt, b32, x.dtype)
-        ctx.save_for_backward(x, norm_weight, weight, rstd, mean, x_col, x_cs)
-        _save_train_ctx(ctx, (x_fmt, w_fmt, grad_fmt), (grad_rounding, seed, step), wgrad_split_k, x, bias)
-        ctx.norm, ctx.norm_backward = norm, norm_backward
-        ctx.norm_dtypes = tuple(None if t is None else t.dtype for t in (norm_weight, norm_bias))
+        y = _norm_linear_forward(ctx, x, res, norm_weight, norm_bias, weight, bias, norm, x_fmt, w_fmt, grad_fmt, need_col, grad_rounding,
+                                 seed, step, wgrad_split_k, norm_backward)
         return y.reshape(x.shape[:-1] + (N,))
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        x, norm_weight, weight, rstd, mean, x_col, x_cs = ctx.saved_tensors
-        x_fmt, w_fmt, grad_fmt = ctx.fmts
-        need_dx, need_dnw, need_dnb, need_dw, need_db = ctx.needs_input_grad[:5]
-        need_dxhat = need_dx or need_dnw or need_dnb
+        x = ctx.saved_tensors[0]
+        dx, dnw, dnb, dw, db = _norm_linear_backward(ctx, dy, ctx.needs_input_grad[:5])
+        return (None if dx is None else dx.reshape(x.shape), dnw, dnb, dw, db) + (None,) * 11
+
+
+class _MXAddNormLinearFunction(torch.autograd.Function):
+    """h = x + residual, y = Q(norm(h)) Q(W)^T + b: two outputs; the backward is ``_MXNormLinearFunction``'s with the gradient that
+    reaches ``h`` from its other users added to the norm's input gradient in front of its one rounding"""
+
+    @staticmethod
+    def forward(ctx, x, residual, norm_weight, norm_bias, weight, bias, norm, eps, x_fmt, w_fmt, grad_fmt, need_col, grad_rounding, seed,
+                step, wgrad_split_k, norm_backward):
         N, K = weight.shape
-        dy2 = dy.reshape(-1, N).contiguous()
-        dx = dnw = dnb = dw = db = None
-        if need_dxhat or need_dw:
-            g_row, g_rs, g_col, g_cs = _quantize_grad(ctx, lambda *sr: mx_quantize_2way(dy2, grad_fmt if need_dxhat else None,
-                                                                                         grad_fmt if need_dw else None, *sr))
-        if need_dxhat:
-            _, _, w_col, w_cs = mx_quantize_2way(weight, None, w_fmt)
-            dxhat = mx_matmul(g_row, g_rs, grad_fmt, w_col, w_cs, w_fmt, None, torch.float32)
-            if ctx.norm_backward == "fused":
-                dx, dnw, dnb = mx_norm_backward(dxhat, x.reshape(-1, K), rstd, mean, norm_weight, norm=ctx.norm, need_dx=need_dx,
-                                                need_dweight=need_dnw, need_dbias=need_dnb)
-            else:
-                xhat = _norm_xhat(x.reshape(-1, K), rstd, mean)
-                dx, dnw, dnb = _norm_backward(dxhat, xhat, rstd, norm_weight, ctx.norm, need_dx, need_dnw, need_dnb)
-            dx = None if dx is None else dx.to(ctx.x_dtype).reshape(x.shape)
-            dnw = None if dnw is None else dnw.to(ctx.norm_dtypes[0])
-            dnb = None if dnb is None else dnb.to(ctx.norm_dtypes[1])
-        if need_dw:
-            dw = mx_matmul(g_col, g_cs, grad_fmt, x_col, x_cs, x_fmt, None, weight.dtype, split_k=ctx.wgrad_split_k)
-        if need_db:
-            db = dy2.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
-        return (dx, dnw, dnb, dw, db) + (None,) * 11
+        res = mx_add_norm_quantize(x.reshape(-1, K), residual.reshape(-1, K), norm_weight, norm_bias, norm=norm, eps=eps, fmt=x_fmt,
+                                   col_fmt=x_fmt if need_col else None, return_stats=True)
+        h = res[0]
+        y = _norm_linear_forward(ctx, h, res[1:], norm_weight, norm_bias, weight, bias, norm, x_fmt, w_fmt, grad_fmt, need_col,
+                                 grad_rounding, seed, step, wgrad_split_k, norm_backward)
+        ctx.in_dtype, ctx.in_shape = x.dtype, x.shape
+        ctx.set_materialize_grads(False)        # (an h nobody else used has no incoming gradient: no tensor of zeros is added)
+        return y.reshape(x.shape[:-1] + (N,)), h.reshape(x.shape)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy, dh_in):
+        need_x, need_res = ctx.needs_input_grad[:2]
+        h, weight = ctx.saved_tensors[0], ctx.saved_tensors[2]
+        if dy is None:                          # (only h was used: the product's gradients are those of a zero dy)
+            dy = torch.zeros(ctx.in_shape[:-1] + (weight.shape[0],), dtype=h.dtype, device=h.device)
+        if dh_in is not None:
+            dh_in = dh_in.reshape(h.shape).contiguous()
+        dh, dnw, dnb, dw, db = _norm_linear_backward(ctx, dy, (need_x or need_res,) + tuple(ctx.needs_input_grad[2:6]), dh_in)
+        dh = None if dh is None else dh.reshape(ctx.in_shape)
+        dx = dh.to(ctx.in_dtype) if need_x else None
+        return (dx, dh if need_res else None, dnw, dnb, dw, db) + (None,) * 11
+
+
+def _check_norm_linear(x, norm_weight, norm_bias, weight, bias, norm, eps, fmts, grad_rounding, step, wgrad_split_k, norm_backward) -> bool:
+    """the operands and options of ``mx_norm_linear``; returns whether the forward has to produce the col pair"""
+    _check_train_entry(x, weight, bias, fmts, grad_rounding, step, wgrad_split_k)
+    if weight.dim() != 2:
+        raise ValueError(f"weight must be [N, K], got shape {tuple(weight.shape)}")
+    if x.dim() < 1 or x.shape[-1] != weight.shape[1]:
+        raise ValueError(f"x {tuple(x.shape)} and weight {tuple(weight.shape)} disagree on K (their last dimensions)")
+    _check_norm_args(x, norm_weight, norm_bias, norm, eps)
+    _check_bias_shape(bias, weight.shape[0])
+    _check_norm_backward(norm_backward)
+    return torch.is_grad_enabled() and weight.requires_grad
 
 
 def mx_norm_linear(x: torch.Tensor, norm_weight: Optional[torch.Tensor], norm_bias: Optional[torch.Tensor], weight: torch.Tensor,
@@ -444,15 +581,8 @@ def mx_norm_linear(x: torch.Tensor, norm_weight: Optional[torch.Tensor], norm_bi
     the CPU and the GPU.  The forward, ``dW`` and ``db`` do not depend on it.  Either way each result is cast once to its tensor's
     dtype.  Gradients nobody asks for are not computed; without grad the col pair is not produced.  ``grad_rounding``, ``seed``,
     ``step`` and ``wgrad_split_k`` are ``mx_linear``'s and touch the two forms of ``dy`` and the ``dW`` product alone."""
-    _check_train_entry(x, weight, bias, (x_fmt, w_fmt, grad_fmt), grad_rounding, step, wgrad_split_k)
-    if weight.dim() != 2:
-        raise ValueError(f"weight must be [N, K], got shape {tuple(weight.shape)}")
-    if x.dim() < 1 or x.shape[-1] != weight.shape[1]:
-        raise ValueError(f"x {tuple(x.shape)} and weight {tuple(weight.shape)} disagree on K (their last dimensions)")
-    _check_norm_args(x, norm_weight, norm_bias, norm, eps)
-    _check_bias_shape(bias, weight.shape[0])
-    _check_norm_backward(norm_backward)
-    need_col = torch.is_grad_enabled() and weight.requires_grad
+    need_col = _check_norm_linear(x, norm_weight, norm_bias, weight, bias, norm, eps, (x_fmt, w_fmt, grad_fmt), grad_rounding, step,
+                                  wgrad_split_k, norm_backward)
     return _MXNormLinearFunction.apply(x, norm_weight, norm_bias, weight, bias, norm, float(eps), x_fmt, w_fmt, grad_fmt, need_col,
                                        grad_rounding, seed, step, wgrad_split_k, norm_backward)
 
@@ -527,5 +657,68 @@ class MXTrainNormLinear(_MXTrainMixin, nn.Module):
                                             out_dtype))
 
 
-__all__ = ["mx_norm_quantize", "mx_norm_backward", "MXRMSNorm", "MXLayerNorm", "mx_norm_linear", "MXTrainNormLinear", "MX_NORMS",
-           "MX_NORM_BACKWARDS"]
+def mx_add_norm_linear(x: torch.Tensor, residual: torch.Tensor, norm_weight: Optional[torch.Tensor], norm_bias: Optional[torch.Tensor],
+                       weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, norm: str = "rms", eps: float = 1e-6,
+                       x_fmt: str = "mxfp8_e4m3", w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2", grad_rounding: str = "nearest",
+                       seed: int = 0, step: Optional[torch.Tensor] = None, wgrad_split_k="auto", norm_backward: str = "fused"):
+    """The head of a pre-norm block as one differentiable function: ``h = x + residual`` (``x`` the previous branch's output,
+    ``residual`` the stream, same shape; ``h`` in ``residual.dtype``, one float32 addition rounded once) and
+    ``y = mx_norm_linear(h, norm_weight, norm_bias, weight, bias, ...)``.  Returns ``(y, h)``: ``y [..., N]`` in ``h``'s dtype with
+    ``mx_norm_linear(h, ...)``'s bits, and the new stream for the next add.  The forward is ``mx_add_norm_quantize`` and ``mx_matmul``.
+    The backward receives ``dy`` and ``dh_in``, what reaches ``h`` from its other users (None when nobody used it):
+
+        dh = (mx_norm_linear's float32 input gradient) + dh_in        rounded once to h's dtype
+
+    With ``norm_backward="fused"`` (the default HERE: nothing pins this function to torch's reduction order) that is
+    ``mx_norm_backward(..., dresidual=dh_in)``, the addition in the kernel that writes ``dx``; with ``"torch"`` it is
+    ``_norm_backward`` in float32, ``+ dh_in.float()``, one cast.  The gradient of ``residual`` is ``dh``, that of ``x`` is ``dh``
+    too (``dh.to(x.dtype)`` where the dtypes differ: a torch op).  ``dW``, ``db``, ``d norm_weight`` and ``d norm_bias`` are exactly
+    ``mx_norm_linear``'s, as are the remaining options."""
+    need_col = _check_norm_linear(x, norm_weight, norm_bias, weight, bias, norm, eps, (x_fmt, w_fmt, grad_fmt), grad_rounding, step,
+                                  wgrad_split_k, norm_backward)
+    _check_residual(x, residual)
+    return _MXAddNormLinearFunction.apply(x, residual, norm_weight, norm_bias, weight, bias, norm, float(eps), x_fmt, w_fmt, grad_fmt,
+                                          need_col, grad_rounding, seed, step, wgrad_split_k, norm_backward)
+
+
+class MXAddNormLinear(nn.Module):
+    """What ``MXTrainAddNormLinear.to_inference()`` returns: ``forward(x, residual) -> (y, h)`` from an ``MXRMSNorm`` / ``MXLayerNorm``
+    called with the residual (``norm``) and the ``MXLinear`` behind it (``linear``)"""
+
+    def __init__(self, norm: nn.Module, linear: nn.Module):
+        super().__init__()
+        self.norm, self.linear = norm, linear
+
+    def forward(self, x: torch.Tensor, residual: torch.Tensor):
+        act, h = self.norm(x, residual)
+        return self.linear(act), h
+
+
+class MXTrainAddNormLinear(MXTrainNormLinear):
+    """``MXTrainNormLinear`` with the residual add of a pre-norm block in front: ``forward(x, residual) -> (y, h)`` is
+    ``mx_add_norm_linear``.  The constructor, ``from_float``, the parameters and the ``state_dict`` are ``MXTrainNormLinear``'s, except
+    that ``norm_backward`` defaults to ``"fused"``."""
+
+    def __init__(self, *args, norm_backward: str = "fused", **kw):
+        super().__init__(*args, norm_backward=norm_backward, **kw)
+
+    @classmethod
+    def from_float(cls, norm_module: nn.Module, linear: nn.Linear, *args, norm_backward: str = "fused", **kw):
+        return super().from_float(norm_module, linear, *args, norm_backward=norm_backward, **kw)
+
+    def forward(self, x: torch.Tensor, residual: torch.Tensor):
+        x, seed, step = self._mx_input(x)
+        return mx_add_norm_linear(x, residual, self.norm_weight, self.norm_bias, self.weight, self.bias, norm=self.norm,
+                                  eps=_eps_of(self.eps, residual), x_fmt=self.x_fmt, w_fmt=self.w_fmt, grad_fmt=self.grad_fmt,
+                                  grad_rounding=self.grad_rounding, seed=seed, step=step, wgrad_split_k=self.wgrad_split_k,
+                                  norm_backward=self.norm_backward)
+
+    def to_inference(self, out_dtype: torch.dtype = torch.float32) -> MXAddNormLinear:
+        """``MXAddNormLinear`` on the current parameters: the same ``(y, h)`` bits as this layer's forward for a stream of dtype
+        ``out_dtype``"""
+        head, linear = super().to_inference(out_dtype)
+        return MXAddNormLinear(head, linear)
+
+
+__all__ = ["mx_norm_quantize", "mx_add_norm_quantize", "mx_norm_backward", "MXRMSNorm", "MXLayerNorm", "mx_norm_linear",
+           "mx_add_norm_linear", "MXTrainNormLinear", "MXTrainAddNormLinear", "MXAddNormLinear", "MX_NORMS", "MX_NORM_BACKWARDS"]

@@ -1892,6 +1892,70 @@ int qs_mx_add_norm_quant_v(const qs_mx_add_norm_quant_args* args);
  * QS_ERR_* the call would return */
 int qs_mx_add_norm_quant_route(const qs_mx_add_norm_quant_args* args);
 
+/* ---- MX softmax quantizer (scale, additive mask and softmax in front of the one-way quantizer) ---------------------------------------
+ * Added without raising QS_ABI_VERSION (28), by the same rule as qs_mx_matmul_v above: symbols are only added.
+ *
+ * The MX operand of p = softmax(s * scale (+ mask)) over the last axis of s [G, T, S] (CONTIGUOUS, S innermost; float32, bf16 or fp16)
+ * without u, e or the float p in memory: the attention weights as the codes the P . V product multiplies.  It is NOT defined through a
+ * library's exp: the exponential below is part of the definition, so the bytes are the same on every device.
+ * Definition (normative), for the row s_0 .. s_(S-1) at (g, t).  All arithmetic is float32 on the widened inputs, every operation
+ * rounded on its own (no contraction, no FMA); `/` is the correctly rounded IEEE division.
+ *   L   = S, or with `causal` min(t + 1, S): the lower triangle aligned top-left; T != S is allowed
+ *   u_j = s_j * scale              without a mask
+ *       = (s_j * scale) + a_j      with one; a is the row (t) of mask [T, S] (mask_slices 1) or the row (g, t) of mask [G, T, S]
+ *       = -inf                     for L <= j < S, whatever s_j and a_j hold (they are not read)
+ *   m   = max_j u_j
+ *   t_j = u_j - m                                                                    (<= 0)
+ *   e_j = E(t_j)
+ *   Z   = sum(e) in the row-sum order of the MX normalising quantizer above with C = S: a function of S alone
+ *   p_j = e_j / Z
+ *   E(t):  n = rint(t * 1.44269504f)                            ties to even; 1.44269504f is 0x3fb8aa3b
+ *          r = (t - n * 0.693359375f) - n * (-2.12194440e-4f)   Cody-Waite: 0.693359375f is 0x3f318000 (n * it is exact),
+ *                                                               -2.12194440e-4f is 0xb95e8083
+ *          P = c7; P = P * r + c_k for k = 6 .. 0               Horner, the multiplication and the addition rounded separately;
+ *                                                               c_k = 1 / k! rounded to float32: c7 = 0x39500d01 (1 / 5040),
+ *                                                               0x3ab60b61, 0x3c088889, 0x3d2aaaab, 0x3e2aaaab, 0.5f, 1.0f, c0 = 1.0f
+ *          E = P * 2^n                                          exact: n in [-126, 0], and P > 1 at n = -126
+ *          E = +0 where t < -87.0f or t = -inf
+ *     E(0) = 1.0f exactly, so the row's maximum contributes exactly 1 and Z >= 1.  Against exp in float64 the largest relative error
+ *     found on [-87, 0] is below one float32 ulp (tests/test_mx_softmax.py asserts the bound).
+ *   Exceptional rows: a row whose u holds a NaN, or whose m is +inf, or whose m is -inf (every column masked; L = 0 cannot occur) is
+ *   NaN in EVERY element of p, the columns behind L included: scale byte 0xFF and zero codes in each of its blocks.  A -inf beside a
+ *   finite m is a plain zero.  Rows do not influence each other.
+ * Outputs: codes [G, T, S] / scales [G, T, ceil(S / 32)] are bit for bit the codes and scales qs_mx_quant_fwd_v writes for p with
+ * blocks along S in `format`, rounding to nearest-even -- stochastic rounding is not offered.  Nothing else is written; no atomics, no
+ * workspace; ONE launch on `stream`, nothing read by the host.  A wave owns a row; a row of S <= 1024 is read from memory once, a
+ * longer one three times (the bytes do not depend on which).  A causal row reads nothing at or behind L.
+ *   - Checks, in order: QS_ERR_ARG: a null or too short descriptor, s, codes or scales NULL, format no enum qs_mx_format, causal neither
+ *     0 nor 1, G, T or S negative, mask given with mask_slices neither 1 nor G; QS_ERR_DTYPE: sdt none of the three; QS_ERR_ALIGN: s not
+ *     aligned to its element or mask not to 4 bytes; QS_ERR_ARG: G * T * S beyond 64 bits or more rows than a launch takes.
+ *     `scale` is any float (a NaN makes every row NaN).  mask and causal may be given together (the definition covers it).
+ *   - G == 0, T == 0 or S == 0: nothing is enqueued, 0 is returned.
+ *   - QS_MX_SOFTMAX_ROUTE_VEC (16-byte loads of s and mask, 8-byte stores of codes): S % 32 == 0, s and mask 16-byte aligned and codes
+ *     8-byte aligned.  Anything else takes QS_MX_SOFTMAX_ROUTE_PLAIN, element accesses each predicated on its own index: any T, S >= 1,
+ *     any element-aligned base, same bits. */
+typedef struct qs_mx_softmax_quant_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_softmax_quant_args) as the caller compiled it */
+    int32_t format;                  /* enum qs_mx_format */
+    int32_t sdt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    int32_t causal;                  /* 0 or 1 */
+    float scale;
+    int32_t reserved0;               /* 0 */
+    const void* s;                   /* [G, T, S] row-major */
+    const float* mask;               /* [T, S] or [G, T, S], additive, nullable (none) */
+    int64_t mask_slices;             /* 1: mask is [T, S], shared by the slices; G: it is [G, T, S].  Read only with a mask */
+    uint8_t* codes;                  /* [G, T, S] */
+    uint8_t* scales;                 /* [G, T, ceil(S / 32)] */
+    int64_t G, T, S;
+    qs_stream_t stream;
+} qs_mx_softmax_quant_args;
+int qs_mx_softmax_quant_v(const qs_mx_softmax_quant_args* args);
+/* the kernel qs_mx_softmax_quant_v launches for these operands, nothing enqueued: QS_MX_SOFTMAX_ROUTE_*, 0 for an empty tensor, or the
+ * QS_ERR_* the call would return */
+#define QS_MX_SOFTMAX_ROUTE_VEC 1
+#define QS_MX_SOFTMAX_ROUTE_PLAIN 2
+int qs_mx_softmax_quant_route(const qs_mx_softmax_quant_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

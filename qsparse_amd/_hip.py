@@ -148,6 +148,8 @@ SIGNATURES = {
     "qs_mx_norm_bwd_res_route": (c_int, [_P]),
     "qs_mx_add_norm_quant_v": (c_int, [_P]),
     "qs_mx_add_norm_quant_route": (c_int, [_P]),
+    "qs_mx_softmax_quant_v": (c_int, [_P]),
+    "qs_mx_softmax_quant_route": (c_int, [_P]),
 }
 
 
@@ -373,6 +375,13 @@ class MxNormBwdResArgs(ctypes.Structure):
 class MxAddNormQuantArgs(ctypes.Structure):
     """`qs_mx_add_norm_quant_args` of include/qsparse_hip.h"""
     _fields_ = MxNormQuantArgs._fields_ + [("residual", c_void_p), ("h", c_void_p), ("rdt", c_int32), ("reserved0", c_int32)]
+
+
+class MxSoftmaxQuantArgs(ctypes.Structure):
+    """`qs_mx_softmax_quant_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("format", c_int32), ("sdt", c_int32), ("causal", c_int32), ("scale", c_float),
+                ("reserved0", c_int32), ("s", c_void_p), ("mask", c_void_p), ("mask_slices", c_int64), ("codes", c_void_p),
+                ("scales", c_void_p), ("G", c_int64), ("T", c_int64), ("S", c_int64), ("stream", c_void_p)]
 
 
 class MxGroupedWgradArgs(ctypes.Structure):
@@ -1662,6 +1671,31 @@ def mx_add_norm_quant(x: torch.Tensor, residual: torch.Tensor, weight: Optional[
     mx_add_norm_last_route = None
     res, mx_add_norm_last_route = _mx_norm_quant_run("mx_add_norm_quant", a, x, weight, bias, norm, eps, row_fmt, col_fmt, (residual, h))
     return (h,) + res
+
+
+MX_SOFTMAX_ROUTE_VEC, MX_SOFTMAX_ROUTE_PLAIN = 1, 2
+mx_softmax_last_route = None     # the QS_MX_SOFTMAX_ROUTE_* of the last `mx_softmax_quant` launch (None: an empty tensor)
+
+
+def mx_softmax_quant(s: torch.Tensor, mask: Optional[torch.Tensor], scale: float, causal: bool, fmt: str):
+    """scale, mask and softmax in front of the MX quantizer (qs_mx_softmax_quant_v) on a contiguous GPU tensor `s` [G, T, S] and a
+    contiguous float32 additive `mask` [T, S] or [G, T, S] (or None): returns (codes [G, T, S], scales [G, T, ceil(S / 32)]), uint8,
+    from ONE launch."""
+    global mx_softmax_last_route
+    load()
+    G, T, S = s.shape
+    codes = torch.empty((G, T, S), dtype=torch.uint8, device=s.device)
+    scales = torch.empty((G, T, (S + MX_BLOCK - 1) // MX_BLOCK), dtype=torch.uint8, device=s.device)
+    mx_softmax_last_route = None
+    if G and T and S:
+        a = MxSoftmaxQuantArgs()
+        a.format, a.sdt, a.causal, a.scale = MX_FORMATS.index(fmt), dt(s), int(bool(causal)), float(scale)
+        a.s, a.mask, a.codes, a.scales = _ptr(s), _ptr(mask), _ptr(codes), _ptr(scales)
+        a.mask_slices = 1 if mask is None or mask.dim() == 2 else G
+        a.G, a.T, a.S = G, T, S
+        a.stream = _stream(s)
+        mx_softmax_last_route = _mx_run("mx_softmax_quant", a, (s, mask, codes, scales))
+    return codes, scales
 
 
 MX_NORM_BWD_ROUTE_VEC, MX_NORM_BWD_ROUTE_PLAIN = 1, 2

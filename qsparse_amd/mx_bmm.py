@@ -90,6 +90,9 @@ def mx_bmm(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: t
     return y if out_fmt is None else _codes_out_cpu(y, out_fmt, act)
 
 
+MX_ATTENTION_SOFTMAX = ("torch", "fused")
+
+
 def _attention_mask(attn_mask, is_causal: bool, T: int, S: int, device):
     """the additive float32 mask of `mx_attention`, or None"""
     if attn_mask is not None and is_causal:
@@ -113,7 +116,7 @@ def _attention_mask(attn_mask, is_causal: bool, T: int, S: int, device):
 
 def mx_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: Optional[torch.Tensor] = None, is_causal: bool = False,
                  scale: Optional[float] = None, *, qk_fmt: str = "mxfp8_e4m3", p_fmt: str = "mxfp8_e4m3", v_fmt: str = "mxfp8_e4m3",
-                 out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+                 out_dtype: torch.dtype = torch.float32, softmax: str = "torch") -> torch.Tensor:
     """Inference-side scaled dot-product attention whose two matrix products run on MX codes.  ``q [..., T, d]``, ``k [..., S, d]``
     and ``v [..., S, dv]`` are float32 / bfloat16 / float16 tensors with equal leading dimensions (at least one); the result is
     ``[..., T, dv]`` in ``out_dtype``.  It is DEFINED as this composition of public calls, and is bit for bit that composition on
@@ -131,6 +134,12 @@ def mx_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: O
            is one layout pass over ``v``: the product wants K (here ``S``) innermost and takes no strided operand
         8. ``mx_bmm(p, v^T)`` to ``out_dtype``
 
+    ``softmax="fused"`` (keyword; the default ``"torch"`` is the composition above, bit for bit as it always was) replaces steps 3 - 6
+    by ONE call, ``mx_softmax_quantize(s, attn_mask, scale=scale, is_causal=is_causal, fmt=p_fmt)``: on the GPU one launch that reads
+    ``s`` once and writes only ``p``'s codes, with ``is_causal`` handed down so that no ``[T, S]`` mask tensor is built.  With
+    ``"fused"`` the result is DEFINED as that composition, bit for bit on either device; its ``p`` comes from ``mx_softmax_quantize``'s
+    own written-out exponential, not from ``torch.softmax``, so the two settings usually agree but are not each other's definition.
+
     No dropout and no gradient: a tensor that requires grad while gradients are enabled is refused -- the training side of attention
     is not offered.  A row of the mask that admits no key gives NaN, as softmax does."""
     for name, t in (("q", q), ("k", k), ("v", v)):
@@ -147,6 +156,8 @@ def mx_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: O
     for fmt in (qk_fmt, p_fmt, v_fmt):
         _mx_format(fmt)
     _check_dtype("out_dtype", out_dtype)
+    if softmax not in MX_ATTENTION_SOFTMAX:
+        raise ValueError(f"unknown softmax {softmax!r}: one of {MX_ATTENTION_SOFTMAX}")
     lead, (T, d), S = tuple(q.shape[:-2]), q.shape[-2:], k.shape[-2]
     if tuple(k.shape[:-2]) != lead or tuple(v.shape[:-2]) != lead:
         raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)} and v {tuple(v.shape)} disagree on their leading dimensions (nothing "
@@ -157,14 +168,22 @@ def mx_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: O
         raise ValueError(f"k {tuple(k.shape)} and v {tuple(v.shape)} disagree on S (their second-to-last dimensions)")
     if d < 1 or S < 1:
         raise ValueError("mx_attention needs d >= 1 and S >= 1")
+    fused = softmax == "fused"
+    if fused and attn_mask is not None and is_causal:
+        raise ValueError("give attn_mask or is_causal, not both")
     with torch.no_grad():
-        mask = _attention_mask(attn_mask, is_causal, T, S, q.device)
+        mask = None if fused else _attention_mask(attn_mask, is_causal, T, S, q.device)
         _, qc, qsc = quantize_with_mx(q.detach(), qk_fmt, -1, return_codes=True)
         _, kc, ksc = quantize_with_mx(k.detach(), qk_fmt, -1, return_codes=True)
-        s = mx_bmm(qc, qsc, qk_fmt, kc, ksc, qk_fmt) * (d ** -0.5 if scale is None else scale)
-        if mask is not None:
-            s = s + mask
-        _, pc, psc = quantize_with_mx(torch.softmax(s, -1), p_fmt, -1, return_codes=True)
+        s = mx_bmm(qc, qsc, qk_fmt, kc, ksc, qk_fmt)
+        if fused:
+            from qsparse_amd.mx_softmax import mx_softmax_quantize     # (it takes `_attention_mask` from this module)
+            pc, psc = mx_softmax_quantize(s, attn_mask, scale=d ** -0.5 if scale is None else scale, is_causal=is_causal, fmt=p_fmt)
+        else:
+            s = s * (d ** -0.5 if scale is None else scale)
+            if mask is not None:
+                s = s + mask
+            _, pc, psc = quantize_with_mx(torch.softmax(s, -1), p_fmt, -1, return_codes=True)
         _, vc, vsc = quantize_with_mx(v.detach().transpose(-1, -2).contiguous(), v_fmt, -1, return_codes=True)
         return mx_bmm(pc, psc, p_fmt, vc, vsc, v_fmt, None, out_dtype)
 
@@ -175,10 +194,11 @@ class MXMultiheadAttention(nn.Module):
     takes ``x`` ``[T, B, E]`` (``[B, T, E]`` with ``batch_first``) and returns ``(output, None)``, the pair ``nn.MultiheadAttention``
     returns without its weights; the mask goes to ``mx_attention`` as it is (``[T, T]`` or anything that broadcasts to ``[B, h, T,
     T]``).  It is a thin composition -- ``in_proj(x)``, split, ``mx_attention``, merge, ``out_proj`` -- and equals it bit for bit.
-    ``need_weights`` and ``key_padding_mask`` are not offered."""
+    ``need_weights`` and ``key_padding_mask`` are not offered.  ``softmax`` (``"torch"`` or ``"fused"``) is ``mx_attention``'s keyword,
+    stored and passed on."""
 
     def __init__(self, in_proj: MXLinear, out_proj: MXLinear, num_heads: int, batch_first: bool = False, *, qk_fmt: str = "mxfp8_e4m3",
-                 p_fmt: str = "mxfp8_e4m3", v_fmt: str = "mxfp8_e4m3"):
+                 p_fmt: str = "mxfp8_e4m3", v_fmt: str = "mxfp8_e4m3", softmax: str = "torch"):
         super().__init__()
         if not isinstance(in_proj, MXLinear) or not isinstance(out_proj, MXLinear):
             raise TypeError("in_proj and out_proj must be MXLinear layers")
@@ -192,6 +212,9 @@ class MXMultiheadAttention(nn.Module):
             raise ValueError(f"num_heads must be an int >= 1 that divides embed_dim {E}, got {num_heads!r}")
         for fmt in (qk_fmt, p_fmt, v_fmt):
             _mx_format(fmt)
+        if softmax not in MX_ATTENTION_SOFTMAX:
+            raise ValueError(f"unknown softmax {softmax!r}: one of {MX_ATTENTION_SOFTMAX}")
+        self.softmax = softmax
         self.in_proj, self.out_proj = in_proj, out_proj
         self.embed_dim, self.num_heads, self.batch_first = E, num_heads, bool(batch_first)
         self.qk_fmt, self.p_fmt, self.v_fmt = qk_fmt, p_fmt, v_fmt
@@ -202,7 +225,7 @@ class MXMultiheadAttention(nn.Module):
 
     @classmethod
     def from_float(cls, mha: nn.MultiheadAttention, act_fmt: str = "mxfp8_e4m3", w_fmt: str = "mxfp8_e4m3", *, qk_fmt: str = "mxfp8_e4m3",
-                   p_fmt: str = "mxfp8_e4m3", v_fmt: str = "mxfp8_e4m3"):
+                   p_fmt: str = "mxfp8_e4m3", v_fmt: str = "mxfp8_e4m3", softmax: str = "torch"):
         """from a float self-attention module: both weights quantized with ``quantize_with_mx(w, w_fmt, 1, return_codes=True)``"""
         if not isinstance(mha, nn.MultiheadAttention):
             raise TypeError(f"MXMultiheadAttention.from_float needs an nn.MultiheadAttention, got {type(mha).__name__}")
@@ -217,7 +240,7 @@ class MXMultiheadAttention(nn.Module):
             for w, b in ((mha.in_proj_weight, mha.in_proj_bias), (mha.out_proj.weight, mha.out_proj.bias)):
                 _, codes, scales = quantize_with_mx(w.detach(), w_fmt, 1, return_codes=True)
                 layers.append(MXLinear(codes, scales, w_fmt, None if b is None else b.detach(), act_fmt))
-        return cls(*layers, mha.num_heads, mha.batch_first, qk_fmt=qk_fmt, p_fmt=p_fmt, v_fmt=v_fmt)
+        return cls(*layers, mha.num_heads, mha.batch_first, qk_fmt=qk_fmt, p_fmt=p_fmt, v_fmt=v_fmt, softmax=softmax)
 
     def forward(self, x: torch.Tensor, attn_mask: Optional[torch.Tensor] = None, is_causal: bool = False, *, need_weights: bool = False,
                 key_padding_mask: Optional[torch.Tensor] = None):
@@ -231,7 +254,7 @@ class MXMultiheadAttention(nn.Module):
         xb = x if self.batch_first else x.transpose(0, 1)
         B, T = xb.shape[:2]
         q, k, v = (t.reshape(B, T, h, E // h).transpose(1, 2) for t in self.in_proj(xb).chunk(3, -1))
-        o = mx_attention(q, k, v, attn_mask, is_causal, qk_fmt=self.qk_fmt, p_fmt=self.p_fmt, v_fmt=self.v_fmt)
+        o = mx_attention(q, k, v, attn_mask, is_causal, qk_fmt=self.qk_fmt, p_fmt=self.p_fmt, v_fmt=self.v_fmt, softmax=self.softmax)
         y = self.out_proj(o.transpose(1, 2).reshape(B, T, E))
         return (y if self.batch_first else y.transpose(0, 1)), None
 

@@ -1956,6 +1956,113 @@ int qs_mx_softmax_quant_v(const qs_mx_softmax_quant_args* args);
 #define QS_MX_SOFTMAX_ROUTE_PLAIN 2
 int qs_mx_softmax_quant_route(const qs_mx_softmax_quant_args* args);
 
+/* ---- MX two-way softmax quantizer (the MX softmax quantizer with p's transposed pair and the row statistics) ----------------------------
+ * Added without raising QS_ABI_VERSION (28): symbols are only added; qs_mx_softmax_quant_args and qs_mx_softmax_quant_v above are
+ * unchanged.
+ *
+ * The training side's forward.  p [G, T, S] is the p of the MX softmax quantizer above, to the bit (same u, m, E, Z, same exceptional
+ * rows).  Outputs:
+ *   row_codes [G, T, S] / row_scales [G, T, ceil(S / 32)]   bit for bit what qs_mx_softmax_quant_v writes in `row_format`
+ *   col_codes [G, S, T] / col_scales [G, S, ceil(T / 32)]   (col_format != -1) slice by slice the codes and scales of p^T with blocks
+ *                                                           along T in `col_format`: the operand of dV = P^T dO.  A row of p that is
+ *                                                           NaN as a whole puts 0xFF into every column block it touches.
+ *   m [G T], Z [G T]                                        the row maximum (m + 0.0f: a zero maximum of either sign is +0) and the
+ *                                                           row sum of the definition, float32; both are the
+ *                                                           quiet NaN 0x7fc00000 for a row that is NaN as a whole (its u holds a NaN,
+ *                                                           m = +inf, or nothing is admitted).  Always written: the second launch reads
+ *                                                           them.
+ * Rounding is to nearest-even.  Two launches on `stream`, nothing read by the host, no atomics, no workspace beyond m and Z: a
+ * statistics launch (one wave per row) that writes m and Z, then the tile of the MX two-way quantizer (128 rows of T x 64 columns of
+ * S) per slice with p_j = E(u_j - m) / Z as its widen step -- E is evaluated in both launches, to the same bits.  A causal row reads
+ * nothing at or behind L.  Without a col pair the second launch skips the LDS staging, the barrier and its second phase.
+ *   - Checks, in order: QS_ERR_ARG: a null or too short descriptor, s, row_codes, row_scales, m or Z NULL, row_format no enum
+ *     qs_mx_format, col_format neither -1 nor one, a NULL pointer of a given col pair, causal neither 0 nor 1, G, T or S negative, mask
+ *     given with mask_slices neither 1 nor G; QS_ERR_DTYPE: sdt none of the three; QS_ERR_ALIGN: s not aligned to its element, or mask,
+ *     m or Z not to 4 bytes; QS_ERR_ARG: G * T * S beyond 64 bits, more rows or more tiles than a launch takes.
+ *   - G == 0, T == 0 or S == 0: nothing is enqueued, 0 is returned.
+ *   - The route rule is qs_mx_softmax_quant_v's: QS_MX_SOFTMAX_ROUTE_VEC (16-byte loads of s and mask, 4-byte stores of row codes) with
+ *     S % 32 == 0, s and mask 16-byte aligned and row_codes 8-byte aligned; the col pair then leaves in 16-byte stores where
+ *     T % 16 == 0 and col_codes is 16-byte aligned, else in byte stores.  Anything else takes QS_MX_SOFTMAX_ROUTE_PLAIN, element
+ *     accesses each predicated on its own index: any T, S >= 1, any element-aligned base, same bits. */
+typedef struct qs_mx_softmax_quant2_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_softmax_quant2_args) as the caller compiled it */
+    int32_t row_format, col_format;  /* enum qs_mx_format, may differ; col_format -1: the col pair is skipped */
+    int32_t sdt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    int32_t causal;                  /* 0 or 1 */
+    float scale;
+    const void* s;                   /* [G, T, S] row-major */
+    const float* mask;               /* [T, S] or [G, T, S], additive, nullable (none) */
+    int64_t mask_slices;             /* 1: mask is [T, S], shared by the slices; G: it is [G, T, S].  Read only with a mask */
+    uint8_t* row_codes;              /* [G, T, S] */
+    uint8_t* row_scales;             /* [G, T, ceil(S / 32)] */
+    uint8_t* col_codes;              /* [G, S, T] */
+    uint8_t* col_scales;             /* [G, S, ceil(T / 32)] */
+    float* m;                        /* [G T]: written */
+    float* Z;                        /* [G T]: written */
+    int64_t G, T, S;
+    qs_stream_t stream;
+} qs_mx_softmax_quant2_args;
+int qs_mx_softmax_quant2_v(const qs_mx_softmax_quant2_args* args);
+/* the kernels qs_mx_softmax_quant2_v launches for these operands, nothing enqueued: QS_MX_SOFTMAX_ROUTE_*, 0 for an empty tensor, or
+ * the QS_ERR_* the call would return */
+int qs_mx_softmax_quant2_route(const qs_mx_softmax_quant2_args* args);
+
+/* ---- MX softmax backward quantizer (the softmax backward in front of the two-way quantizer) ----------------------------------------------
+ * Added without raising QS_ABI_VERSION (28): symbols are only added.
+ *
+ * From dp [G, T, S] (the gradient with respect to p; float32, bf16 or fp16, CONTIGUOUS), the forward's s, mask, scale and causal, and
+ * the m and Z qs_mx_softmax_quant2_v wrote: the two MX pairs of ds, the gradient with respect to s.  Definition (normative), for the
+ * row (g, t); all arithmetic is float32 on the widened inputs, every operation rounded on its own (no contraction, no FMA):
+ *   u_j  as in the MX softmax quantizer;   p_j = E(u_j - m) / Z      the forward's p, to the bit (+0 for L <= j < S)
+ *   D    = sum_j (p_j * dp_j)              in the row-sum order of the MX normalising quantizer with C = S: a function of S alone.
+ *                                          dp_j is read for every j < S, behind L too
+ *   ds_j = (p_j * (dp_j - D)) * scale
+ *   a row whose m is NaN is NaN in every element of p, hence of ds.  A NaN or an Inf in dp makes D, hence its row of ds, NaN.
+ * Outputs: row_codes [G, T, S] / row_scales and col_codes [G, S, T] / col_scales are bit for bit what qs_mx_quant2_batched_v writes
+ * for the float32 ds [G, T, S] with the same formats, rounding, seed, step and index_base -- the same Philox words: stream 0 at index
+ * index_base + (g T + t) S + j for the row pair, stream 1 at index_base + (g S + j) T + t for the col pair, `step` read on the device.
+ * A pair whose format is -1 is skipped.  Two launches on `stream`, nothing read by the host, no atomics: a row launch (one wave per row)
+ * that forms p again from s, m and Z and writes D [G T] -- the caller's float32 workspace --, then the tile of the two-way quantizer
+ * per slice with the ds expression as its widen step.  Neither p nor ds is ever written.
+ *   - Checks, in order: QS_ERR_ARG: a null or too short descriptor, rounding no QS_MX_ROUND_*, step not 8-byte aligned, index_base no
+ *     multiple of 4, dp, s, m, Z or D NULL, both formats -1, a format neither -1 nor an enum qs_mx_format, a NULL pointer of a given
+ *     pair, causal neither 0 nor 1, G, T or S negative, mask given with mask_slices neither 1 nor G; QS_ERR_DTYPE: sdt or ddt none of
+ *     the three; QS_ERR_ALIGN: s or dp not aligned to its element, or mask, m, Z or D not to 4 bytes; QS_ERR_ARG: G * T * S beyond 64
+ *     bits, more rows or more tiles than a launch takes.
+ *   - G == 0, T == 0 or S == 0: nothing is enqueued, 0 is returned.
+ *   - QS_MX_SOFTMAX_ROUTE_VEC: S % 32 == 0, s, dp and mask 16-byte aligned and, with a col pair, T % 16 == 0 and col_codes 16-byte
+ *     aligned (row codes leave in 4-byte stores where row_codes is 4-byte aligned).  Anything else takes QS_MX_SOFTMAX_ROUTE_PLAIN:
+ *     any T, S >= 1, any element-aligned base, same bits. */
+typedef struct qs_mx_softmax_bwd_quant_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_softmax_bwd_quant_args) as the caller compiled it */
+    int32_t row_format, col_format;  /* enum qs_mx_format, may differ; -1: that pair is skipped */
+    int32_t sdt;                     /* dtype of s: QS_F32, QS_BF16 or QS_F16 */
+    int32_t ddt;                     /* dtype of dp, likewise */
+    int32_t causal;                  /* 0 or 1 */
+    float scale;
+    int32_t rounding;                /* QS_MX_ROUND_* */
+    const void* dp;                  /* [G, T, S] row-major */
+    const void* s;                   /* [G, T, S] row-major */
+    const float* mask;               /* [T, S] or [G, T, S], additive, nullable (none) */
+    int64_t mask_slices;             /* 1 or G, as above */
+    const float* m;                  /* [G T] */
+    const float* Z;                  /* [G T] */
+    float* D;                        /* [G T]: workspace, written */
+    uint8_t* row_codes;              /* [G, T, S] */
+    uint8_t* row_scales;             /* [G, T, ceil(S / 32)] */
+    uint8_t* col_codes;              /* [G, S, T] */
+    uint8_t* col_scales;             /* [G, S, ceil(T / 32)] */
+    int64_t G, T, S;
+    qs_stream_t stream;
+    uint64_t seed;
+    const int64_t* step;             /* device pointer, nullable (0) */
+    uint64_t index_base;             /* a multiple of 4 */
+} qs_mx_softmax_bwd_quant_args;
+int qs_mx_softmax_bwd_quant_v(const qs_mx_softmax_bwd_quant_args* args);
+/* the kernels qs_mx_softmax_bwd_quant_v launches for these operands, nothing enqueued: QS_MX_SOFTMAX_ROUTE_*, 0 for an empty tensor,
+ * or the QS_ERR_* the call would return */
+int qs_mx_softmax_bwd_quant_route(const qs_mx_softmax_bwd_quant_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

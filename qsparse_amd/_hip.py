@@ -150,6 +150,10 @@ SIGNATURES = {
     "qs_mx_add_norm_quant_route": (c_int, [_P]),
     "qs_mx_softmax_quant_v": (c_int, [_P]),
     "qs_mx_softmax_quant_route": (c_int, [_P]),
+    "qs_mx_softmax_quant2_v": (c_int, [_P]),
+    "qs_mx_softmax_quant2_route": (c_int, [_P]),
+    "qs_mx_softmax_bwd_quant_v": (c_int, [_P]),
+    "qs_mx_softmax_bwd_quant_route": (c_int, [_P]),
 }
 
 
@@ -382,6 +386,23 @@ class MxSoftmaxQuantArgs(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("format", c_int32), ("sdt", c_int32), ("causal", c_int32), ("scale", c_float),
                 ("reserved0", c_int32), ("s", c_void_p), ("mask", c_void_p), ("mask_slices", c_int64), ("codes", c_void_p),
                 ("scales", c_void_p), ("G", c_int64), ("T", c_int64), ("S", c_int64), ("stream", c_void_p)]
+
+
+class MxSoftmaxQuant2Args(ctypes.Structure):
+    """`qs_mx_softmax_quant2_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("row_format", c_int32), ("col_format", c_int32), ("sdt", c_int32), ("causal", c_int32),
+                ("scale", c_float), ("s", c_void_p), ("mask", c_void_p), ("mask_slices", c_int64), ("row_codes", c_void_p),
+                ("row_scales", c_void_p), ("col_codes", c_void_p), ("col_scales", c_void_p), ("m", c_void_p), ("Z", c_void_p),
+                ("G", c_int64), ("T", c_int64), ("S", c_int64), ("stream", c_void_p)]
+
+
+class MxSoftmaxBwdQuantArgs(ctypes.Structure):
+    """`qs_mx_softmax_bwd_quant_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("row_format", c_int32), ("col_format", c_int32), ("sdt", c_int32), ("ddt", c_int32),
+                ("causal", c_int32), ("scale", c_float), ("rounding", c_int32), ("dp", c_void_p), ("s", c_void_p), ("mask", c_void_p),
+                ("mask_slices", c_int64), ("m", c_void_p), ("Z", c_void_p), ("D", c_void_p), ("row_codes", c_void_p),
+                ("row_scales", c_void_p), ("col_codes", c_void_p), ("col_scales", c_void_p), ("G", c_int64), ("T", c_int64), ("S", c_int64),
+                ("stream", c_void_p), ("seed", ctypes.c_uint64), ("step", c_void_p), ("index_base", ctypes.c_uint64)]
 
 
 class MxGroupedWgradArgs(ctypes.Structure):
@@ -1696,6 +1717,64 @@ def mx_softmax_quant(s: torch.Tensor, mask: Optional[torch.Tensor], scale: float
         a.stream = _stream(s)
         mx_softmax_last_route = _mx_run("mx_softmax_quant", a, (s, mask, codes, scales))
     return codes, scales
+
+
+mx_softmax_quant2_last_route = None     # the QS_MX_SOFTMAX_ROUTE_* of the last `mx_softmax_quant2` launch (None: an empty tensor)
+
+
+def mx_softmax_quant2(s: torch.Tensor, mask: Optional[torch.Tensor], scale: float, causal: bool, row_fmt: str, col_fmt: Optional[str],
+                      out=None):
+    """the two-way form of `mx_softmax_quant` (qs_mx_softmax_quant2_v), same operands: returns (row_codes [G, T, S], row_scales
+    [G, T, ceil(S / 32)], col_codes [G, S, T] | None, col_scales [G, S, ceil(T / 32)] | None, m [G, T], Z [G, T]) -- the pairs uint8,
+    the row statistics float32 -- from two launches.  `out`: the six tensors (None for a skipped col pair), contiguous, to write instead
+    of new ones, as the guard-byte tests carve them."""
+    global mx_softmax_quant2_last_route
+    load()
+    G, T, S = s.shape
+    pairs = _mx_quant2_outs((G,), T, S, row_fmt, col_fmt, s.device, None if out is None else out[:4])
+    m, Z = (_mx_new_or_out((G, T), torch.float32, s.device, None if out is None else out[4 + i], "out: dense float32") for i in range(2))
+    mx_softmax_quant2_last_route = None
+    if G and T and S:
+        a = MxSoftmaxQuant2Args()
+        a.row_format = MX_FORMATS.index(row_fmt)
+        a.col_format = MX_FORMATS.index(col_fmt) if col_fmt is not None else -1
+        a.sdt, a.causal, a.scale = dt(s), int(bool(causal)), float(scale)
+        a.s, a.mask = _ptr(s), _ptr(mask)
+        a.mask_slices = 1 if mask is None or mask.dim() == 2 else G
+        a.row_codes, a.row_scales, a.col_codes, a.col_scales = (_ptr(t) for t in pairs)
+        a.m, a.Z = _ptr(m), _ptr(Z)
+        a.G, a.T, a.S = G, T, S
+        a.stream = _stream(s)
+        mx_softmax_quant2_last_route = _mx_run("mx_softmax_quant2", a, (s, mask) + pairs + (m, Z))
+    return pairs + (m, Z)
+
+
+mx_softmax_bwd_last_route = None     # the QS_MX_SOFTMAX_ROUTE_* of the last `mx_softmax_bwd_quant` launch (None: an empty tensor)
+
+
+def mx_softmax_bwd_quant(dp: torch.Tensor, s: torch.Tensor, m: torch.Tensor, Z: torch.Tensor, mask: Optional[torch.Tensor], scale: float,
+                         causal: bool, row_fmt: Optional[str], col_fmt: Optional[str], rounding: str = "nearest", seed: int = 0,
+                         step: Optional[torch.Tensor] = None, index_base: int = 0, out=None):
+    """the softmax backward in front of the two-way MX quantizer (qs_mx_softmax_bwd_quant_v) on contiguous GPU tensors `dp`, `s`
+    [G, T, S], float32 `m`, `Z` [G, T] and a contiguous float32 additive `mask` [T, S] or [G, T, S] (or None): returns (row_codes
+    [G, T, S], row_scales [G, T, ceil(S / 32)], col_codes [G, S, T], col_scales [G, S, ceil(T / 32)]), uint8, a pair None where its
+    format is None -- two launches and the float32 row sums D [G, T] allocated here; ds is never written.  `out`: the four tensors (None
+    for a skipped pair) to write instead of new ones, as the guard-byte tests carve them."""
+    global mx_softmax_bwd_last_route
+    load()
+    G, T, S = s.shape
+    outs = _mx_quant2_outs((G,), T, S, row_fmt, col_fmt, s.device, out)
+    mx_softmax_bwd_last_route = None
+    if G and T and S:
+        D = torch.empty((G, T), dtype=torch.float32, device=s.device)
+        a = MxSoftmaxBwdQuantArgs()
+        _mx_quant2_operands(a, dp, row_fmt, col_fmt, outs, rounding, seed, step, index_base, absent=-1)
+        a.sdt, a.ddt, a.causal, a.scale = dt(s), dt(dp), int(bool(causal)), float(scale)
+        a.dp, a.s, a.mask, a.m, a.Z, a.D = _ptr(dp), _ptr(s), _ptr(mask), _ptr(m), _ptr(Z), _ptr(D)
+        a.mask_slices = 1 if mask is None or mask.dim() == 2 else G
+        a.G, a.T, a.S = G, T, S
+        mx_softmax_bwd_last_route = _mx_run("mx_softmax_bwd_quant", a, (dp, s, mask, m, Z) + outs)
+    return outs
 
 
 MX_NORM_BWD_ROUTE_VEC, MX_NORM_BWD_ROUTE_PLAIN = 1, 2

@@ -17,8 +17,9 @@ from torch.autograd.function import once_differentiable
 
 from qsparse_amd import _hip
 from qsparse_amd._mx_common import _check_dtype, _check_train_entry, _MXTrainMixin, _quantize_grad, _save_train_ctx
-from qsparse_amd.mx_bmm import MXMultiheadAttention, _attention_mask, mx_bmm
+from qsparse_amd.mx_bmm import MX_ATTENTION_SOFTMAX, MXMultiheadAttention, _attention_mask, mx_bmm
 from qsparse_amd.mx_gemm import MXTrainLinear
+from qsparse_amd.mx_softmax import mx_softmax_backward_quantize, mx_softmax_quantize
 from qsparse_amd.quantize import MX_BLOCK, _mx_aten, _mx_check_rounding, _mx_format, _mx_sr_words
 
 _LAYOUTS = ("nk", "kn")
@@ -200,10 +201,66 @@ def mx_bmm_train(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] 
                                 grad_rounding, seed, step)
 
 
+class _MXFusedAttentionFunction(torch.autograd.Function):
+    """the table of `mx_attention_train(softmax="fused")` on MX codes: ONE function over (q, k, v), because ds has to reach the dq / dk
+    products as codes.  `need_q` / `need_k` / `need_v`: that gradient can be asked for -- decided by mx_attention_train, where the
+    grad mode is still the caller's"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, attn_mask, is_causal, scale, qk_fmt, p_fmt, v_fmt, grad_fmt, need_q, need_k, need_v, grad_rounding, seed,
+                step):
+        need_ds = need_q or need_k
+        q_row, q_rs, q_col, q_cs = mx_quantize_2way_batched(q, qk_fmt, qk_fmt if need_k else None)
+        k_row, k_rs, k_col, k_cs = mx_quantize_2way_batched(k, qk_fmt, qk_fmt if need_q else None)
+        s = mx_bmm(q_row, q_rs, qk_fmt, k_row, k_rs, qk_fmt)
+        p = mx_softmax_quantize(s, attn_mask, scale=scale, is_causal=is_causal, fmt=p_fmt, col_fmt=p_fmt if need_v else None,
+                                return_stats=True)
+        p_col, p_cs = p[2:4] if need_v else (None, None)
+        m, Z = p[-2:]
+        # v [.., S, dv] as the "kn" layout takes it: the col pair (blocks along S) for the forward, the row pair (along dv) for dp
+        v_n, v_ns, v_k, v_ks = mx_quantize_2way_batched(v, v_fmt if need_ds else None, v_fmt)
+        o = mx_bmm(p[0], p[1], p_fmt, v_k, v_ks, v_fmt, None, q.dtype)
+        if need_ds or need_v:       # s, the row statistics and the code pairs the backward multiplies (None where nobody asks)
+            ctx.save_for_backward(s if need_ds else None, m if need_ds else None, Z if need_ds else None, q_col, q_cs, k_col, k_cs, p_col,
+                                  p_cs, v_n, v_ns)
+        ctx.fmts, ctx.sr = (qk_fmt, p_fmt, v_fmt, grad_fmt), (grad_rounding, seed, step)
+        ctx.mask, ctx.is_causal, ctx.scale = attn_mask, is_causal, scale          # (the mask is held by reference)
+        ctx.dtypes = (q.dtype, k.dtype, v.dtype)
+        return o
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, do):
+        s, m, Z, q_col, q_cs, k_col, k_cs, p_col, p_cs, v_n, v_ns = ctx.saved_tensors
+        qk_fmt, p_fmt, v_fmt, grad_fmt = ctx.fmts
+        rounding, seed, step = ctx.sr
+        need_q, need_k, need_v = ctx.needs_input_grad[:3]
+        need_q, need_k, need_v = need_q and k_col is not None, need_k and q_col is not None, need_v and p_col is not None
+        need_ds = need_q or need_k
+        dq = dk = dv = None
+        if need_ds or need_v:
+            g_row, g_rs, g_col, g_cs = _quantize_grad(ctx, lambda *sr: mx_quantize_2way_batched(do, grad_fmt if need_ds else None,
+                                                                                                 grad_fmt if need_v else None, *sr))
+        if need_v:
+            dv = mx_bmm(p_col, p_cs, p_fmt, g_col, g_cs, grad_fmt, None, ctx.dtypes[2])
+        if need_ds:
+            dp = mx_bmm(g_row, g_rs, grad_fmt, v_n, v_ns, v_fmt)
+            ds_row, ds_rs, ds_col, ds_cs = mx_softmax_backward_quantize(
+                dp, s, m, Z, ctx.mask, scale=ctx.scale, is_causal=ctx.is_causal, row_fmt=grad_fmt if need_q else None,
+                col_fmt=grad_fmt if need_k else None, rounding=rounding, seed=seed + 1, step=step)
+            if rounding == "stochastic" and step is not None:
+                step.add_(1)
+        if need_q:
+            dq = mx_bmm(ds_row, ds_rs, grad_fmt, k_col, k_cs, qk_fmt, None, ctx.dtypes[0])
+        if need_k:
+            dk = mx_bmm(ds_col, ds_cs, grad_fmt, q_col, q_cs, qk_fmt, None, ctx.dtypes[1])
+        return (dq, dk, dv) + (None,) * 13
+
+
 def mx_attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: Optional[torch.Tensor] = None,
                        is_causal: bool = False, scale: Optional[float] = None, *, qk_fmt: str = "mxfp8_e4m3", p_fmt: str = "mxfp8_e4m3",
                        v_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2", grad_rounding: str = "nearest", seed: int = 0,
-                       step: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       step: Optional[torch.Tensor] = None, softmax: str = "torch") -> torch.Tensor:
     """Scaled dot-product attention that TRAINS through its two matrix products on MX codes.  ``q [..., T, d]``, ``k [..., S, d]``,
     ``v [..., S, dv]`` as ``mx_attention`` takes them; the result is ``[..., T, dv]`` in ``q.dtype``.  It is DEFINED as this composition
     of public differentiable calls and is bit for bit that composition, forward and backward, on either device:
@@ -216,7 +273,32 @@ def mx_attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_m
     with ``grad_fmt``, ``grad_rounding`` and ``step`` handed to both.  Autograd supplies the softmax backward on the float32 ``p``
     (which it keeps: 4 bytes per element); ``v`` is never transposed in memory -- the ``"kn"`` forward multiplies its col pair, blocks
     along ``S``.  A stochastic step advances ``step`` by two.  The forward value is bit for bit ``mx_attention(q, k, v, ...,
-    out_dtype=q.dtype)``.  No dropout."""
+    out_dtype=q.dtype)``.  No dropout.
+
+    ``softmax="fused"`` (keyword; the default ``"torch"`` is the composition above, bit for bit as it always was) is ONE autograd
+    function over ``(q, k, v)`` in which no float ``p`` and no float ``ds`` ever exists.  It is DEFINED as this composition of public
+    calls, with ``Q2`` = ``mx_quantize_2way_batched``, and equals it bit for bit on either device.  Forward:
+
+        1. ``Q2(q, qk_fmt, qk_fmt)`` and ``Q2(k, qk_fmt, qk_fmt)``: the row pairs (blocks along ``d``) for the forward, the col pairs
+           (along ``T`` / ``S``) for ``dk`` / ``dq`` -- a col pair only where the OTHER operand requires grad
+        2. ``s = mx_bmm(q_row, k_row)`` in float32
+        3. ``p_row, [p_col,] m, Z = mx_softmax_quantize(s, attn_mask, scale=scale, is_causal=is_causal, fmt=p_fmt, col_fmt=p_fmt if v
+           requires grad else None, return_stats=True)``
+        4. ``Q2(v, v_fmt, v_fmt)``: the col pair (blocks along ``S``) for the forward, the row pair (along ``dv``) for ``dp`` where
+           ``q`` or ``k`` requires grad; ``v`` is never transposed in memory
+        5. ``o = mx_bmm(p_row, v_col)`` to ``q.dtype``: bit for bit ``mx_attention(..., softmax="fused", out_dtype=q.dtype)``
+
+    It keeps ``s``, ``m``, ``Z`` and the code pairs the backward multiplies; the mask is held by reference.  Backward, from ``dO``:
+
+        6. ``Q2(dO, grad_fmt, grad_fmt, grad_rounding, seed, step)``
+        7. ``dv = mx_bmm(p_col, dO_col)`` to ``v.dtype``;  ``dp = mx_bmm(dO_row, v_row)`` in float32
+        8. ``ds_row, ds_col = mx_softmax_backward_quantize(dp, s, m, Z, attn_mask, scale=scale, is_causal=is_causal, row_fmt=grad_fmt,
+           col_fmt=grad_fmt, rounding=grad_rounding, seed=seed + 1, step=step)`` -- with the ``step`` that 6. has advanced
+        9. ``dq = mx_bmm(ds_row, k_col)`` to ``q.dtype``;  ``dk = mx_bmm(ds_col, q_col)`` to ``k.dtype``
+
+    Pairs and gradients nobody asks for are not computed (only ``dv``: no call 8., no col pairs of ``q`` / ``k``).  A stochastic step
+    advances ``step`` by one after 6. and by one after 8.: by two.  ``attn_mask`` gets no gradient, and a floating one that requires
+    grad is refused."""
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
@@ -224,6 +306,10 @@ def mx_attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_m
             raise ValueError(f"{name} needs at least 3 dimensions [..., {'T' if name == 'q' else 'S'}, d], got shape {tuple(t.shape)}")
     if k.shape[-2] != v.shape[-2]:
         raise ValueError(f"k {tuple(k.shape)} and v {tuple(v.shape)} disagree on S (their second-to-last dimensions)")
+    if softmax not in MX_ATTENTION_SOFTMAX:
+        raise ValueError(f"unknown softmax {softmax!r}: one of {MX_ATTENTION_SOFTMAX}")
+    if softmax == "fused":
+        return _attention_train_fused(q, k, v, attn_mask, is_causal, scale, qk_fmt, p_fmt, v_fmt, grad_fmt, grad_rounding, seed, step)
     mask = _attention_mask(attn_mask, is_causal, q.shape[-2], k.shape[-2], q.device)
     sr = dict(grad_fmt=grad_fmt, grad_rounding=grad_rounding, step=step)
     s = mx_bmm_train(q, k, a_fmt=qk_fmt, b_fmt=qk_fmt, out_dtype=torch.float32, seed=seed + 1, **sr)
@@ -231,6 +317,36 @@ def mx_attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_m
     if mask is not None:
         s = s + mask
     return mx_bmm_train(torch.softmax(s, -1), v, b_layout="kn", a_fmt=p_fmt, b_fmt=v_fmt, out_dtype=q.dtype, seed=seed, **sr)
+
+
+def _attention_train_fused(q, k, v, attn_mask, is_causal, scale, qk_fmt, p_fmt, v_fmt, grad_fmt, grad_rounding, seed, step):
+    """the checks of `mx_attention_train(softmax="fused")` beyond the shared ones, then the autograd function"""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        _check_dtype(name, t.dtype)
+        if t.device != q.device:
+            raise ValueError(f"q is on {q.device} but {name} on {t.device}")
+    for fmt in (qk_fmt, p_fmt, v_fmt, grad_fmt):
+        _mx_format(fmt)
+    _mx_check_rounding(grad_rounding, step, q)
+    lead, d = tuple(q.shape[:-2]), q.shape[-1]
+    if tuple(k.shape[:-2]) != lead or tuple(v.shape[:-2]) != lead:
+        raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)} and v {tuple(v.shape)} disagree on their leading dimensions (nothing "
+                         "is broadcast)")
+    if k.shape[-1] != d:
+        raise ValueError(f"q {tuple(q.shape)} and k {tuple(k.shape)} disagree on d (their last dimensions)")
+    if min(q.shape[-2], k.shape[-2], d, v.shape[-1]) < 1:
+        raise ValueError("mx_attention_train needs T, S, d, dv >= 1: each is the contraction length of one of its products")
+    if attn_mask is not None and is_causal:
+        raise ValueError("give attn_mask or is_causal, not both")
+    if scale is not None and (isinstance(scale, bool) or not isinstance(scale, (int, float))):
+        raise TypeError(f"scale must be a float, got {type(scale).__name__}")
+    grad = torch.is_grad_enabled()
+    if isinstance(attn_mask, torch.Tensor) and grad and attn_mask.requires_grad:
+        raise RuntimeError('mx_attention_train(softmax="fused") has no gradient for attn_mask: a mask that requires grad is refused')
+    _attention_mask(attn_mask, False, q.shape[-2], k.shape[-2], q.device)       # (its checks, where the caller can still read them)
+    return _MXFusedAttentionFunction.apply(q, k, v, attn_mask, bool(is_causal), float(d ** -0.5 if scale is None else scale), qk_fmt,
+                                           p_fmt, v_fmt, grad_fmt, grad and q.requires_grad, grad and k.requires_grad,
+                                           grad and v.requires_grad, grad_rounding, seed, step)
 
 
 class MXTrainMultiheadAttention(_MXTrainMixin, nn.Module):
@@ -242,11 +358,13 @@ class MXTrainMultiheadAttention(_MXTrainMixin, nn.Module):
     ``add_zero_attn`` in ``from_float``) and attention dropout, which it does not have.
 
     ``grad_rounding="stochastic"`` goes to both linear layers (each with a counter of its own, ``MXTrainLinear``) and to the attention,
-    for which the layer owns ``sr_seed`` and a non-persistent int64 buffer ``sr_step`` that a step advances by two."""
+    for which the layer owns ``sr_seed`` and a non-persistent int64 buffer ``sr_step`` that a step advances by two.  ``softmax``
+    (``"torch"`` or ``"fused"``) is ``mx_attention_train``'s keyword; ``to_inference()`` hands it on, so a fused training layer converts
+    to an ``MXMultiheadAttention`` with the same forward bits."""
 
     def __init__(self, in_proj: MXTrainLinear, out_proj: MXTrainLinear, num_heads: int, batch_first: bool = False, *,
                  qk_fmt: str = "mxfp8_e4m3", p_fmt: str = "mxfp8_e4m3", v_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2",
-                 grad_rounding: str = "nearest", seed: Optional[int] = None):
+                 grad_rounding: str = "nearest", seed: Optional[int] = None, softmax: str = "torch"):
         super().__init__()
         if not isinstance(in_proj, MXTrainLinear) or not isinstance(out_proj, MXTrainLinear):
             raise TypeError("in_proj and out_proj must be MXTrainLinear layers")
@@ -256,19 +374,23 @@ class MXTrainMultiheadAttention(_MXTrainMixin, nn.Module):
                              f"[{out_proj.out_features}, {out_proj.in_features}]")
         if isinstance(num_heads, bool) or not isinstance(num_heads, int) or num_heads < 1 or E % num_heads:
             raise ValueError(f"num_heads must be an int >= 1 that divides embed_dim {E}, got {num_heads!r}")
+        if softmax not in MX_ATTENTION_SOFTMAX:
+            raise ValueError(f"unknown softmax {softmax!r}: one of {MX_ATTENTION_SOFTMAX}")
         self._init_mx(dict(qk_fmt=qk_fmt, p_fmt=p_fmt, v_fmt=v_fmt, grad_fmt=grad_fmt), grad_rounding, seed, in_proj.weight)
+        self.softmax = softmax
         self.in_proj, self.out_proj = in_proj, out_proj
         self.embed_dim, self.num_heads, self.batch_first = E, num_heads, bool(batch_first)
 
     def extra_repr(self) -> str:
         sr = f", grad_rounding={self.grad_rounding!r}" if self.grad_rounding != "nearest" else ""
+        sm = f", softmax={self.softmax!r}" if self.softmax != "torch" else ""
         return (f"embed_dim={self.embed_dim}, num_heads={self.num_heads}, batch_first={self.batch_first}, qk_fmt={self.qk_fmt!r}, "
-                f"p_fmt={self.p_fmt!r}, v_fmt={self.v_fmt!r}, grad_fmt={self.grad_fmt!r}{sr}")
+                f"p_fmt={self.p_fmt!r}, v_fmt={self.v_fmt!r}, grad_fmt={self.grad_fmt!r}{sr}{sm}")
 
     @classmethod
     def from_float(cls, mha: nn.MultiheadAttention, x_fmt: str = "mxfp8_e4m3", w_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2", *,
                    qk_fmt: str = "mxfp8_e4m3", p_fmt: str = "mxfp8_e4m3", v_fmt: str = "mxfp8_e4m3", grad_rounding: str = "nearest",
-                   seed: Optional[int] = None):
+                   seed: Optional[int] = None, softmax: str = "torch"):
         """a layer on ``mha``'s own parameters (shared, not copied): ``in_proj_weight`` / ``in_proj_bias`` and ``out_proj``'s"""
         if not isinstance(mha, nn.MultiheadAttention):
             raise TypeError(f"MXTrainMultiheadAttention.from_float needs an nn.MultiheadAttention, got {type(mha).__name__}")
@@ -287,7 +409,7 @@ class MXTrainMultiheadAttention(_MXTrainMixin, nn.Module):
         in_proj = MXTrainLinear(E, 3 * E, bias=mha.in_proj_bias is not None, device="meta", seed=seed, **opts)._adopt(packed)
         out_proj = MXTrainLinear.from_linear(mha.out_proj, seed=None if seed is None else seed + 1, **opts)
         layer = cls(in_proj, out_proj, mha.num_heads, mha.batch_first, qk_fmt=qk_fmt, p_fmt=p_fmt, v_fmt=v_fmt, grad_fmt=grad_fmt,
-                    grad_rounding=grad_rounding, seed=None if seed is None else seed + 2)
+                    grad_rounding=grad_rounding, seed=None if seed is None else seed + 2, softmax=softmax)
         return layer.train(mha.training)
 
     def forward(self, x: torch.Tensor, attn_mask: Optional[torch.Tensor] = None, is_causal: bool = False, *, need_weights: bool = False,
@@ -304,14 +426,14 @@ class MXTrainMultiheadAttention(_MXTrainMixin, nn.Module):
         q, k, v = (t.view(B, T, h, E // h).transpose(1, 2) for t in self.in_proj(xb).chunk(3, -1))      # views: nothing is copied
         seed, step = self._mx_sr()
         o = mx_attention_train(q, k, v, attn_mask, is_causal, qk_fmt=self.qk_fmt, p_fmt=self.p_fmt, v_fmt=self.v_fmt,
-                               grad_fmt=self.grad_fmt, grad_rounding=self.grad_rounding, seed=seed, step=step)
+                               grad_fmt=self.grad_fmt, grad_rounding=self.grad_rounding, seed=seed, step=step, softmax=self.softmax)
         y = self.out_proj(o.transpose(1, 2).reshape(B, T, E))
         return (y if self.batch_first else y.transpose(0, 1)), None
 
     def to_inference(self) -> MXMultiheadAttention:
-        """the ``MXMultiheadAttention`` on the current weights, in this layer's attention formats"""
+        """the ``MXMultiheadAttention`` on the current weights, in this layer's attention formats and ``softmax`` setting"""
         return MXMultiheadAttention(self.in_proj.to_inference(), self.out_proj.to_inference(), self.num_heads, self.batch_first,
-                                    qk_fmt=self.qk_fmt, p_fmt=self.p_fmt, v_fmt=self.v_fmt)
+                                    qk_fmt=self.qk_fmt, p_fmt=self.p_fmt, v_fmt=self.v_fmt, softmax=self.softmax)
 
 
 __all__ = ["mx_quantize_2way_batched", "mx_bmm_train", "mx_attention_train", "MXTrainMultiheadAttention"]

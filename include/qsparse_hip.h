@@ -2063,6 +2063,80 @@ int qs_mx_softmax_bwd_quant_v(const qs_mx_softmax_bwd_quant_args* args);
  * or the QS_ERR_* the call would return */
 int qs_mx_softmax_bwd_quant_route(const qs_mx_softmax_bwd_quant_args* args);
 
+/* ---- MX rotary embedding (rotary position embedding as a dense call and in front of the batched two-way quantizer) ------------------
+ * Added without raising QS_ABI_VERSION (28), by the same rule as qs_mx_matmul_v above: symbols are only added.
+ *
+ * Operands.  x holds G = G0 G1 slices [R, C] addressed exactly as the MX batched two-way quantizer addresses them (unit stride along
+ * C, the three element strides x_stride_g0 / x_stride_g1 / x_stride_r), float32 / bf16 / f16; R is the sequence length T, C the head
+ * dimension d, even, h = C / 2.  cos and sin are float32, contiguous, [R, h], shared by every slice.
+ * Definition (normative).  Pair j (0 <= j < h) of row t of a slice is
+ *   interleaved == 0   (a, b) = (x[t, j], x[t, j + h])    and lands in y[t, j], y[t, j + h]        (rotate-half: Llama / NeoX)
+ *   interleaved != 0   (a, b) = (x[t, 2 j], x[t, 2 j + 1]) and lands in y[t, 2 j], y[t, 2 j + 1]  (GPT-J)
+ * and, with c = cos[t, j], s = sin[t, j] (inverse != 0: s = -sin[t, j], an exact negation), every operation a float32 operation
+ * rounded to nearest on its own, nothing contracted into an FMA:
+ *   y_a = (a * c) - (b * s)
+ *   y_b = (b * c) + (a * s)
+ * x is widened to float32 exactly.  NaN, Inf and signed zeros are whatever these four products, one difference and one sum give;
+ * nothing is special-cased.  The inverse call is bit for bit the forward call on -sin, and it is the gradient of the forward with
+ * respect to x: there is no other backward formula.
+ *
+ * qs_mx_rope_v writes y dense, [G, R, C] in ydt, each element rounded once from float32 (round to nearest even), from ONE launch.
+ * qs_mx_rope_quant2_v writes, from ONE launch, the four outputs of qs_mx_quant2_batched_v (round to nearest; same shapes, same
+ * nullable-pair rule, at least one pair) for the float32 y above: bit for bit qs_mx_quant2_batched_v on that y as a dense float32
+ * [G, R, C] tensor.  y is never rounded to x's dtype and never written.
+ * Nothing outside the G R C addressed elements of x and the R h elements of each table is read; nothing but the outputs is written;
+ * no atomics, no workspace.
+ *   - checks in qs_mx_quant2_batched_v's order and with its status codes.  QS_ERR_ARG in addition: cos or sin missing, C odd, y
+ *     missing (qs_mx_rope_v).  QS_ERR_DTYPE: xdt, ydt.  QS_ERR_ALIGN: x (y) not aligned to its element, cos or sin not to 4 bytes.
+ *   - G0, G1, R or C equal to 0: nothing is enqueued, 0 is returned.
+ *   - QS_MX_ROPE_ROUTE_VEC (16-byte loads of x): qs_mx_quant2_batched_v's conditions for QS_MX_Q2_ROUTE_TILE_VEC (for qs_mx_rope_v
+ *     those on x, C and the strides, and y 16-byte aligned), cos and sin 16-byte aligned and, with interleaved == 0, h a multiple
+ *     of the lane's vector (8 two-byte elements, 4 float32).  Anything else takes QS_MX_ROPE_ROUTE_PLAIN: element accesses predicated
+ *     one by one, any even C, any R >= 1, any element-aligned base, the same bits. */
+#define QS_MX_ROPE_ROUTE_VEC 1
+#define QS_MX_ROPE_ROUTE_PLAIN 2
+typedef struct qs_mx_rope_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_rope_args) as the caller compiled it */
+    int32_t xdt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    int32_t ydt;                     /* likewise */
+    int32_t interleaved;             /* 0: pairs (j, j + h); else pairs (2 j, 2 j + 1) */
+    int32_t inverse;                 /* 0 or 1: -sin in place of sin */
+    int32_t reserved0;
+    const void* x;                   /* slice (g0, g1), row r, column c at x[g0 x_stride_g0 + g1 x_stride_g1 + r x_stride_r + c] */
+    void* y;                         /* [G, R, C], dense */
+    const float* cos;                /* [R, C / 2] */
+    const float* sin;                /* [R, C / 2] */
+    int64_t G0, G1, R, C;            /* G = G0 G1 slices */
+    int64_t x_stride_g0, x_stride_g1, x_stride_r;   /* in elements */
+    qs_stream_t stream;
+} qs_mx_rope_args;
+int qs_mx_rope_v(const qs_mx_rope_args* args);
+/* the kernel qs_mx_rope_v launches for these operands, nothing enqueued: QS_MX_ROPE_ROUTE_*, 0 for an empty tensor, or the QS_ERR_*
+ * the call would return */
+int qs_mx_rope_route(const qs_mx_rope_args* args);
+
+typedef struct qs_mx_rope_quant2_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_rope_quant2_args) as the caller compiled it */
+    int32_t row_format, col_format;  /* enum qs_mx_format, may differ */
+    int32_t xdt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    int32_t interleaved;             /* as qs_mx_rope_args */
+    int32_t inverse;
+    const void* x;                   /* as qs_mx_rope_args */
+    const float* cos;                /* [R, C / 2] */
+    const float* sin;                /* [R, C / 2] */
+    uint8_t* row_codes;              /* nullable with row_scales; [G, R, C] */
+    uint8_t* row_scales;             /* [G, R, ceil(C / 32)] */
+    uint8_t* col_codes;              /* nullable with col_scales; [G, C, R] */
+    uint8_t* col_scales;             /* [G, C, ceil(R / 32)] */
+    int64_t G0, G1, R, C;            /* G = G0 G1 slices */
+    int64_t x_stride_g0, x_stride_g1, x_stride_r;   /* in elements */
+    qs_stream_t stream;
+} qs_mx_rope_quant2_args;
+int qs_mx_rope_quant2_v(const qs_mx_rope_quant2_args* args);
+/* the kernel qs_mx_rope_quant2_v launches for these operands, nothing enqueued: QS_MX_ROPE_ROUTE_*, 0 for an empty tensor, or the
+ * QS_ERR_* the call would return */
+int qs_mx_rope_quant2_route(const qs_mx_rope_quant2_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

@@ -24,6 +24,7 @@ from qsparse_amd.mx_grouped import MXGroupedLinear, MXMoEFeedForward, mx_grouped
 from qsparse_amd.mx_grouped_train import MXTrainGroupedLinear, MXTrainMoEFeedForward, mx_grouped_linear, mx_grouped_weight_grad
 from qsparse_amd.mx_norm import (MXAddNormLinear, MXLayerNorm, MXRMSNorm, MXTrainAddNormLinear, MXTrainNormLinear, mx_add_norm_linear,
                                  mx_add_norm_quantize, mx_norm_backward, mx_norm_linear, mx_norm_quantize)
+from qsparse_amd.mx_rope import mx_rope, mx_rope_quantize, mx_rope_table
 from qsparse_amd.mx_softmax import mx_softmax_backward_quantize, mx_softmax_quantize
 from qsparse_amd.quantize import (AdaptiveQuantizer, DecimalQuantizer, MXQuantizer, ScalerQuantizer, quantize,
                                   quantize_with_decimal, quantize_with_line, quantize_with_mx, quantize_with_scaler)

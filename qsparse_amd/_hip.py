@@ -154,6 +154,10 @@ SIGNATURES = {
     "qs_mx_softmax_quant2_route": (c_int, [_P]),
     "qs_mx_softmax_bwd_quant_v": (c_int, [_P]),
     "qs_mx_softmax_bwd_quant_route": (c_int, [_P]),
+    "qs_mx_rope_v": (c_int, [_P]),
+    "qs_mx_rope_route": (c_int, [_P]),
+    "qs_mx_rope_quant2_v": (c_int, [_P]),
+    "qs_mx_rope_quant2_route": (c_int, [_P]),
 }
 
 
@@ -260,6 +264,23 @@ class MxQuant2BatchedArgs(ctypes.Structure):
     """`qs_mx_quant2_batched_args` of include/qsparse_hip.h"""
     _fields_ = MxQuant2Args._fields_ + [("G0", c_int64), ("G1", c_int64), ("x_stride_g0", c_int64), ("x_stride_g1", c_int64),
                                         ("x_stride_r", c_int64)]
+
+
+class MxRopeArgs(ctypes.Structure):
+    """`qs_mx_rope_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("xdt", c_int32), ("ydt", c_int32), ("interleaved", c_int32), ("inverse", c_int32),
+                ("reserved0", c_int32), ("x", c_void_p), ("y", c_void_p), ("cos", c_void_p), ("sin", c_void_p),
+                ("G0", c_int64), ("G1", c_int64), ("R", c_int64), ("C", c_int64),
+                ("x_stride_g0", c_int64), ("x_stride_g1", c_int64), ("x_stride_r", c_int64), ("stream", c_void_p)]
+
+
+class MxRopeQuant2Args(ctypes.Structure):
+    """`qs_mx_rope_quant2_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("row_format", c_int32), ("col_format", c_int32), ("xdt", c_int32),
+                ("interleaved", c_int32), ("inverse", c_int32), ("x", c_void_p), ("cos", c_void_p), ("sin", c_void_p),
+                ("row_codes", c_void_p), ("row_scales", c_void_p), ("col_codes", c_void_p), ("col_scales", c_void_p),
+                ("G0", c_int64), ("G1", c_int64), ("R", c_int64), ("C", c_int64),
+                ("x_stride_g0", c_int64), ("x_stride_g1", c_int64), ("x_stride_r", c_int64), ("stream", c_void_p)]
 
 
 class MxConv2dArgs(ctypes.Structure):
@@ -1633,6 +1654,62 @@ def mx_quant2_batched(x: torch.Tensor, G0: int, G1: int, R: int, C: int, strides
         a.R, a.C, a.G0, a.G1 = R, C, G0, G1
         a.x_stride_g0, a.x_stride_g1, a.x_stride_r = strides
         mx_quant2_batched_last_route = _mx_run("mx_quant2_batched", a, (x,) + outs)
+    return outs
+
+
+MX_ROPE_ROUTE_VEC, MX_ROPE_ROUTE_PLAIN = 1, 2
+mx_rope_last_route = None             # the QS_MX_ROPE_ROUTE_* of the last `mx_rope` launch (None: an empty tensor), for tests and tools
+mx_rope_quant2_last_route = None      # likewise of the last `mx_rope_quant2` launch
+
+
+def _mx_rope_operands(a, x: torch.Tensor, G0: int, G1: int, R: int, C: int, strides, cos: torch.Tensor, sin: torch.Tensor,
+                      interleaved: bool, inverse: bool):
+    """fill what the two rotary descriptors share: x and its slices, the tables, the two flags, the stream"""
+    assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous(), \
+        "cos / sin: contiguous float32"
+    assert tuple(cos.shape) == (R, C // 2) and tuple(sin.shape) == (R, C // 2) and cos.device == x.device and sin.device == x.device, \
+        "cos / sin: [R, C / 2] on x's device"
+    a.x, a.xdt, a.cos, a.sin = _ptr(x), dt(x), _ptr(cos), _ptr(sin)
+    a.R, a.C, a.G0, a.G1 = R, C, G0, G1
+    a.x_stride_g0, a.x_stride_g1, a.x_stride_r = strides
+    a.interleaved, a.inverse = int(bool(interleaved)), int(bool(inverse))
+    a.stream = _stream(x)
+
+
+def mx_rope(x: torch.Tensor, G0: int, G1: int, R: int, C: int, strides, cos: torch.Tensor, sin: torch.Tensor, interleaved: bool,
+            inverse: bool, out_dtype: torch.dtype, out=None) -> torch.Tensor:
+    """the rotary embedding (qs_mx_rope_v): `x` is a GPU tensor whose memory holds G0 x G1 slices [R, C] as `mx_quant2_batched` takes
+    them, `cos` / `sin` contiguous float32 [R, C / 2].  Returns the dense y [G, R, C] in `out_dtype` from ONE launch.  `out`: a
+    contiguous tensor of that dtype and size to write instead of a new one, as the guard-byte tests carve it."""
+    global mx_rope_last_route
+    load()
+    G = G0 * G1
+    y = _mx_new_or_out((G, R, C), out_dtype, x.device, out, "out: dense, of out_dtype")
+    mx_rope_last_route = None
+    if G and R and C:
+        a = MxRopeArgs()
+        _mx_rope_operands(a, x, G0, G1, R, C, strides, cos, sin, interleaved, inverse)
+        a.y, a.ydt = _ptr(y), _DT[out_dtype]
+        mx_rope_last_route = _mx_run("mx_rope", a, (x, cos, sin, y))
+    return y
+
+
+def mx_rope_quant2(x: torch.Tensor, G0: int, G1: int, R: int, C: int, strides, cos: torch.Tensor, sin: torch.Tensor, interleaved: bool,
+                   inverse: bool, row_fmt: Optional[str], col_fmt: Optional[str], out=None):
+    """the rotary embedding in front of the batched two-way MX quantizer (qs_mx_rope_quant2_v), operands as `mx_rope`: returns what
+    `mx_quant2_batched` returns for the rotated float32 tensor, which is never written -- from ONE launch.  `out` as there."""
+    global mx_rope_quant2_last_route
+    load()
+    G = G0 * G1
+    outs = _mx_quant2_outs((G,), R, C, row_fmt, col_fmt, x.device, out)
+    mx_rope_quant2_last_route = None
+    if G and R and C:
+        a = MxRopeQuant2Args()
+        _mx_rope_operands(a, x, G0, G1, R, C, strides, cos, sin, interleaved, inverse)
+        a.row_format = MX_FORMATS.index(row_fmt) if row_fmt is not None else 0
+        a.col_format = MX_FORMATS.index(col_fmt) if col_fmt is not None else 0
+        a.row_codes, a.row_scales, a.col_codes, a.col_scales = (_ptr(t) for t in outs)
+        mx_rope_quant2_last_route = _mx_run("mx_rope_quant2", a, (x, cos, sin) + outs)
     return outs
 
 

@@ -208,10 +208,17 @@ class _MXFusedAttentionFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, v, attn_mask, is_causal, scale, qk_fmt, p_fmt, v_fmt, grad_fmt, need_q, need_k, need_v, grad_rounding, seed,
-                step):
+                step, rope, rope_interleaved):
         need_ds = need_q or need_k
-        q_row, q_rs, q_col, q_cs = mx_quantize_2way_batched(q, qk_fmt, qk_fmt if need_k else None)
-        k_row, k_rs, k_col, k_cs = mx_quantize_2way_batched(k, qk_fmt, qk_fmt if need_q else None)
+        if rope is None:
+            q_row, q_rs, q_col, q_cs = mx_quantize_2way_batched(q, qk_fmt, qk_fmt if need_k else None)
+            k_row, k_rs, k_col, k_cs = mx_quantize_2way_batched(k, qk_fmt, qk_fmt if need_q else None)
+        else:
+            from qsparse_amd.mx_rope import mx_rope_quantize       # (it imports this module)
+            q_row, q_rs, q_col, q_cs = mx_rope_quantize(q, rope[0], rope[1], row_fmt=qk_fmt, col_fmt=qk_fmt if need_k else None,
+                                                        interleaved=rope_interleaved)
+            k_row, k_rs, k_col, k_cs = mx_rope_quantize(k, rope[2], rope[3], row_fmt=qk_fmt, col_fmt=qk_fmt if need_q else None,
+                                                        interleaved=rope_interleaved)
         s = mx_bmm(q_row, q_rs, qk_fmt, k_row, k_rs, qk_fmt)
         p = mx_softmax_quantize(s, attn_mask, scale=scale, is_causal=is_causal, fmt=p_fmt, col_fmt=p_fmt if need_v else None,
                                 return_stats=True)
@@ -226,6 +233,7 @@ class _MXFusedAttentionFunction(torch.autograd.Function):
         ctx.fmts, ctx.sr = (qk_fmt, p_fmt, v_fmt, grad_fmt), (grad_rounding, seed, step)
         ctx.mask, ctx.is_causal, ctx.scale = attn_mask, is_causal, scale          # (the mask is held by reference)
         ctx.dtypes = (q.dtype, k.dtype, v.dtype)
+        ctx.rope, ctx.rope_interleaved = rope, rope_interleaved                   # (the tables are held by reference)
         return o
 
     @staticmethod
@@ -250,17 +258,25 @@ class _MXFusedAttentionFunction(torch.autograd.Function):
                 col_fmt=grad_fmt if need_k else None, rounding=rounding, seed=seed + 1, step=step)
             if rounding == "stochastic" and step is not None:
                 step.add_(1)
+        rope = ctx.rope
         if need_q:
-            dq = mx_bmm(ds_row, ds_rs, grad_fmt, k_col, k_cs, qk_fmt, None, ctx.dtypes[0])
+            dq = mx_bmm(ds_row, ds_rs, grad_fmt, k_col, k_cs, qk_fmt, None, ctx.dtypes[0] if rope is None else torch.float32)
         if need_k:
-            dk = mx_bmm(ds_col, ds_cs, grad_fmt, q_col, q_cs, qk_fmt, None, ctx.dtypes[1])
-        return (dq, dk, dv) + (None,) * 13
+            dk = mx_bmm(ds_col, ds_cs, grad_fmt, q_col, q_cs, qk_fmt, None, ctx.dtypes[1] if rope is None else torch.float32)
+        if rope is not None:        # the products gave the gradients of the ROTATED q and k, in float32: back through the rotation
+            from qsparse_amd.mx_rope import mx_rope
+            if need_q:
+                dq = mx_rope(dq, rope[0], rope[1], interleaved=ctx.rope_interleaved, inverse=True, out_dtype=ctx.dtypes[0])
+            if need_k:
+                dk = mx_rope(dk, rope[2], rope[3], interleaved=ctx.rope_interleaved, inverse=True, out_dtype=ctx.dtypes[1])
+        return (dq, dk, dv) + (None,) * 15
 
 
 def mx_attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: Optional[torch.Tensor] = None,
                        is_causal: bool = False, scale: Optional[float] = None, *, qk_fmt: str = "mxfp8_e4m3", p_fmt: str = "mxfp8_e4m3",
                        v_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2", grad_rounding: str = "nearest", seed: int = 0,
-                       step: Optional[torch.Tensor] = None, softmax: str = "torch") -> torch.Tensor:
+                       step: Optional[torch.Tensor] = None, softmax: str = "torch", rope=None,
+                       rope_interleaved: bool = False) -> torch.Tensor:
     """Scaled dot-product attention that TRAINS through its two matrix products on MX codes.  ``q [..., T, d]``, ``k [..., S, d]``,
     ``v [..., S, dv]`` as ``mx_attention`` takes them; the result is ``[..., T, dv]`` in ``q.dtype``.  It is DEFINED as this composition
     of public differentiable calls and is bit for bit that composition, forward and backward, on either device:
@@ -298,7 +314,21 @@ def mx_attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_m
 
     Pairs and gradients nobody asks for are not computed (only ``dv``: no call 8., no col pairs of ``q`` / ``k``).  A stochastic step
     advances ``step`` by one after 6. and by one after 8.: by two.  ``attn_mask`` gets no gradient, and a floating one that requires
-    grad is refused."""
+    grad is refused.
+
+    ``rope`` / ``rope_interleaved`` (keywords; ``None`` changes no call, launch or bit) are ``mx_attention``'s: a 2-tuple ``(cos,
+    sin)`` (needs ``T == S``) or a 4-tuple ``(cos_q, sin_q, cos_k, sin_k)`` of ``mx_rope`` tables.  With ``softmax="torch"`` the call
+    is DEFINED as the first composition above on ``mx_rope(q, cos_q, sin_q, interleaved=rope_interleaved, out_dtype=torch.float32)``
+    and ``mx_rope(k, cos_k, sin_k, ...)`` -- differentiable calls, nothing is fused -- with the result still in ``q.dtype``.  With
+    ``softmax="fused"`` it is the second composition with these steps replaced, ``RQ`` = ``mx_rope_quantize``:
+
+        1. ``RQ(q, cos_q, sin_q, row_fmt=qk_fmt, col_fmt=qk_fmt, interleaved=rope_interleaved)`` and ``RQ(k, cos_k, sin_k, ...)`` -- a
+           col pair only where the OTHER operand requires grad, as before; the rotated ``q`` / ``k`` are never written
+        9. ``dq_rot = mx_bmm(ds_row, k_col)`` and ``dk_rot = mx_bmm(ds_col, q_col)`` **to float32**, then ``dq = mx_rope(dq_rot, cos_q,
+           sin_q, interleaved=rope_interleaved, inverse=True, out_dtype=q.dtype)`` and ``dk = mx_rope(dk_rot, cos_k, sin_k, ...,
+           inverse=True, out_dtype=k.dtype)``: one rounding to the input's dtype, as the ``"torch"`` composition gives
+
+    The tables get no gradient; one that requires grad is refused."""
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
@@ -308,18 +338,29 @@ def mx_attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_m
         raise ValueError(f"k {tuple(k.shape)} and v {tuple(v.shape)} disagree on S (their second-to-last dimensions)")
     if softmax not in MX_ATTENTION_SOFTMAX:
         raise ValueError(f"unknown softmax {softmax!r}: one of {MX_ATTENTION_SOFTMAX}")
+    out_dtype = q.dtype
+    if rope is not None:
+        from qsparse_amd.mx_rope import _attention_rope, mx_rope       # (it imports this module)
+        if k.shape[-1] != q.shape[-1]:
+            raise ValueError(f"q {tuple(q.shape)} and k {tuple(k.shape)} disagree on d (their last dimensions)")
+        rope = _attention_rope(rope, q.shape[-2], k.shape[-2], q.shape[-1], q.device)
     if softmax == "fused":
-        return _attention_train_fused(q, k, v, attn_mask, is_causal, scale, qk_fmt, p_fmt, v_fmt, grad_fmt, grad_rounding, seed, step)
+        return _attention_train_fused(q, k, v, attn_mask, is_causal, scale, qk_fmt, p_fmt, v_fmt, grad_fmt, grad_rounding, seed, step,
+                                      rope, bool(rope_interleaved))
+    if rope is not None:
+        q = mx_rope(q, rope[0], rope[1], interleaved=rope_interleaved, out_dtype=torch.float32)
+        k = mx_rope(k, rope[2], rope[3], interleaved=rope_interleaved, out_dtype=torch.float32)
     mask = _attention_mask(attn_mask, is_causal, q.shape[-2], k.shape[-2], q.device)
     sr = dict(grad_fmt=grad_fmt, grad_rounding=grad_rounding, step=step)
     s = mx_bmm_train(q, k, a_fmt=qk_fmt, b_fmt=qk_fmt, out_dtype=torch.float32, seed=seed + 1, **sr)
     s = s * (q.shape[-1] ** -0.5 if scale is None else scale)
     if mask is not None:
         s = s + mask
-    return mx_bmm_train(torch.softmax(s, -1), v, b_layout="kn", a_fmt=p_fmt, b_fmt=v_fmt, out_dtype=q.dtype, seed=seed, **sr)
+    return mx_bmm_train(torch.softmax(s, -1), v, b_layout="kn", a_fmt=p_fmt, b_fmt=v_fmt, out_dtype=out_dtype, seed=seed, **sr)
 
 
-def _attention_train_fused(q, k, v, attn_mask, is_causal, scale, qk_fmt, p_fmt, v_fmt, grad_fmt, grad_rounding, seed, step):
+def _attention_train_fused(q, k, v, attn_mask, is_causal, scale, qk_fmt, p_fmt, v_fmt, grad_fmt, grad_rounding, seed, step, rope=None,
+                           rope_interleaved=False):
     """the checks of `mx_attention_train(softmax="fused")` beyond the shared ones, then the autograd function"""
     for name, t in (("q", q), ("k", k), ("v", v)):
         _check_dtype(name, t.dtype)
@@ -346,7 +387,7 @@ def _attention_train_fused(q, k, v, attn_mask, is_causal, scale, qk_fmt, p_fmt, 
     _attention_mask(attn_mask, False, q.shape[-2], k.shape[-2], q.device)       # (its checks, where the caller can still read them)
     return _MXFusedAttentionFunction.apply(q, k, v, attn_mask, bool(is_causal), float(d ** -0.5 if scale is None else scale), qk_fmt,
                                            p_fmt, v_fmt, grad_fmt, grad and q.requires_grad, grad and k.requires_grad,
-                                           grad and v.requires_grad, grad_rounding, seed, step)
+                                           grad and v.requires_grad, grad_rounding, seed, step, rope, rope_interleaved)
 
 
 class MXTrainMultiheadAttention(_MXTrainMixin, nn.Module):
@@ -360,7 +401,8 @@ class MXTrainMultiheadAttention(_MXTrainMixin, nn.Module):
     ``grad_rounding="stochastic"`` goes to both linear layers (each with a counter of its own, ``MXTrainLinear``) and to the attention,
     for which the layer owns ``sr_seed`` and a non-persistent int64 buffer ``sr_step`` that a step advances by two.  ``softmax``
     (``"torch"`` or ``"fused"``) is ``mx_attention_train``'s keyword; ``to_inference()`` hands it on, so a fused training layer converts
-    to an ``MXMultiheadAttention`` with the same forward bits."""
+    to an ``MXMultiheadAttention`` with the same forward bits.  ``forward``'s ``rope`` / ``rope_interleaved`` are
+    ``mx_attention_train``'s: call arguments, not state, so ``to_inference()`` has nothing to carry."""
 
     def __init__(self, in_proj: MXTrainLinear, out_proj: MXTrainLinear, num_heads: int, batch_first: bool = False, *,
                  qk_fmt: str = "mxfp8_e4m3", p_fmt: str = "mxfp8_e4m3", v_fmt: str = "mxfp8_e4m3", grad_fmt: str = "mxfp8_e5m2",
@@ -413,7 +455,7 @@ class MXTrainMultiheadAttention(_MXTrainMixin, nn.Module):
         return layer.train(mha.training)
 
     def forward(self, x: torch.Tensor, attn_mask: Optional[torch.Tensor] = None, is_causal: bool = False, *, need_weights: bool = False,
-                key_padding_mask: Optional[torch.Tensor] = None):
+                key_padding_mask: Optional[torch.Tensor] = None, rope=None, rope_interleaved: bool = False):
         if need_weights:
             raise ValueError("need_weights=True is not offered: the attention weights exist only inside mx_attention_train")
         if key_padding_mask is not None:
@@ -426,7 +468,8 @@ class MXTrainMultiheadAttention(_MXTrainMixin, nn.Module):
         q, k, v = (t.view(B, T, h, E // h).transpose(1, 2) for t in self.in_proj(xb).chunk(3, -1))      # views: nothing is copied
         seed, step = self._mx_sr()
         o = mx_attention_train(q, k, v, attn_mask, is_causal, qk_fmt=self.qk_fmt, p_fmt=self.p_fmt, v_fmt=self.v_fmt,
-                               grad_fmt=self.grad_fmt, grad_rounding=self.grad_rounding, seed=seed, step=step, softmax=self.softmax)
+                               grad_fmt=self.grad_fmt, grad_rounding=self.grad_rounding, seed=seed, step=step, softmax=self.softmax,
+                               rope=rope, rope_interleaved=rope_interleaved)
         y = self.out_proj(o.transpose(1, 2).reshape(B, T, E))
         return (y if self.batch_first else y.transpose(0, 1)), None
 

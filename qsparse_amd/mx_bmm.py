@@ -116,7 +116,7 @@ def _attention_mask(attn_mask, is_causal: bool, T: int, S: int, device):
 
 def mx_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: Optional[torch.Tensor] = None, is_causal: bool = False,
                  scale: Optional[float] = None, *, qk_fmt: str = "mxfp8_e4m3", p_fmt: str = "mxfp8_e4m3", v_fmt: str = "mxfp8_e4m3",
-                 out_dtype: torch.dtype = torch.float32, softmax: str = "torch") -> torch.Tensor:
+                 out_dtype: torch.dtype = torch.float32, softmax: str = "torch", rope=None, rope_interleaved: bool = False) -> torch.Tensor:
     """Inference-side scaled dot-product attention whose two matrix products run on MX codes.  ``q [..., T, d]``, ``k [..., S, d]``
     and ``v [..., S, dv]`` are float32 / bfloat16 / float16 tensors with equal leading dimensions (at least one); the result is
     ``[..., T, dv]`` in ``out_dtype``.  It is DEFINED as this composition of public calls, and is bit for bit that composition on
@@ -139,6 +139,13 @@ def mx_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: O
     ``s`` once and writes only ``p``'s codes, with ``is_causal`` handed down so that no ``[T, S]`` mask tensor is built.  With
     ``"fused"`` the result is DEFINED as that composition, bit for bit on either device; its ``p`` comes from ``mx_softmax_quantize``'s
     own written-out exponential, not from ``torch.softmax``, so the two settings usually agree but are not each other's definition.
+
+    ``rope`` (keyword; ``None`` changes no call, launch or bit) rotates ``q`` and ``k`` in front of their quantizer, in either softmax
+    mode: a 2-tuple ``(cos, sin)`` of ``mx_rope`` tables ``[T, d / 2]`` rotates both and needs ``T == S``, a 4-tuple ``(cos_q, sin_q,
+    cos_k, sin_k)`` takes ``[T, d / 2]`` and ``[S, d / 2]`` tables (decoding against a longer key sequence); ``rope_interleaved`` is
+    ``mx_rope``'s ``interleaved``.  Step 1 then is the row pair of ``mx_rope_quantize(q, cos_q, sin_q, row_fmt=qk_fmt,
+    interleaved=rope_interleaved)`` and of ``mx_rope_quantize(k, cos_k, sin_k, ...)``: on the GPU one launch each that reads ``q`` /
+    ``k`` where it lies and never writes the rotated tensor.
 
     No dropout and no gradient: a tensor that requires grad while gradients are enabled is refused -- the training side of attention
     is not offered.  A row of the mask that admits no key gives NaN, as softmax does."""
@@ -171,10 +178,17 @@ def mx_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: O
     fused = softmax == "fused"
     if fused and attn_mask is not None and is_causal:
         raise ValueError("give attn_mask or is_causal, not both")
+    if rope is not None:
+        from qsparse_amd.mx_rope import _attention_rope, mx_rope_quantize      # (it takes the batched quantizer, which imports this module)
+        rope = _attention_rope(rope, T, S, d, q.device)
     with torch.no_grad():
         mask = None if fused else _attention_mask(attn_mask, is_causal, T, S, q.device)
-        _, qc, qsc = quantize_with_mx(q.detach(), qk_fmt, -1, return_codes=True)
-        _, kc, ksc = quantize_with_mx(k.detach(), qk_fmt, -1, return_codes=True)
+        if rope is None:
+            _, qc, qsc = quantize_with_mx(q.detach(), qk_fmt, -1, return_codes=True)
+            _, kc, ksc = quantize_with_mx(k.detach(), qk_fmt, -1, return_codes=True)
+        else:
+            qc, qsc = mx_rope_quantize(q, rope[0], rope[1], row_fmt=qk_fmt, interleaved=rope_interleaved)[:2]
+            kc, ksc = mx_rope_quantize(k, rope[2], rope[3], row_fmt=qk_fmt, interleaved=rope_interleaved)[:2]
         s = mx_bmm(qc, qsc, qk_fmt, kc, ksc, qk_fmt)
         if fused:
             from qsparse_amd.mx_softmax import mx_softmax_quantize     # (it takes `_attention_mask` from this module)
@@ -195,7 +209,7 @@ class MXMultiheadAttention(nn.Module):
     returns without its weights; the mask goes to ``mx_attention`` as it is (``[T, T]`` or anything that broadcasts to ``[B, h, T,
     T]``).  It is a thin composition -- ``in_proj(x)``, split, ``mx_attention``, merge, ``out_proj`` -- and equals it bit for bit.
     ``need_weights`` and ``key_padding_mask`` are not offered.  ``softmax`` (``"torch"`` or ``"fused"``) is ``mx_attention``'s keyword,
-    stored and passed on."""
+    stored and passed on; ``forward``'s ``rope`` / ``rope_interleaved`` are ``mx_attention``'s too, call arguments and not state."""
 
     def __init__(self, in_proj: MXLinear, out_proj: MXLinear, num_heads: int, batch_first: bool = False, *, qk_fmt: str = "mxfp8_e4m3",
                  p_fmt: str = "mxfp8_e4m3", v_fmt: str = "mxfp8_e4m3", softmax: str = "torch"):
@@ -243,7 +257,7 @@ class MXMultiheadAttention(nn.Module):
         return cls(*layers, mha.num_heads, mha.batch_first, qk_fmt=qk_fmt, p_fmt=p_fmt, v_fmt=v_fmt, softmax=softmax)
 
     def forward(self, x: torch.Tensor, attn_mask: Optional[torch.Tensor] = None, is_causal: bool = False, *, need_weights: bool = False,
-                key_padding_mask: Optional[torch.Tensor] = None):
+                key_padding_mask: Optional[torch.Tensor] = None, rope=None, rope_interleaved: bool = False):
         if need_weights:
             raise ValueError("need_weights=True is not offered: the attention weights exist only as MX codes inside mx_attention")
         if key_padding_mask is not None:
@@ -254,7 +268,8 @@ class MXMultiheadAttention(nn.Module):
         xb = x if self.batch_first else x.transpose(0, 1)
         B, T = xb.shape[:2]
         q, k, v = (t.reshape(B, T, h, E // h).transpose(1, 2) for t in self.in_proj(xb).chunk(3, -1))
-        o = mx_attention(q, k, v, attn_mask, is_causal, qk_fmt=self.qk_fmt, p_fmt=self.p_fmt, v_fmt=self.v_fmt, softmax=self.softmax)
+        o = mx_attention(q, k, v, attn_mask, is_causal, qk_fmt=self.qk_fmt, p_fmt=self.p_fmt, v_fmt=self.v_fmt, softmax=self.softmax,
+                         rope=rope, rope_interleaved=rope_interleaved)
         y = self.out_proj(o.transpose(1, 2).reshape(B, T, E))
         return (y if self.batch_first else y.transpose(0, 1)), None
 

@@ -3,12 +3,10 @@
 // transposed, when asked for -- with blocks along R in a second one.  y is never written.  The add-norm quantizer is the same two
 // launches with a statistics kernel that forms and stores h = x + residual first, and the quantizing launch on h.
 // Host side: argument checks, route, launch configuration.  No allocation, no synchronisation.
-#include "qs_host.h"
+#include "qs_mx_quant2_host.h"
 #include "qs_mx_norm.h"
 
 namespace {
-
-inline bool aligned4(const void* p) { return (((uintptr_t)p) & 3u) == 0; }
 
 // what qs_mx_add_norm_quant_args has beyond qs_mx_norm_quant_args
 struct NormAdd {
@@ -20,10 +18,9 @@ struct NormAdd {
 // the checks of qs_mx_norm_quant_v -- with `add`, of qs_mx_add_norm_quant_v -- and the kernels it launches for these operands:
 // QS_MX_NORM_ROUTE_*, 0 for an empty tensor, QS_ERR_*
 int mx_norm_route(const qs_mx_norm_quant_args& a, const NormAdd* add = nullptr) {
-    const bool layer = a.mode == QS_MX_NORM_LAYER, col = a.col_format != -1;
+    const bool layer = a.mode == QS_MX_NORM_LAYER;
     if (a.mode != QS_MX_NORM_RMS && !layer) return QS_ERR_ARG;
-    if (!a.x || (add && (!add->residual || !add->h)) || !a.row_codes || !a.row_scales || !a.rstd || (layer && !a.mean)) return QS_ERR_ARG;
-    if (!mx_format_ok(a.row_format) || (col && (!mx_format_ok(a.col_format) || !a.col_codes || !a.col_scales))) return QS_ERR_ARG;
+    if (!a.x || (add && (!add->residual || !add->h)) || !a.rstd || (layer && !a.mean) || !mxq2_pairs_by_format(a, true).ok) return QS_ERR_ARG;
     if (!(a.eps >= 0.0f) || a.eps > 3.0e38f) return QS_ERR_ARG;                  // (also refuses a NaN)
     if (a.R < 0 || a.C < 0) return QS_ERR_ARG;
     if (!dt_ok(a.xdt) || (add && !dt_ok(add->rdt))) return QS_ERR_DTYPE;
@@ -32,9 +29,7 @@ int mx_norm_route(const qs_mx_norm_quant_args& a, const NormAdd* add = nullptr) 
         return QS_ERR_ALIGN;
     if (add && (((uintptr_t)add->residual | (uintptr_t)add->h) & (dt_size(add->rdt) - 1)) != 0) return QS_ERR_ALIGN;
     if (a.R == 0 || a.C == 0) return 0;
-    if (a.R > INT64_MAX / a.C) return QS_ERR_ARG;
-    const int64_t tiles = ((a.R + kMxq2Rows - 1) / kMxq2Rows) * ((a.C + kMxq2Cols - 1) / kMxq2Cols);
-    if ((a.C + kMxq2Cols - 1) / kMxq2Cols > kMaxGrid || tiles > kMaxGrid) return QS_ERR_ARG;
+    if (a.R > INT64_MAX / a.C || !mxq2_grid_ok(a.R, a.C)) return QS_ERR_ARG;
     if (add && (a.R + kMxnStatRows - 1) / kMxnStatRows > kMaxGrid) return QS_ERR_ARG;
     const bool vec = a.C % QS_MX_BLOCK == 0 && aligned16(a.x) && aligned16(a.weight) && aligned16(a.bias) &&
                      (!add || (aligned16(add->residual) && aligned16(add->h)));
@@ -45,17 +40,13 @@ int mx_norm_route(const qs_mx_norm_quant_args& a, const NormAdd* add = nullptr) 
 template <bool VEC>
 void mx_norm_apply_enqueue(const qs_mx_norm_quant_args& a, const void* x, int xdt) {
     const bool layer = a.mode == QS_MX_NORM_LAYER, col = a.col_format != -1;
-    // a col pair that is not asked for keeps a valid descriptor the kernel never reads, and null pointers whatever the caller left there
-    const MxFormat fr = mx_format(a.row_format), fc = mx_format(col ? a.col_format : 0);
-    uint8_t *cc = col ? a.col_codes : nullptr, *cs = col ? a.col_scales : nullptr;
+    const Mxq2Launch l = mxq2_launch(a, true, col, a.R, a.C);
     const float* mean = layer ? a.mean : nullptr;
-    const int tiles_c = (int)((a.C + kMxq2Cols - 1) / kMxq2Cols);
-    const int64_t grid = ((a.R + kMxq2Rows - 1) / kMxq2Rows) * tiles_c;
-    const int row_vec = VEC && aligned4(a.row_codes), col_vec = VEC && col && a.R % 16 == 0 && aligned16(cc);
+    const int row_vec = VEC && mxq2_row_vec(l, 4), col_vec = VEC && col && a.R % 16 == 0 && aligned16(l.col_codes);
     with_dtype(xdt, [&](auto X) {
-        hipLaunchKernelGGL((mx_norm_apply_kernel<decltype(X)::value, VEC>), dim3((unsigned)grid), dim3(kMxq2Threads), 0,
-                           (hipStream_t)a.stream, fr, fc, x, a.weight, a.bias, (const float*)a.rstd, mean, a.row_codes, a.row_scales, cc,
-                           cs, a.R, a.C, tiles_c, row_vec, col_vec);
+        hipLaunchKernelGGL((mx_norm_apply_kernel<decltype(X)::value, VEC>), dim3((unsigned)l.tiles), dim3(kMxq2Threads), 0,
+                           (hipStream_t)a.stream, l.fr, l.fc, x, a.weight, a.bias, (const float*)a.rstd, mean, l.row_codes, l.row_scales,
+                           l.col_codes, l.col_scales, a.R, a.C, l.tiles_c, row_vec, col_vec);
         return 0;
     });
 }

@@ -5,12 +5,11 @@
 // Host side: argument checks, workspace layout, route, launch configuration.  No allocation, no synchronisation.
 #include <stddef.h>
 
-#include "qs_host.h"
+#include "qs_mx_quant2_host.h"
 #include "qs_mx_norm_bwd.h"
 
 namespace {
 
-inline bool aligned4(const void* p) { return (((uintptr_t)p) & 3u) == 0; }
 inline uint64_t up16(uint64_t n) { return (n + 15u) & ~(uint64_t)15u; }
 
 // the workspace: c1 [R] and, in layer mode, c2 [R] when dx is asked for; the partials of dweight and of dbias, [ceil(R / 128), C]
@@ -25,8 +24,8 @@ int norm_bwd_plan(int64_t R, int64_t C, bool layer, bool need_dx, bool need_cols
     if (R < 0 || C < 0) return QS_ERR_ARG;
     if (R == 0 || C == 0) return 0;
     if (R > INT64_MAX / C) return QS_ERR_ARG;
-    const int64_t tiles_r = (R + kMxq2Rows - 1) / kMxq2Rows, tiles_c = (C + kMxq2Cols - 1) / kMxq2Cols;
-    if (tiles_c > kMaxGrid || tiles_r * tiles_c > kMaxGrid || (R + kMxnStatRows - 1) / kMxnStatRows > kMaxGrid) return QS_ERR_ARG;
+    const int64_t tiles_r = mxq2_tiles_r(R);
+    if (!mxq2_grid_ok(R, C) || (R + kMxnStatRows - 1) / kMxnStatRows > kMaxGrid) return QS_ERR_ARG;
     uint64_t at = 0;
     if (need_dx) {
         out->c1 = at;
@@ -87,8 +86,8 @@ void norm_bwd_enqueue(const qs_mx_norm_bwd_res_args& a, const NormBwdPlan& plan)
     float* c2 = (a.dx && layer) ? (float*)(ws + plan.c2) : nullptr;
     float* pw = a.dweight ? (float*)(ws + plan.pw) : nullptr;
     float* pb = a.dbias ? (float*)(ws + plan.pb) : nullptr;
-    const int64_t tiles_r = (a.R + kMxq2Rows - 1) / kMxq2Rows;
-    const int tiles_c = (int)((a.C + kMxq2Cols - 1) / kMxq2Cols);
+    const int64_t tiles_r = mxq2_tiles_r(a.R);
+    const int tiles_c = (int)mxq2_tiles_c(a.C);
     hipStream_t s = (hipStream_t)a.stream;
     if (a.dx)
         hipLaunchKernelGGL((mx_norm_bwd_stats_kernel<XD, GD, VEC>), dim3((unsigned)((a.R + kMxnStatRows - 1) / kMxnStatRows)),

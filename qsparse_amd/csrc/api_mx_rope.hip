@@ -2,17 +2,10 @@
 // strided slices [R, C] of x are rotated by the [R, C / 2] tables in float32 and written, rounded once, to a dense y [G, R, C] in any
 // of the three dtypes -- one element-wise launch.  Its inverse flag makes it its own backward.
 // Host side: argument checks, route, launch configuration.  No allocation, no synchronisation.
-#include "qs_host.h"
+#include "qs_mx_quant2_host.h"
 #include "qs_mx_rope.h"
 
 namespace {
-
-// a * b into *out unless it passes INT64_MAX (a, b >= 0)
-bool mul_ok(int64_t a, int64_t b, int64_t* out) {
-    if (a != 0 && b > INT64_MAX / a) return false;
-    *out = a * b;
-    return true;
-}
 
 // the checks of qs_mx_rope_v, in qs_mx_quant2_batched_v's order, and the kernel it launches for these operands: QS_MX_ROPE_ROUTE_*, 0
 // for an empty tensor, QS_ERR_*
@@ -24,13 +17,8 @@ int mx_rope_route(const qs_mx_rope_args& a) {
         (((uintptr_t)a.cos) & 3u) != 0 || (((uintptr_t)a.sin) & 3u) != 0)
         return QS_ERR_ALIGN;
     if (a.G0 == 0 || a.G1 == 0 || a.R == 0 || a.C == 0) return 0;
-    if (a.x_stride_r < a.C || a.x_stride_g0 < 0 || a.x_stride_g1 < 0) return QS_ERR_ARG;
-    // the output's G R C and the last element of x, both within int64
-    int64_t G, n, e0, e1, er;
-    if (!mul_ok(a.G0, a.G1, &G) || !mul_ok(a.R, a.C, &n) || !mul_ok(G, n, &n)) return QS_ERR_ARG;
-    if (!mul_ok(a.G0 - 1, a.x_stride_g0, &e0) || !mul_ok(a.G1 - 1, a.x_stride_g1, &e1) || !mul_ok(a.R - 1, a.x_stride_r, &er))
-        return QS_ERR_ARG;
-    if (e0 > INT64_MAX - e1 || e0 + e1 > INT64_MAX - er || e0 + e1 + er > INT64_MAX - a.C) return QS_ERR_ARG;
+    int64_t G, n;
+    if (!mxq2_slices_ok(a, &G, &n)) return QS_ERR_ARG;
     const int64_t v = a.xdt == QS_F32 ? 4 : 8;
     // one lane per group of v columns: G R ceil(C / v) lanes in work-groups of kBlock
     if ((n + v - 1) / v + a.R * G > kMaxGrid * (int64_t)kBlock) return QS_ERR_ARG;

@@ -102,6 +102,13 @@ inline int mean_lanes(int64_t total) {
 constexpr size_t kLast2MaxLds = 63 * 1024;    // qs_mean_last2's [H*W + W + 8] float tile (a workgroup may hold 64 KiB)
 
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+inline bool aligned4(const void* p) { return (((uintptr_t)p) & 3u) == 0; }
+// a * b into *out unless it passes INT64_MAX (a, b >= 0)
+inline bool mul_ok(int64_t a, int64_t b, int64_t* out) {
+    if (a != 0 && b > INT64_MAX / a) return false;
+    *out = a * b;
+    return true;
+}
 inline size_t dt_size(int dt) { return dt == QS_F32 ? 4 : 2; }
 inline bool mx_format_ok(int f) { return f >= 0 && f <= QS_MX_FP4_E2M1; }      // enum qs_mx_format
 constexpr int64_t kMaxGrid = 0x7fffffff;

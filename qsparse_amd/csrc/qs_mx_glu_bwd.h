@@ -5,8 +5,9 @@
 // is computed in registers from ONE read of dh [T, H] and v [T, 2 H] and leaves as the two MX pairs of qs_mx_quant2.h -- row codes
 // [T, 2 H] / scales [T, 2 H / 32] and, transposed, col codes [2 H, T] / scales [2 H, ceil(T / 32)].  dv itself is float32, is never
 // rounded to a narrower type and never exists in memory.  The per-element arithmetic of the quantizer is qs_mx.h's, act is
-// mx_glu_act of qs_mx_glu.h.  This file states the loads and the derivative; what follows once a value is a float under a scale --
-// the row block's maximum, the encode step, the code stores, the whole of phase 2 -- is qs_mx_quant2.h's shared functions.
+// mx_glu_act of qs_mx_glu.h.  This file states the loads' operands and the derivative; the four-element load (mxq2_load4f), the staging
+// store (mxq2_stage), the row pair of a pass (mxq2_emit_row) and the whole of phase 2 (mxq2_col_phase) are qs_mx_quant2.h's shared
+// functions.
 //
 // A work-group of 256 lanes owns mxq2_tile's tile, 128 rows x 64 dv columns = the hidden units [32 q, 32 q + 32) of 128 tokens: the
 // interleave puts the gate and the up column of a hidden unit into the same tile, 32 columns apart.
@@ -38,26 +39,6 @@ __device__ __forceinline__ float mx_glu_act_grad(float g, int act) {
     return gelu_grad_factor(g);
 }
 
-// four consecutive elements of a row as float32: one aligned load of 16 (float32) or 8 bytes (VEC), or four element loads
-template <int DT, bool VEC>
-__device__ __forceinline__ void mxgb_load4(const void* __restrict__ p, int64_t e, bool in, float (&out)[4]) {
-    using raw_t = typename Mxq2Raw<DT>::type;
-    if constexpr (VEC && DT == QS_F32) {
-        u32x4 a = {0u, 0u, 0u, 0u};
-        if (in) a = ld16<true>((const u32x4*)((const raw_t*)p + e));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) out[j] = __uint_as_float(a[j]);
-    } else if constexpr (VEC) {
-        u32x2 a = {0u, 0u};
-        if (in) a = __builtin_nontemporal_load((const u32x2*)((const raw_t*)p + e));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) out[j] = mxq2_widen<DT>((raw_t)(a[j >> 1] >> ((j & 1) * 16)));
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) out[j] = in ? mxq2_widen<DT>(((const raw_t*)p)[e + j]) : 0.0f;
-    }
-}
-
 constexpr int kMxgbUnits = 4;                                   // hidden units per lane and pass
 constexpr int kMxgbLpr = QS_MX_BLOCK / kMxgbUnits;              // 8 lanes per tile row (and per row block)
 constexpr int kMxgbRpp = kMxq2Threads / kMxgbLpr;               // 32 tile rows per pass
@@ -82,46 +63,32 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_glu_bwd_quant2_kernel(MxForma
 
     // ---- phase 1: load, derivative, stage, row pair --------------------------------------------------------------------------
     const int lrow = tid / kMxgbLpr, t0 = (tid % kMxgbLpr) * kMxgbUnits;
+    const int64_t gg = c0 + t0, gh = q * QS_MX_BLOCK + t0;      // the lane's first gate column of v / dv and its first hidden unit
     float g[kMxgbPasses][4], u[kMxgbPasses][4], d[kMxgbPasses][4];
 #pragma unroll
-    for (int p = 0; p < kMxgbPasses; ++p) {
+    for (int p = 0; p < kMxgbPasses; ++p) {                     // (the loads' column tests never bind: C % 64 == 0)
         const int64_t gr = r0 + p * kMxgbRpp + lrow;
-        mxgb_load4<VDT, VEC>(v, gr * C + c0 + t0, gr < R, g[p]);
-        mxgb_load4<VDT, VEC>(v, gr * C + c0 + QS_MX_BLOCK + t0, gr < R, u[p]);
-        mxgb_load4<DDT, VEC>(dh, gr * H + q * QS_MX_BLOCK + t0, gr < R, d[p]);
+        mxq2_load4f<VDT, VEC>(v, gr * C + gg, gr < R, gg, C, g[p]);
+        mxq2_load4f<VDT, VEC>(v, gr * C + gg + QS_MX_BLOCK, gr < R, gg + QS_MX_BLOCK, C, u[p]);
+        mxq2_load4f<DDT, VEC>(dh, gr * H + gh, gr < R, gh, H, d[p]);
     }
 #pragma unroll
     for (int p = 0; p < kMxgbPasses; ++p) {
-        const int64_t gr = r0 + p * kMxgbRpp + lrow;
+        const int trow = p * kMxgbRpp + lrow;
+        const int64_t gr = r0 + trow;
         float dv[2][4];                                         // [0]: the gate block's columns c0 + t0 .., [1]: the up block's, 32 on
-        uint32_t am[2] = {0u, 0u};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             dv[0][j] = (d[p][j] * u[p][j]) * mx_glu_act_grad(g[p][j], act);
             dv[1][j] = d[p][j] * mx_glu_act(g[p][j], act);
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const uint32_t a = mx_abs_bits(dv[b][j]);
-                am[b] = a > am[b] ? a : am[b];
-            }
         }
-        if (col_codes) {                                        // (rows past T hold +0: every input was taken as 0)
-            float* trow = tile + (p * kMxgbRpp + lrow) * kMxq2Cols + t0;
-            *(u32x4*)trow = u32x4{__float_as_uint(dv[0][0]), __float_as_uint(dv[0][1]), __float_as_uint(dv[0][2]), __float_as_uint(dv[0][3])};
-            *(u32x4*)(trow + QS_MX_BLOCK) =
-                u32x4{__float_as_uint(dv[1][0]), __float_as_uint(dv[1][1]), __float_as_uint(dv[1][2]), __float_as_uint(dv[1][3])};
-        }
-        if (!row_codes) continue;                               // (kernel-uniform)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const MxScale s = mx_scale(mxq2_block_max<kMxgbLpr>(am[b]), fr);
-            const int64_t gc = c0 + b * QS_MX_BLOCK + t0;       // (a multiple of 4, as C and sr.base: one Philox call for the four)
-            uint32_t c[4];
-            mx_encode_run<4, SR, true>(dv[b], s, fr, key, 0u, sr.base + (uint64_t)(gr * C + gc), c);
-            if (gr < R) {
-                if ((tid % kMxgbLpr) == 0) row_scales[gr * nbc + (gc >> 5)] = (uint8_t)s.byte;
-                mxq2_store_row<4, true>(row_codes + gr * C + gc, c, VEC && row_vec, gc, C);
-            }
+        for (int b = 0; b < 2; ++b) {                           // (rows past T hold +0: every input was taken as 0)
+            const int64_t gc = gg + b * QS_MX_BLOCK;            // (a multiple of 4, as C and sr.base: one Philox call for the four)
+            if (col_codes) mxq2_stage<4>(tile, trow, t0 + b * QS_MX_BLOCK, dv[b]);
+            if (row_codes)                                      // (kernel-uniform, as col_codes; FULL: gc + 4 <= C)
+                mxq2_emit_row<4, VEC, true, SR, true>(dv[b], fr, row_codes, row_scales, gr, gc, R, C, nbc, row_vec, key,
+                                                      sr.base + (uint64_t)(gr * C + gc));
         }
     }
     if (!col_codes) return;                                     // (kernel-uniform)

@@ -13,6 +13,9 @@
 //     16-byte store per lane and pass (the 16 lanes of a row write 64 consecutive dwords: no bank is hit twice per 32-bank phase).
 //   Phase 2 is qs_mx_quant2.h's mxq2_col_phase on a float32 tile, with `col_vec` as its run-time store rule: lane (c = tid & 63, b = tid >> 6) walks the 32 rows of a column block, the
 //     transposition happens in registers.  Elements outside [R, C] are +0 in the tile, as the quantizer's short last blocks.
+// The apply kernel's four-element load is qs_mx_quant2.h's mxq2_load4.  Its staging store and the row pair of a pass stay its OWN text
+// and do not call mxq2_stage / mxq2_emit_row: through them the compiler kept 68 - 80 VGPRs in place of 94 - 108, another occupancy
+// step, and the calls of tools/bench_mx_norm.py were 1.3 - 2.3 % slower than the parent's.
 // The per-element arithmetic of the quantizer is qs_mx.h's; nothing of it is restated here.  No atomics, no workspace beyond rstd /
 // mean; a null col pair skips the LDS traffic, the barrier and phase 2 (kernel-uniform).  VEC = false is the same text with element
 // accesses, each predicated on its own index: any R, C >= 1, any element-aligned base.  Rounding is to nearest only.
@@ -192,7 +195,7 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_add_norm_stats_kernel(const v
 
 constexpr int kMxnV = 4;                                        // elements per lane and pass of the apply kernel
 constexpr int kMxnLpr = kMxq2Cols / kMxnV;                      // 16 lanes per tile row
-constexpr int kMxnLpb = QS_MX_BLOCK / kMxnV;                    // 8 lanes per row block
+constexpr int kMxnLpb = QS_MX_BLOCK / kMxnV;                    // 8 lanes per row block (qs_mx_softmax_train.h's own row pair)
 constexpr int kMxnRpp = kMxq2Threads / kMxnLpr;                 // 16 tile rows per pass
 constexpr int kMxnPasses = kMxq2Rows / kMxnRpp;                 // 8
 
@@ -221,22 +224,7 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_norm_apply_kernel(MxFormat fr
 #pragma unroll
     for (int p = 0; p < kMxnPasses; ++p) {
         const int64_t gr = r0 + p * kMxnRpp + lrow;
-        if constexpr (VEC) {                                    // (C % 4 == 0: the lane's 4 elements are inside or outside together)
-            if constexpr (XDT == QS_F32) {
-                u32x4 a = {0u, 0u, 0u, 0u};
-                if (gr < R && gc < C) a = ld16<true>((const u32x4*)((const raw_t*)x + gr * C + gc));
-#pragma unroll
-                for (int j = 0; j < kMxnV; ++j) raw[p][j] = a[j];
-            } else {
-                u32x2 a = {0u, 0u};
-                if (gr < R && gc < C) a = __builtin_nontemporal_load((const u32x2*)((const raw_t*)x + gr * C + gc));
-#pragma unroll
-                for (int j = 0; j < kMxnV; ++j) raw[p][j] = (raw_t)(a[j >> 1] >> ((j & 1) * 16));
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < kMxnV; ++j) raw[p][j] = (gr < R && gc + j < C) ? ((const raw_t*)x)[gr * C + gc + j] : (raw_t)0;
-        }
+        mxq2_load4<XDT, VEC>(x, gr * C + gc, gr < R, gc, C, raw[p]);
         rs[p] = gr < R ? rstd[gr] : 0.0f;
         mu[p] = (mean && gr < R) ? mean[gr] : 0.0f;
     }

@@ -6,8 +6,8 @@
 //     into the workspace.  A lane takes 8 consecutive elements of dxhat, x and weight per pass of 512; both sums go through
 //     mxn_add_quads / mxn_fold of qs_mx_norm.h, so their order is the forward's by construction.  One walk over the row.
 //   mx_norm_bwd_apply_kernel   the 128 x 64 tile of mx_norm_apply_kernel with its lane layout: a lane holds 4 consecutive elements of
-//     a row in 8 passes of 16 rows; the loads of a tile -- dxhat, x, and per row rstd, mean, c1, c2 -- are all issued before the first
-//     use.  It writes dx (rounded once to x's dtype; with RES, dresidual's tile is one more of those loads and is added to the float32
+//     a row in 8 passes of 16 rows; the loads of a tile -- dxhat, x (qs_mx_quant2.h's mxq2_load4, the one thing this kernel borrows
+//     from the tile's phase 1), and per row rstd, mean, c1, c2 -- are all issued before the first use.  It writes dx (rounded once to x's dtype; with RES, dresidual's tile is one more of those loads and is added to the float32
 //     value in front of that rounding) and keeps, per lane and column, the sums of dxhat xhat and of dxhat over its 8
 //     rows l, l + 16, .. l + 112 in ascending order: the header's 16 strided partial sums of a row tile.  Those meet in LDS
 //     ([2][16][64] float32, one 16-byte store per lane and array: the 16 lanes of a row write 64 consecutive dwords), where the
@@ -63,29 +63,6 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_norm_bwd_stats_kernel(const v
     }
 }
 
-// the lane's 4 elements at `off` of a tensor of dtype DT as raw bits; what lies outside is 0
-template <int DT, bool VEC>
-__device__ __forceinline__ void mxnb_load4(const void* __restrict__ p, int64_t off, bool row_in, int64_t gc, int64_t C,
-                                           typename Mxq2Raw<DT>::type (&raw)[kMxnV]) {
-    using raw_t = typename Mxq2Raw<DT>::type;
-    if constexpr (VEC) {                                        // (C % 4 == 0: the lane's 4 elements are inside or outside together)
-        if constexpr (DT == QS_F32) {
-            u32x4 a = {0u, 0u, 0u, 0u};
-            if (row_in && gc < C) a = ld16<true>((const u32x4*)((const raw_t*)p + off));
-#pragma unroll
-            for (int j = 0; j < kMxnV; ++j) raw[j] = a[j];
-        } else {
-            u32x2 a = {0u, 0u};
-            if (row_in && gc < C) a = __builtin_nontemporal_load((const u32x2*)((const raw_t*)p + off));
-#pragma unroll
-            for (int j = 0; j < kMxnV; ++j) raw[j] = (raw_t)(a[j >> 1] >> ((j & 1) * 16));
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < kMxnV; ++j) raw[j] = (row_in && gc + j < C) ? ((const raw_t*)p)[off + j] : (raw_t)0;
-    }
-}
-
 constexpr int kMxnbParts = kMxnRpp;                             // 16 strided partial sums per column of a row tile
 
 // `dx`, `pw`, `pb` are each nullable (kernel-uniform): dx with c1 (and c2 in layer mode), pw / pb the partials of dweight / dbias.
@@ -117,9 +94,9 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_norm_bwd_apply_kernel(const v
     for (int p = 0; p < kMxnPasses; ++p) {
         const int64_t gr = r0 + p * kMxnRpp + lrow;
         const bool row_in = gr < R;
-        mxnb_load4<XDT, VEC>(x, gr * C + gc, row_in, gc, C, xr[p]);
-        mxnb_load4<GDT, VEC>(dxhat, gr * C + gc, row_in, gc, C, gr_[p]);
-        if constexpr (RES) mxnb_load4<XDT, VEC>(dres, gr * C + gc, row_in, gc, C, rr[p]);
+        mxq2_load4<XDT, VEC>(x, gr * C + gc, row_in, gc, C, xr[p]);
+        mxq2_load4<GDT, VEC>(dxhat, gr * C + gc, row_in, gc, C, gr_[p]);
+        if constexpr (RES) mxq2_load4<XDT, VEC>(dres, gr * C + gc, row_in, gc, C, rr[p]);
         rs[p] = row_in ? rstd[gr] : 0.0f;
         mu[p] = (mean && row_in) ? mean[gr] : 0.0f;
         k1[p] = (dx && row_in) ? c1[gr] : 0.0f;

@@ -48,7 +48,8 @@ __device__ __forceinline__ float mxq2_widen(typename Mxq2Raw<XDT>::type raw) {
 
 __device__ __forceinline__ uint32_t mxq2_pack4(const uint32_t* c) { return c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24); }
 
-// ---- what every kernel on this tile shares (this file, qs_mx_glu_bwd.h, qs_mx_norm.h): all that happens once a value is a float ----
+// ---- what every kernel on this tile shares (this file, qs_mx_glu_bwd.h, qs_mx_norm.h, qs_mx_softmax_train.h, qs_mx_rope.h; the loads
+// also qs_mx_norm_bwd.h): all that happens once a value is a float, and phase 1's own steps further down (3z) ----
 // the maximum of `am` over the LPB adjacent lanes of a row block
 template <int LPB>
 __device__ __forceinline__ uint32_t mxq2_block_max(uint32_t am) {
@@ -103,6 +104,96 @@ __device__ __forceinline__ void mxq2_store_row(uint8_t* out, const uint32_t (&c)
     }
 }
 
+// ---- phase 1 of the kernels on this tile: the kernels state their loads' operands and the arithmetic between load and
+// emit; the load of a lane's four elements, the staging store, the row-pair emit and the slice decode stand here once.  (The softmax
+// kernels and the norm kernel's emit keep a text of their own: measured slower, or another occupancy step, on these.) ----
+// the lane's four consecutive elements at p + e (in elements of DT), column gc of a row, as raw bits: those below `lim` of a row that
+// exists (`row`); the others are 0 and are not loaded.  VEC: gc % 4 == 0 and the four are in memory together -- one non-temporal load
+// of 16 (float32) or 8 bytes under `gc < lim`; otherwise four element loads, each under `gc + j < lim`
+template <int DT, bool VEC>
+__device__ __forceinline__ void mxq2_load4(const void* __restrict__ p, int64_t e, bool row, int64_t gc, int64_t lim,
+                                           typename Mxq2Raw<DT>::type (&raw)[4]) {
+    using raw_t = typename Mxq2Raw<DT>::type;
+    if constexpr (VEC && DT == QS_F32) {
+        u32x4 a = {0u, 0u, 0u, 0u};
+        if (row && gc < lim) a = ld16<true>((const u32x4*)((const raw_t*)p + e));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) raw[j] = a[j];
+    } else if constexpr (VEC) {
+        u32x2 a = {0u, 0u};
+        if (row && gc < lim) a = __builtin_nontemporal_load((const u32x2*)((const raw_t*)p + e));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) raw[j] = (raw_t)(a[j >> 1] >> ((j & 1) * 16));
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) raw[j] = (row && gc + j < lim) ? ((const raw_t*)p)[e + j] : (raw_t)0;
+    }
+}
+
+// the same four, widened at once
+template <int DT, bool VEC>
+__device__ __forceinline__ void mxq2_load4f(const void* __restrict__ p, int64_t e, bool row, int64_t gc, int64_t lim, float (&out)[4]) {
+    typename Mxq2Raw<DT>::type raw[4];
+    mxq2_load4<DT, VEC>(p, e, row, gc, lim, raw);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out[j] = mxq2_widen<DT>(raw[j]);
+}
+
+// a lane's V floats into the float tile [128][64] at tile row `trow`, column `lcol`: 16-byte stores
+template <int V>
+__device__ __forceinline__ void mxq2_stage(float* tile, int trow, int lcol, const float (&y)[V]) {
+#pragma unroll
+    for (int j = 0; j < V; j += 4)
+        *(u32x4*)(tile + trow * kMxq2Cols + lcol + j) =
+            u32x4{__float_as_uint(y[j]), __float_as_uint(y[j + 1]), __float_as_uint(y[j + 2]), __float_as_uint(y[j + 3])};
+}
+
+// The row pair of one pass: the lane's V values `y` of row gr from column gc on -- a row block is the 32 / V adjacent lanes -- to the
+// block's scale byte (stored by its first lane) and the lane's V codes.  `index`: the absolute index of the lane's first code in
+// stream 0 (sr.base included; unused without SR).  FULL, `row_vec`: mxq2_store_row's; QUAD: mx_encode_run's.  Every lane of the block
+// must call it (the maximum is a shuffle); what lies outside [R, C] is not stored.
+template <int V, bool VEC, bool FULL, bool SR, bool QUAD>
+__device__ __forceinline__ void mxq2_emit_row(const float (&y)[V], MxFormat fr, uint8_t* __restrict__ row_codes,
+                                              uint8_t* __restrict__ row_scales, int64_t gr, int64_t gc, int64_t R, int64_t C, int64_t nbc,
+                                              int row_vec, MxSrKey key, uint64_t index) {
+    constexpr int LPB = QS_MX_BLOCK / V;                  // lanes per row block
+    uint32_t am = 0;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const uint32_t a = mx_abs_bits(y[j]);
+        am = a > am ? a : am;
+    }
+    const MxScale s = mx_scale(mxq2_block_max<LPB>(am), fr);
+    uint32_t c[V];
+    mx_encode_run<V, SR, QUAD>(y, s, fr, key, 0u, index, c);
+    if (gr < R && gc < C) {
+        if ((threadIdx.x % LPB) == 0) row_scales[gr * nbc + (gc >> 5)] = (uint8_t)s.byte;
+        mxq2_store_row<V, FULL>(row_codes + gr * C + gc, c, VEC && row_vec, gc, C);
+    }
+}
+
+// Where the tile of this block lies, for the kernels that fold G slices into the linear block index as mx_bmm_kernel does (gridDim.y
+// stops at 65535):  block = g * tiles + tile,  tile = tile_r * tiles_c + tile_c,  tiles = tiles_r * tiles_c per slice
+struct Mxq2At {
+    int64_t g, r0, c0;                                    // slice, first row and column inside the slice
+};
+__device__ __forceinline__ Mxq2At mxq2_at(int tiles, int tiles_c) {
+    const unsigned t = blockIdx.x % (unsigned)tiles;
+    return Mxq2At{(int64_t)(blockIdx.x / (unsigned)tiles), (int64_t)(t / (unsigned)tiles_c) * kMxq2Rows,
+                  (int64_t)(t % (unsigned)tiles_c) * kMxq2Cols};
+}
+
+// the four output pointers moved to slice g of the dense outputs [G, R, C] / [G, C, R]; a null pair stays null
+__device__ __forceinline__ void mxq2_to_slice(int64_t g, int64_t R, int64_t C, uint8_t* __restrict__& row_codes,
+                                              uint8_t* __restrict__& row_scales, uint8_t* __restrict__& col_codes,
+                                              uint8_t* __restrict__& col_scales) {
+    const int64_t nbc = (C + QS_MX_BLOCK - 1) / QS_MX_BLOCK, nbr = (R + QS_MX_BLOCK - 1) / QS_MX_BLOCK;
+    if (row_codes) row_codes += g * R * C;
+    row_scales += g * R * nbc;
+    if (col_codes) col_codes += g * C * R;
+    col_scales += g * C * nbr;
+}
+
 // Phase 2, after the barrier: lane (cc = tid & 63, cb = tid >> 6) walks the column block tile[32 cb .. 32 cb + 31][cc] and writes its
 // 32 codes and its scale byte into the transposed col pair.  The tile holds raw elements of type XDT, or floats (widened by nothing).
 // `col_vec`: R % 16 == 0 and col_codes is 16-byte aligned, so each half of the block is inside or outside as a whole and leaves as one
@@ -142,7 +233,8 @@ __device__ __forceinline__ void mxq2_col_phase(const T* tile, MxFormat fc, uint8
 
 // The tile's two phases as a function of the bases and the row pitch of x: the tile at (r0, c0) of x [R, C] whose row r begins at
 // x + r * pitch.  mx_quant2_batched_kernel calls it with ONE SLICE's x, outputs, R and C and the slice's row stride, mx_quant2_kernel
-// with the whole tensor and pitch = C.  Only the loads are the tile's own; everything behind them is the shared functions above.
+// with the whole tensor and pitch = C.  Only the loads (16 bytes per lane, the raw LDS tile) are the tile's own; the row pair is
+// mxq2_emit_row, phase 2 mxq2_col_phase.
 // `row_vec`: row_codes is aligned to the V bytes a lane stores at once (VEC only; otherwise byte stores).  `sr.base` is the index of
 // the pairs' first code: index_base, plus g R C for slice g.
 template <int XDT, bool VEC, bool SR>
@@ -152,7 +244,6 @@ __device__ __forceinline__ void mxq2_tile(MxFormat fr, MxFormat fc, const void* 
                                           int64_t r0, int64_t c0, int row_vec, MxSr sr) {
     using raw_t = typename Mxq2Raw<XDT>::type;
     constexpr int V = XDT == QS_F32 ? 4 : 8;              // elements per lane and pass: 16 bytes
-    constexpr int LPB = QS_MX_BLOCK / V;                  // lanes per row block
     constexpr int LPR = kMxq2Cols / V;                    // lanes per tile row
     constexpr int RPP = kMxq2Threads / LPR;               // tile rows per pass
     constexpr int PASSES = kMxq2Rows / RPP;
@@ -192,20 +283,11 @@ __device__ __forceinline__ void mxq2_tile(MxFormat fr, MxFormat fc, const void* 
         for (int p = 0; p < PASSES; ++p) {
             const int64_t gr = r0 + p * RPP + lrow;
             float v[V];
-            uint32_t am = 0;
 #pragma unroll
-            for (int j = 0; j < V; ++j) {
-                v[j] = mxq2_widen<XDT>(raw[p][j]);
-                const uint32_t a = mx_abs_bits(v[j]);
-                am = a > am ? a : am;
-            }
-            const MxScale s = mx_scale(mxq2_block_max<LPB>(am), fr);
-            uint32_t c[V];                                // (VEC: C % V == 0, gc % V == 0: the lane's first index is a multiple of 4)
-            mx_encode_run<V, SR, VEC>(v, s, fr, key, 0u, sr.base + (uint64_t)(gr * C + gc), c);
-            if (gr < R && gc < C) {
-                if ((tid % LPB) == 0) row_scales[gr * nbc + (gc >> 5)] = (uint8_t)s.byte;
-                mxq2_store_row<V, VEC>(row_codes + gr * C + gc, c, VEC && row_vec, gc, C);
-            }
+            for (int j = 0; j < V; ++j) v[j] = mxq2_widen<XDT>(raw[p][j]);
+            // (VEC: C % V == 0, gc % V == 0: the lane's first index is a multiple of 4)
+            mxq2_emit_row<V, VEC, VEC, SR, VEC>(v, fr, row_codes, row_scales, gr, gc, R, C, nbc, row_vec, key,
+                                                sr.base + (uint64_t)(gr * C + gc));
         }
     }
     if (!col_codes) return;                               // (kernel-uniform)
@@ -231,9 +313,7 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_quant2_kernel(MxFormat fr, Mx
 
 // The batched, strided form (include/qsparse_hip.h, "MX batched two-way quantizer"): G = G0 G1 slices [R, C] of x, slice g = g0 G1 +
 // g1 at x + g0 sg0 + g1 sg1 with the row pitch `pitch` (all in elements), dense outputs [G, R, C] / [G, C, R].  One work-group per tile
-// per slice, the slice folded into the linear block index as mx_bmm_kernel does (gridDim.y stops at 65535):
-//   block = g * tiles + tile,  tile = tile_r * tiles_c + tile_c,  tiles = tiles_r * tiles_c
-// A tile lies inside one slice and mxq2_tile predicates on that slice's R and C: no block spans two slices, nothing of slice g + 1
+// per slice, the slice folded into the linear block index (mxq2_at).  A tile lies inside one slice and mxq2_tile predicates on that slice's R and C: no block spans two slices, nothing of slice g + 1
 // is read for the short last block of slice g.  The random word of a code is indexed in the whole dense output: base + g R C.
 template <int XDT, bool VEC, bool SR>
 __global__ __launch_bounds__(kMxq2Threads) void mx_quant2_batched_kernel(MxFormat fr, MxFormat fc, const void* __restrict__ x,
@@ -242,14 +322,11 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_quant2_batched_kernel(MxForma
                                                                          uint8_t* __restrict__ col_codes, uint8_t* __restrict__ col_scales,
                                                                          int64_t R, int64_t C, int tiles, int tiles_c, int row_vec, MxSr sr) {
     using raw_t = typename Mxq2Raw<XDT>::type;
-    const unsigned t = blockIdx.x % (unsigned)tiles;
-    const int64_t g = blockIdx.x / (unsigned)tiles;
-    const int64_t r0 = (int64_t)(t / (unsigned)tiles_c) * kMxq2Rows, c0 = (int64_t)(t % (unsigned)tiles_c) * kMxq2Cols;
-    const int64_t nbc = (C + QS_MX_BLOCK - 1) / QS_MX_BLOCK, nbr = (R + QS_MX_BLOCK - 1) / QS_MX_BLOCK;
-    sr.base += (uint64_t)(g * R * C);
-    mxq2_tile<XDT, VEC, SR>(fr, fc, (const raw_t*)x + (g / G1) * sg0 + (g % G1) * sg1, pitch, row_codes ? row_codes + g * R * C : nullptr,
-                            row_scales + g * R * nbc, col_codes ? col_codes + g * C * R : nullptr, col_scales + g * C * nbr, R, C, r0, c0,
-                            row_vec, sr);
+    const Mxq2At at = mxq2_at(tiles, tiles_c);
+    mxq2_to_slice(at.g, R, C, row_codes, row_scales, col_codes, col_scales);
+    sr.base += (uint64_t)(at.g * R * C);
+    mxq2_tile<XDT, VEC, SR>(fr, fc, (const raw_t*)x + (at.g / G1) * sg0 + (at.g % G1) * sg1, pitch, row_codes, row_scales, col_codes,
+                            col_scales, R, C, at.r0, at.c0, row_vec, sr);
 }
 
 }  // namespace qs

@@ -18,7 +18,10 @@
 // mx_rope_quant2_kernel is mx_quant2_batched_kernel's tile (128 x 64, 256 lanes, the slice folded into the linear block index) with
 // this as phase 1: the passes are taken in groups of kRopeGroup whose loads -- x, partner, tables -- are all issued before the first
 // use; the rotated float32 values go to a float LDS tile [128][64] (32 KB, as mx_norm_apply_kernel stages its values), the row pair is
-// encoded from registers (mx_encode_run), phase 2 is mxq2_col_phase.  A null col pair skips LDS and the barrier.
+// encoded from registers, phase 2 is mxq2_col_phase.  A null col pair skips LDS and the barrier.  The kernel states its loads (a lane's
+// V elements, its partners and the tables: rope_load, whose half layout reads every line twice and so loads it plainly), the rotation and
+// kRopeGroup; the slice decode (mxq2_at, mxq2_to_slice), the staging store (mxq2_stage) and the row pair of a pass (mxq2_emit_row) are
+// qs_mx_quant2.h's.
 // mx_rope_kernel is the element-wise form: one lane per V columns, dense output in any of the three dtypes.
 #pragma once
 #include "qs_mx_quant2.h"
@@ -153,7 +156,6 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_rope_quant2_kernel(MxFormat f
                                                                       int inverse) {
     using raw_t = typename Mxq2Raw<XDT>::type;
     constexpr int V = RopeLane<XDT>::V;
-    constexpr int LPB = QS_MX_BLOCK / V;                        // lanes per row block
     constexpr int LPR = kMxq2Cols / V;                          // lanes per tile row
     constexpr int RPP = kMxq2Threads / LPR;                     // tile rows per pass
     constexpr int PASSES = kMxq2Rows / RPP;
@@ -161,16 +163,12 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_rope_quant2_kernel(MxFormat f
     __shared__ __attribute__((aligned(16))) float tile[kMxq2Rows * kMxq2Cols];
 
     const int tid = threadIdx.x;
-    const unsigned t = blockIdx.x % (unsigned)tiles;
-    const int64_t g = blockIdx.x / (unsigned)tiles;
-    const int64_t r0 = (int64_t)(t / (unsigned)tiles_c) * kMxq2Rows, c0 = (int64_t)(t % (unsigned)tiles_c) * kMxq2Cols;
+    const Mxq2At at = mxq2_at(tiles, tiles_c);
+    const int64_t r0 = at.r0, c0 = at.c0;
     const int64_t nbc = (C + QS_MX_BLOCK - 1) / QS_MX_BLOCK, nbr = (R + QS_MX_BLOCK - 1) / QS_MX_BLOCK;
     const int64_t h = C >> 1;
-    const raw_t* xs = (const raw_t*)x + (g / G1) * sg0 + (g % G1) * sg1;
-    if (row_codes) row_codes += g * R * C;
-    row_scales += g * R * nbc;
-    if (col_codes) col_codes += g * C * R;
-    col_scales += g * C * nbr;
+    const raw_t* xs = (const raw_t*)x + (at.g / G1) * sg0 + (at.g % G1) * sg1;
+    mxq2_to_slice(at.g, R, C, row_codes, row_scales, col_codes, col_scales);
 
     // ---- phase 1: load, rotate, stage, row pair ------------------------------------------------------------------------------
     const int lrow = tid / LPR, lcol = (tid % LPR) * V;
@@ -191,27 +189,9 @@ __global__ __launch_bounds__(kMxq2Threads) void mx_rope_quant2_kernel(MxFormat f
             const int64_t gr = r0 + trow;
             float y[V];
             rope_rotate<XDT, IL>(L[q], gc, h, inverse, y);
-            if (col_codes) {
-#pragma unroll
-                for (int j = 0; j < V; j += 4)
-                    *(u32x4*)(tile + trow * kMxq2Cols + lcol + j) =
-                        u32x4{__float_as_uint(y[j]), __float_as_uint(y[j + 1]), __float_as_uint(y[j + 2]), __float_as_uint(y[j + 3])};
-            }
-            if (row_codes) {
-                uint32_t am = 0;
-#pragma unroll
-                for (int j = 0; j < V; ++j) {
-                    const uint32_t a = mx_abs_bits(y[j]);
-                    am = a > am ? a : am;
-                }
-                const MxScale s = mx_scale(mxq2_block_max<LPB>(am), fr);
-                uint32_t c[V];
-                mx_encode_run<V, false, false>(y, s, fr, MxSrKey{0u, 0u}, 0u, 0ull, c);
-                if (gr < R && gc < C) {
-                    if ((tid % LPB) == 0) row_scales[gr * nbc + (gc >> 5)] = (uint8_t)s.byte;
-                    mxq2_store_row<V, VEC>(row_codes + gr * C + gc, c, VEC && row_vec, gc, C);
-                }
-            }
+            if (col_codes) mxq2_stage<V>(tile, trow, lcol, y);
+            if (row_codes)                                      // (kernel-uniform, as col_codes)
+                mxq2_emit_row<V, VEC, VEC, false, false>(y, fr, row_codes, row_scales, gr, gc, R, C, nbc, row_vec, MxSrKey{0u, 0u}, 0ull);
         }
     }
     if (!col_codes) return;                                     // (kernel-uniform)

@@ -17,7 +17,9 @@
 //     the words are those qs_mx_quant2_batched_v draws for ds [G, T, S] -- stream 0 at index (g T + t) S + j for the row pair, stream 1
 //     at (g S + j) T + t for the col pair.
 // What follows once a value is a float under a scale -- the block maximum, the encode step, the code stores, the whole of phase 2 --
-// is qs_mx_quant2.h's shared functions.  No atomics; a null pair skips its phase, a null col pair also the LDS traffic and the barrier
+// is qs_mx_quant2.h's shared functions.  Phase 1 keeps its OWN statement here (mst_load4, mst_tile, mst_emit) and does not call
+// qs_mx_quant2.h's mxq2_load4f / mxq2_at / mxq2_emit_row: on them four VEC instantiations of the backward kernel went from 91 - 96 to
+// 97 - 103 VGPRs, a wave per SIMD fewer.  No atomics; a null pair skips its phase, a null col pair also the LDS traffic and the barrier
 // (kernel-uniform).  VEC = false is the same text with element accesses, each predicated on its own index: any T, S >= 1, any
 // element-aligned base.  A causal row loads nothing of s or the mask at or behind its limit.
 #pragma once

@@ -15,14 +15,31 @@ CPU path, at the smallest shapes that reach each combination:
 
 test_mx_quant2_gpu.py, test_mx_quant2_batched_gpu.py, test_mx_glu_train_gpu.py and test_mx_norm_gpu.py reach R = 144 too, with other
 formats, against other references or with both pairs only; the cases here are the ones named above in one place, per format width
-(FP8, FP6, FP4 on each side) and for float32 and bfloat16."""
+(FP8, FP6, FP4 on each side) and for float32 and bfloat16.
+
+And what only the parameters of the shared PHASE 1 tell apart (mxq2_load4, mxq2_stage, mxq2_emit_row, mxq2_at / mxq2_to_slice, called
+by mxq2_tile, the GLU and the RoPE kernel, the load also by the norm kernel; the two softmax kernels and the norm kernel's emit state
+the same steps themselves, DESIGN.md 3z, and are pinned here alike), for the six kernels on the tile at shapes the other files do not have:
+
+    all six, PLAIN, [130, 36], [33, 68]  every input one element off its 16 bytes, so that every kernel takes element accesses: a lane
+                                  group cut by the edge (36 = 32 + 4: half a two-byte lane's 8; 68 = 64 + 4: a second tile of one
+                                  lane) and rows cut inside a pass (130 = 128 + 2, 33).  Row pair alone, col pair alone, both -- the
+                                  norm and the forward softmax kernel have no call without a row pair -- nearest and, where the kernel
+                                  has it, stochastic; the sliced kernels with G = 3.  The GLU kernel at T = 33 and T = 130, H = 32.
+    softmax backward, 3 x [48, 64]  stochastic, VEC, index_base = 12: the row pair's quad index behind a slice offset, as the batched
+                                  kernel's above
+    causal softmax, T = S = 40    the limit t + 1 cuts inside a lane's four columns in three rows of four, on both softmax kernels"""
 import pytest
 import torch
 
 import mx_norm_ref as NR
+import mx_rope_ref as RR
+import mx_softmax_ref as SMR
 import qsparse_amd as qs
-from qsparse_amd import _hip, mx_glu_backward_quantize, mx_norm_quantize, mx_quantize_2way, mx_quantize_2way_batched
+from qsparse_amd import (_hip, mx_glu_backward_quantize, mx_norm_quantize, mx_quantize_2way, mx_quantize_2way_batched, mx_rope_quantize,
+                         mx_softmax_backward_quantize, mx_softmax_quantize)
 from qsparse_amd.mx_batched_train import _slice_strides
+from qsparse_amd.mx_softmax import _softmax_ds
 from qsparse_amd.quantize import _mx_aten, _mx_sr_words
 
 pytestmark = pytest.mark.gpu
@@ -157,3 +174,153 @@ def test_batched_stochastic_slices_at_an_index_base(dtype, row_fmt, col_fmt):
     want = cpu_pair(x, row_fmt, 0, base) + cpu_pair(x.transpose(1, 2).contiguous(), col_fmt, 1, base)
     for g in range(G):                                # slice by slice: a wrong g R C shows in the slices behind the first
         agree([t[g] for t in got], [t[g] for t in want], (g, row_fmt, col_fmt))
+
+
+# ---- phase 1: every kernel on the PLAIN route, the edge inside a lane group and inside a pass --------------------------------------------
+SCALE = 0.37
+KINDS = ("row", "col", "both")
+PLAIN_SHAPES = ((130, 36), (33, 68))
+
+
+def off(t):
+    """`t` on the device, contiguous, at a base one element off its 16 bytes: no kernel takes a vector load from it"""
+    flat = torch.empty(t.numel() + 1, dtype=t.dtype, device=DEV)
+    out = flat[1:].view(t.shape).copy_(t)
+    assert out.data_ptr() % 16 != 0 and out.is_contiguous()
+    return out
+
+
+def same_bytes(got, want, what):
+    assert len(got) == len(want), what
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert (g is None) == (w is None), (i, what)
+        if g is not None:
+            assert g.shape == w.shape and torch.equal(g.cpu().contiguous().view(torch.uint8), w.contiguous().view(torch.uint8)), (i, what)
+
+
+def pair_formats(kind, row_fmt, col_fmt):
+    return (None if kind == "col" else row_fmt, None if kind == "row" else col_fmt)
+
+
+def p1_quant2(x, rf, cf, sr, put, device):
+    return mx_quantize_2way(put(x), rf, cf, **rounding(sr, device)), _hip.mx_quant2_last_route
+
+
+def p1_batched(x, rf, cf, sr, put, device):
+    return mx_quantize_2way_batched(put(x), rf, cf, **rounding(sr, device)), _hip.mx_quant2_batched_last_route
+
+
+def p1_norm(x, rf, cf, sr, put, device):
+    x, w, b = x
+    return mx_norm_quantize(put(x), w.to(device), b.to(device), norm="layer", eps=NR.EPS, fmt=rf, col_fmt=cf), _hip.mx_norm_last_route
+
+
+def p1_softmax(x, rf, cf, sr, put, device):
+    return mx_softmax_quantize(put(x), scale=SCALE, fmt=rf, col_fmt=cf, return_stats=True), _hip.mx_softmax_quant2_last_route
+
+
+def p1_softmax_bwd(x, rf, cf, sr, put, device):
+    s, dp, m, Z = x
+    got = mx_softmax_backward_quantize(put(dp), put(s), m.to(device), Z.to(device), scale=SCALE, row_fmt=rf, col_fmt=cf,
+                                       **rounding(sr, device))
+    return got, _hip.mx_softmax_bwd_last_route
+
+
+def p1_rope(x, rf, cf, sr, put, device):
+    x, cos, sin = x
+    got = ()
+    for interleaved, inverse in ((False, False), (True, True)):
+        got += mx_rope_quantize(put(x), cos.to(device), sin.to(device), row_fmt=rf, col_fmt=cf, interleaved=interleaved, inverse=inverse)
+    return got, _hip.mx_rope_quant2_last_route
+
+
+def p1_inputs(kernel, R, C, dtype):
+    if kernel == "quant2":
+        return randn((R, C), dtype, 31)
+    if kernel == "batched":
+        return randn((3, R, C), dtype, 32)
+    if kernel == "norm":
+        return NR.inputs(33, R, C, dtype)
+    if kernel == "rope":
+        return (RR.inputs(34, (3, R, C), dtype),) + tuple(RR.tables(R, C, 35))
+    s = SMR.scores(36, (3, R, C), dtype)
+    if kernel == "softmax":
+        return s
+    m, Z = mx_softmax_quantize(s, scale=SCALE, fmt="mxfp8_e4m3", return_stats=True)[-2:]
+    return s, randn((3, R, C), dtype, 37), m, Z
+
+
+# kernel: (run, PLAIN of its route family, has a call without a row pair, rounds stochastically)
+P1 = {"quant2": (p1_quant2, _hip.MX_Q2_ROUTE_TILE_PLAIN, True, True), "batched": (p1_batched, _hip.MX_Q2_ROUTE_TILE_PLAIN, True, True),
+      "norm": (p1_norm, _hip.MX_NORM_ROUTE_PLAIN, False, False), "softmax": (p1_softmax, _hip.MX_SOFTMAX_ROUTE_PLAIN, False, False),
+      "softmax_bwd": (p1_softmax_bwd, _hip.MX_SOFTMAX_ROUTE_PLAIN, True, True), "rope": (p1_rope, _hip.MX_ROPE_ROUTE_PLAIN, True, False)}
+
+
+@pytest.mark.parametrize("R,C", PLAIN_SHAPES, ids=[f"{r}x{c}" for r, c in PLAIN_SHAPES])
+@pytest.mark.parametrize("kernel", list(P1))
+@pytest.mark.parametrize("row_fmt,col_fmt", PAIRS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=str)
+def test_phase_one_on_the_plain_route(dtype, row_fmt, col_fmt, kernel, R, C):
+    run, plain, col_alone, stochastic = P1[kernel]
+    x = p1_inputs(kernel, R, C, dtype)
+    for kind in KINDS if col_alone else ("row", "both"):
+        rf, cf = pair_formats(kind, row_fmt, col_fmt)
+        for sr in (False, True) if stochastic else (False,):
+            want, _ = run(x, rf, cf, sr, lambda t: t, "cpu")
+            got, route = run(x, rf, cf, sr, off, DEV)
+            assert route == plain, (kernel, kind, sr)
+            same_bytes(got, want, (kernel, kind, sr))
+
+
+@pytest.mark.parametrize("T", (33, 130))
+@pytest.mark.parametrize("row_fmt,col_fmt", PAIRS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=str)
+def test_glu_phase_one_on_the_plain_route(dtype, row_fmt, col_fmt, T):
+    dh, v = randn((T, 32), dtype, 41), randn((T, 64), dtype, 42)     # (H = 32: dv is [T, 64], one tile column; relu, as above)
+    for kind in KINDS:
+        rf, cf = pair_formats(kind, row_fmt, col_fmt)
+        for sr in (False, True):
+            want = mx_glu_backward_quantize(dh, v, act="relu", row_fmt=rf, col_fmt=cf, **rounding(sr, "cpu"))
+            got = mx_glu_backward_quantize(off(dh), off(v), act="relu", row_fmt=rf, col_fmt=cf, **rounding(sr, DEV))
+            assert _hip.mx_glu_bwd_last_route == _hip.MX_Q2_ROUTE_TILE_PLAIN, (kind, sr)
+            same_bytes(got, want, (kind, sr))
+
+
+# ---- the softmax backward's quad index behind a slice offset and an index base -----------------------------------------------------------
+@pytest.mark.parametrize("row_fmt,col_fmt", PAIRS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=str)
+def test_softmax_backward_stochastic_slices_at_an_index_base(dtype, row_fmt, col_fmt):
+    G, T, S, base = 3, 48, 64, 12
+    s, dp = SMR.scores(51, (G, T, S), dtype), randn((G, T, S), dtype, 52)
+    m, Z = mx_softmax_quantize(s, scale=SCALE, fmt=row_fmt, return_stats=True)[-2:]
+    ds = _softmax_ds(dp, s, m, Z, None, SCALE, False)
+    step = torch.tensor([STEP], device=DEV)
+    for kind in KINDS:
+        rf, cf = pair_formats(kind, row_fmt, col_fmt)
+        got = _hip.mx_softmax_bwd_quant(dp.to(DEV), s.to(DEV), m.to(DEV), Z.to(DEV), None, SCALE, False, rf, cf, "stochastic", SEED, step,
+                                        base)
+        assert _hip.mx_softmax_bwd_last_route == _hip.MX_SOFTMAX_ROUTE_VEC, kind
+        want = (tuple(cpu_pair(ds, rf, 0, base)) if rf else (None, None)) + \
+               (tuple(cpu_pair(ds.transpose(1, 2).contiguous(), cf, 1, base)) if cf else (None, None))
+        for g in range(G):                                # slice by slice: a wrong g T S shows in the slices behind the first
+            same_bytes([t if t is None else t[g] for t in got], [t if t is None else t[g] for t in want], (g, kind))
+
+
+# ---- a causal limit inside a lane's four columns ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("row_fmt,col_fmt", PAIRS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=str)
+def test_causal_limit_inside_a_lanes_four(dtype, row_fmt, col_fmt):
+    G, T, S = 2, 40, 40
+    s, dp = SMR.scores(61, (G, T, S), dtype), randn((G, T, S), dtype, 62)
+    for cf in (None, col_fmt):
+        want = mx_softmax_quantize(s, scale=SCALE, is_causal=True, fmt=row_fmt, col_fmt=cf, return_stats=True)
+        got = mx_softmax_quantize(s.to(DEV), scale=SCALE, is_causal=True, fmt=row_fmt, col_fmt=cf, return_stats=True)
+        same_bytes(got, want, ("forward", cf))
+    m, Z = want[-2:]
+    for kind in KINDS:
+        rf, cf = pair_formats(kind, row_fmt, col_fmt)
+        for sr in (False, True):
+            wantb = mx_softmax_backward_quantize(dp, s, m, Z, scale=SCALE, is_causal=True, row_fmt=rf, col_fmt=cf, **rounding(sr, "cpu"))
+            gotb = mx_softmax_backward_quantize(dp.to(DEV), s.to(DEV), m.to(DEV), Z.to(DEV), scale=SCALE, is_causal=True, row_fmt=rf,
+                                                col_fmt=cf, **rounding(sr, DEV))
+            same_bytes(gotb, wantb, ("backward", kind, sr))

@@ -11,6 +11,7 @@ done once, when a layer is built.  ``H`` must be a multiple of 32: a block of 32
 Training through the gated products is ``mx_glu_train.py``; its forward asks the products here for the pre-activations with
 ``preact_dtype``.  Not offered: stochastic rounding of the output, ``split_k``, the tanh GELU, gated ``mx_bmm`` /
 convolutions; the ``act`` keyword of ``mx_matmul`` and its kin stays ``None`` or ``"relu"``."""
+import math
 from typing import Optional
 
 import torch
@@ -26,6 +27,7 @@ from qsparse_amd.mx_grouped import _check_b as _check_grouped_b
 from qsparse_amd.quantize import MX_BLOCK, _mx_format, quantize_with_mx
 
 GLU_ACTS = ("silu", "gelu", "relu")
+_GELU_ALPHA = math.sqrt(0.5)
 
 
 def _check_hidden(H: int, what: str):
@@ -81,8 +83,12 @@ def mx_glu_deinterleave(combined: torch.Tensor, dim: Optional[int] = None):
 
 
 def _glu_act(g: torch.Tensor, act: str) -> torch.Tensor:
-    """act(g) in torch ops, float32: what the CPU paths evaluate"""
-    return F.silu(g) if act == "silu" else F.gelu(g) if act == "gelu" else _act(g, "relu")
+    """act(g) in torch ops, float32: what the CPU paths evaluate.  gelu is the header's expression op by op, as ``_glu_dv`` has it: ATen's
+    vectorized CPU ``F.gelu`` carries an erf of 1e-7 absolute error, which the cancellation in 1 + erf turns into 2e-4 of gelu(-3),
+    five times the bound that follows from the header (tests/mx_glu_ref.py)"""
+    if act == "gelu":
+        return (g * 0.5) * (1.0 + torch.erf(g * _GELU_ALPHA))
+    return F.silu(g) if act == "silu" else _act(g, "relu")
 
 
 def _check_glu(fn: str, act, out_fmt, out_dtype, b_codes, preact_dtype=None):

@@ -2137,6 +2137,59 @@ int qs_mx_rope_quant2_v(const qs_mx_rope_quant2_args* args);
  * QS_ERR_* the call would return */
 int qs_mx_rope_quant2_route(const qs_mx_rope_quant2_args* args);
 
+/* ---- MX flash attention (Q . K^T, the softmax quantizer and P . V on MX codes in one launch) -------------------------------------------
+ * Added without raising QS_ABI_VERSION (28), by the same rule as qs_mx_matmul_v above: symbols are only added.
+ *
+ * Definition (normative): y [G, T, dv] holds, bit for bit, the bytes this chain of the entry points above writes --
+ *   1. qs_mx_bmm_v:            s [G, T, S] float32 = q . k^T, a = q (qk_format), b = k (qk_format), K = d, no bias
+ *   2. qs_mx_softmax_quant_v:  p's codes [G, T, S] / scales [G, T, ceil(S / 32)] in p_format from s with mask, mask_slices, scale, causal
+ *   3. qs_mx_bmm_v:            y = p . vt^T in ydt, a = p (p_format), b = vt (v_format), K = S, no bias
+ * -- so everything those sections say holds here: the walk along K and the MFMA order of the products, the float32 operations of the
+ * softmax and its row-sum order, the exceptional rows (a NaN in u, m = +-inf or nothing admitted: the row of p is NaN as a whole through
+ * the scale byte 0xFF, hence NaN in that row of y only), zero codes and the byte 127 past d and S.  Neither s, nor p, nor p's codes are
+ * written to memory: ONE launch on `stream`, no workspace, no atomics, nothing read by the host.
+ *   - Operands, all dense: q_codes [G, T, d] and k_codes [G, S, d] with blocks along d, vt_codes [G, dv, S] with blocks along S (v
+ *     transposed), their scales [G, T, ceil(d / 32)], [G, S, ceil(d / 32)], [G, dv, ceil(S / 32)]; mask NULL, [T, S] (mask_slices 1) or
+ *     [G, T, S] (mask_slices G), additive float32.  `causal` is aligned top-left; T != S is allowed; `scale` is any float.
+ *   - Supported range: S <= 512, 1 <= d <= 128, dv <= 128 -- a whole row of scores stays on chip.  Anything outside is QS_ERR_ARG;
+ *     there is no other kernel behind this entry point.  Any T and G.
+ *   - Checks, in order: QS_ERR_ARG: a null or too short descriptor, a NULL operand or y, a format no enum qs_mx_format, causal neither 0
+ *     nor 1, a negative extent, S > 512, d > 128, dv > 128, mask given with mask_slices neither 1 nor G; QS_ERR_DTYPE: ydt none of the
+ *     three; QS_ERR_ALIGN: y not aligned to its element or mask not to 4 bytes.  G == 0, T == 0, S == 0 or dv == 0: nothing is
+ *     enqueued, 0 is returned.  Then QS_ERR_ARG: d == 0, G * T beyond 64 bits, or G * ceil(T / 64) beyond 2^31 - 1 work-groups.
+ *   - One work-group per (slice, 64 query rows).  With `causal` the keys at or behind the work-group's last row + 1 are not read in
+ *     step 1 (their scores are -inf by definition); vt is read in full.
+ *   - QS_MX_FLASH_ROUTE_VEC (16-byte loads of codes and mask): d % 16 == 0, S % 16 == 0 and q_codes, k_codes, vt_codes and mask
+ *     16-byte aligned -- qs_mx_bmm_route's rule for each code operand.  Anything else takes QS_MX_FLASH_ROUTE_PLAIN, byte and element
+ *     loads each predicated on its own index: any d, S and base, same bits. */
+typedef struct qs_mx_flash_attention_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_flash_attention_args) as the caller compiled it */
+    int32_t qk_format;               /* enum qs_mx_format of q and k */
+    int32_t p_format;                /* ... of the attention weights */
+    int32_t v_format;                /* ... of vt */
+    int32_t ydt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    int32_t causal;                  /* 0 or 1 */
+    float scale;
+    int32_t reserved0;               /* 0 */
+    const uint8_t* q_codes;          /* [G, T, d] */
+    const uint8_t* q_scales;         /* [G, T, ceil(d / 32)] */
+    const uint8_t* k_codes;          /* [G, S, d] */
+    const uint8_t* k_scales;         /* [G, S, ceil(d / 32)] */
+    const uint8_t* vt_codes;         /* [G, dv, S] */
+    const uint8_t* vt_scales;        /* [G, dv, ceil(S / 32)] */
+    const float* mask;               /* [T, S] or [G, T, S], additive, nullable (none) */
+    int64_t mask_slices;             /* 1 or G; read only with a mask */
+    void* y;                         /* [G, T, dv] dense */
+    int64_t G, T, S, d, dv;
+    qs_stream_t stream;
+} qs_mx_flash_attention_args;
+int qs_mx_flash_attention_v(const qs_mx_flash_attention_args* args);
+/* the kernel qs_mx_flash_attention_v launches for these operands, nothing enqueued: QS_MX_FLASH_ROUTE_*, 0 for an empty problem, or
+ * the QS_ERR_* the call would return */
+#define QS_MX_FLASH_ROUTE_VEC 1
+#define QS_MX_FLASH_ROUTE_PLAIN 2
+int qs_mx_flash_attention_route(const qs_mx_flash_attention_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

@@ -158,6 +158,8 @@ SIGNATURES = {
     "qs_mx_rope_route": (c_int, [_P]),
     "qs_mx_rope_quant2_v": (c_int, [_P]),
     "qs_mx_rope_quant2_route": (c_int, [_P]),
+    "qs_mx_flash_attention_v": (c_int, [_P]),
+    "qs_mx_flash_attention_route": (c_int, [_P]),
 }
 
 
@@ -407,6 +409,15 @@ class MxSoftmaxQuantArgs(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("format", c_int32), ("sdt", c_int32), ("causal", c_int32), ("scale", c_float),
                 ("reserved0", c_int32), ("s", c_void_p), ("mask", c_void_p), ("mask_slices", c_int64), ("codes", c_void_p),
                 ("scales", c_void_p), ("G", c_int64), ("T", c_int64), ("S", c_int64), ("stream", c_void_p)]
+
+
+class MxFlashAttentionArgs(ctypes.Structure):
+    """`qs_mx_flash_attention_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("qk_format", c_int32), ("p_format", c_int32), ("v_format", c_int32), ("ydt", c_int32),
+                ("causal", c_int32), ("scale", c_float), ("reserved0", c_int32), ("q_codes", c_void_p), ("q_scales", c_void_p),
+                ("k_codes", c_void_p), ("k_scales", c_void_p), ("vt_codes", c_void_p), ("vt_scales", c_void_p), ("mask", c_void_p),
+                ("mask_slices", c_int64), ("y", c_void_p), ("G", c_int64), ("T", c_int64), ("S", c_int64), ("d", c_int64),
+                ("dv", c_int64), ("stream", c_void_p)]
 
 
 class MxSoftmaxQuant2Args(ctypes.Structure):
@@ -1794,6 +1805,35 @@ def mx_softmax_quant(s: torch.Tensor, mask: Optional[torch.Tensor], scale: float
         a.stream = _stream(s)
         mx_softmax_last_route = _mx_run("mx_softmax_quant", a, (s, mask, codes, scales))
     return codes, scales
+
+
+MX_FLASH_ROUTE_VEC, MX_FLASH_ROUTE_PLAIN = 1, 2
+MX_FLASH_MAX_S, MX_FLASH_MAX_D = 512, 128      # the range qs_mx_flash_attention_v takes: S; d and dv
+mx_flash_last_route = None       # the QS_MX_FLASH_ROUTE_* of the last `mx_flash_attention` launch (None: an empty problem)
+
+
+def mx_flash_attention(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, k_codes: torch.Tensor, k_scales: torch.Tensor,
+                       vt_codes: torch.Tensor, vt_scales: torch.Tensor, v_fmt: str, mask: Optional[torch.Tensor], scale: float,
+                       causal: bool, p_fmt: str, out_dtype: torch.dtype, out=None) -> torch.Tensor:
+    """attention on MX codes in ONE launch (qs_mx_flash_attention_v): `q_codes` [G, T, d], `k_codes` [G, S, d], `vt_codes` [G, dv, S]
+    uint8 with their scales, all contiguous GPU tensors, `mask` contiguous float32 [T, S] or [G, T, S] or None.  Returns y [G, T, dv] in
+    `out_dtype`.  `out`: a contiguous tensor of G T dv elements of `out_dtype` to write instead, as the guard-byte tests carve it."""
+    global mx_flash_last_route
+    load()
+    (G, T, d), S, dv = q_codes.shape, k_codes.shape[1], vt_codes.shape[1]
+    y = _mx_new_or_out((G, T, dv), out_dtype, q_codes.device, out, "out: G T dv elements of out_dtype")
+    mx_flash_last_route = None
+    if G and T and S and dv:
+        a = MxFlashAttentionArgs()
+        a.qk_format, a.p_format, a.v_format = MX_FORMATS.index(qk_fmt), MX_FORMATS.index(p_fmt), MX_FORMATS.index(v_fmt)
+        a.ydt, a.causal, a.scale = _DT[out_dtype], int(bool(causal)), float(scale)
+        a.q_codes, a.q_scales, a.k_codes, a.k_scales = _ptr(q_codes), _ptr(q_scales), _ptr(k_codes), _ptr(k_scales)
+        a.vt_codes, a.vt_scales, a.mask, a.y = _ptr(vt_codes), _ptr(vt_scales), _ptr(mask), _ptr(y)
+        a.mask_slices = 1 if mask is None or mask.dim() == 2 else G
+        a.G, a.T, a.S, a.d, a.dv = G, T, S, d, dv
+        a.stream = _stream(q_codes)
+        mx_flash_last_route = _mx_run("mx_flash_attention", a, (q_codes, q_scales, k_codes, k_scales, vt_codes, vt_scales, mask, y))
+    return y
 
 
 mx_softmax_quant2_last_route = None     # the QS_MX_SOFTMAX_ROUTE_* of the last `mx_softmax_quant2` launch (None: an empty tensor)

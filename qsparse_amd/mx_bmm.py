@@ -91,6 +91,7 @@ def mx_bmm(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: t
 
 
 MX_ATTENTION_SOFTMAX = ("torch", "fused")
+MX_ATTENTION_IMPL = ("composed", "flash")
 
 
 def _attention_mask(attn_mask, is_causal: bool, T: int, S: int, device):
@@ -116,7 +117,8 @@ def _attention_mask(attn_mask, is_causal: bool, T: int, S: int, device):
 
 def mx_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: Optional[torch.Tensor] = None, is_causal: bool = False,
                  scale: Optional[float] = None, *, qk_fmt: str = "mxfp8_e4m3", p_fmt: str = "mxfp8_e4m3", v_fmt: str = "mxfp8_e4m3",
-                 out_dtype: torch.dtype = torch.float32, softmax: str = "torch", rope=None, rope_interleaved: bool = False) -> torch.Tensor:
+                 out_dtype: torch.dtype = torch.float32, softmax: str = "torch", rope=None, rope_interleaved: bool = False,
+                 impl: str = "composed") -> torch.Tensor:
     """Inference-side scaled dot-product attention whose two matrix products run on MX codes.  ``q [..., T, d]``, ``k [..., S, d]``
     and ``v [..., S, dv]`` are float32 / bfloat16 / float16 tensors with equal leading dimensions (at least one); the result is
     ``[..., T, dv]`` in ``out_dtype``.  It is DEFINED as this composition of public calls, and is bit for bit that composition on
@@ -147,6 +149,11 @@ def mx_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: O
     interleaved=rope_interleaved)`` and of ``mx_rope_quantize(k, cos_k, sin_k, ...)``: on the GPU one launch each that reads ``q`` /
     ``k`` where it lies and never writes the rotated tensor.
 
+    ``impl`` (keyword; ``"composed"``, the default, changes no call, launch or bit) ``= "flash"`` needs ``softmax="fused"`` and replaces
+    steps 2 - 8 but the quantizers by ONE call, ``mx_flash_attention`` (``mx_flash.py``): on the GPU one launch that writes neither ``s``
+    nor ``p``'s codes.  It is bit for bit the ``"composed"`` result and takes ``S <= 512``, ``d <= 128``, ``dv <= 128`` only; ``rope``
+    works with it unchanged.
+
     No dropout and no gradient: a tensor that requires grad while gradients are enabled is refused -- the training side of attention
     is not offered.  A row of the mask that admits no key gives NaN, as softmax does."""
     for name, t in (("q", q), ("k", k), ("v", v)):
@@ -165,6 +172,10 @@ def mx_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: O
     _check_dtype("out_dtype", out_dtype)
     if softmax not in MX_ATTENTION_SOFTMAX:
         raise ValueError(f"unknown softmax {softmax!r}: one of {MX_ATTENTION_SOFTMAX}")
+    if impl not in MX_ATTENTION_IMPL:
+        raise ValueError(f"unknown impl {impl!r}: one of {MX_ATTENTION_IMPL}")
+    if impl == "flash" and softmax != "fused":
+        raise ValueError('impl="flash" is defined through mx_softmax_quantize: it needs softmax="fused"')
     lead, (T, d), S = tuple(q.shape[:-2]), q.shape[-2:], k.shape[-2]
     if tuple(k.shape[:-2]) != lead or tuple(v.shape[:-2]) != lead:
         raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)} and v {tuple(v.shape)} disagree on their leading dimensions (nothing "
@@ -189,6 +200,11 @@ def mx_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: O
         else:
             qc, qsc = mx_rope_quantize(q, rope[0], rope[1], row_fmt=qk_fmt, interleaved=rope_interleaved)[:2]
             kc, ksc = mx_rope_quantize(k, rope[2], rope[3], row_fmt=qk_fmt, interleaved=rope_interleaved)[:2]
+        if impl == "flash":
+            from qsparse_amd.mx_flash import mx_flash_attention        # (it takes `mx_bmm` from this module)
+            _, vc, vsc = quantize_with_mx(v.detach().transpose(-1, -2).contiguous(), v_fmt, -1, return_codes=True)
+            return mx_flash_attention(qc, qsc, qk_fmt, kc, ksc, vc, vsc, v_fmt, attn_mask, scale=d ** -0.5 if scale is None else scale,
+                                      is_causal=is_causal, p_fmt=p_fmt, out_dtype=out_dtype)
         s = mx_bmm(qc, qsc, qk_fmt, kc, ksc, qk_fmt)
         if fused:
             from qsparse_amd.mx_softmax import mx_softmax_quantize     # (it takes `_attention_mask` from this module)
@@ -209,10 +225,10 @@ class MXMultiheadAttention(nn.Module):
     returns without its weights; the mask goes to ``mx_attention`` as it is (``[T, T]`` or anything that broadcasts to ``[B, h, T,
     T]``).  It is a thin composition -- ``in_proj(x)``, split, ``mx_attention``, merge, ``out_proj`` -- and equals it bit for bit.
     ``need_weights`` and ``key_padding_mask`` are not offered.  ``softmax`` (``"torch"`` or ``"fused"``) is ``mx_attention``'s keyword,
-    stored and passed on; ``forward``'s ``rope`` / ``rope_interleaved`` are ``mx_attention``'s too, call arguments and not state."""
+    stored and passed on, and so is ``impl``; ``forward``'s ``rope`` / ``rope_interleaved`` are ``mx_attention``'s too, call arguments and not state."""
 
     def __init__(self, in_proj: MXLinear, out_proj: MXLinear, num_heads: int, batch_first: bool = False, *, qk_fmt: str = "mxfp8_e4m3",
-                 p_fmt: str = "mxfp8_e4m3", v_fmt: str = "mxfp8_e4m3", softmax: str = "torch"):
+                 p_fmt: str = "mxfp8_e4m3", v_fmt: str = "mxfp8_e4m3", softmax: str = "torch", impl: str = "composed"):
         super().__init__()
         if not isinstance(in_proj, MXLinear) or not isinstance(out_proj, MXLinear):
             raise TypeError("in_proj and out_proj must be MXLinear layers")
@@ -228,7 +244,9 @@ class MXMultiheadAttention(nn.Module):
             _mx_format(fmt)
         if softmax not in MX_ATTENTION_SOFTMAX:
             raise ValueError(f"unknown softmax {softmax!r}: one of {MX_ATTENTION_SOFTMAX}")
-        self.softmax = softmax
+        if impl not in MX_ATTENTION_IMPL:
+            raise ValueError(f"unknown impl {impl!r}: one of {MX_ATTENTION_IMPL}")
+        self.softmax, self.impl = softmax, impl
         self.in_proj, self.out_proj = in_proj, out_proj
         self.embed_dim, self.num_heads, self.batch_first = E, num_heads, bool(batch_first)
         self.qk_fmt, self.p_fmt, self.v_fmt = qk_fmt, p_fmt, v_fmt
@@ -239,7 +257,7 @@ class MXMultiheadAttention(nn.Module):
 
     @classmethod
     def from_float(cls, mha: nn.MultiheadAttention, act_fmt: str = "mxfp8_e4m3", w_fmt: str = "mxfp8_e4m3", *, qk_fmt: str = "mxfp8_e4m3",
-                   p_fmt: str = "mxfp8_e4m3", v_fmt: str = "mxfp8_e4m3", softmax: str = "torch"):
+                   p_fmt: str = "mxfp8_e4m3", v_fmt: str = "mxfp8_e4m3", softmax: str = "torch", impl: str = "composed"):
         """from a float self-attention module: both weights quantized with ``quantize_with_mx(w, w_fmt, 1, return_codes=True)``"""
         if not isinstance(mha, nn.MultiheadAttention):
             raise TypeError(f"MXMultiheadAttention.from_float needs an nn.MultiheadAttention, got {type(mha).__name__}")
@@ -254,7 +272,7 @@ class MXMultiheadAttention(nn.Module):
             for w, b in ((mha.in_proj_weight, mha.in_proj_bias), (mha.out_proj.weight, mha.out_proj.bias)):
                 _, codes, scales = quantize_with_mx(w.detach(), w_fmt, 1, return_codes=True)
                 layers.append(MXLinear(codes, scales, w_fmt, None if b is None else b.detach(), act_fmt))
-        return cls(*layers, mha.num_heads, mha.batch_first, qk_fmt=qk_fmt, p_fmt=p_fmt, v_fmt=v_fmt, softmax=softmax)
+        return cls(*layers, mha.num_heads, mha.batch_first, qk_fmt=qk_fmt, p_fmt=p_fmt, v_fmt=v_fmt, softmax=softmax, impl=impl)
 
     def forward(self, x: torch.Tensor, attn_mask: Optional[torch.Tensor] = None, is_causal: bool = False, *, need_weights: bool = False,
                 key_padding_mask: Optional[torch.Tensor] = None, rope=None, rope_interleaved: bool = False):
@@ -269,7 +287,7 @@ class MXMultiheadAttention(nn.Module):
         B, T = xb.shape[:2]
         q, k, v = (t.reshape(B, T, h, E // h).transpose(1, 2) for t in self.in_proj(xb).chunk(3, -1))
         o = mx_attention(q, k, v, attn_mask, is_causal, qk_fmt=self.qk_fmt, p_fmt=self.p_fmt, v_fmt=self.v_fmt, softmax=self.softmax,
-                         rope=rope, rope_interleaved=rope_interleaved)
+                         rope=rope, rope_interleaved=rope_interleaved, impl=self.impl)
         y = self.out_proj(o.transpose(1, 2).reshape(B, T, E))
         return (y if self.batch_first else y.transpose(0, 1)), None
 

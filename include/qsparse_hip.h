@@ -2190,6 +2190,40 @@ int qs_mx_flash_attention_v(const qs_mx_flash_attention_args* args);
 #define QS_MX_FLASH_ROUTE_PLAIN 2
 int qs_mx_flash_attention_route(const qs_mx_flash_attention_args* args);
 
+/* ---- MX flash attention, streamed (online softmax on MX codes, any S, in one launch) ---------------------------------------------------
+ * Added without raising QS_ABI_VERSION (28): symbols are only added.  Both entry points take qs_mx_flash_attention_args as above
+ * (reserved0 still 0) with the same operands, and lift the bound on S: any S >= 1, d <= 128, dv <= 128, any T and G, every format
+ * triple, the three ydt.  Registers and LDS of the kernel do not depend on S.
+ *
+ * Definition (normative).  The bytes are NOT the chain's of the section above: p is never normalised before it is quantized.  Per
+ * slice g and query row t the state is m = -inf, Z = +0, acc[dv] = +0 and a sticky flag bad = false.  For c = 0, 1, ... the chunk is
+ * the key columns [128 c, min(S, 128 c + 128)); the width 128 is part of the definition, as 512 is part of the row sum's.
+ *   1. s = qs_mx_bmm_v(q, k[chunk]) in float32: one MFMA step along d from a zero accumulator.
+ *   2. u_j = s_j * scale (+ mask_j); u_j = -inf where `causal` excludes j (j > t, top-left aligned).  Every float32 operation is
+ *      rounded on its own.
+ *   3. bad |= any_j (u_j is NaN or u_j == +inf).
+ *   4. m' = max(m, max_j u_j), NaNs skipped.
+ *   5. e_j = E(u_j - m'), alpha = E(m - m'); E is the softmax quantizer's exponential, which maps a NaN argument to +0 (so -inf - -inf
+ *      needs no special case).
+ *   6. z = the row sum of the MX norm quantizer over e padded with zeros to 128 columns: quads, the partial sums 4 f + g, the tree.
+ *   7. (ec, es) = the MX quantizer (nearest) on e padded to 128 in p_format, blocks of 32 along the keys; a block wholly past S is
+ *      zero codes under the byte 127.
+ *   8. o = qs_mx_bmm_v(ec / es, vt[:, chunk]) in float32: one MFMA step from zero; vt's codes past S are read as zero, its scale
+ *      blocks wholly past S as 127.
+ *   9. If the causal limit admits no column of this chunk for row t (128 c >= t + 1) the row's state is left exactly as it was.
+ *      Otherwise m = m', Z = Z * alpha + z, acc = acc * alpha + o: a multiply, then an add, no contraction.
+ * Only the causal limit elides a chunk, a mask never does: a NaN scale byte or an Inf code in vt poisons exactly the rows whose limit
+ * reaches that chunk, and a chunk masked to -inf throughout still goes through the product.  After the last chunk y = acc / Z (IEEE
+ * division per element) rounded once to ydt; a row that is bad, or that admits nothing (Z = 0), is the quiet NaN as a whole.
+ *   - Checks: qs_mx_flash_attention_v's, in its order, without S > 512; after the empty problems (nothing enqueued, 0 returned)
+ *     QS_ERR_ARG for d == 0, for G * T * S (or an operand's byte count) beyond 64 bits and for G * ceil(T / 64) beyond 2^31 - 1
+ *     work-groups.
+ *   - ONE launch on `stream`, one work-group per (slice, 64 query rows), no workspace, no atomics, nothing read by the host.  With
+ *     `causal` the keys and the columns of vt behind the chunk that holds the work-group's last row are not read.
+ *   - Routes: QS_MX_FLASH_ROUTE_VEC / _PLAIN by qs_mx_flash_attention_route's rule; the same bits. */
+int qs_mx_flash_attention_streamed_v(const qs_mx_flash_attention_args* args);
+int qs_mx_flash_attention_streamed_route(const qs_mx_flash_attention_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

@@ -160,6 +160,8 @@ SIGNATURES = {
     "qs_mx_rope_quant2_route": (c_int, [_P]),
     "qs_mx_flash_attention_v": (c_int, [_P]),
     "qs_mx_flash_attention_route": (c_int, [_P]),
+    "qs_mx_flash_attention_streamed_v": (c_int, [_P]),
+    "qs_mx_flash_attention_streamed_route": (c_int, [_P]),
 }
 
 
@@ -1814,10 +1816,11 @@ mx_flash_last_route = None       # the QS_MX_FLASH_ROUTE_* of the last `mx_flash
 
 def mx_flash_attention(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, k_codes: torch.Tensor, k_scales: torch.Tensor,
                        vt_codes: torch.Tensor, vt_scales: torch.Tensor, v_fmt: str, mask: Optional[torch.Tensor], scale: float,
-                       causal: bool, p_fmt: str, out_dtype: torch.dtype, out=None) -> torch.Tensor:
+                       causal: bool, p_fmt: str, out_dtype: torch.dtype, out=None, streamed: bool = False) -> torch.Tensor:
     """attention on MX codes in ONE launch (qs_mx_flash_attention_v): `q_codes` [G, T, d], `k_codes` [G, S, d], `vt_codes` [G, dv, S]
     uint8 with their scales, all contiguous GPU tensors, `mask` contiguous float32 [T, S] or [G, T, S] or None.  Returns y [G, T, dv] in
-    `out_dtype`.  `out`: a contiguous tensor of G T dv elements of `out_dtype` to write instead, as the guard-byte tests carve it."""
+    `out_dtype`.  `out`: a contiguous tensor of G T dv elements of `out_dtype` to write instead, as the guard-byte tests carve it.
+    `streamed`: qs_mx_flash_attention_streamed_v on the same descriptor -- any S, the chunk recurrence's numerics."""
     global mx_flash_last_route
     load()
     (G, T, d), S, dv = q_codes.shape, k_codes.shape[1], vt_codes.shape[1]
@@ -1832,7 +1835,8 @@ def mx_flash_attention(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: st
         a.mask_slices = 1 if mask is None or mask.dim() == 2 else G
         a.G, a.T, a.S, a.d, a.dv = G, T, S, d, dv
         a.stream = _stream(q_codes)
-        mx_flash_last_route = _mx_run("mx_flash_attention", a, (q_codes, q_scales, k_codes, k_scales, vt_codes, vt_scales, mask, y))
+        mx_flash_last_route = _mx_run("mx_flash_attention_streamed" if streamed else "mx_flash_attention", a,
+                                      (q_codes, q_scales, k_codes, k_scales, vt_codes, vt_scales, mask, y))
     return y
 
 

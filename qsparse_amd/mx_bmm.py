@@ -91,7 +91,7 @@ def mx_bmm(a_codes: torch.Tensor, a_scales: torch.Tensor, a_fmt: str, b_codes: t
 
 
 MX_ATTENTION_SOFTMAX = ("torch", "fused")
-MX_ATTENTION_IMPL = ("composed", "flash")
+MX_ATTENTION_IMPL = ("composed", "flash", "flash_streamed")
 
 
 def _attention_mask(attn_mask, is_causal: bool, T: int, S: int, device):
@@ -152,7 +152,8 @@ def mx_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: O
     ``impl`` (keyword; ``"composed"``, the default, changes no call, launch or bit) ``= "flash"`` needs ``softmax="fused"`` and replaces
     steps 2 - 8 but the quantizers by ONE call, ``mx_flash_attention`` (``mx_flash.py``): on the GPU one launch that writes neither ``s``
     nor ``p``'s codes.  It is bit for bit the ``"composed"`` result and takes ``S <= 512``, ``d <= 128``, ``dv <= 128`` only; ``rope``
-    works with it unchanged.
+    works with it unchanged.  ``impl="flash_streamed"`` needs ``softmax="fused"`` too and makes the same call with ``rows="streamed"``:
+    any ``S``, one launch, and the chunk recurrence's numerics (``mx_flash._streamed_def``) instead of the composition's bits.
 
     No dropout and no gradient: a tensor that requires grad while gradients are enabled is refused -- the training side of attention
     is not offered.  A row of the mask that admits no key gives NaN, as softmax does."""
@@ -174,8 +175,8 @@ def mx_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: O
         raise ValueError(f"unknown softmax {softmax!r}: one of {MX_ATTENTION_SOFTMAX}")
     if impl not in MX_ATTENTION_IMPL:
         raise ValueError(f"unknown impl {impl!r}: one of {MX_ATTENTION_IMPL}")
-    if impl == "flash" and softmax != "fused":
-        raise ValueError('impl="flash" is defined through mx_softmax_quantize: it needs softmax="fused"')
+    if impl != "composed" and softmax != "fused":
+        raise ValueError(f'impl="{impl}" is defined through mx_softmax_quantize: it needs softmax="fused"')
     lead, (T, d), S = tuple(q.shape[:-2]), q.shape[-2:], k.shape[-2]
     if tuple(k.shape[:-2]) != lead or tuple(v.shape[:-2]) != lead:
         raise ValueError(f"q {tuple(q.shape)}, k {tuple(k.shape)} and v {tuple(v.shape)} disagree on their leading dimensions (nothing "
@@ -200,11 +201,12 @@ def mx_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: O
         else:
             qc, qsc = mx_rope_quantize(q, rope[0], rope[1], row_fmt=qk_fmt, interleaved=rope_interleaved)[:2]
             kc, ksc = mx_rope_quantize(k, rope[2], rope[3], row_fmt=qk_fmt, interleaved=rope_interleaved)[:2]
-        if impl == "flash":
+        if impl != "composed":
             from qsparse_amd.mx_flash import mx_flash_attention        # (it takes `mx_bmm` from this module)
             _, vc, vsc = quantize_with_mx(v.detach().transpose(-1, -2).contiguous(), v_fmt, -1, return_codes=True)
             return mx_flash_attention(qc, qsc, qk_fmt, kc, ksc, vc, vsc, v_fmt, attn_mask, scale=d ** -0.5 if scale is None else scale,
-                                      is_causal=is_causal, p_fmt=p_fmt, out_dtype=out_dtype)
+                                      is_causal=is_causal, p_fmt=p_fmt, out_dtype=out_dtype,
+                                      rows="streamed" if impl == "flash_streamed" else "resident")
         s = mx_bmm(qc, qsc, qk_fmt, kc, ksc, qk_fmt)
         if fused:
             from qsparse_amd.mx_softmax import mx_softmax_quantize     # (it takes `_attention_mask` from this module)

@@ -2224,6 +2224,70 @@ int qs_mx_flash_attention_route(const qs_mx_flash_attention_args* args);
 int qs_mx_flash_attention_streamed_v(const qs_mx_flash_attention_args* args);
 int qs_mx_flash_attention_streamed_route(const qs_mx_flash_attention_args* args);
 
+/* ---- MX flash attention, decode (split-KV grouped-query attention on MX codes, the valid length read on the device) --------------------
+ * Added without raising QS_ABI_VERSION (28): symbols are only added.  A few query tokens q [B, Hq, T, d] against a cache k [B, Hkv, S, d],
+ * vt [B, Hkv, dv, S] with Hq = r * Hkv: query head h uses key/value head h / r, and the cache is read once per group of r heads.
+ *
+ * Definition (normative).  Per sequence b let L = clamp(kv_len[b], 0, S) (S without kv_len).  The R = r * T packed rows of (b, hk) are
+ * rho = (h % r) * T + t.  Row rho admits the keys j < lim, lim = L, or with `causal` (aligned BOTTOM-RIGHT: token t admits j <= L - T + t)
+ * lim = clamp(L - T + t + 1, 0, L).  For T == S == L that is the top-left triangle of the sections above; for T != S it is not.
+ *   1. Chunks are the 128-key chunks of the streamed section, aligned at key 0: chunk c is the keys [128 c, 128 c + 128).
+ *   2. With chunks = ceil(S / 128), n = kv_splits and cps = ceil(chunks / n), split i owns the chunks [i cps, (i + 1) cps).  Splits are
+ *      counted on S, not on L.
+ *   3. Within a split the state (m, Z, acc, bad) starts at (-inf, +0, +0, false) and follows the streamed section's steps 1 - 9
+ *      unchanged -- the same E, the same row sum on 128 columns, e quantized unnormalised to p_format, one MFMA step from zero per
+ *      product, Z * alpha + z and acc * alpha + o as a multiply and an add -- with no mask and u_j = -inf where j >= lim.
+ *   4. The recurrence is applied to the operands of sequence b SLICED TO L, i.e. with L in the place of S: keys >= L give u = -inf by
+ *      select, so a NaN there is dropped; vt codes at columns >= L are read as zero; the scale byte of a vt block wholly past L is read
+ *      as 127, a block that straddles L keeps its byte; a block of e wholly past L is zero codes under the byte 127.
+ *   5. A chunk wholly at or past L, or wholly at or behind a row's lim (128 c >= lim), is not applied to that row.
+ *   6. A split with no applied chunk yields m = -inf, Z = 0, acc = 0.
+ *   7. Combination runs over ALL n splits in ascending order, none skipped: M = max_i m_i, a_i = E(m_i - M); Z = Z_0 * a_0, then
+ *      Z = Z + Z_i * a_i for i = 1 .. n - 1; acc likewise per column; every multiply and add is rounded on its own.
+ *   8. y = acc / Z (IEEE division) rounded once to ydt.  A row that is bad in any split, or has Z == 0, is the quiet NaN as a whole.
+ * With n == 1, no kv_len and causal == 0 the bytes are qs_mx_flash_attention_streamed_v's on the cache repeated r times (E(0) = 1).
+ *   - Range: R = r * T <= 64, S >= 1, 1 <= d <= 128, dv <= 128, every format triple, the three ydt, kv_splits >= 1 (the count is part of
+ *     the numerics; the caller chooses it).
+ *   - kv_len: NULL or int32 [B] in device memory, read by the kernel: nothing is read by the host, the call can be captured in a graph
+ *     and kv_len rewritten between replays.
+ *   - workspace: kv_splits > 1 needs B * Hkv * R * kv_splits * (dv + 3) floats of device memory (the records (m, Z, bad, acc[dv]) of
+ *     every row and split), the caller's; its contents need no initialisation and mean nothing afterwards.  kv_splits == 1: not read,
+ *     may be NULL, ONE launch; otherwise two launches on `stream`, the second combining.  No atomics, no counters: deterministic.
+ *   - Checks, in order: QS_ERR_ARG: a null or too short descriptor, a NULL operand or y, a format no enum qs_mx_format, causal neither 0
+ *     nor 1, a negative extent, kv_splits < 1, d > 128, dv > 128; QS_ERR_DTYPE: ydt none of the three; QS_ERR_ALIGN: y not aligned to
+ *     its element, kv_len or workspace not to 4 bytes.  B == 0, Hq == 0, T == 0 or dv == 0: nothing is enqueued, 0 is returned.  Then
+ *     QS_ERR_ARG: Hkv == 0, Hq % Hkv != 0, r * T > 64, S == 0, d == 0, S > 2^31 - 129, a byte count beyond 64 bits, more waves than
+ *     4 * (2^31 - 1), or kv_splits > 1 with workspace NULL or workspace_bytes too small.
+ *   - One wave per (b, hk, 16 packed rows, split), four to a work-group; keys at or behind min(L, the tile's largest lim) are not read.
+ *   - Routes: QS_MX_FLASH_ROUTE_VEC (16-byte loads of codes): d % 16 == 0, S % 16 == 0 and q_codes, k_codes, vt_codes 16-byte aligned;
+ *     anything else QS_MX_FLASH_ROUTE_PLAIN, byte loads each predicated on its own index: the same bits. */
+typedef struct qs_mx_flash_decode_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_flash_decode_args) as the caller compiled it */
+    int32_t qk_format;               /* enum qs_mx_format of q and k */
+    int32_t p_format;                /* ... of the attention weights */
+    int32_t v_format;                /* ... of vt */
+    int32_t ydt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    int32_t causal;                  /* 0 or 1, bottom-right aligned */
+    float scale;
+    int32_t kv_splits;               /* >= 1 */
+    const uint8_t* q_codes;          /* [B, Hq, T, d] */
+    const uint8_t* q_scales;         /* [B, Hq, T, ceil(d / 32)] */
+    const uint8_t* k_codes;          /* [B, Hkv, S, d] */
+    const uint8_t* k_scales;         /* [B, Hkv, S, ceil(d / 32)] */
+    const uint8_t* vt_codes;         /* [B, Hkv, dv, S] */
+    const uint8_t* vt_scales;        /* [B, Hkv, dv, ceil(S / 32)] */
+    const int32_t* kv_len;           /* [B], device memory, nullable (every sequence sees S keys) */
+    float* workspace;                /* see above; nullable with kv_splits == 1 */
+    int64_t workspace_bytes;
+    void* y;                         /* [B, Hq, T, dv] dense */
+    int64_t B, Hq, Hkv, T, S, d, dv;
+    qs_stream_t stream;
+} qs_mx_flash_decode_args;
+int qs_mx_flash_decode_v(const qs_mx_flash_decode_args* args);
+/* the route qs_mx_flash_decode_v takes for these operands, nothing enqueued: QS_MX_FLASH_ROUTE_*, 0 for an empty problem, or the
+ * QS_ERR_* the call would return */
+int qs_mx_flash_decode_route(const qs_mx_flash_decode_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

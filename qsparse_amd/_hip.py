@@ -162,6 +162,8 @@ SIGNATURES = {
     "qs_mx_flash_attention_route": (c_int, [_P]),
     "qs_mx_flash_attention_streamed_v": (c_int, [_P]),
     "qs_mx_flash_attention_streamed_route": (c_int, [_P]),
+    "qs_mx_flash_decode_v": (c_int, [_P]),
+    "qs_mx_flash_decode_route": (c_int, [_P]),
 }
 
 
@@ -420,6 +422,15 @@ class MxFlashAttentionArgs(ctypes.Structure):
                 ("k_codes", c_void_p), ("k_scales", c_void_p), ("vt_codes", c_void_p), ("vt_scales", c_void_p), ("mask", c_void_p),
                 ("mask_slices", c_int64), ("y", c_void_p), ("G", c_int64), ("T", c_int64), ("S", c_int64), ("d", c_int64),
                 ("dv", c_int64), ("stream", c_void_p)]
+
+
+class MxFlashDecodeArgs(ctypes.Structure):
+    """`qs_mx_flash_decode_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("qk_format", c_int32), ("p_format", c_int32), ("v_format", c_int32), ("ydt", c_int32),
+                ("causal", c_int32), ("scale", c_float), ("kv_splits", c_int32), ("q_codes", c_void_p), ("q_scales", c_void_p),
+                ("k_codes", c_void_p), ("k_scales", c_void_p), ("vt_codes", c_void_p), ("vt_scales", c_void_p), ("kv_len", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", c_int64), ("y", c_void_p), ("B", c_int64), ("Hq", c_int64), ("Hkv", c_int64),
+                ("T", c_int64), ("S", c_int64), ("d", c_int64), ("dv", c_int64), ("stream", c_void_p)]
 
 
 class MxSoftmaxQuant2Args(ctypes.Structure):
@@ -1837,6 +1848,35 @@ def mx_flash_attention(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: st
         a.stream = _stream(q_codes)
         mx_flash_last_route = _mx_run("mx_flash_attention_streamed" if streamed else "mx_flash_attention", a,
                                       (q_codes, q_scales, k_codes, k_scales, vt_codes, vt_scales, mask, y))
+    return y
+
+
+def mx_flash_decode(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, k_codes: torch.Tensor, k_scales: torch.Tensor,
+                    vt_codes: torch.Tensor, vt_scales: torch.Tensor, v_fmt: str, kv_len: Optional[torch.Tensor], scale: float, causal: bool,
+                    p_fmt: str, out_dtype: torch.dtype, kv_splits: int, out=None) -> torch.Tensor:
+    """grouped-query attention on MX codes for decoding (qs_mx_flash_decode_v): `q_codes` [B, Hq, T, d], `k_codes` [B, Hkv, S, d],
+    `vt_codes` [B, Hkv, dv, S] uint8 with their scales, all contiguous GPU tensors, `kv_len` int32 [B] on the device or None, `kv_splits`
+    an explicit count.  Returns y [B, Hq, T, dv] in `out_dtype` from one launch (`kv_splits` == 1) or two; the workspace of the split
+    states is a `torch.empty` of this call.  `out`: a contiguous tensor of B Hq T dv elements of `out_dtype` to write instead, as the
+    guard-byte tests carve it.  The route lands in `mx_flash_last_route`."""
+    global mx_flash_last_route
+    load()
+    (B, Hq, T, d), (_, Hkv, S, _), dv = q_codes.shape, k_codes.shape, vt_codes.shape[2]
+    y = _mx_new_or_out((B, Hq, T, dv), out_dtype, q_codes.device, out, "out: B Hq T dv elements of out_dtype")
+    mx_flash_last_route = None
+    if B and Hq and T and dv:
+        a = MxFlashDecodeArgs()
+        a.qk_format, a.p_format, a.v_format = MX_FORMATS.index(qk_fmt), MX_FORMATS.index(p_fmt), MX_FORMATS.index(v_fmt)
+        a.ydt, a.causal, a.scale, a.kv_splits = _DT[out_dtype], int(bool(causal)), float(scale), int(kv_splits)
+        a.q_codes, a.q_scales, a.k_codes, a.k_scales = _ptr(q_codes), _ptr(q_scales), _ptr(k_codes), _ptr(k_scales)
+        a.vt_codes, a.vt_scales, a.kv_len, a.y = _ptr(vt_codes), _ptr(vt_scales), _ptr(kv_len), _ptr(y)
+        ws = None
+        if kv_splits > 1:       # (m, Z, bad, acc[dv]) of every packed row and split; the kernels write every record they read
+            ws = torch.empty(B * Hkv * (Hq // Hkv * T) * kv_splits * (dv + 3), dtype=torch.float32, device=q_codes.device)
+            a.workspace, a.workspace_bytes = _ptr(ws), ws.numel() * 4
+        a.B, a.Hq, a.Hkv, a.T, a.S, a.d, a.dv = B, Hq, Hkv, T, S, d, dv
+        a.stream = _stream(q_codes)
+        mx_flash_last_route = _mx_run("mx_flash_decode", a, (q_codes, q_scales, k_codes, k_scales, vt_codes, vt_scales, kv_len, y))
     return y
 
 

@@ -32,6 +32,39 @@ _check_k = partial(_mx_common._check_operand, what="[..., S, d]", least=3, most=
 _check_vt = partial(_mx_common._check_operand, what="[..., dv, S]", least=3, most=None, needs="at least 3 dimensions")
 
 
+def _empty_state(G: int, T: int, dv: int, dev):
+    """the chunk recurrence's state before any chunk: ``(m, Z, acc, bad)`` = (-inf, 0, 0, False) per row"""
+    return (torch.full((G, T, 1), float("-inf"), dtype=torch.float32, device=dev), torch.zeros((G, T, 1), dtype=torch.float32, device=dev),
+            torch.zeros((G, T, dv), dtype=torch.float32, device=dev), torch.zeros((G, T, 1), dtype=torch.bool, device=dev))
+
+
+def _chunk_step(state, c: int, qc, qs, qk_fmt: str, kc, ks, vc, vs, v_fmt: str, mask, scale: float, lim, p_fmt: str):
+    """One step of the chunk recurrence, shared by ``_streamed_def`` and ``_decode_def``: chunk ``c`` -- the keys ``[128 c, min(S, 128 c +
+    128))`` of ``kc [G, S, d]`` / ``vc [G, dv, S]`` -- applied to ``state = (m, Z, acc, bad)``.  ``lim`` is None or an integer tensor
+    ``[T, 1]``: row t admits the columns ``j < lim[t]``, and a chunk that starts at or behind ``lim[t]`` leaves the row's state as it was."""
+    m, Z, acc, bad = state
+    (G, T, _), S, dev = qc.shape, kc.shape[1], qc.device
+    f = lambda v: torch.tensor(v, dtype=torch.float32, device=dev)
+    lo, hi = c * _CHUNK, min(S, (c + 1) * _CHUNK)
+    u = mx_bmm(qc, qs, qk_fmt, kc[:, lo:hi].contiguous(), ks[:, lo:hi].contiguous(), qk_fmt) * f(scale)
+    if mask is not None:
+        u = u + mask[..., lo:hi]
+    if lim is not None:
+        u = torch.where(torch.arange(lo, hi, device=dev)[None, :] < lim, u, f(float("-inf")))
+    bad_c = (u.isnan() | (u == float("inf"))).any(-1, keepdim=True)
+    m2 = torch.maximum(m, torch.where(u.isnan(), f(float("-inf")), u).amax(-1, keepdim=True))
+    e, alpha = F.pad(_exp_def(u - m2), (0, _CHUNK - (hi - lo))), _exp_def(m - m2)
+    z = _row_sum(e.reshape(G * T, _CHUNK)).reshape(G, T, 1)
+    _, ec, es = quantize_with_mx(e, p_fmt, -1, return_codes=True)
+    es = es.clone()
+    es[..., -(-(hi - lo) // 32):] = 127                         # a block wholly past S: zero codes under the byte 127
+    vcc = F.pad(vc[..., lo:hi], (0, _CHUNK - (hi - lo)))        # codes past S are zero, scale blocks wholly past S are 127
+    vsc = F.pad(vs[..., 4 * c:4 * c + 4], (0, 4 - vs[..., 4 * c:4 * c + 4].shape[-1]), value=127)
+    o = mx_bmm(ec, es, p_fmt, vcc.contiguous(), vsc.contiguous(), v_fmt)
+    live = (lim > lo) if lim is not None else torch.ones((T, 1), dtype=torch.bool, device=dev)
+    return tuple(torch.where(live, new, old) for new, old in ((m2, m), (Z * alpha + z, Z), (acc * alpha + o, acc), (bad | bad_c, bad)))
+
+
 def _streamed_def(qc, qs, qk_fmt: str, kc, ks, vc, vs, v_fmt: str, mask, scale: float, causal: bool, p_fmt: str, out_dtype):
     """The streamed kernel's definition (``include/qsparse_hip.h``, "MX flash attention, streamed") on ``qc [G, T, d]``, ``kc [G, S, d]``,
     ``vc [G, dv, S]`` with their scales and an additive float32 ``mask`` ``[T, S]`` / ``[G, T, S]`` or None, on either device: per chunk
@@ -39,34 +72,56 @@ def _streamed_def(qc, qs, qk_fmt: str, kc, ks, vc, vs, v_fmt: str, mask, scale: 
     and its row sum, ``quantize_with_mx`` for ``e``'s codes, one ``mx_bmm`` against that slice of ``vt``, then ``Z = Z * alpha + z`` and
     ``acc = acc * alpha + o``; ``acc / Z`` at the end.  The CPU path of ``rows="streamed"``, and what tests compare the GPU against."""
     (G, T, _), S, dv, dev = qc.shape, kc.shape[1], vc.shape[1], qc.device
-    f = lambda v: torch.tensor(v, dtype=torch.float32, device=dev)
-    chunks = -(-S // _CHUNK)
-    vcp = F.pad(vc, (0, chunks * _CHUNK - S))                   # codes past S are zero, scale blocks wholly past S are 127
-    vsp = F.pad(vs, (0, 4 * chunks - vs.shape[-1]), value=127)
-    m = torch.full((G, T, 1), float("-inf"), dtype=torch.float32, device=dev)
-    Z = torch.zeros((G, T, 1), dtype=torch.float32, device=dev)
-    acc = torch.zeros((G, T, dv), dtype=torch.float32, device=dev)
-    bad = torch.zeros((G, T, 1), dtype=torch.bool, device=dev)
     rows = torch.arange(T, device=dev)[:, None]
-    for c in range(chunks):
-        lo, hi = c * _CHUNK, min(S, (c + 1) * _CHUNK)
-        u = mx_bmm(qc, qs, qk_fmt, kc[:, lo:hi].contiguous(), ks[:, lo:hi].contiguous(), qk_fmt) * f(scale)
-        if mask is not None:
-            u = u + mask[..., lo:hi]
-        if causal:                                              # column j of row t is admitted where j <= t
-            u = torch.where(torch.arange(lo, hi, device=dev)[None, :] <= rows, u, f(float("-inf")))
-        bad_c = (u.isnan() | (u == float("inf"))).any(-1, keepdim=True)
-        m2 = torch.maximum(m, torch.where(u.isnan(), f(float("-inf")), u).amax(-1, keepdim=True))
-        e, alpha = F.pad(_exp_def(u - m2), (0, _CHUNK - (hi - lo))), _exp_def(m - m2)
-        z = _row_sum(e.reshape(G * T, _CHUNK)).reshape(G, T, 1)
-        _, ec, es = quantize_with_mx(e, p_fmt, -1, return_codes=True)
-        es = es.clone()
-        es[..., -(-(hi - lo) // 32):] = 127                     # a block wholly past S: zero codes under the byte 127
-        o = mx_bmm(ec, es, p_fmt, vcp[..., lo:lo + _CHUNK].contiguous(), vsp[..., 4 * c:4 * c + 4].contiguous(), v_fmt)
-        live = (rows >= lo) if causal else torch.ones_like(rows, dtype=torch.bool)      # else the row's limit admits nothing here
-        m, Z, acc, bad = (torch.where(live, new, old) for new, old in ((m2, m), (Z * alpha + z, Z), (acc * alpha + o, acc),
-                                                                       (bad | bad_c, bad)))
-    return torch.where(bad | (Z == 0), f(float("nan")), acc / Z).to(out_dtype)
+    state = _empty_state(G, T, dv, dev)
+    for c in range(-(-S // _CHUNK)):                            # column j of row t is admitted where j <= t
+        state = _chunk_step(state, c, qc, qs, qk_fmt, kc, ks, vc, vs, v_fmt, mask, scale, rows + 1 if causal else None, p_fmt)
+    return _finish(*state, out_dtype)
+
+
+def _finish(m, Z, acc, bad, out_dtype):
+    """``acc / Z``; a row that is bad, or that admitted nothing, is NaN as a whole"""
+    return torch.where(bad | (Z == 0), torch.tensor(float("nan"), dtype=torch.float32, device=Z.device), acc / Z).to(out_dtype)
+
+
+def _decode_splits(waves_at_one_split: int, chunks: int) -> int:
+    """``kv_splits="auto"``: enough splits of the key axis to put about one wave on each of the 1024 SIMDs (256 CUs x 4) of an MI355X,
+    never more than the ``chunks`` of 128 keys there are.  A pure function of the shapes -- no device is asked -- because the split
+    count is part of the numerics."""
+    return min(max(1, chunks), max(1, 1024 // max(1, waves_at_one_split)))
+
+
+def _decode_def(qc, qs, qk_fmt: str, kc, ks, vc, vs, v_fmt: str, kv_len, scale: float, causal: bool, p_fmt: str, out_dtype, splits: int):
+    """The decode kernel's definition (``include/qsparse_hip.h``, "MX flash attention, decode") on ``qc [B, Hq, T, d]``, ``kc [B, Hkv, S,
+    d]``, ``vc [B, Hkv, dv, S]`` with their scales and ``kv_len`` (None or int32 ``[B]``), on either device.  Per sequence the operands
+    are sliced to ``L_b`` keys; split i owns the chunks ``[i cps, (i + 1) cps)``, ``cps = ceil(ceil(S / 128) / splits)``, and walks them
+    with ``_chunk_step`` from the empty state; the splits are combined in ascending order, none skipped.  It reads ``kv_len`` on the
+    host: it is what the tests compare against, not what a graph captures."""
+    (B, Hq, T, d), (_, Hkv, S, _), dv, dev = qc.shape, kc.shape, vc.shape[2], qc.device
+    r = Hq // Hkv
+    cps = -(-(-(-S // _CHUNK)) // splits)
+    lens = [S] * B if kv_len is None else [min(max(int(n), 0), S) for n in kv_len.tolist()]
+    tok = (torch.arange(r * T, device=dev) % T)[:, None]         # packed row rho is query head hk r + rho // T, token rho % T
+    out = []
+    for b, L in enumerate(lens):
+        q = (qc[b].reshape(Hkv, r * T, d), qs[b].reshape(Hkv, r * T, -1))
+        kv = (kc[b, :, :L], ks[b, :, :L], vc[b, :, :, :L], vs[b, :, :, :-(-L // 32)])
+        lim = (tok + (L - T + 1)).clamp(min=0) if causal else None      # bottom-right: token t admits the keys j <= L - T + t
+        states = []
+        for i in range(splits):
+            state = _empty_state(Hkv, r * T, dv, dev)
+            for c in range(i * cps, min((i + 1) * cps, -(-L // _CHUNK))):
+                state = _chunk_step(state, c, *q, qk_fmt, *kv[:2], *kv[2:], v_fmt, None, scale, lim, p_fmt)
+            states.append(state)
+        M = states[0][0]
+        for st in states[1:]:
+            M = torch.maximum(M, st[0])
+        Z = acc = bad = None
+        for i, (m_i, Z_i, acc_i, bad_i) in enumerate(states):
+            a_i = _exp_def(m_i - M)
+            Z, acc, bad = (Z_i * a_i, acc_i * a_i, bad_i) if i == 0 else (Z + Z_i * a_i, acc + acc_i * a_i, bad | bad_i)
+        out.append(_finish(M, Z, acc, bad, out_dtype).reshape(Hq, T, dv))
+    return torch.stack(out)
 
 
 def mx_flash_attention(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, k_codes: torch.Tensor, k_scales: torch.Tensor,
@@ -157,4 +212,84 @@ def mx_flash_attention(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: st
                                        streamed=streamed).reshape(lead + (T, dv))
 
 
-__all__ = ["mx_flash_attention"]
+_check_q4 = partial(_mx_common._check_operand, what="[B, Hq, T, d]", least=4, most=4, needs="exactly 4 dimensions")
+_check_k4 = partial(_mx_common._check_operand, what="[B, Hkv, S, d]", least=4, most=4, needs="exactly 4 dimensions")
+_check_vt4 = partial(_mx_common._check_operand, what="[B, Hkv, dv, S]", least=4, most=4, needs="exactly 4 dimensions")
+MX_DECODE_MAX_ROWS = 64          # r * T: the packed rows of a GQA group that one (sequence, kv head) serves
+
+
+def mx_flash_decode(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, k_codes: torch.Tensor, k_scales: torch.Tensor,
+                    vt_codes: torch.Tensor, vt_scales: torch.Tensor, v_fmt: str, kv_len: Optional[torch.Tensor] = None, *, scale: float,
+                    is_causal: bool = False, p_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32,
+                    kv_splits="auto") -> torch.Tensor:
+    """Grouped-query attention on MX codes for decoding: ``q_codes [B, Hq, T, d]`` (a few new tokens) against a cache ``k_codes [B, Hkv,
+    S, d]`` / ``vt_codes [B, Hkv, dv, S]``, all exactly 4-D uint8 codes with the scales ``mx_flash_attention`` takes.  ``Hq = r * Hkv`` and
+    query head ``h`` uses key/value head ``h // r`` -- the ``repeat_interleave`` convention of ``F.scaled_dot_product_attention(
+    enable_gqa=True)`` -- but the cache is read ONCE per group, not ``r`` times.  Returns ``[B, Hq, T, dv]`` in ``out_dtype``.
+
+    ``kv_len`` (None, or an int32 tensor ``[B]`` on the operands' device): sequence ``b`` sees exactly its first ``L_b = clamp(kv_len[b],
+    0, S)`` keys; whatever the cache holds behind them -- NaN included -- is not seen.  It is read ON the device: no host
+    synchronisation, so the call can be captured in a graph and ``kv_len`` updated in place between replays.
+
+    ``is_causal`` is aligned BOTTOM-RIGHT, the decoding convention: token ``t`` admits the keys ``j <= L_b - T + t``.  For ``T == S ==
+    L_b`` that is the top-left triangle of ``mx_flash_attention``; for ``T != S`` the two calls differ.
+
+    ``kv_splits`` (an int ``>= 1`` or ``"auto"``) cuts the key axis into that many runs of whole chunks of 128 keys, counted on ``S``;
+    each run is walked with the streamed kernel's chunk recurrence and the runs are combined in ascending order.  The count is part of
+    the numerics (``_decode_def``, the header's "MX flash attention, decode"; bit for bit on either device); ``"auto"`` is
+    ``_decode_splits``, a function of the shapes alone.  With ``kv_splits=1``, no ``kv_len`` and no ``is_causal`` the result is, bit
+    for bit, ``mx_flash_attention(rows="streamed")`` on the ``repeat_interleave``d cache.
+
+    Supported range: ``r * T <= 64``, ``S >= 1``, ``1 <= d <= 128``, ``1 <= dv <= 128``, every format triple, ``out_dtype`` float32 /
+    bfloat16 / float16; anything else raises ``ValueError`` naming the bound.  GPU tensors take one launch (``kv_splits == 1``) or two;
+    CPU tensors evaluate ``_decode_def``.  Never differentiable; no arbitrary mask."""
+    _check_q4("q", q_codes, q_scales, qk_fmt)
+    _check_k4("k", k_codes, k_scales, qk_fmt)
+    _check_vt4("vt", vt_codes, vt_scales, v_fmt)
+    _mx_format(p_fmt)
+    _check_dtype("out_dtype", out_dtype)
+    (B, Hq, T, d), (_, Hkv, S, _), dv, dev = q_codes.shape, k_codes.shape, vt_codes.shape[2], q_codes.device
+    if k_codes.shape[0] != B or tuple(vt_codes.shape[:2]) != (B, Hkv):
+        raise ValueError(f"q_codes {tuple(q_codes.shape)}, k_codes {tuple(k_codes.shape)} and vt_codes {tuple(vt_codes.shape)} disagree on "
+                         "B or Hkv")
+    if Hkv < 1 or Hq % Hkv != 0:
+        raise ValueError(f"Hq = {Hq} is no multiple of Hkv = {Hkv}: query head h uses key/value head h // (Hq / Hkv)")
+    if k_codes.shape[-1] != d:
+        raise ValueError(f"q_codes {tuple(q_codes.shape)} and k_codes {tuple(k_codes.shape)} disagree on d (their last dimensions)")
+    if vt_codes.shape[-1] != S:
+        raise ValueError(f"k_codes {tuple(k_codes.shape)} [B, Hkv, S, d] and vt_codes {tuple(vt_codes.shape)} [B, Hkv, dv, S] disagree on S")
+    R = Hq // Hkv * T
+    if R > MX_DECODE_MAX_ROWS:
+        raise ValueError(f"mx_flash_decode takes (Hq / Hkv) * T <= {MX_DECODE_MAX_ROWS}, got {Hq // Hkv} * {T} = {R}: longer runs of "
+                         'queries take mx_flash_attention(..., rows="streamed") on the repeated cache')
+    if S < 1:
+        raise ValueError(f"mx_flash_decode takes S >= 1, got S = {S}")
+    for name, n in (("d", d), ("dv", dv)):
+        if n > _hip.MX_FLASH_MAX_D or (n < 1 and name == "d"):
+            raise ValueError(f"mx_flash_decode takes 1 <= {name} <= {_hip.MX_FLASH_MAX_D}, got {name} = {n}")
+    for name, t in (("k_codes", k_codes), ("vt_codes", vt_codes)):
+        if t.device != dev:
+            raise ValueError(f"q_codes is on {dev} but {name} on {t.device}")
+    if kv_len is not None:
+        if not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or tuple(kv_len.shape) != (B,) or kv_len.device != dev:
+            raise ValueError(f"kv_len must be an int32 tensor of shape ({B},) on {dev}, got "
+                             + (f"{kv_len.dtype} {tuple(kv_len.shape)} on {kv_len.device}" if isinstance(kv_len, torch.Tensor)
+                                else type(kv_len).__name__))
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)):
+        raise TypeError(f"scale must be a float, got {type(scale).__name__}")
+    chunks = -(-S // _CHUNK)
+    if kv_splits == "auto":
+        kv_splits = _decode_splits(B * Hkv * -(-R // 16), chunks)
+    elif isinstance(kv_splits, bool) or not isinstance(kv_splits, int) or kv_splits < 1:
+        raise ValueError(f'kv_splits must be an int >= 1 or "auto", got {kv_splits!r}')
+    if 0 in (B, Hq, T, dv):
+        return q_codes.new_empty((B, Hq, T, dv), dtype=out_dtype)
+    with torch.no_grad():
+        ops = (q_codes.contiguous(), q_scales.contiguous(), qk_fmt, k_codes.contiguous(), k_scales.contiguous(),
+               vt_codes.contiguous(), vt_scales.contiguous(), v_fmt, None if kv_len is None else kv_len.contiguous())
+        if not q_codes.is_cuda:
+            return _decode_def(*ops, float(scale), bool(is_causal), p_fmt, out_dtype, kv_splits)
+        return _hip.mx_flash_decode(*ops, float(scale), bool(is_causal), p_fmt, out_dtype, kv_splits)
+
+
+__all__ = ["mx_flash_attention", "mx_flash_decode"]

@@ -2288,6 +2288,75 @@ int qs_mx_flash_decode_v(const qs_mx_flash_decode_args* args);
  * QS_ERR_* the call would return */
 int qs_mx_flash_decode_route(const qs_mx_flash_decode_args* args);
 
+/* ---- MX KV cache append (writing new tokens into the cache qs_mx_flash_decode_v reads, the write position read on the device) ----------
+ * Added without raising QS_ABI_VERSION (28): symbols are only added.  T new tokens per sequence, k_new [B, Hkv, T, d] and v_new [B, Hkv,
+ * T, dv] (and optionally q_new [B, Hq, T, d]) in xdt, go into k_codes [B, Hkv, S, d] / k_scales (blocks along d) and vt_codes [B, Hkv,
+ * dv, S] / vt_scales (blocks along S).  v_tail, float32 [B, Hkv, dv, 32], holds the exact float32 values of the open block of vt: column
+ * j % 32 is position j for j in [32 floor(L / 32), L); its other columns mean nothing.
+ *
+ * Definition (normative).  Per sequence b let L = clamp(kv_len[b], 0, S) and L' = min(L + T, S).  kv_len is only read: the caller
+ * advances it.  Rounding is to nearest.
+ *   1. Token t has position L + t.  A token whose position is >= S is not stored; q is not stored anywhere, so its rows all exist.
+ *   2. Rotation (cos, sin given; d even): row t of every head of k_new -- and of q_new -- is rotated by table row min(L + t, P - 1) with
+ *      the float32 sequence of "MX rotary embedding" (forward, half or interleaved layout): each multiply, subtract and add rounded on
+ *      its own.  Without tables the rows are widened to float32 unchanged.
+ *   3. K: for every stored token, row L + t of k_codes / k_scales of each kv head is the MX quantizer (qs_mx_quant_fwd_v, nearest) along
+ *      d of that float32 row in qk_format.  No other row is written.
+ *   4. Q: q_codes [B, Hq, T, d] / q_scales [B, Hq, T, ceil(d / 32)], dense outputs, are the same quantizer on q's float32 rows.
+ *   5. V: with the history h[j], j in [32 floor(L / 32), L'), taken from v_tail for j < L and from v_new (widened to float32) for
+ *      j >= L, every 32-column block of vt that holds a position in [L, L') is written anew, per channel: its scale byte and its codes
+ *      are the MX quantizer's in v_format on the block's history padded with +0 -- so vt_codes[..., :L'] and vt_scales[..., :ceil(L' /
+ *      32)] are what the quantizer gives along S on all L' tokens at once, and the columns [L', min(S, 32 ceil(L' / 32))) of the open
+ *      block are zero codes.  A block with a NaN or Inf carries the byte 0xFF and zero codes, as the quantizer defines.  Blocks before
+ *      32 floor(L / 32) and behind the last touched block, and every column >= S, are not written.
+ *   6. v_tail: if L' % 32 != 0, the columns j % 32 of the positions j in [max(L, 32 floor(L' / 32)), L') receive h[j].  Nothing else of
+ *      v_tail is written.
+ *   7. L == S (T tokens that all do not fit): nothing is written but q's outputs.
+ *   - Range: 1 <= d <= 128, 1 <= dv <= 128, 1 <= S, T <= 2^30, Hq % Hkv == 0, P >= S, the five formats, the three xdt (one for k_new,
+ *     v_new and q_new).
+ *   - Checks, in order: QS_ERR_ARG: a null or too short descriptor, a NULL cache operand, v_tail, kv_len, k_new or v_new, a format no
+ *     enum qs_mx_format, interleaved neither 0 nor 1, one of cos / sin without the other, q_new without q_codes / q_scales, a negative
+ *     extent, d > 128, dv > 128; QS_ERR_DTYPE: xdt none of the three; QS_ERR_ALIGN: k_new, v_new or q_new not aligned to its element,
+ *     v_tail, kv_len, cos or sin not to 4 bytes.  B == 0 or T == 0: nothing is enqueued, 0 is returned.  Then QS_ERR_ARG: Hkv == 0,
+ *     Hq % Hkv != 0 (with q_new), S == 0, d == 0, dv == 0, S or T > 2^30, tables with an odd d or P < S, an index beyond 64 bits, more
+ *     than 2^31 - 1 work-groups.
+ *   - ONE launch on `stream`; no workspace, no atomics, no counters, nothing read by the host: the call can be captured in a graph and
+ *     kv_len rewritten between replays.  One work-group owns the first and the last touched block of a (b, kv head): it reads v_tail,
+ *     passes a barrier, and writes v_tail last.
+ *   - Routes: QS_MX_KV_APPEND_ROUTE_VEC (16-byte loads of the inputs, 16-byte stores of vt's codes): d and dv multiples of the lane's
+ *     vector (8 two-byte elements, 4 float32), with tables in the half layout also d / 2; k_new, v_new, q_new, cos, sin and vt_codes
+ *     16-byte aligned, k_codes and q_codes aligned to the vector's code bytes, S % 16 == 0.  Anything else takes
+ *     QS_MX_KV_APPEND_ROUTE_PLAIN, element and byte accesses each predicated on its own index: the same bits. */
+#define QS_MX_KV_APPEND_ROUTE_VEC 1
+#define QS_MX_KV_APPEND_ROUTE_PLAIN 2
+typedef struct qs_mx_kv_append_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_kv_append_args) as the caller compiled it */
+    int32_t qk_format;               /* enum qs_mx_format of k (and q) */
+    int32_t v_format;                /* ... of vt */
+    int32_t xdt;                     /* QS_F32, QS_BF16 or QS_F16: k_new, v_new, q_new */
+    int32_t interleaved;             /* 0: pairs (i, i + d / 2); 1: pairs (2 i, 2 i + 1); read with cos / sin only */
+    int32_t reserved0;               /* 0 */
+    uint8_t* k_codes;                /* [B, Hkv, S, d], written in place */
+    uint8_t* k_scales;               /* [B, Hkv, S, ceil(d / 32)] */
+    uint8_t* vt_codes;               /* [B, Hkv, dv, S] */
+    uint8_t* vt_scales;              /* [B, Hkv, dv, ceil(S / 32)] */
+    float* v_tail;                   /* [B, Hkv, dv, 32], read and written */
+    const int32_t* kv_len;           /* [B], device memory, only read */
+    const void* k_new;               /* [B, Hkv, T, d] dense */
+    const void* v_new;               /* [B, Hkv, T, dv] dense */
+    const void* q_new;               /* [B, Hq, T, d] dense, nullable */
+    const float* cos;                /* [P, d / 2], nullable together with sin: no rotation */
+    const float* sin;
+    uint8_t* q_codes;                /* [B, Hq, T, d], with q_new */
+    uint8_t* q_scales;               /* [B, Hq, T, ceil(d / 32)] */
+    int64_t B, Hq, Hkv, T, S, d, dv, P;
+    qs_stream_t stream;
+} qs_mx_kv_append_args;
+int qs_mx_kv_append_v(const qs_mx_kv_append_args* args);
+/* the route qs_mx_kv_append_v takes for these operands, nothing enqueued: QS_MX_KV_APPEND_ROUTE_*, 0 for an empty problem, or the
+ * QS_ERR_* the call would return */
+int qs_mx_kv_append_route(const qs_mx_kv_append_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

@@ -164,6 +164,8 @@ SIGNATURES = {
     "qs_mx_flash_attention_streamed_route": (c_int, [_P]),
     "qs_mx_flash_decode_v": (c_int, [_P]),
     "qs_mx_flash_decode_route": (c_int, [_P]),
+    "qs_mx_kv_append_v": (c_int, [_P]),
+    "qs_mx_kv_append_route": (c_int, [_P]),
 }
 
 
@@ -431,6 +433,16 @@ class MxFlashDecodeArgs(ctypes.Structure):
                 ("k_codes", c_void_p), ("k_scales", c_void_p), ("vt_codes", c_void_p), ("vt_scales", c_void_p), ("kv_len", c_void_p),
                 ("workspace", c_void_p), ("workspace_bytes", c_int64), ("y", c_void_p), ("B", c_int64), ("Hq", c_int64), ("Hkv", c_int64),
                 ("T", c_int64), ("S", c_int64), ("d", c_int64), ("dv", c_int64), ("stream", c_void_p)]
+
+
+class MxKvAppendArgs(ctypes.Structure):
+    """`qs_mx_kv_append_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("qk_format", c_int32), ("v_format", c_int32), ("xdt", c_int32),
+                ("interleaved", c_int32), ("reserved0", c_int32), ("k_codes", c_void_p), ("k_scales", c_void_p), ("vt_codes", c_void_p),
+                ("vt_scales", c_void_p), ("v_tail", c_void_p), ("kv_len", c_void_p), ("k_new", c_void_p), ("v_new", c_void_p),
+                ("q_new", c_void_p), ("cos", c_void_p), ("sin", c_void_p), ("q_codes", c_void_p), ("q_scales", c_void_p),
+                ("B", c_int64), ("Hq", c_int64), ("Hkv", c_int64), ("T", c_int64), ("S", c_int64), ("d", c_int64), ("dv", c_int64),
+                ("P", c_int64), ("stream", c_void_p)]
 
 
 class MxSoftmaxQuant2Args(ctypes.Structure):
@@ -1878,6 +1890,41 @@ def mx_flash_decode(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, 
         a.stream = _stream(q_codes)
         mx_flash_last_route = _mx_run("mx_flash_decode", a, (q_codes, q_scales, k_codes, k_scales, vt_codes, vt_scales, kv_len, y))
     return y
+
+
+MX_KV_APPEND_ROUTE_VEC, MX_KV_APPEND_ROUTE_PLAIN = 1, 2
+mx_kv_append_last_route = None   # the QS_MX_KV_APPEND_ROUTE_* of the last `mx_kv_append` launch (None: an empty problem)
+
+
+def mx_kv_append(k_codes: torch.Tensor, k_scales: torch.Tensor, qk_fmt: str, vt_codes: torch.Tensor, vt_scales: torch.Tensor, v_fmt: str,
+                 v_tail: torch.Tensor, kv_len: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, q_new: Optional[torch.Tensor],
+                 cos: Optional[torch.Tensor], sin: Optional[torch.Tensor], interleaved: bool, q_out=None):
+    """T new tokens into the MX KV cache in ONE launch (qs_mx_kv_append_v): the cache `k_codes` [B, Hkv, S, d], `vt_codes` [B, Hkv, dv,
+    S] with their scales and the float32 `v_tail` [B, Hkv, dv, 32] are contiguous GPU tensors written in place; `kv_len` int32 [B] is
+    read by the kernel; `k_new` [B, Hkv, T, d], `v_new` [B, Hkv, T, dv], `q_new` [B, Hq, T, d] or None are contiguous and of one dtype;
+    `cos` / `sin` float32 [P, d / 2] or both None.  Returns (q_codes, q_scales) for a `q_new`, else None.  `q_out`: the two tensors to
+    write instead, contiguous, as the guard-byte tests carve them.  The route lands in `mx_kv_append_last_route`."""
+    global mx_kv_append_last_route
+    load()
+    (B, Hkv, S, d), dv, T = k_codes.shape, vt_codes.shape[2], k_new.shape[2]
+    q = None
+    if q_new is not None:
+        Hq = q_new.shape[1]
+        q = tuple(_mx_new_or_out(shape, torch.uint8, k_codes.device, None if q_out is None else q_out[i], "q_out: dense uint8")
+                  for i, shape in enumerate(((B, Hq, T, d), (B, Hq, T, (d + MX_BLOCK - 1) // MX_BLOCK))))
+    mx_kv_append_last_route = None
+    if B and T:
+        a = MxKvAppendArgs()
+        a.qk_format, a.v_format, a.xdt, a.interleaved = MX_FORMATS.index(qk_fmt), MX_FORMATS.index(v_fmt), dt(k_new), int(bool(interleaved))
+        a.k_codes, a.k_scales, a.vt_codes, a.vt_scales = _ptr(k_codes), _ptr(k_scales), _ptr(vt_codes), _ptr(vt_scales)
+        a.v_tail, a.kv_len, a.k_new, a.v_new, a.q_new = _ptr(v_tail), _ptr(kv_len), _ptr(k_new), _ptr(v_new), _ptr(q_new)
+        a.cos, a.sin = _ptr(cos), _ptr(sin)
+        if q is not None:
+            a.q_codes, a.q_scales, a.Hq = _ptr(q[0]), _ptr(q[1]), q_new.shape[1]
+        a.B, a.Hkv, a.T, a.S, a.d, a.dv, a.P = B, Hkv, T, S, d, dv, 0 if cos is None else cos.shape[0]
+        a.stream = _stream(k_codes)
+        mx_kv_append_last_route = _mx_run("mx_kv_append", a, (k_new, v_new, q_new) + (q or ()))
+    return q
 
 
 mx_softmax_quant2_last_route = None     # the QS_MX_SOFTMAX_ROUTE_* of the last `mx_softmax_quant2` launch (None: an empty tensor)

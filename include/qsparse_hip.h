@@ -2357,6 +2357,104 @@ int qs_mx_kv_append_v(const qs_mx_kv_append_args* args);
  * QS_ERR_* the call would return */
 int qs_mx_kv_append_route(const qs_mx_kv_append_args* args);
 
+/* ---- MX flash attention, paged decode (qs_mx_flash_decode_v on a cache of pages named by a block table read on the device) ----------
+ * Added without raising QS_ABI_VERSION (28): symbols are only added.  Layout: `page`, the keys per page, is a power of two >= 32 -- it
+ * divides the chunk of 128 or is a multiple of it, and a block of 32 along S never straddles a page.  The pool is k_pool [P, Hkv, page,
+ * d] with k_pool_scales [P, Hkv, page, ceil(d / 32)] and vt_pool [P, Hkv, dv, page] with vt_pool_scales [P, Hkv, dv, page / 32], all
+ * contiguous.  block_table is int32 [B, NP] in device memory: position j of sequence b lives in pool page block_table[b, j / page], row
+ * j % page of k_pool and column j % page of vt_pool.  The logical capacity is S = NP * page.  Several sequences may name one page.
+ *
+ * Definition (normative).  The result IS "MX flash attention, decode" on the gathered cache k[b, hk, n * page + i] = k_pool[
+ * block_table[b, n], hk, i] (the scales alike; vt along its last axis), with S = NP * page: splits are counted on that S, kv_len is
+ * required.  With L = clamp(kv_len[b], 0, S):
+ *   1. Entries block_table[b, n] with n * page >= L are never turned into an address; they may hold anything.
+ *   2. An entry with n * page < L outside [0, P) is not dereferenced: its page reads as zero codes under the scale byte 127, for k and
+ *      for vt.  (A guard, not a feature.)
+ *   - Range, workspace, launches: as qs_mx_flash_decode_v; 1 <= P <= 2^31 - 1, NP >= 1, NP * page <= 2^31 - 129.
+ *   - Checks, in order: QS_ERR_ARG: a null or too short descriptor, a NULL operand, block_table, kv_len or y, a format no enum
+ *     qs_mx_format, causal neither 0 nor 1, a negative extent, kv_splits < 1, d > 128, dv > 128; QS_ERR_DTYPE: ydt none of the three;
+ *     QS_ERR_ALIGN: y not aligned to its element, block_table, kv_len or workspace not to 4 bytes.  B == 0, Hq == 0, T == 0 or dv == 0:
+ *     nothing is enqueued, 0 is returned.  Then QS_ERR_ARG: Hkv == 0, Hq % Hkv != 0, r * T > 64, P < 1, P > 2^31 - 1, NP < 1, d == 0, a
+ *     page that is no power of two >= 32, NP * page > 2^31 - 129, a byte count beyond 64 bits, more waves than 4 * (2^31 - 1), or
+ *     kv_splits > 1 with workspace NULL or workspace_bytes too small.
+ *   - Each wave holds 64 table entries in one vector register, loaded where n * page is below its last admitted key, and broadcasts
+ *     the page numbers of a chunk out of it: no table load on the per-chunk path but one per 64 pages.
+ *   - Routes: QS_MX_FLASH_ROUTE_VEC: d % 16 == 0 and q_codes, k_pool, vt_pool 16-byte aligned (every page base is then aligned);
+ *     anything else QS_MX_FLASH_ROUTE_PLAIN: the same bits. */
+typedef struct qs_mx_flash_decode_paged_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_flash_decode_paged_args) as the caller compiled it */
+    int32_t qk_format;               /* enum qs_mx_format of q and k */
+    int32_t p_format;                /* ... of the attention weights */
+    int32_t v_format;                /* ... of vt */
+    int32_t ydt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    int32_t causal;                  /* 0 or 1, bottom-right aligned */
+    float scale;
+    int32_t kv_splits;               /* >= 1 */
+    const uint8_t* q_codes;          /* [B, Hq, T, d] */
+    const uint8_t* q_scales;         /* [B, Hq, T, ceil(d / 32)] */
+    const uint8_t* k_pool;           /* [P, Hkv, page, d] */
+    const uint8_t* k_pool_scales;    /* [P, Hkv, page, ceil(d / 32)] */
+    const uint8_t* vt_pool;          /* [P, Hkv, dv, page] */
+    const uint8_t* vt_pool_scales;   /* [P, Hkv, dv, page / 32] */
+    const int32_t* block_table;      /* [B, NP], device memory */
+    const int32_t* kv_len;           /* [B], device memory */
+    float* workspace;                /* as qs_mx_flash_decode_args; nullable with kv_splits == 1 */
+    int64_t workspace_bytes;
+    void* y;                         /* [B, Hq, T, dv] dense */
+    int64_t B, Hq, Hkv, T, P, NP, page, d, dv;
+    qs_stream_t stream;
+} qs_mx_flash_decode_paged_args;
+int qs_mx_flash_decode_paged_v(const qs_mx_flash_decode_paged_args* args);
+/* the route qs_mx_flash_decode_paged_v takes for these operands, nothing enqueued: QS_MX_FLASH_ROUTE_*, 0 for an empty problem, or the
+ * QS_ERR_* the call would return */
+int qs_mx_flash_decode_paged_route(const qs_mx_flash_decode_paged_args* args);
+
+/* ---- MX KV cache append, paged (qs_mx_kv_append_v into the pool that qs_mx_flash_decode_paged_v reads) -----------------------------------
+ * Added without raising QS_ABI_VERSION (28): symbols are only added.  The layout is the section's above; v_tail [B, Hkv, dv, 32] and
+ * kv_len [B] stay per sequence, not paged.
+ *
+ * Definition (normative).  "MX KV cache append" with S = NP * page and every position translated through the table: K row L + t goes to
+ * row (L + t) % page of page block_table[b, (L + t) / page]; every 32-column block of vt that receives a position is quantized anew
+ * from v_tail and the new values inside its page (a block never crosses a page); v_tail is updated as there; tokens at positions >= S
+ * are dropped; rotation tables are indexed by the logical position; q's codes are returned.
+ *   1. A token whose entry is outside [0, P) is not stored and its block of vt is skipped; v_tail advances as if it had been stored.
+ *   2. Every byte of the pool outside the touched rows and blocks keeps its value, all pages that no touched position names included.
+ *   3. One call must not write one page for two sequences (the caller's duty): the result for that page is unspecified, but no access
+ *      leaves the pool.
+ *   - Table entries are looked up after L is known and only for positions < S.
+ *   - Range and checks: as qs_mx_kv_append_v with block_table among the NULL and 4-byte alignment checks, then QS_ERR_ARG: P_pool < 1
+ *     or > 2^31 - 1, NP < 1, a page that is no power of two >= 32, NP * page > 2^30, tables with fewer rows than NP * page.
+ *   - Routes: QS_MX_KV_APPEND_ROUTE_VEC by qs_mx_kv_append_route's rule with the pool in the cache's place (page % 16 == 0 always
+ *     holds); anything else QS_MX_KV_APPEND_ROUTE_PLAIN: the same bits.  ONE launch, graph-capturable. */
+typedef struct qs_mx_kv_append_paged_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_kv_append_paged_args) as the caller compiled it */
+    int32_t qk_format;               /* enum qs_mx_format of k (and q) */
+    int32_t v_format;                /* ... of vt */
+    int32_t xdt;                     /* QS_F32, QS_BF16 or QS_F16: k_new, v_new, q_new */
+    int32_t interleaved;             /* as qs_mx_kv_append_args */
+    int32_t reserved0;               /* 0 */
+    uint8_t* k_pool;                 /* [P_pool, Hkv, page, d], written in place */
+    uint8_t* k_pool_scales;          /* [P_pool, Hkv, page, ceil(d / 32)] */
+    uint8_t* vt_pool;                /* [P_pool, Hkv, dv, page] */
+    uint8_t* vt_pool_scales;         /* [P_pool, Hkv, dv, page / 32] */
+    float* v_tail;                   /* [B, Hkv, dv, 32], read and written */
+    const int32_t* block_table;      /* [B, NP], device memory, only read */
+    const int32_t* kv_len;           /* [B], device memory, only read */
+    const void* k_new;               /* [B, Hkv, T, d] dense */
+    const void* v_new;               /* [B, Hkv, T, dv] dense */
+    const void* q_new;               /* [B, Hq, T, d] dense, nullable */
+    const float* cos;                /* [P, d / 2], nullable together with sin: no rotation */
+    const float* sin;
+    uint8_t* q_codes;                /* [B, Hq, T, d], with q_new */
+    uint8_t* q_scales;               /* [B, Hq, T, ceil(d / 32)] */
+    int64_t B, Hq, Hkv, T, P_pool, NP, page, d, dv, P;
+    qs_stream_t stream;
+} qs_mx_kv_append_paged_args;
+int qs_mx_kv_append_paged_v(const qs_mx_kv_append_paged_args* args);
+/* the route qs_mx_kv_append_paged_v takes for these operands, nothing enqueued: QS_MX_KV_APPEND_ROUTE_*, 0 for an empty problem, or the
+ * QS_ERR_* the call would return */
+int qs_mx_kv_append_paged_route(const qs_mx_kv_append_paged_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

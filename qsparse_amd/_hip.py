@@ -166,6 +166,10 @@ SIGNATURES = {
     "qs_mx_flash_decode_route": (c_int, [_P]),
     "qs_mx_kv_append_v": (c_int, [_P]),
     "qs_mx_kv_append_route": (c_int, [_P]),
+    "qs_mx_flash_decode_paged_v": (c_int, [_P]),
+    "qs_mx_flash_decode_paged_route": (c_int, [_P]),
+    "qs_mx_kv_append_paged_v": (c_int, [_P]),
+    "qs_mx_kv_append_paged_route": (c_int, [_P]),
 }
 
 
@@ -443,6 +447,26 @@ class MxKvAppendArgs(ctypes.Structure):
                 ("q_new", c_void_p), ("cos", c_void_p), ("sin", c_void_p), ("q_codes", c_void_p), ("q_scales", c_void_p),
                 ("B", c_int64), ("Hq", c_int64), ("Hkv", c_int64), ("T", c_int64), ("S", c_int64), ("d", c_int64), ("dv", c_int64),
                 ("P", c_int64), ("stream", c_void_p)]
+
+
+class MxFlashDecodePagedArgs(ctypes.Structure):
+    """`qs_mx_flash_decode_paged_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("qk_format", c_int32), ("p_format", c_int32), ("v_format", c_int32), ("ydt", c_int32),
+                ("causal", c_int32), ("scale", c_float), ("kv_splits", c_int32), ("q_codes", c_void_p), ("q_scales", c_void_p),
+                ("k_pool", c_void_p), ("k_pool_scales", c_void_p), ("vt_pool", c_void_p), ("vt_pool_scales", c_void_p),
+                ("block_table", c_void_p), ("kv_len", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_int64), ("y", c_void_p),
+                ("B", c_int64), ("Hq", c_int64), ("Hkv", c_int64), ("T", c_int64), ("P", c_int64), ("NP", c_int64), ("page", c_int64),
+                ("d", c_int64), ("dv", c_int64), ("stream", c_void_p)]
+
+
+class MxKvAppendPagedArgs(ctypes.Structure):
+    """`qs_mx_kv_append_paged_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("qk_format", c_int32), ("v_format", c_int32), ("xdt", c_int32),
+                ("interleaved", c_int32), ("reserved0", c_int32), ("k_pool", c_void_p), ("k_pool_scales", c_void_p), ("vt_pool", c_void_p),
+                ("vt_pool_scales", c_void_p), ("v_tail", c_void_p), ("block_table", c_void_p), ("kv_len", c_void_p), ("k_new", c_void_p),
+                ("v_new", c_void_p), ("q_new", c_void_p), ("cos", c_void_p), ("sin", c_void_p), ("q_codes", c_void_p),
+                ("q_scales", c_void_p), ("B", c_int64), ("Hq", c_int64), ("Hkv", c_int64), ("T", c_int64), ("P_pool", c_int64),
+                ("NP", c_int64), ("page", c_int64), ("d", c_int64), ("dv", c_int64), ("P", c_int64), ("stream", c_void_p)]
 
 
 class MxSoftmaxQuant2Args(ctypes.Structure):
@@ -1892,6 +1916,34 @@ def mx_flash_decode(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, 
     return y
 
 
+def mx_flash_decode_paged(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, k_pool: torch.Tensor, k_pool_scales: torch.Tensor,
+                          vt_pool: torch.Tensor, vt_pool_scales: torch.Tensor, v_fmt: str, block_table: torch.Tensor, kv_len: torch.Tensor,
+                          scale: float, causal: bool, p_fmt: str, out_dtype: torch.dtype, kv_splits: int, out=None) -> torch.Tensor:
+    """`mx_flash_decode` on a paged cache (qs_mx_flash_decode_paged_v): `q_codes` [B, Hq, T, d], the pool `k_pool` [P, Hkv, page, d],
+    `vt_pool` [P, Hkv, dv, page] uint8 with their scales, `block_table` int32 [B, NP] and `kv_len` int32 [B], all contiguous GPU tensors
+    -- the table and the lengths are read by the kernel.  Returns y [B, Hq, T, dv] in `out_dtype` from one launch (`kv_splits` == 1) or
+    two.  `out`: as `mx_flash_decode`.  The route lands in `mx_flash_last_route`."""
+    global mx_flash_last_route
+    load()
+    (B, Hq, T, d), (P, Hkv, page, _), dv, NP = q_codes.shape, k_pool.shape, vt_pool.shape[2], block_table.shape[1]
+    y = _mx_new_or_out((B, Hq, T, dv), out_dtype, q_codes.device, out, "out: B Hq T dv elements of out_dtype")
+    mx_flash_last_route = None
+    if B and Hq and T and dv:
+        a = MxFlashDecodePagedArgs()
+        a.qk_format, a.p_format, a.v_format = MX_FORMATS.index(qk_fmt), MX_FORMATS.index(p_fmt), MX_FORMATS.index(v_fmt)
+        a.ydt, a.causal, a.scale, a.kv_splits = _DT[out_dtype], int(bool(causal)), float(scale), int(kv_splits)
+        a.q_codes, a.q_scales, a.k_pool, a.k_pool_scales = _ptr(q_codes), _ptr(q_scales), _ptr(k_pool), _ptr(k_pool_scales)
+        a.vt_pool, a.vt_pool_scales, a.block_table, a.kv_len, a.y = _ptr(vt_pool), _ptr(vt_pool_scales), _ptr(block_table), _ptr(kv_len), _ptr(y)
+        ws = None
+        if kv_splits > 1:       # (m, Z, bad, acc[dv]) of every packed row and split; the kernels write every record they read
+            ws = torch.empty(B * Hkv * (Hq // Hkv * T) * kv_splits * (dv + 3), dtype=torch.float32, device=q_codes.device)
+            a.workspace, a.workspace_bytes = _ptr(ws), ws.numel() * 4
+        a.B, a.Hq, a.Hkv, a.T, a.P, a.NP, a.page, a.d, a.dv = B, Hq, Hkv, T, P, NP, page, d, dv
+        a.stream = _stream(q_codes)
+        mx_flash_last_route = _mx_run("mx_flash_decode_paged", a, (q_codes, q_scales, block_table, kv_len, y))
+    return y
+
+
 MX_KV_APPEND_ROUTE_VEC, MX_KV_APPEND_ROUTE_PLAIN = 1, 2
 mx_kv_append_last_route = None   # the QS_MX_KV_APPEND_ROUTE_* of the last `mx_kv_append` launch (None: an empty problem)
 
@@ -1924,6 +1976,37 @@ def mx_kv_append(k_codes: torch.Tensor, k_scales: torch.Tensor, qk_fmt: str, vt_
         a.B, a.Hkv, a.T, a.S, a.d, a.dv, a.P = B, Hkv, T, S, d, dv, 0 if cos is None else cos.shape[0]
         a.stream = _stream(k_codes)
         mx_kv_append_last_route = _mx_run("mx_kv_append", a, (k_new, v_new, q_new) + (q or ()))
+    return q
+
+
+def mx_kv_append_paged(k_pool: torch.Tensor, k_pool_scales: torch.Tensor, qk_fmt: str, vt_pool: torch.Tensor, vt_pool_scales: torch.Tensor,
+                       v_fmt: str, v_tail: torch.Tensor, block_table: torch.Tensor, kv_len: torch.Tensor, k_new: torch.Tensor,
+                       v_new: torch.Tensor, q_new: Optional[torch.Tensor], cos: Optional[torch.Tensor], sin: Optional[torch.Tensor],
+                       interleaved: bool, q_out=None):
+    """`mx_kv_append` into a paged cache in ONE launch (qs_mx_kv_append_paged_v): the pool `k_pool` [P, Hkv, page, d], `vt_pool` [P, Hkv,
+    dv, page] with their scales and the float32 `v_tail` [B, Hkv, dv, 32] are contiguous GPU tensors written in place; `block_table`
+    int32 [B, NP] and `kv_len` int32 [B] are read by the kernel; the new tokens, the tables, the return value and `q_out` as
+    `mx_kv_append`.  The route lands in `mx_kv_append_last_route`."""
+    global mx_kv_append_last_route
+    load()
+    (P, Hkv, page, d), dv, (B, NP), T = k_pool.shape, vt_pool.shape[2], block_table.shape, k_new.shape[2]
+    q = None
+    if q_new is not None:
+        Hq = q_new.shape[1]
+        q = tuple(_mx_new_or_out(shape, torch.uint8, k_pool.device, None if q_out is None else q_out[i], "q_out: dense uint8")
+                  for i, shape in enumerate(((B, Hq, T, d), (B, Hq, T, (d + MX_BLOCK - 1) // MX_BLOCK))))
+    mx_kv_append_last_route = None
+    if B and T:
+        a = MxKvAppendPagedArgs()
+        a.qk_format, a.v_format, a.xdt, a.interleaved = MX_FORMATS.index(qk_fmt), MX_FORMATS.index(v_fmt), dt(k_new), int(bool(interleaved))
+        a.k_pool, a.k_pool_scales, a.vt_pool, a.vt_pool_scales = _ptr(k_pool), _ptr(k_pool_scales), _ptr(vt_pool), _ptr(vt_pool_scales)
+        a.v_tail, a.block_table, a.kv_len = _ptr(v_tail), _ptr(block_table), _ptr(kv_len)
+        a.k_new, a.v_new, a.q_new, a.cos, a.sin = _ptr(k_new), _ptr(v_new), _ptr(q_new), _ptr(cos), _ptr(sin)
+        if q is not None:
+            a.q_codes, a.q_scales, a.Hq = _ptr(q[0]), _ptr(q[1]), q_new.shape[1]
+        a.B, a.Hkv, a.T, a.P_pool, a.NP, a.page, a.d, a.dv, a.P = B, Hkv, T, P, NP, page, d, dv, 0 if cos is None else cos.shape[0]
+        a.stream = _stream(k_pool)
+        mx_kv_append_last_route = _mx_run("mx_kv_append_paged", a, (k_new, v_new, q_new, block_table) + (q or ()))
     return q
 
 

@@ -138,7 +138,8 @@ __device__ __forceinline__ void mxd_pv_p(int p_format, int v_format, A&&... args
     }
 }
 
-__global__ __launch_bounds__(kMxgThreads, 1) void mx_flash_decode_kernel(MxFormat fp, MxdArgs a) {
+// (`inline`, here and on the combine kernel: qs_mx_flash_decode_paged.h includes this header into a second unit)
+inline __global__ __launch_bounds__(kMxgThreads, 1) void mx_flash_decode_kernel(MxFormat fp, MxdArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[4 * kMxfBounce];
     const int tid = threadIdx.x, lane = tid & 63, i = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -334,7 +335,7 @@ __global__ __launch_bounds__(kMxgThreads, 1) void mx_flash_decode_kernel(MxForma
 
 // y from the n split states of each row, in the definition's order: M = max m_i, a_i = E(m_i - M), Z = Z_0 a_0 (+ Z_i a_i ...), acc
 // likewise, every multiply and add on its own; one thread per (output row, 4 columns)
-__global__ __launch_bounds__(256) void mx_flash_decode_combine_kernel(MxdArgs a, int64_t quads) {
+inline __global__ __launch_bounds__(256) void mx_flash_decode_combine_kernel(MxdArgs a, int64_t quads) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int nq = (a.dv + 3) / 4;
     if (e >= quads) return;

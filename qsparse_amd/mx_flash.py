@@ -292,4 +292,117 @@ def mx_flash_decode(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, 
         return _hip.mx_flash_decode(*ops, float(scale), bool(is_causal), p_fmt, out_dtype, kv_splits)
 
 
-__all__ = ["mx_flash_attention", "mx_flash_decode"]
+MX_PAGE_MIN = 32                 # keys per page: a power of two >= 32, so a block of 32 along S never straddles a page
+_check_kp = partial(_mx_common._check_operand, what="[P, Hkv, page, d]", least=4, most=4, needs="exactly 4 dimensions")
+_check_vtp = partial(_mx_common._check_operand, what="[P, Hkv, dv, page]", least=4, most=4, needs="exactly 4 dimensions",
+                     axis=" (page / 32 blocks)")
+
+
+def _check_pool(fn: str, k_pool, k_pool_scales, qk_fmt: str, vt_pool, vt_pool_scales, v_fmt: str, block_table, kv_len, B=None):
+    """the paged operands of ``fn``: the pool pair, ``block_table`` int32 ``[B, NP]`` and ``kv_len`` int32 ``[B]`` on the pool's device"""
+    _check_kp("k_pool", k_pool, k_pool_scales, qk_fmt)
+    (P, Hkv, page, _), dev = k_pool.shape, k_pool.device
+    if page < MX_PAGE_MIN or page & (page - 1):
+        raise ValueError(f"{fn} takes a page (k_pool's third dimension) that is a power of two >= {MX_PAGE_MIN}, got page = {page}")
+    _check_vtp("vt_pool", vt_pool, vt_pool_scales, v_fmt)
+    if tuple(vt_pool.shape[:2]) != (P, Hkv) or vt_pool.shape[3] != page:
+        raise ValueError(f"k_pool {tuple(k_pool.shape)} [P, Hkv, page, d] and vt_pool {tuple(vt_pool.shape)} [P, Hkv, dv, page] disagree on "
+                         "P, Hkv or page")
+    if P < 1 or Hkv < 1:
+        raise ValueError(f"{fn} takes a pool of P >= 1 pages and Hkv >= 1, got P = {P}, Hkv = {Hkv}")
+    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or \
+            (B is not None and block_table.shape[0] != B) or block_table.shape[1] < 1 or block_table.device != dev:
+        raise ValueError(f"block_table must be an int32 tensor of shape ({'B' if B is None else B}, NP >= 1) on {dev}, got "
+                         + (f"{block_table.dtype} {tuple(block_table.shape)} on {block_table.device}"
+                            if isinstance(block_table, torch.Tensor) else type(block_table).__name__))
+    B = block_table.shape[0]
+    if not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or tuple(kv_len.shape) != (B,) or kv_len.device != dev:
+        raise ValueError(f"kv_len must be an int32 tensor of shape ({B},) on {dev}, got "
+                         + (f"{kv_len.dtype} {tuple(kv_len.shape)} on {kv_len.device}" if isinstance(kv_len, torch.Tensor)
+                            else type(kv_len).__name__))
+    if vt_pool.device != dev:
+        raise ValueError(f"k_pool is on {dev} but vt_pool on {vt_pool.device}")
+
+
+def _paged_gather(k_pool, k_pool_scales, vt_pool, vt_pool_scales, block_table):
+    """the contiguous cache ``(k [B, Hkv, NP * page, d], ks, vt [B, Hkv, dv, NP * page], vts)`` that ``block_table [B, NP]`` names in the
+    pool; the page of an entry outside ``[0, P)`` is zero codes under the scale byte 127"""
+    (B, NP), P = block_table.shape, k_pool.shape[0]
+    idx = block_table.to(torch.int64)
+    ok = ((idx >= 0) & (idx < P)).view(B, NP, 1, 1, 1)
+    idx = idx.clamp(0, P - 1).reshape(-1)
+    pages = [torch.where(ok, t.index_select(0, idx).reshape((B, NP) + t.shape[1:]), torch.tensor(fill, dtype=torch.uint8, device=t.device))
+             for t, fill in ((k_pool, 0), (k_pool_scales, 127), (vt_pool, 0), (vt_pool_scales, 127))]
+    k, ks = (t.permute(0, 2, 1, 3, 4).reshape(B, t.shape[2], NP * t.shape[3], t.shape[4]) for t in pages[:2])
+    vt, vts = (t.permute(0, 2, 3, 1, 4).reshape(B, t.shape[2], t.shape[3], NP * t.shape[4]) for t in pages[2:])
+    return k, ks, vt, vts
+
+
+def _decode_paged_def(qc, qs, qk_fmt: str, k_pool, k_pool_scales, vt_pool, vt_pool_scales, v_fmt: str, block_table, kv_len, scale: float,
+                      causal: bool, p_fmt: str, out_dtype, splits: int):
+    """The paged decode kernel's definition (``include/qsparse_hip.h``, "MX flash attention, paged decode"), on either device:
+    ``_decode_def`` on the gathered cache, ``S = NP * page``.  ``_decode_def`` slices every sequence to ``L_b``, so the entries at or
+    behind ``ceil(L_b / page)`` mean nothing here either."""
+    k, ks, vt, vts = _paged_gather(k_pool, k_pool_scales, vt_pool, vt_pool_scales, block_table)
+    return _decode_def(qc, qs, qk_fmt, k, ks, vt, vts, v_fmt, kv_len, scale, causal, p_fmt, out_dtype, splits)
+
+
+def mx_flash_decode_paged(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, k_pool: torch.Tensor, k_pool_scales: torch.Tensor,
+                          vt_pool: torch.Tensor, vt_pool_scales: torch.Tensor, v_fmt: str, block_table: torch.Tensor, kv_len: torch.Tensor,
+                          *, scale: float, is_causal: bool = False, p_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32,
+                          kv_splits="auto") -> torch.Tensor:
+    """``mx_flash_decode`` on a PAGED cache.  The pool is ``k_pool [P, Hkv, page, d]`` / ``k_pool_scales [P, Hkv, page, ceil(d / 32)]`` and
+    ``vt_pool [P, Hkv, dv, page]`` / ``vt_pool_scales [P, Hkv, dv, page / 32]``, contiguous, ``page`` a power of two ``>= 32``.
+    ``block_table`` (int32 ``[B, NP]`` on the operands' device) says where a sequence's keys live: position ``j`` of sequence ``b`` is row
+    ``j % page`` of ``k_pool[block_table[b, j // page]]`` and column ``j % page`` of ``vt_pool[...]``.  Several sequences may name one page
+    (a shared prefix).  The logical capacity is ``S = NP * page``; ``kv_len`` (int32 ``[B]``) is required.
+
+    The result IS ``mx_flash_decode`` on the gathered cache, bit for bit on either device (``_decode_paged_def``): splits are counted on
+    ``S = NP * page``, ``"auto"`` is ``_decode_splits(B * Hkv * ceil(R / 16), ceil(S / 128))``, ``is_causal`` is bottom-right.  The table
+    and the lengths are read ON the device: the call can be captured in a graph and both rewritten in place between replays.
+
+    With ``L_b = clamp(kv_len[b], 0, S)``, the entries ``block_table[b, n]`` with ``n * page >= L_b`` are never turned into an address and
+    may hold anything.  An entry in the live range that lies outside ``[0, P)`` is not dereferenced either: its page reads as zero
+    codes under the scale byte 127.  That is a guard, not a feature.
+
+    Supported range: that of ``mx_flash_decode`` (``r * T <= 64``, ``d, dv <= 128``, every format triple, three output dtypes); anything
+    else raises ``ValueError``.  GPU tensors take one launch (``kv_splits == 1``) or two (``qs_mx_flash_decode_paged_v``; no fallback
+    and no gathered copy); CPU tensors evaluate ``_decode_paged_def``."""
+    _check_q4("q", q_codes, q_scales, qk_fmt)
+    _mx_format(p_fmt)
+    _check_dtype("out_dtype", out_dtype)
+    (B, Hq, T, d), dev = q_codes.shape, q_codes.device
+    _check_pool("mx_flash_decode_paged", k_pool, k_pool_scales, qk_fmt, vt_pool, vt_pool_scales, v_fmt, block_table, kv_len, B)
+    (P, Hkv, page, _), dv, NP = k_pool.shape, vt_pool.shape[2], block_table.shape[1]
+    if k_pool.device != dev:
+        raise ValueError(f"q_codes is on {dev} but k_pool on {k_pool.device}")
+    if Hq % Hkv != 0:
+        raise ValueError(f"Hq = {Hq} is no multiple of Hkv = {Hkv}: query head h uses key/value head h // (Hq / Hkv)")
+    if k_pool.shape[-1] != d:
+        raise ValueError(f"q_codes {tuple(q_codes.shape)} and k_pool {tuple(k_pool.shape)} disagree on d (their last dimensions)")
+    R = Hq // Hkv * T
+    if R > MX_DECODE_MAX_ROWS:
+        raise ValueError(f"mx_flash_decode_paged takes (Hq / Hkv) * T <= {MX_DECODE_MAX_ROWS}, got {Hq // Hkv} * {T} = {R}")
+    for name, n in (("d", d), ("dv", dv)):
+        if n > _hip.MX_FLASH_MAX_D or (n < 1 and name == "d"):
+            raise ValueError(f"mx_flash_decode_paged takes 1 <= {name} <= {_hip.MX_FLASH_MAX_D}, got {name} = {n}")
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)):
+        raise TypeError(f"scale must be a float, got {type(scale).__name__}")
+    if kv_splits == "auto":
+        kv_splits = _decode_splits(B * Hkv * -(-R // 16), -(-NP * page // _CHUNK))
+    elif isinstance(kv_splits, bool) or not isinstance(kv_splits, int) or kv_splits < 1:
+        raise ValueError(f'kv_splits must be an int >= 1 or "auto", got {kv_splits!r}')
+    if 0 in (B, Hq, T, dv):
+        return q_codes.new_empty((B, Hq, T, dv), dtype=out_dtype)
+    for name, t in (("k_pool", k_pool), ("k_pool_scales", k_pool_scales), ("vt_pool", vt_pool), ("vt_pool_scales", vt_pool_scales)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous: the pool is addressed through block_table, not copied")
+    with torch.no_grad():
+        ops = (q_codes.contiguous(), q_scales.contiguous(), qk_fmt, k_pool, k_pool_scales, vt_pool, vt_pool_scales, v_fmt,
+               block_table.contiguous(), kv_len.contiguous())
+        if not q_codes.is_cuda:
+            return _decode_paged_def(*ops, float(scale), bool(is_causal), p_fmt, out_dtype, kv_splits)
+        return _hip.mx_flash_decode_paged(*ops, float(scale), bool(is_causal), p_fmt, out_dtype, kv_splits)
+
+
+__all__ = ["mx_flash_attention", "mx_flash_decode", "mx_flash_decode_paged"]

@@ -12,7 +12,7 @@ import torch
 
 from qsparse_amd import _hip, _mx_common
 from qsparse_amd._mx_common import _check_dtype
-from qsparse_amd.mx_flash import mx_flash_decode
+from qsparse_amd.mx_flash import _check_pool, _paged_gather, mx_flash_decode, mx_flash_decode_paged
 from qsparse_amd.mx_rope import _rope_def
 from qsparse_amd.quantize import MX_BLOCK, _mx_format, quantize_with_mx
 
@@ -165,4 +165,124 @@ class MXKVCache:
                                self.kv_len, **kw)
 
 
-__all__ = ["mx_kv_append", "MXKVCache"]
+def _append_paged_def(k_pool, k_pool_scales, qk_fmt, vt_pool, vt_pool_scales, v_fmt, v_tail, block_table, kv_len, k_new, v_new, q_new, rope,
+                      interleaved):
+    """the paged append's definition (``include/qsparse_hip.h``, "MX KV cache append, paged"): gather the cache the table names,
+    ``_append_def`` on it, and scatter back the pages that hold a position in ``[L_b, L'_b)`` and whose entry lies in ``[0, P)``.  Reads
+    ``kv_len`` and the table on the host: the CPU path, and what the GPU tests compare with"""
+    pools = (k_pool, k_pool_scales, vt_pool, vt_pool_scales)
+    (P, _, page, _), (B, NP), T = k_pool.shape, block_table.shape, k_new.shape[2]
+    k, ks, vt, vts = _paged_gather(*pools, block_table)
+    out = _append_def(k, ks, qk_fmt, vt, vts, v_fmt, v_tail, kv_len, k_new, v_new, q_new, rope, interleaved)
+    S = NP * page
+    for b, L in enumerate(kv_len.clamp(0, S).tolist()):
+        for n in range(L // page, -(-min(L + T, S) // page)):
+            e = int(block_table[b, n])
+            if 0 <= e < P:
+                k_pool[e], k_pool_scales[e] = k[b, :, n * page:(n + 1) * page], ks[b, :, n * page:(n + 1) * page]
+                vt_pool[e], vt_pool_scales[e] = vt[b, ..., n * page:(n + 1) * page], vts[b, ..., n * page // MX_BLOCK:(n + 1) * page // MX_BLOCK]
+    return out
+
+
+def mx_kv_append_paged(k_pool: torch.Tensor, k_pool_scales: torch.Tensor, qk_fmt: str, vt_pool: torch.Tensor, vt_pool_scales: torch.Tensor,
+                       v_fmt: str, v_tail: torch.Tensor, block_table: torch.Tensor, kv_len: torch.Tensor, k_new: torch.Tensor,
+                       v_new: torch.Tensor, *, q_new: Optional[torch.Tensor] = None, rope=None, interleaved: bool = False):
+    """``mx_kv_append`` into the PAGED cache that ``mx_flash_decode_paged`` reads, in place: the pool ``k_pool [P, Hkv, page, d]`` /
+    ``vt_pool [P, Hkv, dv, page]`` with their scales, ``block_table`` (int32 ``[B, NP]``) and ``kv_len`` (int32 ``[B]``) as there; ``v_tail
+    [B, Hkv, dv, 32]`` float32 stays per sequence and is not paged.
+
+    It is ``mx_kv_append``'s rule with ``S = NP * page`` and positions translated through the table (``_append_paged_def``; bit for bit
+    on either device): K row ``L_b + t`` goes to row ``(L_b + t) % page`` of its page; every 32-block of ``vt`` that receives a position is
+    quantized again from ``v_tail`` plus the new values, inside its page; ``v_tail`` is updated as there; tokens at ``>= S`` are dropped;
+    ``rope`` tables (``P_rope >= S`` rows) are indexed by the logical position; ``q_new`` comes back as codes.  A token whose page entry is
+    outside ``[0, P)`` is not stored and its ``vt`` block is skipped, while ``v_tail`` advances as if it had been.  Every byte of the
+    pool outside the touched rows and blocks keeps its value.  One call must not write one page for two sequences -- the caller's
+    duty; the result for that page is unspecified, but no access leaves the pool.
+
+    GPU tensors take ONE launch (``qs_mx_kv_append_paged_v``; no fallback); the table and ``kv_len`` are read on the device and not
+    changed, so the call can be captured in a graph."""
+    _check_pool("mx_kv_append_paged", k_pool, k_pool_scales, qk_fmt, vt_pool, vt_pool_scales, v_fmt, block_table, kv_len)
+    (P, Hkv, page, d), dv, (B, NP), dev = k_pool.shape, vt_pool.shape[2], block_table.shape, k_pool.device
+    S = NP * page
+    for name, n in (("d", d), ("dv", dv)):
+        if not 1 <= n <= MX_KV_MAX_D:
+            raise ValueError(f"mx_kv_append_paged takes 1 <= {name} <= {MX_KV_MAX_D}, got {name} = {n}")
+    if not isinstance(v_tail, torch.Tensor) or v_tail.dtype != torch.float32 or tuple(v_tail.shape) != (B, Hkv, dv, MX_BLOCK):
+        raise ValueError(f"v_tail must be a float32 tensor of shape {(B, Hkv, dv, MX_BLOCK)}, got "
+                         + (f"{v_tail.dtype} {tuple(v_tail.shape)}" if isinstance(v_tail, torch.Tensor) else type(v_tail).__name__))
+    news = (("k_new", k_new, (B, Hkv), d), ("v_new", v_new, (B, Hkv), dv)) + ((("q_new", q_new, (B,), d),) if q_new is not None else ())
+    for name, t, lead, last in news:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+        _check_dtype(name, t.dtype)
+        if t.dim() != 4 or tuple(t.shape[:len(lead)]) != lead or t.shape[3] != last or t.shape[2] != k_new.shape[2]:
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {lead + (('Hq',) if len(lead) == 1 else ()) + ('T', last)} "
+                             f"with k_new's T")
+        if t.dtype != k_new.dtype:
+            raise ValueError(f"k_new is {k_new.dtype} but {name} {t.dtype}: the new tokens share one dtype")
+    T = k_new.shape[2]
+    if T < 1:
+        raise ValueError(f"mx_kv_append_paged takes T >= 1, got T = {T}")
+    if q_new is not None and (q_new.shape[1] < 1 or q_new.shape[1] % Hkv):
+        raise ValueError(f"Hq = {q_new.shape[1]} is no multiple of Hkv = {Hkv}: query head h uses key/value head h // (Hq / Hkv)")
+    if rope is not None:
+        if not isinstance(rope, (tuple, list)) or len(rope) != 2:
+            raise TypeError("rope must be None or a 2-tuple (cos, sin)")
+        if d % 2:
+            raise ValueError(f"rope needs an even d (the last dimension of k_new), got {d}")
+        for name, t in zip(("cos", "sin"), rope):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != d // 2 or t.shape[0] < S:
+                raise ValueError(f"{name} must be a float32 tensor [P, d / 2] = [>= {S}, {d // 2}], got "
+                                 + (f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__))
+        if rope[0].shape != rope[1].shape:
+            raise ValueError(f"cos {tuple(rope[0].shape)} and sin {tuple(rope[1].shape)} disagree on P")
+    for name, t in (("v_tail", v_tail),) + tuple(n[:2] for n in news) + ((("cos", rope[0]), ("sin", rope[1])) if rope is not None else ()):
+        if t.device != dev:
+            raise ValueError(f"k_pool is on {dev} but {name} on {t.device}")
+    for name, t in (("k_pool", k_pool), ("k_pool_scales", k_pool_scales), ("vt_pool", vt_pool), ("vt_pool_scales", vt_pool_scales),
+                    ("v_tail", v_tail)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous: it is written in place")
+    if B == 0:
+        return None if q_new is None else tuple(k_pool.new_empty(q_new.shape[:3] + (n,)) for n in (d, -(-d // MX_BLOCK)))
+    with torch.no_grad():
+        k_new, v_new, q_new = (None if t is None else t.detach().contiguous() for t in (k_new, v_new, q_new))
+        if not k_pool.is_cuda:
+            return _append_paged_def(k_pool, k_pool_scales, qk_fmt, vt_pool, vt_pool_scales, v_fmt, v_tail, block_table, kv_len, k_new,
+                                     v_new, q_new, rope, bool(interleaved))
+        cos, sin = (None, None) if rope is None else (t.contiguous() for t in rope)
+        return _hip.mx_kv_append_paged(k_pool, k_pool_scales, qk_fmt, vt_pool, vt_pool_scales, v_fmt, v_tail, block_table.contiguous(),
+                                       kv_len.contiguous(), k_new, v_new, q_new, cos, sin, bool(interleaved))
+
+
+class MXPagedKVCache:
+    """The buffers of a paged MX KV cache: the pool ``k_pool [P, Hkv, page, d]`` / ``k_pool_scales``, ``vt_pool [P, Hkv, dv, page]`` /
+    ``vt_pool_scales``, and per sequence ``v_tail [B, Hkv, dv, 32]``, ``kv_len`` (int32 ``[B]``, zero) and ``block_table`` (int32 ``[B,
+    NP]``, filled with ``-1``: the caller writes page numbers into it).  ``append`` is ``mx_kv_append_paged`` followed by ``kv_len +=
+    T``; ``attend`` is ``mx_flash_decode_paged``.  Both are graph-capturable; there is no allocator and no other logic."""
+
+    def __init__(self, P: int, B: int, NP: int, Hkv: int, page: int, d: int, dv: int, qk_fmt: str = "mxfp8_e4m3",
+                 v_fmt: str = "mxfp8_e4m3", device=None):
+        _mx_format(qk_fmt), _mx_format(v_fmt)
+        if page < MX_BLOCK or page & (page - 1):
+            raise ValueError(f"MXPagedKVCache takes a page that is a power of two >= {MX_BLOCK}, got page = {page}")
+        z = partial(torch.zeros, dtype=torch.uint8, device=device)
+        self.qk_fmt, self.v_fmt = qk_fmt, v_fmt
+        self.k_pool, self.k_pool_scales = z((P, Hkv, page, d)), z((P, Hkv, page, -(-d // MX_BLOCK)))
+        self.vt_pool, self.vt_pool_scales = z((P, Hkv, dv, page)), z((P, Hkv, dv, page // MX_BLOCK))
+        self.v_tail = torch.zeros((B, Hkv, dv, MX_BLOCK), dtype=torch.float32, device=device)
+        self.kv_len = torch.zeros(B, dtype=torch.int32, device=device)
+        self.block_table = torch.full((B, NP), -1, dtype=torch.int32, device=device)
+
+    def append(self, k: torch.Tensor, v: torch.Tensor, q: Optional[torch.Tensor] = None, rope=None, interleaved: bool = False):
+        out = mx_kv_append_paged(self.k_pool, self.k_pool_scales, self.qk_fmt, self.vt_pool, self.vt_pool_scales, self.v_fmt, self.v_tail,
+                                 self.block_table, self.kv_len, k, v, q_new=q, rope=rope, interleaved=interleaved)
+        self.kv_len += k.shape[2]
+        return out
+
+    def attend(self, q_codes: torch.Tensor, q_scales: torch.Tensor, **kw) -> torch.Tensor:
+        return mx_flash_decode_paged(q_codes, q_scales, self.qk_fmt, self.k_pool, self.k_pool_scales, self.vt_pool, self.vt_pool_scales,
+                                     self.v_fmt, self.block_table, self.kv_len, **kw)
+
+
+__all__ = ["mx_kv_append", "MXKVCache", "mx_kv_append_paged", "MXPagedKVCache"]

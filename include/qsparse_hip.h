@@ -2455,6 +2455,61 @@ int qs_mx_kv_append_paged_v(const qs_mx_kv_append_paged_args* args);
  * QS_ERR_* the call would return */
 int qs_mx_kv_append_paged_route(const qs_mx_kv_append_paged_args* args);
 
+/* ---- MX flash attention, prefill on the cache (a chunk of new tokens against the cache they were appended to, contiguous or paged) ----
+ * Added without raising QS_ABI_VERSION (28): symbols are only added.  T new tokens q [B, Hq, T, d] -- any T, any r = Hq / Hkv -- against
+ * the cache of "MX flash attention, decode" (block_table NULL: k_codes [B, Hkv, S, d], vt_codes [B, Hkv, dv, S]) or the pool of "MX
+ * flash attention, paged decode" (block_table given: k_codes IS k_pool [P, Hkv, page, d], vt_codes IS vt_pool [P, Hkv, dv, page], the
+ * scales alike, S = NP * page and the field S is not read).  kv_len is the length AFTER the append.
+ *
+ * Definition (normative).  The result IS "MX flash attention, decode" with kv_splits = 1 and its bound on R = r * T lifted (on the
+ * gathered cache of the paged section with a table), bit for bit: L = clamp(kv_len[b], 0, S); `causal` is aligned BOTTOM-RIGHT, token t
+ * admits the keys j <= L - T + t, lim = clamp(L - T + t + 1, 0, L); a row that admits nothing -- L - T + t < 0 included -- is the quiet
+ * NaN as a whole.  Identities that follow, all bit for bit: for R <= 64 the bytes are qs_mx_flash_decode_v's at kv_splits = 1; with no
+ * kv_len and causal == 0 they are qs_mx_flash_attention_streamed_v's on the cache repeated r times; in general they are that call's on
+ * the repeated cache sliced to L with the limit passed as an additive -inf mask.  Table entries: rules 1 and 2 of the paged section.
+ *   - Range: T >= 1, any r, S >= 1, 1 <= d <= 128, dv <= 128, every format triple, the three ydt.  No mask, no split of the key axis.
+ *   - kv_len: int32 [B] in device memory, nullable without a table (every sequence sees S keys); block_table: NULL or int32 [B, NP] in
+ *     device memory.  Both are read by the kernel, nothing by the host: the call can be captured in a graph behind
+ *     qs_mx_kv_append(_paged)_v and both rewritten between replays.  ONE launch, no workspace, no atomics: deterministic.
+ *   - Checks, in order (qs_mx_flash_decode_v's): QS_ERR_ARG: a null or too short descriptor, a NULL operand or y, a table without
+ *     kv_len, a format no enum qs_mx_format, causal neither 0 nor 1, a negative extent, d > 128, dv > 128; QS_ERR_DTYPE: ydt none of the
+ *     three; QS_ERR_ALIGN: y not aligned to its element, kv_len or block_table not to 4 bytes.  B == 0, Hq == 0, T == 0 or dv == 0:
+ *     nothing is enqueued, 0 is returned.  Then QS_ERR_ARG: Hkv == 0, Hq % Hkv != 0, d == 0; with a table P < 1, P > 2^31 - 1, NP < 1
+ *     or a page that is no power of two >= 32; S == 0 or S > 2^31 - 129; r * T > 2^31 - 65, B * Hkv > 2^31 - 1, a byte count beyond
+ *     64 bits, more work-groups than 2^31 - 1.
+ *   - One work-group of four waves per (b, hk, 64 packed rows), the rows packed token-major (rho = t * r + h % r): K and vt are read
+ *     once per tile for all r heads; keys at or behind min(L, the tile's largest lim) are not read, and the tiles latest in T are
+ *     dispatched first.
+ *   - Routes: QS_MX_FLASH_ROUTE_VEC (16-byte loads of codes): d % 16 == 0, q_codes, k_codes and vt_codes 16-byte aligned and, without
+ *     a table, S % 16 == 0 (every page base is aligned); anything else QS_MX_FLASH_ROUTE_PLAIN, byte loads each predicated on its own
+ *     index: the same bits. */
+typedef struct qs_mx_flash_prefill_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_flash_prefill_args) as the caller compiled it */
+    int32_t qk_format;               /* enum qs_mx_format of q and k */
+    int32_t p_format;                /* ... of the attention weights */
+    int32_t v_format;                /* ... of vt */
+    int32_t ydt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    int32_t causal;                  /* 0 or 1, bottom-right aligned */
+    float scale;
+    int32_t reserved0;               /* 0 */
+    const uint8_t* q_codes;          /* [B, Hq, T, d] */
+    const uint8_t* q_scales;         /* [B, Hq, T, ceil(d / 32)] */
+    const uint8_t* k_codes;          /* [B, Hkv, S, d], or the pool [P, Hkv, page, d] */
+    const uint8_t* k_scales;         /* [B, Hkv, S, ceil(d / 32)], or [P, Hkv, page, ceil(d / 32)] */
+    const uint8_t* vt_codes;         /* [B, Hkv, dv, S], or [P, Hkv, dv, page] */
+    const uint8_t* vt_scales;        /* [B, Hkv, dv, ceil(S / 32)], or [P, Hkv, dv, page / 32] */
+    const int32_t* block_table;      /* NULL (contiguous cache) or [B, NP], device memory */
+    const int32_t* kv_len;           /* [B], device memory; nullable without a table */
+    void* y;                         /* [B, Hq, T, dv] dense */
+    int64_t B, Hq, Hkv, T, S, d, dv; /* S: without a table */
+    int64_t P, NP, page;             /* with a table; otherwise not read beyond the sign check */
+    qs_stream_t stream;
+} qs_mx_flash_prefill_args;
+int qs_mx_flash_prefill_v(const qs_mx_flash_prefill_args* args);
+/* the route qs_mx_flash_prefill_v takes for these operands, nothing enqueued: QS_MX_FLASH_ROUTE_*, 0 for an empty problem, or the
+ * QS_ERR_* the call would return */
+int qs_mx_flash_prefill_route(const qs_mx_flash_prefill_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

@@ -16,7 +16,7 @@ from qsparse_amd.mx_conv import MXConv2d, mx_conv2d
 from qsparse_amd.mx_conv_train import MXTrainConv2d, mx_conv2d_train, mx_conv2d_weight_grad
 from qsparse_amd.mx_conv_transpose import MXConvTranspose2d, mx_conv2d_input_grad, mx_conv_transpose2d
 from qsparse_amd.mx_gemm import MXActivation, MXLinear, MXTrainLinear, mx_linear, mx_matmul, mx_quantize_2way
-from qsparse_amd.mx_flash import mx_flash_attention, mx_flash_decode, mx_flash_decode_paged
+from qsparse_amd.mx_flash import mx_flash_attention, mx_flash_decode, mx_flash_decode_paged, mx_flash_prefill, mx_flash_prefill_paged
 from qsparse_amd.mx_glu import (MXGatedMoEFeedForward, MXGLULinear, MXGroupedGLULinear, mx_glu_deinterleave, mx_glu_interleave,
                                 mx_glu_matmul, mx_grouped_glu_matmul)
 from qsparse_amd.mx_glu_train import (MXTrainGatedMoEFeedForward, MXTrainGLULinear, MXTrainGroupedGLULinear, mx_glu_backward_quantize,

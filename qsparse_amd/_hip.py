@@ -168,6 +168,8 @@ SIGNATURES = {
     "qs_mx_kv_append_route": (c_int, [_P]),
     "qs_mx_flash_decode_paged_v": (c_int, [_P]),
     "qs_mx_flash_decode_paged_route": (c_int, [_P]),
+    "qs_mx_flash_prefill_v": (c_int, [_P]),
+    "qs_mx_flash_prefill_route": (c_int, [_P]),
     "qs_mx_kv_append_paged_v": (c_int, [_P]),
     "qs_mx_kv_append_paged_route": (c_int, [_P]),
 }
@@ -457,6 +459,15 @@ class MxFlashDecodePagedArgs(ctypes.Structure):
                 ("block_table", c_void_p), ("kv_len", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_int64), ("y", c_void_p),
                 ("B", c_int64), ("Hq", c_int64), ("Hkv", c_int64), ("T", c_int64), ("P", c_int64), ("NP", c_int64), ("page", c_int64),
                 ("d", c_int64), ("dv", c_int64), ("stream", c_void_p)]
+
+
+class MxFlashPrefillArgs(ctypes.Structure):
+    """`qs_mx_flash_prefill_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("qk_format", c_int32), ("p_format", c_int32), ("v_format", c_int32), ("ydt", c_int32),
+                ("causal", c_int32), ("scale", c_float), ("reserved0", c_int32), ("q_codes", c_void_p), ("q_scales", c_void_p),
+                ("k_codes", c_void_p), ("k_scales", c_void_p), ("vt_codes", c_void_p), ("vt_scales", c_void_p), ("block_table", c_void_p),
+                ("kv_len", c_void_p), ("y", c_void_p), ("B", c_int64), ("Hq", c_int64), ("Hkv", c_int64), ("T", c_int64), ("S", c_int64),
+                ("d", c_int64), ("dv", c_int64), ("P", c_int64), ("NP", c_int64), ("page", c_int64), ("stream", c_void_p)]
 
 
 class MxKvAppendPagedArgs(ctypes.Structure):
@@ -1941,6 +1952,36 @@ def mx_flash_decode_paged(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt:
         a.B, a.Hq, a.Hkv, a.T, a.P, a.NP, a.page, a.d, a.dv = B, Hq, Hkv, T, P, NP, page, d, dv
         a.stream = _stream(q_codes)
         mx_flash_last_route = _mx_run("mx_flash_decode_paged", a, (q_codes, q_scales, block_table, kv_len, y))
+    return y
+
+
+def mx_flash_prefill(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, k_codes: torch.Tensor, k_scales: torch.Tensor,
+                     vt_codes: torch.Tensor, vt_scales: torch.Tensor, v_fmt: str, block_table: Optional[torch.Tensor],
+                     kv_len: Optional[torch.Tensor], scale: float, causal: bool, p_fmt: str, out_dtype: torch.dtype, out=None) -> torch.Tensor:
+    """grouped-query attention of T new tokens on the MX KV cache (qs_mx_flash_prefill_v): `q_codes` [B, Hq, T, d] against `k_codes`
+    [B, Hkv, S, d] / `vt_codes` [B, Hkv, dv, S] (`block_table` None) or against the pool [P, Hkv, page, d] / [P, Hkv, dv, page] through
+    `block_table` int32 [B, NP]; `kv_len` int32 [B] on the device (None only without a table); all contiguous GPU tensors.  Returns y
+    [B, Hq, T, dv] in `out_dtype` from one launch.  `out`: as `mx_flash_decode`.  The route lands in `mx_flash_last_route`."""
+    global mx_flash_last_route
+    load()
+    (B, Hq, T, d), Hkv, dv = q_codes.shape, k_codes.shape[1], vt_codes.shape[2]
+    y = _mx_new_or_out((B, Hq, T, dv), out_dtype, q_codes.device, out, "out: B Hq T dv elements of out_dtype")
+    mx_flash_last_route = None
+    if B and Hq and T and dv:
+        a = MxFlashPrefillArgs()
+        a.qk_format, a.p_format, a.v_format = MX_FORMATS.index(qk_fmt), MX_FORMATS.index(p_fmt), MX_FORMATS.index(v_fmt)
+        a.ydt, a.causal, a.scale = _DT[out_dtype], int(bool(causal)), float(scale)
+        a.q_codes, a.q_scales, a.k_codes, a.k_scales = _ptr(q_codes), _ptr(q_scales), _ptr(k_codes), _ptr(k_scales)
+        a.vt_codes, a.vt_scales, a.block_table, a.kv_len, a.y = _ptr(vt_codes), _ptr(vt_scales), _ptr(block_table), _ptr(kv_len), _ptr(y)
+        a.B, a.Hq, a.Hkv, a.T, a.d, a.dv = B, Hq, Hkv, T, d, dv
+        if block_table is None:
+            a.S = k_codes.shape[2]
+            touched = (q_codes, q_scales, k_codes, k_scales, vt_codes, vt_scales, kv_len, y)
+        else:
+            a.P, a.NP, a.page = k_codes.shape[0], block_table.shape[1], k_codes.shape[2]
+            touched = (q_codes, q_scales, block_table, kv_len, y)
+        a.stream = _stream(q_codes)
+        mx_flash_last_route = _mx_run("mx_flash_prefill", a, touched)
     return y
 
 

@@ -405,4 +405,105 @@ def mx_flash_decode_paged(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt:
         return _hip.mx_flash_decode_paged(*ops, float(scale), bool(is_causal), p_fmt, out_dtype, kv_splits)
 
 
-__all__ = ["mx_flash_attention", "mx_flash_decode", "mx_flash_decode_paged"]
+def _check_prefill(fn: str, q_codes, Hkv: int, d_k: int, dv: int, scale, k_shape):
+    """the checks ``mx_flash_prefill`` and ``mx_flash_prefill_paged`` share once their operands have passed their own: the group, ``d``,
+    the head sizes and ``scale``"""
+    (_, Hq, _, d) = q_codes.shape
+    if Hkv < 1 or Hq % Hkv != 0:
+        raise ValueError(f"Hq = {Hq} is no multiple of Hkv = {Hkv}: query head h uses key/value head h // (Hq / Hkv)")
+    if d_k != d:
+        raise ValueError(f"q_codes {tuple(q_codes.shape)} and the keys {tuple(k_shape)} disagree on d (their last dimensions)")
+    for name, n in (("d", d), ("dv", dv)):
+        if n > _hip.MX_FLASH_MAX_D or (n < 1 and name == "d"):
+            raise ValueError(f"{fn} takes 1 <= {name} <= {_hip.MX_FLASH_MAX_D}, got {name} = {n}")
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)):
+        raise TypeError(f"scale must be a float, got {type(scale).__name__}")
+
+
+def mx_flash_prefill(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, k_codes: torch.Tensor, k_scales: torch.Tensor,
+                     vt_codes: torch.Tensor, vt_scales: torch.Tensor, v_fmt: str, kv_len: Optional[torch.Tensor] = None, *, scale: float,
+                     is_causal: bool = False, p_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Grouped-query attention of MANY new tokens against the cache they were just appended to -- chunked prefill, prefix reuse, long
+    speculative or verify runs: ``q_codes [B, Hq, T, d]`` against ``k_codes [B, Hkv, S, d]`` / ``vt_codes [B, Hkv, dv, S]``, the operands
+    of ``mx_flash_decode`` with no bound on ``(Hq / Hkv) * T`` and no ``kv_splits``.  Returns ``[B, Hq, T, dv]`` in ``out_dtype``.
+
+    ``kv_len`` (None, or int32 ``[B]`` on the operands' device) is the length AFTER the append: sequence ``b`` sees its first ``L_b =
+    clamp(kv_len[b], 0, S)`` keys and nothing behind them.  It is read ON the device, so ``mx_kv_append`` and this call fit one captured
+    graph.  ``is_causal`` is aligned BOTTOM-RIGHT: token ``t`` admits the keys ``j <= L_b - T + t``; a row that admits nothing --
+    ``L_b - T + t < 0`` included -- is NaN.
+
+    The result IS ``_decode_def(..., splits=1)``, bit for bit on either device.  So for ``(Hq / Hkv) * T <= 64`` it equals
+    ``mx_flash_decode(kv_splits=1)``; with no ``kv_len`` and no ``is_causal`` it equals ``mx_flash_attention(rows="streamed")`` on the
+    ``repeat_interleave``d cache; in general it equals that call on the repeated cache sliced to ``L_b`` with the bottom-right limit as
+    an additive ``-inf`` mask -- without the copy, the host read of ``kv_len`` or the mask, reading the cache once per group and
+    skipping the chunks of keys above the diagonal.
+
+    Supported range: ``T >= 1``, any ``Hq / Hkv``, ``S >= 1``, ``1 <= d, dv <= 128``, every format triple, ``out_dtype`` float32 /
+    bfloat16 / float16; anything else raises ``ValueError``.  GPU tensors take ONE launch (``qs_mx_flash_prefill_v``, no fallback); CPU
+    tensors evaluate the definition.  Never differentiable; no arbitrary mask."""
+    _check_q4("q", q_codes, q_scales, qk_fmt)
+    _check_k4("k", k_codes, k_scales, qk_fmt)
+    _check_vt4("vt", vt_codes, vt_scales, v_fmt)
+    _mx_format(p_fmt)
+    _check_dtype("out_dtype", out_dtype)
+    (B, Hq, T, d), (_, Hkv, S, _), dv, dev = q_codes.shape, k_codes.shape, vt_codes.shape[2], q_codes.device
+    if k_codes.shape[0] != B or tuple(vt_codes.shape[:2]) != (B, Hkv):
+        raise ValueError(f"q_codes {tuple(q_codes.shape)}, k_codes {tuple(k_codes.shape)} and vt_codes {tuple(vt_codes.shape)} disagree on "
+                         "B or Hkv")
+    if vt_codes.shape[-1] != S:
+        raise ValueError(f"k_codes {tuple(k_codes.shape)} [B, Hkv, S, d] and vt_codes {tuple(vt_codes.shape)} [B, Hkv, dv, S] disagree on S")
+    _check_prefill("mx_flash_prefill", q_codes, Hkv, k_codes.shape[-1], dv, scale, k_codes.shape)
+    if S < 1:
+        raise ValueError(f"mx_flash_prefill takes S >= 1, got S = {S}")
+    for name, t in (("k_codes", k_codes), ("vt_codes", vt_codes)):
+        if t.device != dev:
+            raise ValueError(f"q_codes is on {dev} but {name} on {t.device}")
+    if kv_len is not None:
+        if not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or tuple(kv_len.shape) != (B,) or kv_len.device != dev:
+            raise ValueError(f"kv_len must be an int32 tensor of shape ({B},) on {dev}, got "
+                             + (f"{kv_len.dtype} {tuple(kv_len.shape)} on {kv_len.device}" if isinstance(kv_len, torch.Tensor)
+                                else type(kv_len).__name__))
+    if 0 in (B, Hq, T, dv):
+        return q_codes.new_empty((B, Hq, T, dv), dtype=out_dtype)
+    with torch.no_grad():
+        ops = (q_codes.contiguous(), q_scales.contiguous(), qk_fmt, k_codes.contiguous(), k_scales.contiguous(),
+               vt_codes.contiguous(), vt_scales.contiguous(), v_fmt)
+        kv_len = None if kv_len is None else kv_len.contiguous()
+        if not q_codes.is_cuda:
+            return _decode_def(*ops, kv_len, float(scale), bool(is_causal), p_fmt, out_dtype, 1)
+        return _hip.mx_flash_prefill(*ops, None, kv_len, float(scale), bool(is_causal), p_fmt, out_dtype)
+
+
+def mx_flash_prefill_paged(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, k_pool: torch.Tensor, k_pool_scales: torch.Tensor,
+                           vt_pool: torch.Tensor, vt_pool_scales: torch.Tensor, v_fmt: str, block_table: torch.Tensor, kv_len: torch.Tensor,
+                           *, scale: float, is_causal: bool = False, p_fmt: str = "mxfp8_e4m3",
+                           out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """``mx_flash_prefill`` on a PAGED cache: the pool, ``block_table`` (int32 ``[B, NP]``) and ``kv_len`` (int32 ``[B]``, required, the
+    length AFTER the append) are ``mx_flash_decode_paged``'s, ``S = NP * page``.  The result IS ``mx_flash_prefill`` on the gathered
+    cache -- ``_decode_paged_def(..., splits=1)`` -- bit for bit on either device.  Table and lengths are read ON the device; entries
+    ``block_table[b, n]`` with ``n * page >= L_b`` are never turned into an address, a live entry outside ``[0, P)`` is not
+    dereferenced and reads as zero codes under the scale byte 127.  The pools must be contiguous.  GPU tensors take ONE launch
+    (``qs_mx_flash_prefill_v`` with a table; no gathered copy, no fallback); CPU tensors evaluate the definition."""
+    _check_q4("q", q_codes, q_scales, qk_fmt)
+    _mx_format(p_fmt)
+    _check_dtype("out_dtype", out_dtype)
+    (B, Hq, T, d), dev = q_codes.shape, q_codes.device
+    _check_pool("mx_flash_prefill_paged", k_pool, k_pool_scales, qk_fmt, vt_pool, vt_pool_scales, v_fmt, block_table, kv_len, B)
+    if k_pool.device != dev:
+        raise ValueError(f"q_codes is on {dev} but k_pool on {k_pool.device}")
+    dv = vt_pool.shape[2]
+    _check_prefill("mx_flash_prefill_paged", q_codes, k_pool.shape[1], k_pool.shape[-1], dv, scale, k_pool.shape)
+    if 0 in (B, Hq, T, dv):
+        return q_codes.new_empty((B, Hq, T, dv), dtype=out_dtype)
+    for name, t in (("k_pool", k_pool), ("k_pool_scales", k_pool_scales), ("vt_pool", vt_pool), ("vt_pool_scales", vt_pool_scales)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous: the pool is addressed through block_table, not copied")
+    with torch.no_grad():
+        ops = (q_codes.contiguous(), q_scales.contiguous(), qk_fmt, k_pool, k_pool_scales, vt_pool, vt_pool_scales, v_fmt,
+               block_table.contiguous(), kv_len.contiguous())
+        if not q_codes.is_cuda:
+            return _decode_paged_def(*ops, float(scale), bool(is_causal), p_fmt, out_dtype, 1)
+        return _hip.mx_flash_prefill(*ops, float(scale), bool(is_causal), p_fmt, out_dtype)
+
+
+__all__ = ["mx_flash_attention", "mx_flash_decode", "mx_flash_decode_paged", "mx_flash_prefill", "mx_flash_prefill_paged"]

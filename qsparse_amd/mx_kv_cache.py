@@ -12,7 +12,8 @@ import torch
 
 from qsparse_amd import _hip, _mx_common
 from qsparse_amd._mx_common import _check_dtype
-from qsparse_amd.mx_flash import _check_pool, _paged_gather, mx_flash_decode, mx_flash_decode_paged
+from qsparse_amd.mx_flash import (_check_pool, _paged_gather, mx_flash_decode, mx_flash_decode_paged, mx_flash_prefill,
+                                  mx_flash_prefill_paged)
 from qsparse_amd.mx_rope import _rope_def
 from qsparse_amd.quantize import MX_BLOCK, _mx_format, quantize_with_mx
 
@@ -164,6 +165,11 @@ class MXKVCache:
         return mx_flash_decode(q_codes, q_scales, self.qk_fmt, self.k_codes, self.k_scales, self.vt_codes, self.vt_scales, self.v_fmt,
                                self.kv_len, **kw)
 
+    def prefill(self, q_codes: torch.Tensor, q_scales: torch.Tensor, **kw) -> torch.Tensor:
+        """``mx_flash_prefill`` on the cache: any number of new tokens, behind the ``append`` that stored them"""
+        return mx_flash_prefill(q_codes, q_scales, self.qk_fmt, self.k_codes, self.k_scales, self.vt_codes, self.vt_scales, self.v_fmt,
+                                self.kv_len, **kw)
+
 
 def _append_paged_def(k_pool, k_pool_scales, qk_fmt, vt_pool, vt_pool_scales, v_fmt, v_tail, block_table, kv_len, k_new, v_new, q_new, rope,
                       interleaved):
@@ -283,6 +289,11 @@ class MXPagedKVCache:
     def attend(self, q_codes: torch.Tensor, q_scales: torch.Tensor, **kw) -> torch.Tensor:
         return mx_flash_decode_paged(q_codes, q_scales, self.qk_fmt, self.k_pool, self.k_pool_scales, self.vt_pool, self.vt_pool_scales,
                                      self.v_fmt, self.block_table, self.kv_len, **kw)
+
+    def prefill(self, q_codes: torch.Tensor, q_scales: torch.Tensor, **kw) -> torch.Tensor:
+        """``mx_flash_prefill_paged`` on the cache: any number of new tokens, behind the ``append`` that stored them"""
+        return mx_flash_prefill_paged(q_codes, q_scales, self.qk_fmt, self.k_pool, self.k_pool_scales, self.vt_pool, self.vt_pool_scales,
+                                      self.v_fmt, self.block_table, self.kv_len, **kw)
 
 
 __all__ = ["mx_kv_append", "MXKVCache", "mx_kv_append_paged", "MXPagedKVCache"]

@@ -2510,6 +2510,108 @@ int qs_mx_flash_prefill_v(const qs_mx_flash_prefill_args* args);
  * QS_ERR_* the call would return */
 int qs_mx_flash_prefill_route(const qs_mx_flash_prefill_args* args);
 
+/* ---- MX flash attention, ragged (a batch whose sequences bring different numbers of new tokens, on either cache) ------------------------
+ * Added without raising QS_ABI_VERSION (28): symbols are only added.  The new tokens of all sequences lie on ONE flat axis, token-major
+ * as a QKV projection writes them: q_codes [Ttot, Hq, d], q_scales [Ttot, Hq, ceil(d / 32)], y [Ttot, Hq, dv].  cu_seqlens (int32
+ * [B + 1], device memory, non-decreasing, cu_seqlens[0] == 0) cuts the axis: sequence b owns the tokens [cu[b], cu[b + 1]), T_b =
+ * cu[b + 1] - cu[b], which may be 0.  Ttot may exceed cu[B] (the padding of a fixed token budget): tokens at or behind cu[B] belong to
+ * no sequence, their rows of y are NOT written.  The cache, block_table and kv_len (required; the length AFTER the append) are those of
+ * "MX flash attention, prefill on the cache".
+ *
+ * Definition (normative).  For every b with T_b > 0, the rows [cu[b], cu[b + 1]) of y are, bit for bit, "MX flash attention, prefill on
+ * the cache" of that sequence alone: q = those rows of q_codes viewed [1, Hq, T_b, d], row b of the cache (of the table), kv_len[b], T =
+ * T_b -- so `causal` is bottom-right per sequence, token t of sequence b admits the keys j <= L_b - T_b + t.
+ *   - Guard.  Every entry of cu_seqlens is clamped into [0, Ttot] and a negative length counts as 0: for a malformed cu_seqlens the
+ *     result is unspecified, but no access leaves the operands.  Table entries: rules 1 and 2 of the paged section.
+ *   - cu_seqlens, kv_len and block_table are read by the kernel, nothing by the host: the call can be captured in a graph and all three
+ *     rewritten in place between replays.  ONE launch for any mix of lengths, no workspace, no atomics: deterministic.
+ *   - Range: that of the prefill section; Ttot <= 2^31 - 1.
+ *   - Checks, in order: the prefill section's with cu_seqlens among the NULL and 4-byte alignment checks, kv_len never NULL, Ttot in
+ *     T's place (B == 0, Hq == 0, Ttot == 0 or dv == 0: nothing is enqueued, 0 is returned); then r * Ttot > 2^31 - 65 and
+ *     Hkv * (ceil(r * Ttot / 64) + B) work-groups beyond 2^31 - 1 are QS_ERR_ARG.
+ *   - Grid: ceil(r * Ttot / 64) + B work-groups per kv head, a function of the shapes alone.  Sequence b has ceil(r * T_b / 64) tiles
+ *     of 64 token-major packed rows; a work-group finds its (b, tile) from the prefix sum of these counts, which one of its waves
+ *     computes from cu_seqlens (64 entries per round, a scan, a ballot); work-groups past the total return at once.  Items are taken
+ *     in descending order: the surplus first, then the last sequence, within a sequence the tiles latest in T first.
+ *   - Routes: the prefill section's rule (QS_MX_FLASH_ROUTE_VEC / _PLAIN), the same bits. */
+typedef struct qs_mx_flash_ragged_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_flash_ragged_args) as the caller compiled it */
+    int32_t qk_format;               /* enum qs_mx_format of q and k */
+    int32_t p_format;                /* ... of the attention weights */
+    int32_t v_format;                /* ... of vt */
+    int32_t ydt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    int32_t causal;                  /* 0 or 1, bottom-right aligned per sequence */
+    float scale;
+    int32_t reserved0;               /* 0 */
+    const uint8_t* q_codes;          /* [Ttot, Hq, d] */
+    const uint8_t* q_scales;         /* [Ttot, Hq, ceil(d / 32)] */
+    const uint8_t* k_codes;          /* [B, Hkv, S, d], or the pool [P, Hkv, page, d] */
+    const uint8_t* k_scales;         /* [B, Hkv, S, ceil(d / 32)], or [P, Hkv, page, ceil(d / 32)] */
+    const uint8_t* vt_codes;         /* [B, Hkv, dv, S], or [P, Hkv, dv, page] */
+    const uint8_t* vt_scales;        /* [B, Hkv, dv, ceil(S / 32)], or [P, Hkv, dv, page / 32] */
+    const int32_t* block_table;      /* NULL (contiguous cache) or [B, NP], device memory */
+    const int32_t* kv_len;           /* [B], device memory */
+    const int32_t* cu_seqlens;       /* [B + 1], device memory */
+    void* y;                         /* [Ttot, Hq, dv] dense; rows at or behind cu_seqlens[B] are not written */
+    int64_t B, Hq, Hkv, Ttot, S, d, dv; /* S: without a table */
+    int64_t P, NP, page;             /* with a table; otherwise not read beyond the sign check */
+    qs_stream_t stream;
+} qs_mx_flash_ragged_args;
+int qs_mx_flash_ragged_v(const qs_mx_flash_ragged_args* args);
+/* the route qs_mx_flash_ragged_v takes for these operands, nothing enqueued: QS_MX_FLASH_ROUTE_*, 0 for an empty problem, or the
+ * QS_ERR_* the call would return */
+int qs_mx_flash_ragged_route(const qs_mx_flash_ragged_args* args);
+
+/* ---- MX KV cache append, ragged (qs_mx_kv_append_paged_v for sequences that bring different numbers of tokens) --------------------------
+ * Added without raising QS_ABI_VERSION (28): symbols are only added.  The pool, block_table, kv_len (the length BEFORE the append, not
+ * changed) and v_tail are those of "MX KV cache append, paged".  The new tokens are flat and token-major: k_new [Ttot, Hkv, d], v_new
+ * [Ttot, Hkv, dv], q_new [Ttot, Hq, d] (nullable); cu_seqlens as in the section above.
+ *
+ * Definition (normative).  For every b with T_b > 0: "MX KV cache append, paged" of that sequence alone -- row b of block_table, kv_len
+ * and v_tail, its tokens [cu[b], cu[b + 1]) viewed head-major [1, H, T_b, .] -- bit for bit, every rule of that section (v_tail, the
+ * re-quantized blocks, tokens at positions >= S dropped, dead entries, the rotation by table row min(L_b + t, P - 1)) per sequence.
+ * q's codes come back token-major, q_codes [Ttot, Hq, d] and q_scales [Ttot, Hq, ceil(d / 32)], the q operands of the section above.
+ *   - A sequence with T_b == 0 is untouched: its v_tail is neither read nor written.  Tokens at or behind cu_seqlens[B] are stored
+ *     nowhere and their rows of q_codes / q_scales are NOT written.
+ *   - Guard: cu_seqlens as in the section above -- clamped, a negative length is 0, and a token that its sequence's clamped extent
+ *     does not hold is stored nowhere; unspecified result for a malformed cu_seqlens, no access outside the operands.
+ *   - Range and checks: as qs_mx_kv_append_paged_v with cu_seqlens among the NULL and 4-byte alignment checks and Ttot in T's place
+ *     (B == 0 or Ttot == 0: nothing is enqueued, 0 is returned); Ttot > 2^30, B > 2^31 - 2 or more work-groups than 2^31 - 1 are
+ *     QS_ERR_ARG.  The grid is a function of the shapes alone: ceil(Ttot * (Hkv + Hq) / rows per work-group) row items over the flat
+ *     rows, each finding its sequence by a binary search in cu_seqlens; B * Hkv edge items; floor(Ttot / 32) * Hkv middle blocks,
+ *     mapped through the prefix sum of max(0, floor((T_b - 2) / 32)).
+ *   - Routes: qs_mx_kv_append_paged_route's rule: the same bits.  ONE launch, graph-capturable.  A contiguous-cache form does not
+ *     exist. */
+typedef struct qs_mx_kv_append_ragged_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_kv_append_ragged_args) as the caller compiled it */
+    int32_t qk_format;               /* enum qs_mx_format of k (and q) */
+    int32_t v_format;                /* ... of vt */
+    int32_t xdt;                     /* QS_F32, QS_BF16 or QS_F16: k_new, v_new, q_new */
+    int32_t interleaved;             /* as qs_mx_kv_append_args */
+    int32_t reserved0;               /* 0 */
+    uint8_t* k_pool;                 /* [P_pool, Hkv, page, d], written in place */
+    uint8_t* k_pool_scales;          /* [P_pool, Hkv, page, ceil(d / 32)] */
+    uint8_t* vt_pool;                /* [P_pool, Hkv, dv, page] */
+    uint8_t* vt_pool_scales;         /* [P_pool, Hkv, dv, page / 32] */
+    float* v_tail;                   /* [B, Hkv, dv, 32], read and written */
+    const int32_t* block_table;      /* [B, NP], device memory, only read */
+    const int32_t* kv_len;           /* [B], device memory, only read */
+    const int32_t* cu_seqlens;       /* [B + 1], device memory, only read */
+    const void* k_new;               /* [Ttot, Hkv, d] dense */
+    const void* v_new;               /* [Ttot, Hkv, dv] dense */
+    const void* q_new;               /* [Ttot, Hq, d] dense, nullable */
+    const float* cos;                /* [P, d / 2], nullable together with sin: no rotation */
+    const float* sin;
+    uint8_t* q_codes;                /* [Ttot, Hq, d], with q_new */
+    uint8_t* q_scales;               /* [Ttot, Hq, ceil(d / 32)] */
+    int64_t B, Hq, Hkv, Ttot, P_pool, NP, page, d, dv, P;
+    qs_stream_t stream;
+} qs_mx_kv_append_ragged_args;
+int qs_mx_kv_append_ragged_v(const qs_mx_kv_append_ragged_args* args);
+/* the route qs_mx_kv_append_ragged_v takes for these operands, nothing enqueued: QS_MX_KV_APPEND_ROUTE_*, 0 for an empty problem, or
+ * the QS_ERR_* the call would return */
+int qs_mx_kv_append_ragged_route(const qs_mx_kv_append_ragged_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

@@ -16,14 +16,15 @@ from qsparse_amd.mx_conv import MXConv2d, mx_conv2d
 from qsparse_amd.mx_conv_train import MXTrainConv2d, mx_conv2d_train, mx_conv2d_weight_grad
 from qsparse_amd.mx_conv_transpose import MXConvTranspose2d, mx_conv2d_input_grad, mx_conv_transpose2d
 from qsparse_amd.mx_gemm import MXActivation, MXLinear, MXTrainLinear, mx_linear, mx_matmul, mx_quantize_2way
-from qsparse_amd.mx_flash import mx_flash_attention, mx_flash_decode, mx_flash_decode_paged, mx_flash_prefill, mx_flash_prefill_paged
+from qsparse_amd.mx_flash import (mx_flash_attention, mx_flash_decode, mx_flash_decode_paged, mx_flash_prefill, mx_flash_prefill_paged,
+                                  mx_flash_prefill_ragged, mx_flash_prefill_ragged_paged)
 from qsparse_amd.mx_glu import (MXGatedMoEFeedForward, MXGLULinear, MXGroupedGLULinear, mx_glu_deinterleave, mx_glu_interleave,
                                 mx_glu_matmul, mx_grouped_glu_matmul)
 from qsparse_amd.mx_glu_train import (MXTrainGatedMoEFeedForward, MXTrainGLULinear, MXTrainGroupedGLULinear, mx_glu_backward_quantize,
                                       mx_glu_linear, mx_grouped_glu_linear)
 from qsparse_amd.mx_grouped import MXGroupedLinear, MXMoEFeedForward, mx_grouped_matmul
 from qsparse_amd.mx_grouped_train import MXTrainGroupedLinear, MXTrainMoEFeedForward, mx_grouped_linear, mx_grouped_weight_grad
-from qsparse_amd.mx_kv_cache import MXKVCache, MXPagedKVCache, mx_kv_append, mx_kv_append_paged
+from qsparse_amd.mx_kv_cache import MXKVCache, MXPagedKVCache, mx_kv_append, mx_kv_append_paged, mx_kv_append_ragged_paged
 from qsparse_amd.mx_norm import (MXAddNormLinear, MXLayerNorm, MXRMSNorm, MXTrainAddNormLinear, MXTrainNormLinear, mx_add_norm_linear,
                                  mx_add_norm_quantize, mx_norm_backward, mx_norm_linear, mx_norm_quantize)
 from qsparse_amd.mx_rope import mx_rope, mx_rope_quantize, mx_rope_table

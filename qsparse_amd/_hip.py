@@ -172,6 +172,10 @@ SIGNATURES = {
     "qs_mx_flash_prefill_route": (c_int, [_P]),
     "qs_mx_kv_append_paged_v": (c_int, [_P]),
     "qs_mx_kv_append_paged_route": (c_int, [_P]),
+    "qs_mx_flash_ragged_v": (c_int, [_P]),
+    "qs_mx_flash_ragged_route": (c_int, [_P]),
+    "qs_mx_kv_append_ragged_v": (c_int, [_P]),
+    "qs_mx_kv_append_ragged_route": (c_int, [_P]),
 }
 
 
@@ -478,6 +482,27 @@ class MxKvAppendPagedArgs(ctypes.Structure):
                 ("v_new", c_void_p), ("q_new", c_void_p), ("cos", c_void_p), ("sin", c_void_p), ("q_codes", c_void_p),
                 ("q_scales", c_void_p), ("B", c_int64), ("Hq", c_int64), ("Hkv", c_int64), ("T", c_int64), ("P_pool", c_int64),
                 ("NP", c_int64), ("page", c_int64), ("d", c_int64), ("dv", c_int64), ("P", c_int64), ("stream", c_void_p)]
+
+
+class MxFlashRaggedArgs(ctypes.Structure):
+    """`qs_mx_flash_ragged_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("qk_format", c_int32), ("p_format", c_int32), ("v_format", c_int32), ("ydt", c_int32),
+                ("causal", c_int32), ("scale", c_float), ("reserved0", c_int32), ("q_codes", c_void_p), ("q_scales", c_void_p),
+                ("k_codes", c_void_p), ("k_scales", c_void_p), ("vt_codes", c_void_p), ("vt_scales", c_void_p), ("block_table", c_void_p),
+                ("kv_len", c_void_p), ("cu_seqlens", c_void_p), ("y", c_void_p), ("B", c_int64), ("Hq", c_int64), ("Hkv", c_int64),
+                ("Ttot", c_int64), ("S", c_int64), ("d", c_int64), ("dv", c_int64), ("P", c_int64), ("NP", c_int64), ("page", c_int64),
+                ("stream", c_void_p)]
+
+
+class MxKvAppendRaggedArgs(ctypes.Structure):
+    """`qs_mx_kv_append_ragged_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("qk_format", c_int32), ("v_format", c_int32), ("xdt", c_int32),
+                ("interleaved", c_int32), ("reserved0", c_int32), ("k_pool", c_void_p), ("k_pool_scales", c_void_p), ("vt_pool", c_void_p),
+                ("vt_pool_scales", c_void_p), ("v_tail", c_void_p), ("block_table", c_void_p), ("kv_len", c_void_p),
+                ("cu_seqlens", c_void_p), ("k_new", c_void_p), ("v_new", c_void_p), ("q_new", c_void_p), ("cos", c_void_p),
+                ("sin", c_void_p), ("q_codes", c_void_p), ("q_scales", c_void_p), ("B", c_int64), ("Hq", c_int64), ("Hkv", c_int64),
+                ("Ttot", c_int64), ("P_pool", c_int64), ("NP", c_int64), ("page", c_int64), ("d", c_int64), ("dv", c_int64),
+                ("P", c_int64), ("stream", c_void_p)]
 
 
 class MxSoftmaxQuant2Args(ctypes.Structure):
@@ -1985,6 +2010,38 @@ def mx_flash_prefill(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str,
     return y
 
 
+def mx_flash_ragged(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, k_codes: torch.Tensor, k_scales: torch.Tensor,
+                    vt_codes: torch.Tensor, vt_scales: torch.Tensor, v_fmt: str, block_table: Optional[torch.Tensor], kv_len: torch.Tensor,
+                    cu_seqlens: torch.Tensor, scale: float, causal: bool, p_fmt: str, out_dtype: torch.dtype, out=None) -> torch.Tensor:
+    """grouped-query attention of a ragged batch of new tokens on the MX KV cache (qs_mx_flash_ragged_v): `q_codes` [Ttot, Hq, d],
+    token-major, cut into sequences by `cu_seqlens` int32 [B + 1], against the cache or (with `block_table` int32 [B, NP]) the pool of
+    `mx_flash_prefill`; `kv_len` int32 [B]; all contiguous GPU tensors, the three int32 ones read by the kernel.  Returns y [Ttot, Hq,
+    dv] in `out_dtype` from one launch; rows at or behind cu_seqlens[B] are not written.  `out`: as `mx_flash_decode`.  The route lands
+    in `mx_flash_last_route`."""
+    global mx_flash_last_route
+    load()
+    (Ttot, Hq, d), Hkv, dv, B = q_codes.shape, k_codes.shape[1], vt_codes.shape[2], kv_len.shape[0]
+    y = _mx_new_or_out((Ttot, Hq, dv), out_dtype, q_codes.device, out, "out: Ttot Hq dv elements of out_dtype")
+    mx_flash_last_route = None
+    if B and Hq and Ttot and dv:
+        a = MxFlashRaggedArgs()
+        a.qk_format, a.p_format, a.v_format = MX_FORMATS.index(qk_fmt), MX_FORMATS.index(p_fmt), MX_FORMATS.index(v_fmt)
+        a.ydt, a.causal, a.scale = _DT[out_dtype], int(bool(causal)), float(scale)
+        a.q_codes, a.q_scales, a.k_codes, a.k_scales = _ptr(q_codes), _ptr(q_scales), _ptr(k_codes), _ptr(k_scales)
+        a.vt_codes, a.vt_scales, a.block_table, a.kv_len, a.y = _ptr(vt_codes), _ptr(vt_scales), _ptr(block_table), _ptr(kv_len), _ptr(y)
+        a.cu_seqlens = _ptr(cu_seqlens)
+        a.B, a.Hq, a.Hkv, a.Ttot, a.d, a.dv = B, Hq, Hkv, Ttot, d, dv
+        if block_table is None:
+            a.S = k_codes.shape[2]
+            touched = (q_codes, q_scales, k_codes, k_scales, vt_codes, vt_scales, kv_len, cu_seqlens, y)
+        else:
+            a.P, a.NP, a.page = k_codes.shape[0], block_table.shape[1], k_codes.shape[2]
+            touched = (q_codes, q_scales, block_table, kv_len, cu_seqlens, y)
+        a.stream = _stream(q_codes)
+        mx_flash_last_route = _mx_run("mx_flash_ragged", a, touched)
+    return y
+
+
 MX_KV_APPEND_ROUTE_VEC, MX_KV_APPEND_ROUTE_PLAIN = 1, 2
 mx_kv_append_last_route = None   # the QS_MX_KV_APPEND_ROUTE_* of the last `mx_kv_append` launch (None: an empty problem)
 
@@ -2048,6 +2105,37 @@ def mx_kv_append_paged(k_pool: torch.Tensor, k_pool_scales: torch.Tensor, qk_fmt
         a.B, a.Hkv, a.T, a.P_pool, a.NP, a.page, a.d, a.dv, a.P = B, Hkv, T, P, NP, page, d, dv, 0 if cos is None else cos.shape[0]
         a.stream = _stream(k_pool)
         mx_kv_append_last_route = _mx_run("mx_kv_append_paged", a, (k_new, v_new, q_new, block_table) + (q or ()))
+    return q
+
+
+def mx_kv_append_ragged(k_pool: torch.Tensor, k_pool_scales: torch.Tensor, qk_fmt: str, vt_pool: torch.Tensor, vt_pool_scales: torch.Tensor,
+                        v_fmt: str, v_tail: torch.Tensor, block_table: torch.Tensor, kv_len: torch.Tensor, cu_seqlens: torch.Tensor,
+                        k_new: torch.Tensor, v_new: torch.Tensor, q_new: Optional[torch.Tensor], cos: Optional[torch.Tensor],
+                        sin: Optional[torch.Tensor], interleaved: bool, q_out=None):
+    """`mx_kv_append_paged` for a ragged batch in ONE launch (qs_mx_kv_append_ragged_v): the pool, `v_tail`, `block_table` and `kv_len`
+    as there; `k_new` [Ttot, Hkv, d], `v_new` [Ttot, Hkv, dv], `q_new` [Ttot, Hq, d] or None flat, token-major, contiguous and of one
+    dtype; `cu_seqlens` int32 [B + 1] read by the kernel.  Returns (q_codes [Ttot, Hq, d], q_scales) for a `q_new`, else None; rows at
+    or behind cu_seqlens[B] are not written.  `q_out`: as `mx_kv_append`.  The route lands in `mx_kv_append_last_route`."""
+    global mx_kv_append_last_route
+    load()
+    (P, Hkv, page, d), dv, (B, NP), Ttot = k_pool.shape, vt_pool.shape[2], block_table.shape, k_new.shape[0]
+    q = None
+    if q_new is not None:
+        Hq = q_new.shape[1]
+        q = tuple(_mx_new_or_out(shape, torch.uint8, k_pool.device, None if q_out is None else q_out[i], "q_out: dense uint8")
+                  for i, shape in enumerate(((Ttot, Hq, d), (Ttot, Hq, (d + MX_BLOCK - 1) // MX_BLOCK))))
+    mx_kv_append_last_route = None
+    if B and Ttot:
+        a = MxKvAppendRaggedArgs()
+        a.qk_format, a.v_format, a.xdt, a.interleaved = MX_FORMATS.index(qk_fmt), MX_FORMATS.index(v_fmt), dt(k_new), int(bool(interleaved))
+        a.k_pool, a.k_pool_scales, a.vt_pool, a.vt_pool_scales = _ptr(k_pool), _ptr(k_pool_scales), _ptr(vt_pool), _ptr(vt_pool_scales)
+        a.v_tail, a.block_table, a.kv_len, a.cu_seqlens = _ptr(v_tail), _ptr(block_table), _ptr(kv_len), _ptr(cu_seqlens)
+        a.k_new, a.v_new, a.q_new, a.cos, a.sin = _ptr(k_new), _ptr(v_new), _ptr(q_new), _ptr(cos), _ptr(sin)
+        if q is not None:
+            a.q_codes, a.q_scales, a.Hq = _ptr(q[0]), _ptr(q[1]), q_new.shape[1]
+        a.B, a.Hkv, a.Ttot, a.P_pool, a.NP, a.page, a.d, a.dv, a.P = B, Hkv, Ttot, P, NP, page, d, dv, 0 if cos is None else cos.shape[0]
+        a.stream = _stream(k_pool)
+        mx_kv_append_last_route = _mx_run("mx_kv_append_ragged", a, (k_new, v_new, q_new, block_table, cu_seqlens) + (q or ()))
     return q
 
 

@@ -506,4 +506,125 @@ def mx_flash_prefill_paged(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt
         return _hip.mx_flash_prefill(*ops, float(scale), bool(is_causal), p_fmt, out_dtype)
 
 
-__all__ = ["mx_flash_attention", "mx_flash_decode", "mx_flash_decode_paged", "mx_flash_prefill", "mx_flash_prefill_paged"]
+def _check_cu(fn: str, cu_seqlens, B: int, dev):
+    """``cu_seqlens``: int32 ``[B + 1]`` on the operands' device (its values are the device's business)"""
+    if not isinstance(cu_seqlens, torch.Tensor) or cu_seqlens.dtype != torch.int32 or tuple(cu_seqlens.shape) != (B + 1,) or \
+            cu_seqlens.device != dev:
+        raise ValueError(f"{fn}: cu_seqlens must be an int32 tensor of shape ({B + 1},) = (B + 1,) on {dev}, got "
+                         + (f"{cu_seqlens.dtype} {tuple(cu_seqlens.shape)} on {cu_seqlens.device}" if isinstance(cu_seqlens, torch.Tensor)
+                            else type(cu_seqlens).__name__))
+
+
+def _ragged_def(qc, qs, qk_fmt: str, kc, ks, vc, vs, v_fmt: str, block_table, kv_len, cu_seqlens, scale: float, causal: bool, p_fmt: str,
+                out_dtype):
+    """The ragged launch's definition (``include/qsparse_hip.h``, "MX flash attention, ragged"), on either device: ``mx_flash_prefill``
+    (``_paged`` with a ``block_table``) of every sequence with ``T_b > 0`` by itself, on its rows of ``qc [Ttot, Hq, d]``; rows that no
+    sequence owns stay zero.  It reads ``cu_seqlens`` on the host: what the tests compare against, not what a graph captures."""
+    (Ttot, Hq, _), dv = qc.shape, vc.shape[2]
+    out = qc.new_zeros((Ttot, Hq, dv), dtype=out_dtype)
+    cu = [min(max(int(n), 0), Ttot) for n in cu_seqlens.tolist()]
+    for b, (lo, hi) in enumerate(zip(cu[:-1], cu[1:])):
+        if hi <= lo:
+            continue
+        q = (qc[lo:hi].permute(1, 0, 2)[None], qs[lo:hi].permute(1, 0, 2)[None])
+        if block_table is None:
+            y = _decode_def(*q, qk_fmt, kc[b:b + 1], ks[b:b + 1], vc[b:b + 1], vs[b:b + 1], v_fmt, kv_len[b:b + 1], scale, causal, p_fmt,
+                            out_dtype, 1)
+        else:
+            y = _decode_paged_def(*q, qk_fmt, kc, ks, vc, vs, v_fmt, block_table[b:b + 1], kv_len[b:b + 1], scale, causal, p_fmt, out_dtype, 1)
+        out[lo:hi] = y[0].permute(1, 0, 2)
+    return out
+
+
+def _ragged(q_codes, q_scales, qk_fmt, kc, ks, vc, vs, v_fmt, block_table, kv_len, cu_seqlens, scale, is_causal, p_fmt, out_dtype):
+    """what ``mx_flash_prefill_ragged`` and ``mx_flash_prefill_ragged_paged`` share behind the checks of their cache"""
+    (Ttot, Hq, _), dv, B = q_codes.shape, vc.shape[2], kv_len.shape[0]
+    if 0 in (B, Hq, Ttot, dv):
+        return q_codes.new_zeros((Ttot, Hq, dv), dtype=out_dtype)
+    with torch.no_grad():
+        ops = (q_codes.contiguous(), q_scales.contiguous(), qk_fmt, kc, ks, vc, vs, v_fmt, block_table, kv_len.contiguous(),
+               cu_seqlens.contiguous(), float(scale), bool(is_causal), p_fmt, out_dtype)
+        return _hip.mx_flash_ragged(*ops) if q_codes.is_cuda else _ragged_def(*ops)
+
+
+_check_q3 = partial(_mx_common._check_operand, what="[Ttot, Hq, d]", least=3, most=3, needs="exactly 3 dimensions")
+
+
+def mx_flash_prefill_ragged(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, k_codes: torch.Tensor, k_scales: torch.Tensor,
+                            vt_codes: torch.Tensor, vt_scales: torch.Tensor, v_fmt: str, kv_len: torch.Tensor, cu_seqlens: torch.Tensor,
+                            *, scale: float, is_causal: bool = False, p_fmt: str = "mxfp8_e4m3",
+                            out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """``mx_flash_prefill`` for a RAGGED batch: sequence ``b`` brings ``T_b`` new tokens, a decode step (``T_b = 1``), a prefill chunk of
+    hundreds or none at all, in ONE launch.  The new tokens lie on one flat axis, token-major as a QKV projection writes them:
+    ``q_codes [Ttot, Hq, d]`` / ``q_scales [Ttot, Hq, ceil(d / 32)]``; the result is ``[Ttot, Hq, dv]`` in ``out_dtype``.  The cache is
+    ``mx_flash_prefill``'s, ``k_codes [B, Hkv, S, d]`` / ``vt_codes [B, Hkv, dv, S]``; ``kv_len`` (int32 ``[B]``, required) is the length
+    AFTER the append.
+
+    ``cu_seqlens`` (int32 ``[B + 1]`` on the operands' device, non-decreasing, ``cu_seqlens[0] == 0``) cuts the axis: sequence ``b`` owns
+    the tokens ``[cu[b], cu[b + 1])``.  ``Ttot`` may exceed ``cu[B]`` -- the padding of a fixed token budget -- and tokens at or behind
+    ``cu[B]`` belong to no sequence: the GPU launch does NOT write their rows of the result, whose content is unspecified (the tensor is
+    ``new_empty``); the CPU path leaves them zero.  ``cu_seqlens``, ``kv_len`` (and the table) are read ON the device and never by the
+    host, so the call can be captured in a graph and all of them rewritten in place between replays.  The kernel clamps every entry of
+    ``cu_seqlens`` into ``[0, Ttot]`` and takes a negative length as 0: a malformed ``cu_seqlens`` gives an unspecified result, but no
+    access leaves the operands.
+
+    The result IS ``mx_flash_prefill`` called once per sequence with ``T_b > 0`` on its own rows (``_ragged_def``), bit for bit on
+    either device; ``is_causal`` is bottom-right PER SEQUENCE, token ``t`` of sequence ``b`` admits the keys ``j <= L_b - T_b + t``.
+
+    Supported range: ``mx_flash_prefill``'s -- any ``Hq / Hkv``, ``1 <= d, dv <= 128``, every format triple, three output dtypes;
+    anything else raises ``ValueError`` naming the bound.  GPU tensors take ONE launch (``qs_mx_flash_ragged_v``; no fallback); CPU
+    tensors evaluate the definition.  Never differentiable."""
+    _check_q3("q", q_codes, q_scales, qk_fmt)
+    _check_k4("k", k_codes, k_scales, qk_fmt)
+    _check_vt4("vt", vt_codes, vt_scales, v_fmt)
+    _mx_format(p_fmt)
+    _check_dtype("out_dtype", out_dtype)
+    (B, Hkv, S, _), dv, dev = k_codes.shape, vt_codes.shape[2], q_codes.device
+    if tuple(vt_codes.shape[:2]) != (B, Hkv):
+        raise ValueError(f"k_codes {tuple(k_codes.shape)} and vt_codes {tuple(vt_codes.shape)} disagree on B or Hkv")
+    if vt_codes.shape[-1] != S:
+        raise ValueError(f"k_codes {tuple(k_codes.shape)} [B, Hkv, S, d] and vt_codes {tuple(vt_codes.shape)} [B, Hkv, dv, S] disagree on S")
+    _check_prefill("mx_flash_prefill_ragged", q_codes[None].transpose(1, 2), Hkv, k_codes.shape[-1], dv, scale, k_codes.shape)
+    if S < 1:
+        raise ValueError(f"mx_flash_prefill_ragged takes S >= 1, got S = {S}")
+    for name, t in (("k_codes", k_codes), ("vt_codes", vt_codes)):
+        if t.device != dev:
+            raise ValueError(f"q_codes is on {dev} but {name} on {t.device}")
+    if not isinstance(kv_len, torch.Tensor) or kv_len.dtype != torch.int32 or tuple(kv_len.shape) != (B,) or kv_len.device != dev:
+        raise ValueError(f"kv_len must be an int32 tensor of shape ({B},) on {dev}, got "
+                         + (f"{kv_len.dtype} {tuple(kv_len.shape)} on {kv_len.device}" if isinstance(kv_len, torch.Tensor)
+                            else type(kv_len).__name__))
+    _check_cu("mx_flash_prefill_ragged", cu_seqlens, B, dev)
+    return _ragged(q_codes, q_scales, qk_fmt, k_codes.contiguous(), k_scales.contiguous(), vt_codes.contiguous(),
+                   vt_scales.contiguous(), v_fmt, None, kv_len, cu_seqlens, scale, is_causal, p_fmt, out_dtype)
+
+
+def mx_flash_prefill_ragged_paged(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, k_pool: torch.Tensor, k_pool_scales: torch.Tensor,
+                                  vt_pool: torch.Tensor, vt_pool_scales: torch.Tensor, v_fmt: str, block_table: torch.Tensor,
+                                  kv_len: torch.Tensor, cu_seqlens: torch.Tensor, *, scale: float, is_causal: bool = False,
+                                  p_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """``mx_flash_prefill_ragged`` on a PAGED cache: the pool, ``block_table`` (int32 ``[B, NP]``) and ``kv_len`` (int32 ``[B]``, the length
+    AFTER the append) are ``mx_flash_prefill_paged``'s, ``q_codes [Ttot, Hq, d]`` and ``cu_seqlens`` (int32 ``[B + 1]``) as there.  The
+    result IS ``mx_flash_prefill_paged`` per sequence on row ``b`` of the table (``_ragged_def``), bit for bit on either device; dead
+    and out-of-range table entries follow ``mx_flash_prefill_paged``'s rules.  Rows at or behind ``cu[B]``: not written by the GPU
+    launch (unspecified content), zero on the CPU.  GPU tensors take ONE launch (``qs_mx_flash_ragged_v`` with a table; no gathered
+    copy, no fallback); table, lengths and ``cu_seqlens`` are read on the device."""
+    _check_q3("q", q_codes, q_scales, qk_fmt)
+    _mx_format(p_fmt)
+    _check_dtype("out_dtype", out_dtype)
+    dev = q_codes.device
+    _check_pool("mx_flash_prefill_ragged_paged", k_pool, k_pool_scales, qk_fmt, vt_pool, vt_pool_scales, v_fmt, block_table, kv_len)
+    if k_pool.device != dev:
+        raise ValueError(f"q_codes is on {dev} but k_pool on {k_pool.device}")
+    _check_prefill("mx_flash_prefill_ragged_paged", q_codes[None].transpose(1, 2), k_pool.shape[1], k_pool.shape[-1], vt_pool.shape[2], scale,
+                   k_pool.shape)
+    _check_cu("mx_flash_prefill_ragged_paged", cu_seqlens, block_table.shape[0], dev)
+    for name, t in (("k_pool", k_pool), ("k_pool_scales", k_pool_scales), ("vt_pool", vt_pool), ("vt_pool_scales", vt_pool_scales)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous: the pool is addressed through block_table, not copied")
+    return _ragged(q_codes, q_scales, qk_fmt, k_pool, k_pool_scales, vt_pool, vt_pool_scales, v_fmt,
+                   block_table.contiguous(), kv_len, cu_seqlens, scale, is_causal, p_fmt, out_dtype)
+
+
+__all__ = ["mx_flash_attention", "mx_flash_decode", "mx_flash_decode_paged", "mx_flash_prefill", "mx_flash_prefill_paged",
+           "mx_flash_prefill_ragged", "mx_flash_prefill_ragged_paged"]

@@ -12,8 +12,8 @@ import torch
 
 from qsparse_amd import _hip, _mx_common
 from qsparse_amd._mx_common import _check_dtype
-from qsparse_amd.mx_flash import (_check_pool, _paged_gather, mx_flash_decode, mx_flash_decode_paged, mx_flash_prefill,
-                                  mx_flash_prefill_paged)
+from qsparse_amd.mx_flash import (_check_cu, _check_pool, _paged_gather, mx_flash_decode, mx_flash_decode_paged, mx_flash_prefill,
+                                  mx_flash_prefill_paged, mx_flash_prefill_ragged_paged)
 from qsparse_amd.mx_rope import _rope_def
 from qsparse_amd.quantize import MX_BLOCK, _mx_format, quantize_with_mx
 
@@ -261,11 +261,106 @@ def mx_kv_append_paged(k_pool: torch.Tensor, k_pool_scales: torch.Tensor, qk_fmt
                                        kv_len.contiguous(), k_new, v_new, q_new, cos, sin, bool(interleaved))
 
 
+def _append_ragged_paged_def(k_pool, k_pool_scales, qk_fmt, vt_pool, vt_pool_scales, v_fmt, v_tail, block_table, kv_len, cu_seqlens, k_new,
+                             v_new, q_new, rope, interleaved):
+    """the ragged append's definition (``include/qsparse_hip.h``, "MX KV cache append, ragged"): ``_append_paged_def`` once per sequence
+    with ``T_b > 0``, on row ``b`` of ``block_table``, ``kv_len`` and ``v_tail`` and on its tokens permuted to head-major; q's codes go
+    back token-major, rows that no sequence owns stay zero.  Reads ``cu_seqlens`` on the host"""
+    Ttot, d = k_new.shape[0], k_new.shape[2]
+    out = None if q_new is None else tuple(k_pool.new_zeros(q_new.shape[:2] + (n,)) for n in (d, -(-d // MX_BLOCK)))
+    cu = [min(max(int(n), 0), Ttot) for n in cu_seqlens.tolist()]
+    for b, (lo, hi) in enumerate(zip(cu[:-1], cu[1:])):
+        if hi <= lo:
+            continue
+        k, v, q = (None if t is None else t[lo:hi].permute(1, 0, 2)[None].contiguous() for t in (k_new, v_new, q_new))
+        got = _append_paged_def(k_pool, k_pool_scales, qk_fmt, vt_pool, vt_pool_scales, v_fmt, v_tail[b:b + 1], block_table[b:b + 1],
+                                kv_len[b:b + 1], k, v, q, rope, interleaved)
+        if got is not None:
+            for dst, src in zip(out, got):
+                dst[lo:hi] = src[0].permute(1, 0, 2)
+    return out
+
+
+def mx_kv_append_ragged_paged(k_pool: torch.Tensor, k_pool_scales: torch.Tensor, qk_fmt: str, vt_pool: torch.Tensor,
+                              vt_pool_scales: torch.Tensor, v_fmt: str, v_tail: torch.Tensor, block_table: torch.Tensor, kv_len: torch.Tensor,
+                              k_new: torch.Tensor, v_new: torch.Tensor, cu_seqlens: torch.Tensor, *, q_new: Optional[torch.Tensor] = None,
+                              rope=None, interleaved: bool = False):
+    """``mx_kv_append_paged`` for a RAGGED batch, in place and in ONE launch: sequence ``b`` appends ``T_b`` tokens, one, hundreds or
+    none.  The new tokens are flat and token-major, as a QKV projection writes them -- ``k_new [Ttot, Hkv, d]``, ``v_new [Ttot, Hkv,
+    dv]``, optional ``q_new [Ttot, Hq, d]`` -- and ``cu_seqlens`` (int32 ``[B + 1]`` on the operands' device, non-decreasing, ``cu[0] ==
+    0``) says which sequence owns the tokens ``[cu[b], cu[b + 1])``.  The pool, ``v_tail``, ``block_table`` and ``kv_len`` are
+    ``mx_kv_append_paged``'s; ``kv_len`` is the length BEFORE the append and is not changed.
+
+    It IS ``mx_kv_append_paged`` called once per sequence with ``T_b > 0`` on row ``b`` of ``block_table``, ``kv_len`` and ``v_tail``
+    (``_append_ragged_paged_def``), bit for bit on either device: ``v_tail``, the re-quantization of every touched 32-block of ``vt``
+    from exact float32 values, dropping tokens at positions ``>= S``, the dead-entry guard and ``rope`` (table row ``min(L_b + t, P -
+    1)``) hold per sequence.  A sequence with ``T_b == 0`` is untouched, its ``v_tail`` included.  ``Ttot`` may exceed ``cu[B]``: tokens
+    at or behind ``cu[B]`` are stored nowhere.  ``q_new`` comes back as codes, token-major: ``(q_codes [Ttot, Hq, d], q_scales)``, the
+    operands of ``mx_flash_prefill_ragged_paged``; their rows at or behind ``cu[B]`` are unspecified on the GPU and zero on the CPU.
+
+    ``cu_seqlens``, ``kv_len`` and the table are read ON the device, never by the host: the call can be captured in a graph.  Every entry
+    of ``cu_seqlens`` is clamped into ``[0, Ttot]`` and a negative length is 0; a malformed ``cu_seqlens`` gives an unspecified result,
+    but no access leaves the operands.  Range: ``mx_kv_append_paged``'s (``1 <= d, dv <= 128``); anything else raises ``ValueError``
+    naming the bound.  GPU tensors take ``qs_mx_kv_append_ragged_v`` (no fallback); there is no contiguous-cache form."""
+    fn = "mx_kv_append_ragged_paged"
+    _check_pool(fn, k_pool, k_pool_scales, qk_fmt, vt_pool, vt_pool_scales, v_fmt, block_table, kv_len)
+    (P, Hkv, page, d), dv, (B, NP), dev = k_pool.shape, vt_pool.shape[2], block_table.shape, k_pool.device
+    S = NP * page
+    for name, n in (("d", d), ("dv", dv)):
+        if not 1 <= n <= MX_KV_MAX_D:
+            raise ValueError(f"{fn} takes 1 <= {name} <= {MX_KV_MAX_D}, got {name} = {n}")
+    if not isinstance(v_tail, torch.Tensor) or v_tail.dtype != torch.float32 or tuple(v_tail.shape) != (B, Hkv, dv, MX_BLOCK):
+        raise ValueError(f"v_tail must be a float32 tensor of shape {(B, Hkv, dv, MX_BLOCK)}, got "
+                         + (f"{v_tail.dtype} {tuple(v_tail.shape)}" if isinstance(v_tail, torch.Tensor) else type(v_tail).__name__))
+    _check_cu(fn, cu_seqlens, B, dev)
+    news = (("k_new", k_new, Hkv, d), ("v_new", v_new, Hkv, dv)) + ((("q_new", q_new, None, d),) if q_new is not None else ())
+    for name, t, heads, last in news:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+        _check_dtype(name, t.dtype)
+        if t.dim() != 3 or (heads is not None and t.shape[1] != heads) or t.shape[2] != last or t.shape[0] != k_new.shape[0]:
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected ('Ttot', {'Hq' if heads is None else heads}, {last}) with k_new's Ttot")
+        if t.dtype != k_new.dtype:
+            raise ValueError(f"k_new is {k_new.dtype} but {name} {t.dtype}: the new tokens share one dtype")
+    if q_new is not None and (q_new.shape[1] < 1 or q_new.shape[1] % Hkv):
+        raise ValueError(f"Hq = {q_new.shape[1]} is no multiple of Hkv = {Hkv}: query head h uses key/value head h // (Hq / Hkv)")
+    if rope is not None:
+        if not isinstance(rope, (tuple, list)) or len(rope) != 2:
+            raise TypeError("rope must be None or a 2-tuple (cos, sin)")
+        if d % 2:
+            raise ValueError(f"rope needs an even d (the last dimension of k_new), got {d}")
+        for name, t in zip(("cos", "sin"), rope):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != d // 2 or t.shape[0] < S:
+                raise ValueError(f"{name} must be a float32 tensor [P, d / 2] = [>= {S}, {d // 2}], got "
+                                 + (f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__))
+        if rope[0].shape != rope[1].shape:
+            raise ValueError(f"cos {tuple(rope[0].shape)} and sin {tuple(rope[1].shape)} disagree on P")
+    for name, t in (("v_tail", v_tail),) + tuple(n[:2] for n in news) + ((("cos", rope[0]), ("sin", rope[1])) if rope is not None else ()):
+        if t.device != dev:
+            raise ValueError(f"k_pool is on {dev} but {name} on {t.device}")
+    for name, t in (("k_pool", k_pool), ("k_pool_scales", k_pool_scales), ("vt_pool", vt_pool), ("vt_pool_scales", vt_pool_scales),
+                    ("v_tail", v_tail)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous: it is written in place")
+    if B == 0 or k_new.shape[0] == 0:
+        return None if q_new is None else tuple(k_pool.new_zeros(q_new.shape[:2] + (n,)) for n in (d, -(-d // MX_BLOCK)))
+    with torch.no_grad():
+        k_new, v_new, q_new = (None if t is None else t.detach().contiguous() for t in (k_new, v_new, q_new))
+        if not k_pool.is_cuda:
+            return _append_ragged_paged_def(k_pool, k_pool_scales, qk_fmt, vt_pool, vt_pool_scales, v_fmt, v_tail, block_table, kv_len,
+                                            cu_seqlens, k_new, v_new, q_new, rope, bool(interleaved))
+        cos, sin = (None, None) if rope is None else (t.contiguous() for t in rope)
+        return _hip.mx_kv_append_ragged(k_pool, k_pool_scales, qk_fmt, vt_pool, vt_pool_scales, v_fmt, v_tail, block_table.contiguous(),
+                                        kv_len.contiguous(), cu_seqlens.contiguous(), k_new, v_new, q_new, cos, sin, bool(interleaved))
+
+
 class MXPagedKVCache:
     """The buffers of a paged MX KV cache: the pool ``k_pool [P, Hkv, page, d]`` / ``k_pool_scales``, ``vt_pool [P, Hkv, dv, page]`` /
     ``vt_pool_scales``, and per sequence ``v_tail [B, Hkv, dv, 32]``, ``kv_len`` (int32 ``[B]``, zero) and ``block_table`` (int32 ``[B,
     NP]``, filled with ``-1``: the caller writes page numbers into it).  ``append`` is ``mx_kv_append_paged`` followed by ``kv_len +=
-    T``; ``attend`` is ``mx_flash_decode_paged``.  Both are graph-capturable; there is no allocator and no other logic."""
+    T``; ``attend`` is ``mx_flash_decode_paged``.  ``append_ragged`` / ``prefill_ragged`` are the same pair for a batch whose sequences
+    bring different numbers of tokens (flat token-major operands and ``cu_seqlens``).  All are graph-capturable; there is no allocator
+    and no other logic."""
 
     def __init__(self, P: int, B: int, NP: int, Hkv: int, page: int, d: int, dv: int, qk_fmt: str = "mxfp8_e4m3",
                  v_fmt: str = "mxfp8_e4m3", device=None):
@@ -295,5 +390,19 @@ class MXPagedKVCache:
         return mx_flash_prefill_paged(q_codes, q_scales, self.qk_fmt, self.k_pool, self.k_pool_scales, self.vt_pool, self.vt_pool_scales,
                                       self.v_fmt, self.block_table, self.kv_len, **kw)
 
+    def append_ragged(self, k: torch.Tensor, v: torch.Tensor, cu_seqlens: torch.Tensor, q: Optional[torch.Tensor] = None, rope=None,
+                      interleaved: bool = False):
+        """``mx_kv_append_ragged_paged`` followed by ``kv_len += cu_seqlens[1:] - cu_seqlens[:-1]``, a device op with no host read"""
+        out = mx_kv_append_ragged_paged(self.k_pool, self.k_pool_scales, self.qk_fmt, self.vt_pool, self.vt_pool_scales, self.v_fmt,
+                                        self.v_tail, self.block_table, self.kv_len, k, v, cu_seqlens, q_new=q, rope=rope,
+                                        interleaved=interleaved)
+        self.kv_len += cu_seqlens[1:] - cu_seqlens[:-1]
+        return out
 
-__all__ = ["mx_kv_append", "MXKVCache", "mx_kv_append_paged", "MXPagedKVCache"]
+    def prefill_ragged(self, q_codes: torch.Tensor, q_scales: torch.Tensor, cu_seqlens: torch.Tensor, **kw) -> torch.Tensor:
+        """``mx_flash_prefill_ragged_paged`` on the cache, behind the ``append_ragged`` that stored the tokens"""
+        return mx_flash_prefill_ragged_paged(q_codes, q_scales, self.qk_fmt, self.k_pool, self.k_pool_scales, self.vt_pool,
+                                             self.vt_pool_scales, self.v_fmt, self.block_table, self.kv_len, cu_seqlens, **kw)
+
+
+__all__ = ["mx_kv_append", "MXKVCache", "mx_kv_append_paged", "MXPagedKVCache", "mx_kv_append_ragged_paged"]

@@ -2612,6 +2612,110 @@ int qs_mx_kv_append_ragged_v(const qs_mx_kv_append_ragged_args* args);
  * the QS_ERR_* the call would return */
 int qs_mx_kv_append_ragged_route(const qs_mx_kv_append_ragged_args* args);
 
+/* ---- MX MoE routing (top-k selection, gates and the stable sort by expert of a mixture-of-experts layer) ---------------------------------
+ * Added without raising QS_ABI_VERSION (28): symbols are only added.  logits [T, E] (float32, bfloat16 or float16, widened exactly to
+ * float32; rows `stride` elements apart, elements adjacent) -> gates float32 [T, k], experts int32 [T, k], offs int32 [E], order int32
+ * [T k], inv int32 [T, k].
+ *
+ * Definition (normative; every operation a float32 operation of its own, nothing contracted).
+ *   - Selection.  Slot j of token t is the j-th expert of row t under this total order: a NaN ranks before every number; otherwise the
+ *     larger value ranks first, -0 and +0 being equal; equal values, and NaNs among themselves, go to the LOWER expert index.
+ *     top_j is the logit of slot j, a -0 taken as +0.
+ *   - Gates.  u_j = top_j - top_0; e_j = E(u_j), the exponential of "MX softmax quantizer" (+0 for -inf and for a NaN);
+ *     Z is the balanced tree over 32 slots, e_j = +0 for j >= k: s_j <- s_2j + s_2j+1, five times (for k = 8:
+ *     ((e_0 + e_1) + (e_2 + e_3)) + ((e_4 + e_5) + (e_6 + e_7)); adding +0 is exact); its rounding error grows with log2 k, where that of
+ *     the sum one by one grows with k and, at k = 32, is three times a float32 softmax's.  gate_j = e_j / Z, the correctly rounded division.  A token whose slots hold a NaN,
+ *     or whose top_0 is +inf or -inf, has Z = 0 and every gate NaN: the quiet NaN 0x7fc00000.
+ *   - Sort.  With the flat id i = t k + j: order is the stable sort of the flat ids by expert (ascending expert, ascending i within
+ *     one), inv its inverse (order[inv[t, j]] == t k + j), offs[e] the number of ids whose expert is <= e: the cumulative group ends
+ *     that qs_mx_grouped_matmul_v takes.
+ *   - Range: 1 <= E <= 1024, 1 <= k <= min(E, 32), T >= 0, T k < 2^31; anything else, a NULL operand (workspace excepted where none is
+ *     needed) or a negative stride is QS_ERR_ARG, a dtype that is none of the three QS_ERR_DTYPE, a pointer off its element's (4 bytes
+ *     for the outputs and the workspace) alignment QS_ERR_ALIGN.  T == 0: nothing is enqueued, 0 is returned and offs is NOT written.
+ *   - Routes: QS_MX_MOE_ROUTE_ONE when T <= 64 (one tile): one launch of one work-group, no workspace.  Otherwise
+ *     QS_MX_MOE_ROUTE_TILED, three launches (select per tile of 64 tokens, scan over the tiles, place) through `workspace`, at least
+ *     4 * (ceil(T / 64) + 1) * E bytes (less is QS_ERR_ARG), whose content before and after means nothing.  A deterministic counting
+ *     sort: no atomics, no work-group waits for another, the same result on every run.  Nothing is read by the host. */
+#define QS_MX_MOE_ROUTE_ONE 1
+#define QS_MX_MOE_ROUTE_TILED 2
+typedef struct qs_mx_moe_route_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_moe_route_args) as the caller compiled it */
+    int32_t xdt;                     /* QS_F32, QS_BF16 or QS_F16: logits */
+    int32_t k;
+    int32_t reserved0;               /* 0 */
+    const void* logits;              /* [T, E], rows `stride` elements apart */
+    float* gates;                    /* [T, k] */
+    int32_t* experts;                /* [T, k] */
+    int32_t* offs;                   /* [E] */
+    int32_t* order;                  /* [T k] */
+    int32_t* inv;                    /* [T, k] */
+    void* workspace;                 /* QS_MX_MOE_ROUTE_TILED only */
+    int64_t workspace_bytes;
+    int64_t T, E, stride;
+    qs_stream_t stream;
+} qs_mx_moe_route_args;
+int qs_mx_moe_route_v(const qs_mx_moe_route_args* args);
+/* the route qs_mx_moe_route_v takes for these operands, nothing enqueued: QS_MX_MOE_ROUTE_*, 0 for an empty problem, or the QS_ERR_*
+ * the call would return */
+int qs_mx_moe_route_route(const qs_mx_moe_route_args* args);
+
+/* ---- MX MoE dispatch (the rows of x quantized once and written to the k rows the routing gave them) ------------------------------------
+ * Added without raising QS_ABI_VERSION (28).  x [T, D] (rows `stride` elements apart) and inv int32 [T, k] -> codes uint8 [T k, D],
+ * scales uint8 [T k, ceil(D / 32)].
+ *
+ * Definition (normative).  Rows inv[t, j], j = 0 .. k - 1, of codes / scales hold the bytes "MX block-scaled quantizer" gives row t of
+ * x with blocks along D (rounding to nearest).  With x NULL the input is MX bytes already -- x_codes [T, D], x_scales [T, ceil(D / 32)],
+ * dense -- and the rows are copies.  An inv entry outside [0, T k) is not dereferenced and nothing is stored for it; rows that no
+ * entry names keep the bytes they had.  Two entries that name one row: unspecified which token's bytes it holds.
+ *   - Range: T, D >= 0, 1 <= k <= 32, T k < 2^31, stride >= D; T == 0 or D == 0: nothing is enqueued, 0 is returned.
+ *   - Routes: QS_MX_MOE_DISPATCH_ROUTE_VEC (16-byte loads, 8-byte code stores): D and stride multiples of 8, x 16-byte and codes 8-byte
+ *     aligned (copies: D a multiple of 16, x_codes and codes 16-byte aligned); anything else QS_MX_MOE_DISPATCH_ROUTE_PLAIN: the same
+ *     bytes.  ONE launch; x is read once, T D elements. */
+#define QS_MX_MOE_DISPATCH_ROUTE_VEC 1
+#define QS_MX_MOE_DISPATCH_ROUTE_PLAIN 2
+typedef struct qs_mx_moe_dispatch_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_moe_dispatch_args) as the caller compiled it */
+    int32_t format;                  /* enum qs_mx_format of codes */
+    int32_t xdt;                     /* QS_F32, QS_BF16 or QS_F16: x (ignored with x NULL) */
+    int32_t k;
+    const void* x;                   /* [T, D], or NULL: */
+    const uint8_t* x_codes;          /* [T, D] dense, with x NULL */
+    const uint8_t* x_scales;         /* [T, ceil(D / 32)] dense */
+    const int32_t* inv;              /* [T, k] */
+    uint8_t* codes;                  /* [T k, D] */
+    uint8_t* scales;                 /* [T k, ceil(D / 32)] */
+    int64_t T, D, stride;
+    qs_stream_t stream;
+} qs_mx_moe_dispatch_args;
+int qs_mx_moe_dispatch_v(const qs_mx_moe_dispatch_args* args);
+/* the route qs_mx_moe_dispatch_v takes, nothing enqueued: QS_MX_MOE_DISPATCH_ROUTE_*, 0 for an empty problem, or the QS_ERR_* */
+int qs_mx_moe_dispatch_route(const qs_mx_moe_dispatch_args* args);
+
+/* ---- MX MoE combine (every token's k expert rows times its gates, summed) ------------------------------------------------------------
+ * Added without raising QS_ABI_VERSION (28).  y [T k, D] dense (float32, bfloat16 or float16), inv int32 [T, k], gates float32 [T, k]
+ * -> out [T, D] dense in `odt`.
+ *
+ * Definition (normative).  out[t, c] = ((g_0 y_0) + (g_1 y_1)) + ... over j = 0 .. k - 1 in ascending order, g_j = gates[t, j], y_j =
+ * y[inv[t, j], c] widened to float32; every product and every sum rounded to float32 on its own (no FMA), then ONE rounding to `odt`.
+ * An inv entry outside [0, T k) is not dereferenced: its y_j is +0 (the product is still formed: a NaN gate gives NaN).
+ *   - Range: as dispatch; routes QS_MX_MOE_DISPATCH_ROUTE_VEC (one 16- or 8-byte access per 4 columns): D a multiple of 4, y and out
+ *     aligned to 4 of their elements; else QS_MX_MOE_DISPATCH_ROUTE_PLAIN: the same bits.  ONE launch, no atomics. */
+typedef struct qs_mx_moe_combine_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_moe_combine_args) as the caller compiled it */
+    int32_t ydt;                     /* QS_F32, QS_BF16 or QS_F16: y */
+    int32_t odt;                     /* ... out */
+    int32_t k;
+    const void* y;                   /* [T k, D] */
+    const int32_t* inv;              /* [T, k] */
+    const float* gates;              /* [T, k] */
+    void* out;                       /* [T, D] */
+    int64_t T, D;
+    qs_stream_t stream;
+} qs_mx_moe_combine_args;
+int qs_mx_moe_combine_v(const qs_mx_moe_combine_args* args);
+/* the route qs_mx_moe_combine_v takes, nothing enqueued: QS_MX_MOE_DISPATCH_ROUTE_*, 0 for an empty problem, or the QS_ERR_* */
+int qs_mx_moe_combine_route(const qs_mx_moe_combine_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

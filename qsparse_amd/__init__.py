@@ -24,6 +24,7 @@ from qsparse_amd.mx_glu_train import (MXTrainGatedMoEFeedForward, MXTrainGLULine
                                       mx_glu_linear, mx_grouped_glu_linear)
 from qsparse_amd.mx_grouped import MXGroupedLinear, MXMoEFeedForward, mx_grouped_matmul
 from qsparse_amd.mx_grouped_train import MXTrainGroupedLinear, MXTrainMoEFeedForward, mx_grouped_linear, mx_grouped_weight_grad
+from qsparse_amd.mx_moe import mx_moe_combine, mx_moe_dispatch_quantize, mx_moe_route
 from qsparse_amd.mx_kv_cache import MXKVCache, MXPagedKVCache, mx_kv_append, mx_kv_append_paged, mx_kv_append_ragged_paged
 from qsparse_amd.mx_norm import (MXAddNormLinear, MXLayerNorm, MXRMSNorm, MXTrainAddNormLinear, MXTrainNormLinear, mx_add_norm_linear,
                                  mx_add_norm_quantize, mx_norm_backward, mx_norm_linear, mx_norm_quantize)

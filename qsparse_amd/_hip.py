@@ -176,6 +176,12 @@ SIGNATURES = {
     "qs_mx_flash_ragged_route": (c_int, [_P]),
     "qs_mx_kv_append_ragged_v": (c_int, [_P]),
     "qs_mx_kv_append_ragged_route": (c_int, [_P]),
+    "qs_mx_moe_route_v": (c_int, [_P]),
+    "qs_mx_moe_route_route": (c_int, [_P]),
+    "qs_mx_moe_dispatch_v": (c_int, [_P]),
+    "qs_mx_moe_dispatch_route": (c_int, [_P]),
+    "qs_mx_moe_combine_v": (c_int, [_P]),
+    "qs_mx_moe_combine_route": (c_int, [_P]),
 }
 
 
@@ -503,6 +509,27 @@ class MxKvAppendRaggedArgs(ctypes.Structure):
                 ("sin", c_void_p), ("q_codes", c_void_p), ("q_scales", c_void_p), ("B", c_int64), ("Hq", c_int64), ("Hkv", c_int64),
                 ("Ttot", c_int64), ("P_pool", c_int64), ("NP", c_int64), ("page", c_int64), ("d", c_int64), ("dv", c_int64),
                 ("P", c_int64), ("stream", c_void_p)]
+
+
+class MxMoeRouteArgs(ctypes.Structure):
+    """`qs_mx_moe_route_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("xdt", c_int32), ("k", c_int32), ("reserved0", c_int32), ("logits", c_void_p),
+                ("gates", c_void_p), ("experts", c_void_p), ("offs", c_void_p), ("order", c_void_p), ("inv", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", c_int64), ("T", c_int64), ("E", c_int64), ("stride", c_int64),
+                ("stream", c_void_p)]
+
+
+class MxMoeDispatchArgs(ctypes.Structure):
+    """`qs_mx_moe_dispatch_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("format", c_int32), ("xdt", c_int32), ("k", c_int32), ("x", c_void_p),
+                ("x_codes", c_void_p), ("x_scales", c_void_p), ("inv", c_void_p), ("codes", c_void_p), ("scales", c_void_p),
+                ("T", c_int64), ("D", c_int64), ("stride", c_int64), ("stream", c_void_p)]
+
+
+class MxMoeCombineArgs(ctypes.Structure):
+    """`qs_mx_moe_combine_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("ydt", c_int32), ("odt", c_int32), ("k", c_int32), ("y", c_void_p), ("inv", c_void_p),
+                ("gates", c_void_p), ("out", c_void_p), ("T", c_int64), ("D", c_int64), ("stream", c_void_p)]
 
 
 class MxSoftmaxQuant2Args(ctypes.Structure):
@@ -2137,6 +2164,85 @@ def mx_kv_append_ragged(k_pool: torch.Tensor, k_pool_scales: torch.Tensor, qk_fm
         a.stream = _stream(k_pool)
         mx_kv_append_last_route = _mx_run("mx_kv_append_ragged", a, (k_new, v_new, q_new, block_table, cu_seqlens) + (q or ()))
     return q
+
+
+MX_MOE_ROUTE_ONE, MX_MOE_ROUTE_TILED = 1, 2
+MX_MOE_TILE = 64                 # tokens per tile of the routing's select launch (kMoeTile of qs_mx_moe_route.h)
+MX_MOE_DISPATCH_ROUTE_VEC, MX_MOE_DISPATCH_ROUTE_PLAIN = 1, 2
+mx_moe_route_last_route = None      # the QS_MX_MOE_ROUTE_* of the last `mx_moe_route` launch (None: an empty problem)
+mx_moe_dispatch_last_route = None   # the QS_MX_MOE_DISPATCH_ROUTE_* of the last `mx_moe_dispatch` launch (None: an empty problem)
+mx_moe_combine_last_route = None    # ... of the last `mx_moe_combine` launch
+
+
+def mx_moe_route(logits: torch.Tensor, k: int):
+    """top-k routing of `logits` [T, E] (stride(1) == 1) on the GPU (qs_mx_moe_route_v): returns (gates float32 [T, k], experts int32
+    [T, k], offs int32 [E], order int32 [T k], inv int32 [T, k]) from ONE launch for T <= MX_MOE_TILE, else three through a workspace
+    of 4 (ceil(T / MX_MOE_TILE) + 1) E bytes from torch's caching allocator.  The route lands in `mx_moe_route_last_route`."""
+    global mx_moe_route_last_route
+    load()
+    (T, E), dev = logits.shape, logits.device
+    gates = torch.empty((T, k), dtype=torch.float32, device=dev)
+    experts, inv = (torch.empty((T, k), dtype=torch.int32, device=dev) for _ in range(2))
+    order = torch.empty(T * k, dtype=torch.int32, device=dev)
+    mx_moe_route_last_route = None
+    if not T:
+        return gates, experts, torch.zeros(E, dtype=torch.int32, device=dev), order, inv
+    offs = torch.empty(E, dtype=torch.int32, device=dev)
+    ws = _mx_workspace(4 * ((T + MX_MOE_TILE - 1) // MX_MOE_TILE + 1) * E, dev) if T > MX_MOE_TILE else None
+    a = MxMoeRouteArgs()
+    a.xdt, a.k, a.logits = dt(logits), k, _ptr(logits)
+    a.gates, a.experts, a.offs, a.order, a.inv = _ptr(gates), _ptr(experts), _ptr(offs), _ptr(order), _ptr(inv)
+    a.workspace, a.workspace_bytes = _ptr(ws), 0 if ws is None else ws.numel()
+    a.T, a.E, a.stride = T, E, logits.stride(0) if T > 1 else E
+    a.stream = _stream(logits)
+    mx_moe_route_last_route = _mx_run("mx_moe_route", a, (logits, gates, experts, offs, order, inv))
+    return gates, experts, offs, order, inv
+
+
+def mx_moe_dispatch(x: Optional[torch.Tensor], x_codes: Optional[torch.Tensor], x_scales: Optional[torch.Tensor], inv: torch.Tensor,
+                    fmt: str, out=None):
+    """the rows of `x` [T, D] (stride(1) == 1, rows `stride(0)` apart) quantized once -- or, with `x` None, the dense MX bytes `x_codes`
+    [T, D] / `x_scales` copied -- to the rows `inv` [T, k] (int32, contiguous) names, in ONE launch (qs_mx_moe_dispatch_v): returns
+    (codes uint8 [T k, D], scales uint8 [T k, ceil(D / 32)]), rows that no entry names as torch.empty gave them.  `out`: the two tensors
+    to write instead, contiguous, as the guard-byte tests carve them.  The route lands in `mx_moe_dispatch_last_route`."""
+    global mx_moe_dispatch_last_route
+    load()
+    rows = x_codes if x is None else x
+    (T, D), k = rows.shape, inv.shape[1]
+    codes, scales = (_mx_new_or_out(shape, torch.uint8, rows.device, None if out is None else out[i], "out: dense uint8")
+                     for i, shape in enumerate(((T * k, D), (T * k, (D + MX_BLOCK - 1) // MX_BLOCK))))
+    mx_moe_dispatch_last_route = None
+    if T and D:
+        a = MxMoeDispatchArgs()
+        a.format, a.k = MX_FORMATS.index(fmt), k
+        if x is None:
+            a.x_codes, a.x_scales, a.stride = _ptr(x_codes), _ptr(x_scales), D
+        else:
+            a.x, a.xdt, a.stride = _ptr(x), dt(x), x.stride(0) if T > 1 else D
+        a.inv, a.codes, a.scales = _ptr(inv), _ptr(codes), _ptr(scales)
+        a.T, a.D = T, D
+        a.stream = _stream(rows)
+        mx_moe_dispatch_last_route = _mx_run("mx_moe_dispatch", a, (rows, x_scales, inv, codes, scales))
+    return codes, scales
+
+
+def mx_moe_combine(y: torch.Tensor, inv: torch.Tensor, gates: torch.Tensor, out_dtype: torch.dtype, out=None):
+    """out[t] = sum over j of gates[t, j] y[inv[t, j]] in the definition's float32 order, ONE launch (qs_mx_moe_combine_v): `y` [T k, D],
+    `inv` int32 [T, k] and `gates` float32 [T, k] contiguous; returns [T, D] in `out_dtype`.  `out`: the tensor to write instead.  The
+    route lands in `mx_moe_combine_last_route`."""
+    global mx_moe_combine_last_route
+    load()
+    (T, k), D = inv.shape, y.shape[1]
+    res = _mx_new_or_out((T, D), out_dtype, y.device, out, "out: dense, of out_dtype")
+    mx_moe_combine_last_route = None
+    if T and D:
+        a = MxMoeCombineArgs()
+        a.ydt, a.odt, a.k = dt(y), _DT[out_dtype], k
+        a.y, a.inv, a.gates, a.out = _ptr(y), _ptr(inv), _ptr(gates), _ptr(res)
+        a.T, a.D = T, D
+        a.stream = _stream(y)
+        mx_moe_combine_last_route = _mx_run("mx_moe_combine", a, (y, inv, gates, res))
+    return res
 
 
 mx_softmax_quant2_last_route = None     # the QS_MX_SOFTMAX_ROUTE_* of the last `mx_softmax_quant2` launch (None: an empty tensor)

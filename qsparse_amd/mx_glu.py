@@ -353,12 +353,13 @@ class MXGatedMoEFeedForward(MXMoEFeedForward):
     @classmethod
     def from_float(cls, router: torch.Tensor, w_gate: torch.Tensor, b_gate: Optional[torch.Tensor], w_up: torch.Tensor,
                    b_up: Optional[torch.Tensor], w_down: torch.Tensor, b_down: Optional[torch.Tensor], top_k: int,
-                   w_fmt: str = "mxfp8_e4m3", act_fmt: str = "mxfp8_e4m3", hidden_fmt: str = "mxfp8_e4m3", *, act: str = "silu"):
+                   w_fmt: str = "mxfp8_e4m3", act_fmt: str = "mxfp8_e4m3", hidden_fmt: str = "mxfp8_e4m3", *, act: str = "silu",
+                   routing: str = "torch"):
         """from float tensors: ``router [E, D]``, ``w_gate``, ``w_up`` ``[E, H, D]`` / ``b_gate``, ``b_up`` ``[E, H]``, ``w_down [E, D,
         H]`` / ``b_down [E, D]``.  The hidden activation ``act(gate) * up`` is quantized to ``hidden_fmt`` by ``up``'s epilogue"""
         up = MXGroupedGLULinear.from_float(w_gate, w_up, b_gate, b_up, w_fmt, act_fmt, act=act, out_fmt=hidden_fmt)
         down = MXGroupedLinear.from_float(w_down, b_down, w_fmt, hidden_fmt)
-        return cls(router, up, down, top_k)
+        return cls(router, up, down, top_k, routing=routing)
 
 
 __all__ = ["mx_glu_interleave", "mx_glu_deinterleave", "mx_glu_matmul", "mx_grouped_glu_matmul", "MXGLULinear", "MXGroupedGLULinear",

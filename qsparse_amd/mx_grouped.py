@@ -13,10 +13,11 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from qsparse_amd import _hip, _mx_common
+from qsparse_amd import _hip, _mx_common, mx_moe
 from qsparse_amd._mx_common import MXActivation, _check_codes_out, _check_dtype, _codes_out_cpu
 from qsparse_amd.quantize import _mx_format, mx_dequantize, quantize_with_mx
 
+MOE_ROUTINGS = ("torch", "fused")
 _check_a = partial(_mx_common._check_operand, what="[T, K]", least=2, most=2, needs="2 dimensions")
 _check_b = partial(_mx_common._check_operand, what="[E, N, K]", least=3, most=3, needs="3 dimensions")
 
@@ -212,13 +213,23 @@ class MXMoEFeedForward(nn.Module):
 
     Nothing in it synchronises with the host (the counts are a comparison against ``arange(E)`` summed, not ``torch.bincount``), so it
     can be captured in a graph, and nothing in it is an atomic or an ``index_add_``: the same bits on every run.  No capacity, no token
-    dropping, no shared expert, no training.  ``state_dict`` keys: ``router``, ``up.weight_codes``, ``up.weight_scales``, ``up.bias``,
+    dropping, no shared expert, no training.
+
+    ``routing="fused"`` (keyword; the default ``"torch"`` is the composition above, unchanged) replaces steps 1 to 4 around the two
+    products by the three HIP calls of ``mx_moe.py`` and is DEFINED as, and bit for bit equal to: the same float32 logits;
+    ``mx_moe_route``; ``mx_moe_dispatch_quantize(x, inv, up.act_fmt)`` as an ``MXActivation``; ``down(up(., offs), offs)``;
+    ``mx_moe_combine``.  Its selection breaks ties towards the lower expert and its gates are the written-out float32 softmax of
+    ``mx_moe_route``, so its output is close to, not bit-equal to, the default's.
+
+    ``state_dict`` keys (either routing): ``router``, ``up.weight_codes``, ``up.weight_scales``, ``up.bias``,
     ``down.weight_codes``, ``down.weight_scales``, ``down.bias`` (a bias only where the layer has one)."""
 
     _up_type = MXGroupedLinear      # what `up` must be: the gated block (mx_glu.py) derives from this one and names its own
 
-    def __init__(self, router: torch.Tensor, up: MXGroupedLinear, down: MXGroupedLinear, top_k: int):
+    def __init__(self, router: torch.Tensor, up: MXGroupedLinear, down: MXGroupedLinear, top_k: int, *, routing: str = "torch"):
         super().__init__()
+        if routing not in MOE_ROUTINGS:
+            raise ValueError(f"unknown routing {routing!r}: one of {MOE_ROUTINGS}")
         if not isinstance(up, self._up_type) or not isinstance(down, MXGroupedLinear):
             raise TypeError("up and down must be MXGroupedLinear layers" if self._up_type is MXGroupedLinear else
                             f"up must be an {self._up_type.__name__} layer and down an MXGroupedLinear layer")
@@ -236,7 +247,10 @@ class MXMoEFeedForward(nn.Module):
             raise ValueError("down must return float32 (no out_fmt, out_dtype=torch.float32): the gates weight its rows in float32")
         if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= E:
             raise ValueError(f"top_k must be an int in [1, {E}], got {top_k!r}")
-        self.up, self.down, self.top_k = up, down, top_k
+        if routing == "fused" and (E > mx_moe.MX_MOE_MAX_EXPERTS or top_k > mx_moe.MX_MOE_MAX_TOP_K):
+            raise ValueError(f'routing="fused" takes E <= {mx_moe.MX_MOE_MAX_EXPERTS} and top_k <= {mx_moe.MX_MOE_MAX_TOP_K}, got E = {E}, '
+                             f"top_k = {top_k}")
+        self.up, self.down, self.top_k, self.routing = up, down, top_k, routing
         self.num_experts, self.embed_dim, self.hidden_dim = E, D, H
         self.register_buffer("router", router.detach().to(torch.float32).clone().contiguous())
 
@@ -246,12 +260,12 @@ class MXMoEFeedForward(nn.Module):
     @classmethod
     def from_float(cls, router: torch.Tensor, w_up: torch.Tensor, b_up: Optional[torch.Tensor], w_down: torch.Tensor,
                    b_down: Optional[torch.Tensor], top_k: int, w_fmt: str = "mxfp8_e4m3", act_fmt: str = "mxfp8_e4m3",
-                   hidden_fmt: str = "mxfp8_e4m3"):
+                   hidden_fmt: str = "mxfp8_e4m3", *, routing: str = "torch"):
         """from float tensors: ``router [E, D]``, ``w_up [E, H, D]`` / ``b_up [E, H]``, ``w_down [E, D, H]`` / ``b_down [E, D]``.  The
         hidden activation is ReLU, quantized to ``hidden_fmt`` by ``up``'s epilogue"""
         up = MXGroupedLinear.from_float(w_up, b_up, w_fmt, act_fmt, out_fmt=hidden_fmt, act="relu")
         down = MXGroupedLinear.from_float(w_down, b_down, w_fmt, hidden_fmt)
-        return cls(router, up, down, top_k)
+        return cls(router, up, down, top_k, routing=routing)
 
     def forward(self, x):
         taken = isinstance(x, MXActivation)
@@ -262,6 +276,11 @@ class MXMoEFeedForward(nn.Module):
             if x32.dim() != 2 or x32.shape[1] != self.embed_dim:
                 raise ValueError(f"x must be [T, D] with D = {self.embed_dim}, got shape {tuple(x32.shape)}")
             k, E = self.top_k, self.num_experts
+            if self.routing == "fused":
+                gates, _, offs, _, inv = mx_moe.mx_moe_route(x32 @ self.router.t(), k)
+                fmt = x.fmt if taken else self.up.act_fmt
+                rows = MXActivation(*mx_moe.mx_moe_dispatch_quantize(x, inv, fmt), fmt)
+                return mx_moe.mx_moe_combine(self.down(self.up(rows, offs), offs), inv, gates)
             top, experts = torch.topk(x32 @ self.router.t(), k, -1)
             gates = torch.softmax(top, -1)
             ids = experts.reshape(-1)

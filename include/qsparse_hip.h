@@ -2716,6 +2716,69 @@ int qs_mx_moe_combine_v(const qs_mx_moe_combine_args* args);
 /* the route qs_mx_moe_combine_v takes, nothing enqueued: QS_MX_MOE_DISPATCH_ROUTE_*, 0 for an empty problem, or the QS_ERR_* */
 int qs_mx_moe_combine_route(const qs_mx_moe_combine_args* args);
 
+/* ---- MX flash attention, shared-prefix paged decode (qs_mx_flash_decode_paged_v for sequences whose first keys are the same pages) ------
+ * Added without raising QS_ABI_VERSION (28): symbols are only added.  Operands and layout are "MX flash attention, paged decode"'s, plus
+ * shared_table, int32 [NPs] in device memory -- the pages of the prefix that every sequence of the call begins with -- and shared_len,
+ * int32 [1] in device memory.  Both are read by the kernel, never by the host.  The keys of the shared part are read once per 16 query
+ * rows of the BATCH (ceil(B * R / 16) times per kv head, R = Hq / Hkv * T), not once per sequence.
+ *
+ * Definition (normative).  With page, NP, S = NP * page as there, u = max(128, page):
+ *     Ls = u * floor(clamp(shared_len[0], 0, min(NPs, NP) * page) / u),  Cs = Ls / 128,
+ * and Csmax the same with shared_len at its upper clamp (a function of the shapes).
+ *   1. Merged table.  Page n of sequence b is shared_table[n] where (n + 1) * page <= Ls, else block_table[b, n].  Entries of
+ *      block_table below Ls are never turned into an address and may hold anything; a live entry of either table outside [0, P) reads
+ *      as zero codes under the scale byte 127.
+ *   2. The cache is gathered through the merged table and sliced to L_b = clamp(kv_len[b], 0, S) keys.  kv_len counts the shared keys.
+ *      Row limits are "MX flash attention, decode"'s (causal: bottom-right).
+ *   3. Every row has sp + so = shared_splits + kv_splits runs of chunks of 128 keys, each walked with the chunk recurrence of "MX flash
+ *      attention, streamed" from the empty state: shared run i < sp owns the chunks [i * cps_s, min((i + 1) * cps_s, Cs)), cps_s =
+ *      ceil(max(Csmax, 1) / sp); own run i < so owns [Cs + i * cps, Cs + (i + 1) * cps), cps = ceil(ceil(S / 128) / so); both cut at
+ *      ceil(L_b / 128).  The sp + so states are combined as the splits of "MX flash attention, decode": the maximum over all, then the
+ *      ascending sum, shared runs first, none skipped.
+ *   The result is NOT qs_mx_flash_decode_paged_v's bytes (the runs are cut elsewhere); with shared_len[0] < u it is its values at
+ *   kv_splits = so.  A sequence with L_b < Ls, or L_b = 0, is served by its rows' limits like any other.  One restriction: the keys
+ *   of the shared pages in [L_b, max over the batch of L_b) are live keys of another sequence; their vt codes and vt scale bytes must
+ *   not be NaN, or rows of sequence b that sit in the same tile of 16 become NaN too.
+ *   - Range: as qs_mx_flash_decode_paged_v; NPs >= 1, B * R <= 2^31 - 1.  workspace is required: B * Hkv * R * (sp + so) * (dv + 3)
+ *     floats.  Two launches: the kernel of Hkv * ceil(B * R / 16) * sp + B * Hkv * ceil(R / 16) * so waves, four to a work-group, and
+ *     the combine kernel of qs_mx_flash_decode_v.  No barrier, no atomic, no wave waits for another.
+ *   - Checks, in order: those of qs_mx_flash_decode_paged_v with shared_table and shared_len among the pointers that may not be NULL
+ *     (QS_ERR_ARG) and must be 4-byte aligned (QS_ERR_ALIGN), NPs among the extents and shared_splits < 1 next to kv_splits < 1; then
+ *     QS_ERR_ARG: NPs < 1, NPs > 2^31 - 1, B * R > 2^31 - 1, more waves of both kinds than 4 * (2^31 - 1), workspace NULL or
+ *     workspace_bytes too small.
+ *   - Routes: as qs_mx_flash_decode_paged_v. */
+typedef struct qs_mx_flash_decode_shared_paged_args {
+    uint32_t struct_size;            /* sizeof(qs_mx_flash_decode_shared_paged_args) as the caller compiled it */
+    int32_t qk_format;               /* enum qs_mx_format of q and k */
+    int32_t p_format;                /* ... of the attention weights */
+    int32_t v_format;                /* ... of vt */
+    int32_t ydt;                     /* QS_F32, QS_BF16 or QS_F16 */
+    int32_t causal;                  /* 0 or 1, bottom-right aligned */
+    float scale;
+    int32_t kv_splits;               /* so >= 1: runs of the keys from Ls on */
+    int32_t shared_splits;           /* sp >= 1: runs of the shared keys */
+    int32_t reserved0;               /* 0 */
+    const uint8_t* q_codes;          /* [B, Hq, T, d] */
+    const uint8_t* q_scales;         /* [B, Hq, T, ceil(d / 32)] */
+    const uint8_t* k_pool;           /* [P, Hkv, page, d] */
+    const uint8_t* k_pool_scales;    /* [P, Hkv, page, ceil(d / 32)] */
+    const uint8_t* vt_pool;          /* [P, Hkv, dv, page] */
+    const uint8_t* vt_pool_scales;   /* [P, Hkv, dv, page / 32] */
+    const int32_t* block_table;      /* [B, NP], device memory */
+    const int32_t* kv_len;           /* [B], device memory */
+    const int32_t* shared_table;     /* [NPs], device memory */
+    const int32_t* shared_len;       /* [1], device memory */
+    float* workspace;                /* B * Hkv * R * (sp + so) * (dv + 3) floats, required */
+    int64_t workspace_bytes;
+    void* y;                         /* [B, Hq, T, dv] dense */
+    int64_t B, Hq, Hkv, T, P, NP, NPs, page, d, dv;
+    qs_stream_t stream;
+} qs_mx_flash_decode_shared_paged_args;
+int qs_mx_flash_decode_shared_paged_v(const qs_mx_flash_decode_shared_paged_args* args);
+/* the route qs_mx_flash_decode_shared_paged_v takes for these operands, nothing enqueued: QS_MX_FLASH_ROUTE_*, 0 for an empty problem, or
+ * the QS_ERR_* the call would return */
+int qs_mx_flash_decode_shared_paged_route(const qs_mx_flash_decode_shared_paged_args* args);
+
 /* ---- Aliases kept for v27 callers -------------------------------------------------------------------------------------------
  * v27 had the rounding operands in descriptors and entry points of their own.  Those descriptors were the v28 ones byte for byte, so
  * the type names are typedefs and each function forwards to the entry point above it names: same checks, routes, kernels, bytes. */

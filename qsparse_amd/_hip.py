@@ -182,6 +182,8 @@ SIGNATURES = {
     "qs_mx_moe_dispatch_route": (c_int, [_P]),
     "qs_mx_moe_combine_v": (c_int, [_P]),
     "qs_mx_moe_combine_route": (c_int, [_P]),
+    "qs_mx_flash_decode_shared_paged_v": (c_int, [_P]),
+    "qs_mx_flash_decode_shared_paged_route": (c_int, [_P]),
 }
 
 
@@ -468,6 +470,17 @@ class MxFlashDecodePagedArgs(ctypes.Structure):
                 ("k_pool", c_void_p), ("k_pool_scales", c_void_p), ("vt_pool", c_void_p), ("vt_pool_scales", c_void_p),
                 ("block_table", c_void_p), ("kv_len", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_int64), ("y", c_void_p),
                 ("B", c_int64), ("Hq", c_int64), ("Hkv", c_int64), ("T", c_int64), ("P", c_int64), ("NP", c_int64), ("page", c_int64),
+                ("d", c_int64), ("dv", c_int64), ("stream", c_void_p)]
+
+
+class MxFlashDecodeSharedPagedArgs(ctypes.Structure):
+    """`qs_mx_flash_decode_shared_paged_args` of include/qsparse_hip.h"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("qk_format", c_int32), ("p_format", c_int32), ("v_format", c_int32), ("ydt", c_int32),
+                ("causal", c_int32), ("scale", c_float), ("kv_splits", c_int32), ("shared_splits", c_int32), ("reserved0", c_int32),
+                ("q_codes", c_void_p), ("q_scales", c_void_p), ("k_pool", c_void_p), ("k_pool_scales", c_void_p), ("vt_pool", c_void_p),
+                ("vt_pool_scales", c_void_p), ("block_table", c_void_p), ("kv_len", c_void_p), ("shared_table", c_void_p),
+                ("shared_len", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_int64), ("y", c_void_p), ("B", c_int64),
+                ("Hq", c_int64), ("Hkv", c_int64), ("T", c_int64), ("P", c_int64), ("NP", c_int64), ("NPs", c_int64), ("page", c_int64),
                 ("d", c_int64), ("dv", c_int64), ("stream", c_void_p)]
 
 
@@ -2004,6 +2017,36 @@ def mx_flash_decode_paged(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt:
         a.B, a.Hq, a.Hkv, a.T, a.P, a.NP, a.page, a.d, a.dv = B, Hq, Hkv, T, P, NP, page, d, dv
         a.stream = _stream(q_codes)
         mx_flash_last_route = _mx_run("mx_flash_decode_paged", a, (q_codes, q_scales, block_table, kv_len, y))
+    return y
+
+
+def mx_flash_decode_shared_paged(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, k_pool: torch.Tensor, k_pool_scales: torch.Tensor,
+                                 vt_pool: torch.Tensor, vt_pool_scales: torch.Tensor, v_fmt: str, block_table: torch.Tensor,
+                                 kv_len: torch.Tensor, shared_table: torch.Tensor, shared_len: torch.Tensor, scale: float, causal: bool,
+                                 p_fmt: str, out_dtype: torch.dtype, kv_splits: int, shared_splits: int, out=None) -> torch.Tensor:
+    """`mx_flash_decode_paged` for sequences that share a prefix (qs_mx_flash_decode_shared_paged_v): its operands plus `shared_table`
+    int32 [NPs] and `shared_len` int32 [1], contiguous GPU tensors read by the kernel; `shared_splits` + `kv_splits` records per row.
+    Returns y [B, Hq, T, dv] in `out_dtype` from two launches; the workspace is a `torch.empty` of this call.  `out`: as
+    `mx_flash_decode`.  The route lands in `mx_flash_last_route`."""
+    global mx_flash_last_route
+    load()
+    (B, Hq, T, d), (P, Hkv, page, _), dv, NP = q_codes.shape, k_pool.shape, vt_pool.shape[2], block_table.shape[1]
+    y = _mx_new_or_out((B, Hq, T, dv), out_dtype, q_codes.device, out, "out: B Hq T dv elements of out_dtype")
+    mx_flash_last_route = None
+    if B and Hq and T and dv:
+        a = MxFlashDecodeSharedPagedArgs()
+        a.qk_format, a.p_format, a.v_format = MX_FORMATS.index(qk_fmt), MX_FORMATS.index(p_fmt), MX_FORMATS.index(v_fmt)
+        a.ydt, a.causal, a.scale = _DT[out_dtype], int(bool(causal)), float(scale)
+        a.kv_splits, a.shared_splits = int(kv_splits), int(shared_splits)
+        a.q_codes, a.q_scales, a.k_pool, a.k_pool_scales = _ptr(q_codes), _ptr(q_scales), _ptr(k_pool), _ptr(k_pool_scales)
+        a.vt_pool, a.vt_pool_scales, a.block_table, a.kv_len, a.y = _ptr(vt_pool), _ptr(vt_pool_scales), _ptr(block_table), _ptr(kv_len), _ptr(y)
+        a.shared_table, a.shared_len = _ptr(shared_table), _ptr(shared_len)
+        # (m, Z, bad, acc[dv]) of every packed row and run; the kernel writes every record the combine reads
+        ws = torch.empty(B * Hkv * (Hq // Hkv * T) * (kv_splits + shared_splits) * (dv + 3), dtype=torch.float32, device=q_codes.device)
+        a.workspace, a.workspace_bytes = _ptr(ws), ws.numel() * 4
+        a.B, a.Hq, a.Hkv, a.T, a.P, a.NP, a.NPs, a.page, a.d, a.dv = B, Hq, Hkv, T, P, NP, shared_table.shape[0], page, d, dv
+        a.stream = _stream(q_codes)
+        mx_flash_last_route = _mx_run("mx_flash_decode_shared_paged", a, (q_codes, q_scales, block_table, kv_len, shared_table, y))
     return y
 
 

@@ -113,7 +113,8 @@ struct MxdPaged {
     }
 };
 
-__global__ __launch_bounds__(kMxgThreads, 1) void mx_flash_decode_paged_kernel(MxFormat fp, MxdPagedArgs a) {
+// (`inline`: qs_mx_flash_decode_shared.h includes this header into a second unit; the kernel's code is the same instruction for instruction)
+inline __global__ __launch_bounds__(kMxgThreads, 1) void mx_flash_decode_paged_kernel(MxFormat fp, MxdPagedArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[4 * kMxfBounce];
     const int tid = threadIdx.x, lane = tid & 63, i = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);

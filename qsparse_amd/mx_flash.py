@@ -113,15 +113,21 @@ def _decode_def(qc, qs, qk_fmt: str, kc, ks, vc, vs, v_fmt: str, kv_len, scale: 
             for c in range(i * cps, min((i + 1) * cps, -(-L // _CHUNK))):
                 state = _chunk_step(state, c, *q, qk_fmt, *kv[:2], *kv[2:], v_fmt, None, scale, lim, p_fmt)
             states.append(state)
-        M = states[0][0]
-        for st in states[1:]:
-            M = torch.maximum(M, st[0])
-        Z = acc = bad = None
-        for i, (m_i, Z_i, acc_i, bad_i) in enumerate(states):
-            a_i = _exp_def(m_i - M)
-            Z, acc, bad = (Z_i * a_i, acc_i * a_i, bad_i) if i == 0 else (Z + Z_i * a_i, acc + acc_i * a_i, bad | bad_i)
-        out.append(_finish(M, Z, acc, bad, out_dtype).reshape(Hq, T, dv))
+        out.append(_combine(states, out_dtype).reshape(Hq, T, dv))
     return torch.stack(out)
+
+
+def _combine(states, out_dtype):
+    """the states ``(m, Z, acc, bad)`` of a row's runs of chunks combined in the order given, none skipped: ``M`` the maximum over all,
+    then ``Z = Z_0 a_0 (+ Z_i a_i ...)`` with ``a_i = E(m_i - M)``, ``acc`` alike, every multiply and add on its own; then ``_finish``"""
+    M = states[0][0]
+    for st in states[1:]:
+        M = torch.maximum(M, st[0])
+    Z = acc = bad = None
+    for i, (m_i, Z_i, acc_i, bad_i) in enumerate(states):
+        a_i = _exp_def(m_i - M)
+        Z, acc, bad = (Z_i * a_i, acc_i * a_i, bad_i) if i == 0 else (Z + Z_i * a_i, acc + acc_i * a_i, bad | bad_i)
+    return _finish(M, Z, acc, bad, out_dtype)
 
 
 def mx_flash_attention(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, k_codes: torch.Tensor, k_scales: torch.Tensor,
@@ -347,10 +353,50 @@ def _decode_paged_def(qc, qs, qk_fmt: str, k_pool, k_pool_scales, vt_pool, vt_po
     return _decode_def(qc, qs, qk_fmt, k, ks, vt, vts, v_fmt, kv_len, scale, causal, p_fmt, out_dtype, splits)
 
 
+def _shared_chunks(page: int, NP: int, NPs: int, shared_len: int):
+    """``(Ls, Cs)`` of the shared-prefix decode: the shared keys -- ``shared_len`` clamped to ``[0, min(NPs, NP) * page]`` and rounded DOWN
+    to a whole number of chunks of 128 and of pages -- and their chunks"""
+    u = max(_CHUNK, page)
+    Ls = min(max(shared_len, 0), min(NPs, NP) * page) // u * u
+    return Ls, Ls // _CHUNK
+
+
+def _decode_shared_def(qc, qs, qk_fmt: str, k_pool, k_pool_scales, vt_pool, vt_pool_scales, v_fmt: str, block_table, kv_len, shared_table,
+                       shared_len, scale: float, causal: bool, p_fmt: str, out_dtype, splits: int, shared_splits: int):
+    """The shared-prefix paged decode's definition (``include/qsparse_hip.h``, "MX flash attention, shared-prefix paged decode"), on either
+    device.  The first ``Ls`` keys of every sequence are the pages of ``shared_table``, the others ``block_table``'s; the gathered cache
+    is sliced to ``L_b``; each row has ``shared_splits`` runs of the chunks below ``Cs = Ls / 128`` and ``splits`` runs of the chunks from
+    ``Cs`` on, each walked with ``_chunk_step`` from the empty state, and ``_combine`` takes them in that order.  It reads the lengths
+    on the host: it is what the tests compare against, not what a graph captures."""
+    (B, Hq, T, d), (_, Hkv, page, _), dv, NP, NPs, dev = qc.shape, k_pool.shape, vt_pool.shape[2], block_table.shape[1], shared_table.shape[0], qc.device
+    S, r = NP * page, Hq // Hkv
+    Ls, Cs = _shared_chunks(page, NP, NPs, int(shared_len[0]))
+    merged = block_table.clone()
+    merged[:, :Ls // page] = shared_table[:Ls // page]
+    kc, ks, vc, vs = _paged_gather(k_pool, k_pool_scales, vt_pool, vt_pool_scales, merged)
+    cps_s = -(-max(_shared_chunks(page, NP, NPs, S)[1], 1) // shared_splits)
+    cps = -(-(-(-S // _CHUNK)) // splits)
+    runs = [(i * cps_s, min((i + 1) * cps_s, Cs)) for i in range(shared_splits)] + [(Cs + i * cps, Cs + (i + 1) * cps) for i in range(splits)]
+    tok = (torch.arange(r * T, device=dev) % T)[:, None]
+    out = []
+    for b, L in enumerate(min(max(int(n), 0), S) for n in kv_len.tolist()):
+        q = (qc[b].reshape(Hkv, r * T, d), qs[b].reshape(Hkv, r * T, -1))
+        kv = (kc[b, :, :L], ks[b, :, :L], vc[b, :, :, :L], vs[b, :, :, :-(-L // 32)])
+        lim = (tok + (L - T + 1)).clamp(min=0) if causal else None
+        states = []
+        for lo, hi in runs:
+            state = _empty_state(Hkv, r * T, dv, dev)
+            for c in range(lo, min(hi, -(-L // _CHUNK))):
+                state = _chunk_step(state, c, *q, qk_fmt, *kv[:2], *kv[2:], v_fmt, None, scale, lim, p_fmt)
+            states.append(state)
+        out.append(_combine(states, out_dtype).reshape(Hq, T, dv))
+    return torch.stack(out)
+
+
 def mx_flash_decode_paged(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt: str, k_pool: torch.Tensor, k_pool_scales: torch.Tensor,
                           vt_pool: torch.Tensor, vt_pool_scales: torch.Tensor, v_fmt: str, block_table: torch.Tensor, kv_len: torch.Tensor,
                           *, scale: float, is_causal: bool = False, p_fmt: str = "mxfp8_e4m3", out_dtype: torch.dtype = torch.float32,
-                          kv_splits="auto") -> torch.Tensor:
+                          kv_splits="auto", shared=None, shared_splits="auto") -> torch.Tensor:
     """``mx_flash_decode`` on a PAGED cache.  The pool is ``k_pool [P, Hkv, page, d]`` / ``k_pool_scales [P, Hkv, page, ceil(d / 32)]`` and
     ``vt_pool [P, Hkv, dv, page]`` / ``vt_pool_scales [P, Hkv, dv, page / 32]``, contiguous, ``page`` a power of two ``>= 32``.
     ``block_table`` (int32 ``[B, NP]`` on the operands' device) says where a sequence's keys live: position ``j`` of sequence ``b`` is row
@@ -365,9 +411,21 @@ def mx_flash_decode_paged(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt:
     may hold anything.  An entry in the live range that lies outside ``[0, P)`` is not dereferenced either: its page reads as zero
     codes under the scale byte 127.  That is a guard, not a feature.
 
+    ``shared=(shared_table, shared_len)`` -- int32 ``[NPs >= 1]`` and int32 ``[1]`` on the pool's device, both read ON the device -- says
+    that every sequence BEGINS with the same keys: page ``n`` of every sequence is ``shared_table[n]`` where ``(n + 1) * page <= Ls``,
+    ``Ls`` being ``shared_len[0]`` clamped to ``[0, min(NPs, NP) * page]`` and rounded down to a multiple of ``max(128, page)``;
+    ``block_table`` is not looked at there, and ``kv_len`` still counts those keys.  The kernel then reads the shared keys once per 16
+    query rows of the batch instead of once per sequence.  The result is ``_decode_shared_def``'s, bit for bit on either device (the
+    header's "MX flash attention, shared-prefix paged decode"): ``shared_splits`` runs of the shared chunks, then ``kv_splits`` runs of
+    the chunks behind them, combined in that order -- the same recurrence as the call without ``shared``, cut at other chunks, so not
+    its bytes.  ``shared_splits`` is an int ``>= 1`` or ``"auto"``: ``_decode_splits(Hkv * ceil(B * R / 16), Csmax)``, a function of
+    the shapes alone; without ``shared`` it is ignored.  Vt codes of the shared pages that some sequence of the batch sees must not
+    be NaN, even for a sequence too short to see them.
+
     Supported range: that of ``mx_flash_decode`` (``r * T <= 64``, ``d, dv <= 128``, every format triple, three output dtypes); anything
-    else raises ``ValueError``.  GPU tensors take one launch (``kv_splits == 1``) or two (``qs_mx_flash_decode_paged_v``; no fallback
-    and no gathered copy); CPU tensors evaluate ``_decode_paged_def``."""
+    else raises ``ValueError``.  GPU tensors take one launch (``kv_splits == 1``) or two (``qs_mx_flash_decode_paged_v``, with ``shared``
+    ``qs_mx_flash_decode_shared_paged_v``; no fallback and no gathered copy); CPU tensors evaluate ``_decode_paged_def`` /
+    ``_decode_shared_def``."""
     _check_q4("q", q_codes, q_scales, qk_fmt)
     _mx_format(p_fmt)
     _check_dtype("out_dtype", out_dtype)
@@ -392,6 +450,18 @@ def mx_flash_decode_paged(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt:
         kv_splits = _decode_splits(B * Hkv * -(-R // 16), -(-NP * page // _CHUNK))
     elif isinstance(kv_splits, bool) or not isinstance(kv_splits, int) or kv_splits < 1:
         raise ValueError(f'kv_splits must be an int >= 1 or "auto", got {kv_splits!r}')
+    if shared is not None:
+        if not isinstance(shared, (tuple, list)) or len(shared) != 2:
+            raise ValueError(f"shared must be None or a pair (shared_table, shared_len), got {type(shared).__name__}")
+        for name, t, what in (("shared_table", shared[0], "(NPs >= 1,)"), ("shared_len", shared[1], "(1,)")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] < 1 or \
+                    (name == "shared_len" and t.shape[0] != 1) or t.device != dev:
+                raise ValueError(f"{name} must be an int32 tensor of shape {what} on {dev}, got "
+                                 + (f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__))
+        if shared_splits == "auto":
+            shared_splits = _decode_splits(Hkv * -(-B * R // 16), _shared_chunks(page, NP, shared[0].shape[0], NP * page)[1])
+        elif isinstance(shared_splits, bool) or not isinstance(shared_splits, int) or shared_splits < 1:
+            raise ValueError(f'shared_splits must be an int >= 1 or "auto", got {shared_splits!r}')
     if 0 in (B, Hq, T, dv):
         return q_codes.new_empty((B, Hq, T, dv), dtype=out_dtype)
     for name, t in (("k_pool", k_pool), ("k_pool_scales", k_pool_scales), ("vt_pool", vt_pool), ("vt_pool_scales", vt_pool_scales)):
@@ -400,6 +470,10 @@ def mx_flash_decode_paged(q_codes: torch.Tensor, q_scales: torch.Tensor, qk_fmt:
     with torch.no_grad():
         ops = (q_codes.contiguous(), q_scales.contiguous(), qk_fmt, k_pool, k_pool_scales, vt_pool, vt_pool_scales, v_fmt,
                block_table.contiguous(), kv_len.contiguous())
+        if shared is not None:
+            ops += (shared[0].contiguous(), shared[1].contiguous())
+            fn = _hip.mx_flash_decode_shared_paged if q_codes.is_cuda else _decode_shared_def
+            return fn(*ops, float(scale), bool(is_causal), p_fmt, out_dtype, kv_splits, shared_splits)
         if not q_codes.is_cuda:
             return _decode_paged_def(*ops, float(scale), bool(is_causal), p_fmt, out_dtype, kv_splits)
         return _hip.mx_flash_decode_paged(*ops, float(scale), bool(is_causal), p_fmt, out_dtype, kv_splits)

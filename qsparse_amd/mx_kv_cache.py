@@ -382,6 +382,8 @@ class MXPagedKVCache:
         return out
 
     def attend(self, q_codes: torch.Tensor, q_scales: torch.Tensor, **kw) -> torch.Tensor:
+        """``mx_flash_decode_paged`` on the cache; keywords are forwarded, ``shared=(shared_table, shared_len)`` among them for a batch
+        whose sequences begin with the same pages"""
         return mx_flash_decode_paged(q_codes, q_scales, self.qk_fmt, self.k_pool, self.k_pool_scales, self.vt_pool, self.vt_pool_scales,
                                      self.v_fmt, self.block_table, self.kv_len, **kw)
 
